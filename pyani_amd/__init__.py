@@ -7,7 +7,7 @@ There is no CPU fallback: importing the compute modules without the built librar
 __version__ = "0.1.0"
 
 
-def configure_runtime(hw_queues: int = 8) -> bool:
+def configure_runtime(hw_queues: int = 2) -> bool:
     """See pyani_amd._lib.configure_runtime: GPU_MAX_HW_QUEUES for jobs that also run RCCL (explicit, never at import)."""
     from . import _lib
     return _lib.configure_runtime(hw_queues)
