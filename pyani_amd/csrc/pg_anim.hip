@@ -2,11 +2,12 @@
 // `nucmer --mum` + `delta-filter -1` processes pyani shells out to (pyani/anim.py:240-289) and the parse_delta
 // reduction (anim.py:292-411) with an in-process pipeline over the 2-bit/1-bit packed genomes already resident in HBM.
 //
-//   A1 anim_list_kernel      per genome, once: its 16-mers as (k-mer, position) lists partitioned into 2048 hash groups
+//   A1 anim_list_kernel      per genome, once: its 16-mers as (k-mer, position) lists partitioned into 16384 hash groups
 //                            (every position for the reference role, every 5th strand position for the query role)
-//   A2 anim_seed_kernel      one workgroup per (reference, group): the group's reference k-mers become a hash table in
-//                            LDS; the same group of every query of that reference streams through it (coalesced,
-//                            sequential HBM reads; no random global access except to verify / extend actual hits)
+//   A2 anim_seed_kernel      one workgroup per (block of up to 32 references, group): the group's k-mers of every reference
+//                            of the block become ONE hash table in LDS; the same group of every query of the block streams
+//                            through it once (coalesced, sequential HBM reads).  Fragment mode: anim_seed_pair_kernel, one
+//                            workgroup per (reference, coarse group of 8 groups) and every query of that reference
 //   A3 anim_cluster_wave_kernel  one WAVE per (pair, strand): MUM filter (packed radix sorts + wave-scan containment
 //                            flags), mgaps clustering (lock-free union-find), chain extraction (register / LDS resident)
 //   A4x the extension stage  MUMmer's own postnuc / sw_align (pga_postnuc.inc, pga_postnuc_diag.inc; statement pg_nucmer_core.h,
@@ -23,6 +24,7 @@
 // in lock-step and compared on the GPU by tests/test_anim_gpu.py.  Limits: genomes up to ~14 Mb (a reference k-mer
 // group must fit a 16384-slot LDS table; PG_E_CAPACITY otherwise), chain scores < 2^24.
 #include <tuple>
+#include <unordered_map>
 #include "pg_internal.h"
 #include "pg_anim_core.h"
 #include "pg_nucmer_core.h"
@@ -106,7 +108,8 @@ namespace {
 struct GenomeIdx {
   uint64_t *ref_list = nullptr, *qry_list = nullptr, *qry_list1 = nullptr;   // qry_list1: every position (fragment mode)
   uint32_t *ref_goff = nullptr, *qry_goff = nullptr, *qry_goff1 = nullptr;
-  uint32_t ref_max = 0;   // largest reference group (sizes the LDS table)
+  uint32_t ref_max = 0;        // largest coarse reference group (sizes the per-pair kernel's LDS table)
+  uint32_t ref_max_fine = 0;   // largest reference group (the block kernel's table holds one per slot)
   uint32_t* word_start = nullptr;   // fragment mode, word tier: 4^11 + 1 bucket offsets of the genome's 11-mers ...
   int32_t* word_pos = nullptr;      // ... and their positions
 };
@@ -119,8 +122,13 @@ struct AnimScratch {
   uint32_t* list_cnt = nullptr;   // 2 * SEED_GROUPS counters used by this worker's list builds
   SeedRef* srefs_d = nullptr;
   SeedQry* sqry_d = nullptr;
-  SeedSlice* slice_d = nullptr;   // [SEED_GROUPS][pairs of the batch]
+  SeedSlice* slice_d = nullptr;   // [SEED_CGROUPS][pairs of the batch] (per-pair kernel)
   size_t slice_pairs = 0;
+  SeedBlk* sblk_d = nullptr;      // block kernel: blocks, slots, block queries, pair tables
+  SeedSlot* sslot_d = nullptr;
+  SeedQry* sbq_d = nullptr;
+  int32_t* spt_d = nullptr;
+  size_t sblk_cap = 0, sslot_cap = 0, sbq_cap = 0, spt_cap = 0;
   int32_t* recs_d = nullptr;
   RefDesc* refs_d = nullptr;
   UnitDesc* units_d = nullptr;
@@ -145,7 +153,7 @@ struct AnimScratch {
   uint2* ranges_d = nullptr;
   RangeOut* range_out = nullptr;
   size_t big_cap = 0, range_cap = 0;
-  bool lds_attr_set = false;        // anim_seed_kernel's dynamic-LDS limit has been raised on this context's device
+  bool lds_attr_set = false;        // the probe kernels' dynamic-LDS limit has been raised on this context's device
   // A4x, the postnuc extension stage (pga_postnuc.inc)
   pgn::PnAln* pn = nullptr;         // per-unit alignment lists, sliced by moff like the per-match arrays
   uint8_t* pn_fused = nullptr;      // per chain: already extended / fused / shadowed
@@ -247,7 +255,11 @@ static int anim_ensure_lists(pg_ctx* ctx, AnimScratch* A, const std::vector<int3
   const int rc_all = [&]() -> int {
   int rc;
   bool built = false;
-  if (!A->list_cnt && (rc = regrow(ctx, A->list_cnt, (size_t)2 * SEED_GROUPS))) return rc;
+  if (!A->list_cnt) {
+    if ((rc = regrow(ctx, A->list_cnt, (size_t)2 * SEED_GROUPS))) return rc;
+    PG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(anim_list_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)(2 * SEED_GROUPS * 4)));
+  }
   std::vector<int32_t> fresh_refs;
   for (int role = 0; role < 2; ++role) {
     for (int32_t gid : role ? qry_genomes : ref_genomes) {
@@ -263,18 +275,21 @@ static int anim_ensure_lists(pg_ctx* ctx, AnimScratch* A, const std::vector<int3
       uint32_t*& goff = role ? qgoff : X.ref_goff;
       mine.emplace_back(&list, &goff);
       if ((rc = regrow(ctx, list, bound))) return rc;
-      if ((rc = regrow(ctx, goff, (size_t)n_sub + 2))) return rc;
+      if ((rc = regrow(ctx, goff, (size_t)n_sub + 3))) return rc;
       const uint32_t* codes = ctx->d_codes + G.arena_start / 16;
       const uint32_t* mask = ctx->d_mask + G.arena_start / 32;
       const int32_t n_idx = role ? len / qstep + 1 : len;
       const dim3 grid((uint32_t)(n_idx + LIST_CHUNK - 1) / LIST_CHUNK, role ? 2 : 1);
       PG_HIP(ctx, hipMemsetAsync(A->list_cnt, 0, (size_t)n_sub * 4, cur_stream(ctx)));
       if (grid.x)   // (an empty genome still gets its all-zero offset table from the scan)
-        hipLaunchKernelGGL(anim_list_kernel, grid, dim3(LIST_BLOCK), 0, cur_stream(ctx), codes, mask, len, role, A->list_cnt,
+        hipLaunchKernelGGL(anim_list_kernel, grid, dim3(LIST_BLOCK), (size_t)n_sub * 4, cur_stream(ctx), codes, mask, len, role, A->list_cnt,
                            (const uint32_t*)nullptr, (uint64_t*)nullptr, 0, qstep);
-      hipLaunchKernelGGL(anim_list_scan_kernel, dim3(1), dim3(64), 0, cur_stream(ctx), A->list_cnt, goff, n_sub);
+      if (role)
+        hipLaunchKernelGGL(anim_list_scan_kernel<2 * SEED_GROUPS / LIST_SCAN_BLOCK>, dim3(1), dim3(LIST_SCAN_BLOCK), 0, cur_stream(ctx), A->list_cnt, goff);
+      else
+        hipLaunchKernelGGL(anim_list_scan_kernel<SEED_GROUPS / LIST_SCAN_BLOCK>, dim3(1), dim3(LIST_SCAN_BLOCK), 0, cur_stream(ctx), A->list_cnt, goff);
       if (grid.x)
-        hipLaunchKernelGGL(anim_list_kernel, grid, dim3(LIST_BLOCK), 0, cur_stream(ctx), codes, mask, len, role, A->list_cnt,
+        hipLaunchKernelGGL(anim_list_kernel, grid, dim3(LIST_BLOCK), (size_t)n_sub * 4, cur_stream(ctx), codes, mask, len, role, A->list_cnt,
                            (const uint32_t*)goff, list, 1, qstep);
       if (!role) fresh_refs.push_back(gid);
       built = true;
@@ -282,8 +297,12 @@ static int anim_ensure_lists(pg_ctx* ctx, AnimScratch* A, const std::vector<int3
   }
   PG_HIP(ctx, hipGetLastError());
   if (built) PG_HIP(ctx, hipStreamSynchronize(cur_stream(ctx)));
-  for (int32_t gid : fresh_refs)
-    PG_HIP(ctx, hipMemcpy(&LS->gidx[gid].ref_max, LS->gidx[gid].ref_goff + SEED_GROUPS + 1, 4, hipMemcpyDeviceToHost));
+  for (int32_t gid : fresh_refs) {
+    uint32_t mx[2];   // largest group, largest coarse group
+    PG_HIP(ctx, hipMemcpy(mx, LS->gidx[gid].ref_goff + SEED_GROUPS + 1, 8, hipMemcpyDeviceToHost));
+    LS->gidx[gid].ref_max_fine = mx[0];
+    LS->gidx[gid].ref_max = mx[1];
+  }
   return PG_OK;
   }();
   if (rc_all != PG_OK) {
@@ -316,7 +335,7 @@ void pg_anim_free_scratch(pg_ctx* ctx) {
 static void anim_free_one(pg_ctx* ctx, void*& slot) {
   AnimScratch* A = static_cast<AnimScratch*>(slot);
   if (!A) return;
-  void* ptrs[] = {A->mirror_d, A->big_d, A->ranges_d, A->range_out, A->hits_sorted, A->hit_count, A->hoff, A->hit_cursor, A->hits_d, A->slice_d, A->choff_d, A->list_cnt, A->srefs_d, A->sqry_d, A->recs_d, A->refs_d, A->units_d, A->mem_count, A->moff, A->nch, A->status, A->out, A->mem, A->cm,
+  void* ptrs[] = {A->mirror_d, A->big_d, A->ranges_d, A->range_out, A->hits_sorted, A->hit_count, A->hoff, A->hit_cursor, A->hits_d, A->slice_d, A->sblk_d, A->sslot_d, A->sbq_d, A->spt_d, A->choff_d, A->list_cnt, A->srefs_d, A->sqry_d, A->recs_d, A->refs_d, A->units_d, A->mem_count, A->moff, A->nch, A->status, A->out, A->mem, A->cm,
                   A->iscratch, A->order, A->chains, A->S.alns, A->S.a_rrec,
                   A->S.a_qrec, A->S.idx, A->S.from, A->S.sc, A->wl_d, A->seedbuf, A->seed_total, A->fr_tables, A->fr_pairs,
                   A->fr_slot_pair, A->fr_off, A->fr_nrows, A->fr_ebase, A->fr_entries, A->fr_rows, A->fr_out, A->fr_list, A->fr_nlist, A->fr_wtmp, A->fr_widx,
@@ -574,6 +593,7 @@ int pg_anim_run_batch(pg_ctx* ctx, const int32_t* ref_ids, const int32_t* qry_id
     if ((rc = regrow(ctx, A->status, n_pairs))) return rc;
     if ((rc = regrow(ctx, A->sqry_d, n_pairs))) return rc;
     if ((rc = regrow(ctx, A->out, n_pairs))) return rc;
+    if ((rc = regrow(ctx, A->mirror_d, n_pairs))) return rc;
     A->pairs = n_pairs;
   }
   for (uint32_t r = 0; r < n_refs; ++r) refs[r].rec_start = A->recs_d + ref_rec_off[r];
@@ -606,14 +626,22 @@ int pg_anim_run_batch(pg_ctx* ctx, const int32_t* ref_ids, const int32_t* qry_id
   std::vector<SeedRef> srefs;
   std::vector<SeedQry> sqry(n_pairs);
   std::vector<GenomeIdx> LSv;
-  uint32_t slots = 256, n_srefs = 0;
-  if (n_pairs > A->slice_pairs) {
-    if ((rc = regrow(ctx, A->slice_d, (size_t)n_pairs * SEED_GROUPS))) return rc;
-    if ((rc = regrow(ctx, A->mirror_d, n_pairs))) return rc;
-    A->slice_pairs = n_pairs;
-  }
+  uint32_t slots = 256, n_srefs = 0, n_blks = 0, slot_shift = 0;
   const uint32_t slice_stride = n_pairs;   // the table is laid out for the whole batch even if only a prefix is seeded again
   const bool use_mirror = !frag && !pg_dev_env("PYANI_ANIM_NO_MIRROR");
+  // Seeding kernel: ANIm uses the block kernel (anim_seed_kernel); fragment mode — and ANIm under the development switch
+  // PYANI_SEED_PER_PAIR=1, which tests hold against it — the per-pair kernel (anim_seed_pair_kernel).  PYANI_SEED_BLOCK_SLOTS
+  // (development): the table size a block is planned for (default SEED_MAX_SLOTS).
+  const bool use_blocks = !frag && !(pg_dev_env("PYANI_SEED_PER_PAIR") && atoi(pg_dev_env("PYANI_SEED_PER_PAIR")) == 1);
+  uint32_t blk_slots = SEED_MAX_SLOTS;
+  if (pg_dev_env("PYANI_SEED_BLOCK_SLOTS")) {
+    const int want = atoi(pg_dev_env("PYANI_SEED_BLOCK_SLOTS"));
+    blk_slots = want >= 512 && want <= (int)SEED_MAX_SLOTS ? (uint32_t)want : SEED_MAX_SLOTS;
+  }
+  std::vector<SeedBlk> blks;
+  std::vector<SeedSlot> bslots;
+  std::vector<SeedQry> bqry;
+  std::vector<int32_t> bpair;
   auto prepare = [&](uint32_t limit) -> int {   // roles, seed lists and descriptors for the pairs [0, limit)
     std::fill(mirror.begin(), mirror.end(), -1);
     std::fill(seeded.begin(), seeded.end(), (uint8_t)0);
@@ -658,6 +686,77 @@ int pg_anim_run_batch(pg_ctx* ctx, const int32_t* ref_ids, const int32_t* qry_id
       std::lock_guard<std::mutex> lk(ctx->anim_mu);
       LSv = anim_lists(ctx)->gidx;
     }
+    if (use_blocks) {
+      // Slots: per run of seeded pairs with one reference, a pair listed k times goes to the run's k-th slot (a slot's queries are
+      // distinct).  Blocks: consecutive slots while their largest groups sum to at most half the table and there are at most
+      // SEED_BLOCK_SLOTS of them; per block, its distinct queries (sorted) and the [slot][query] -> pair table.
+      std::vector<int32_t> slot_ref;
+      std::vector<std::vector<uint32_t>> slot_pairs;
+      std::unordered_map<int32_t, uint32_t> occ;
+      uint32_t run_first = 0;
+      int32_t run_ref = -1;
+      for (uint32_t p = 0; p < limit; ++p) {
+        if (!seeded[p]) continue;
+        if (ref_ids[p] != run_ref) { run_ref = ref_ids[p]; run_first = (uint32_t)slot_ref.size(); occ.clear(); }
+        const uint32_t k = occ[qry_ids[p]]++;
+        if (run_first + k == slot_ref.size()) { slot_ref.push_back(run_ref); slot_pairs.emplace_back(); }
+        slot_pairs[run_first + k].push_back(p);
+      }
+      blks.clear(); bslots.clear(); bqry.clear(); bpair.clear();
+      uint32_t max_sum = 1;
+      for (uint32_t s0 = 0; s0 < slot_ref.size();) {
+        uint32_t s1 = s0, sum = 0;
+        while (s1 < slot_ref.size() && s1 - s0 < (uint32_t)SEED_BLOCK_SLOTS) {
+          const uint32_t w = LSv[slot_ref[s1]].ref_max_fine;
+          if (s1 > s0 && 2 * (sum + w) > blk_slots) break;
+          sum += w;
+          ++s1;
+        }
+        max_sum = sum > max_sum ? sum : max_sum;
+        std::vector<int32_t> qs;
+        for (uint32_t t = s0; t < s1; ++t) {
+          const PgGenome& G = ctx->genomes[slot_ref[t]];
+          if (G.stream_len >= SEED_TAB_POS_MASK)
+            return pg_fail(ctx, PG_E_CAPACITY, "anim seeding: a reference position does not fit the block table's 30 bits");
+          bslots.push_back(SeedSlot{LSv[slot_ref[t]].ref_list, LSv[slot_ref[t]].ref_goff});
+          for (uint32_t p : slot_pairs[t]) qs.push_back(qry_ids[p]);
+        }
+        std::sort(qs.begin(), qs.end());
+        qs.erase(std::unique(qs.begin(), qs.end()), qs.end());
+        if (qs.size() >= (1u << 25)) return pg_fail(ctx, PG_E_CAPACITY, "anim seeding: more than 2^25 queries in a block");
+        const SeedBlk Bk{s0, s1, (uint32_t)bqry.size(), (uint32_t)(bqry.size() + qs.size()), (uint32_t)bpair.size()};
+        for (int32_t qg : qs) bqry.push_back(SeedQry{LSv[qg].qry_list, LSv[qg].qry_goff});
+        bpair.resize(bpair.size() + (size_t)(s1 - s0) * qs.size(), -1);
+        for (uint32_t t = s0; t < s1; ++t)
+          for (uint32_t p : slot_pairs[t]) {
+            const size_t qi = (size_t)(std::lower_bound(qs.begin(), qs.end(), qry_ids[p]) - qs.begin());
+            bpair[Bk.pair_tab + (size_t)(t - s0) * qs.size() + qi] = (int32_t)p;
+          }
+        blks.push_back(Bk);
+        s0 = s1;
+      }
+      if (bpair.size() > (size_t)0x7FFFFFFF) return pg_fail(ctx, PG_E_CAPACITY, "anim seeding: block pair tables too large");
+      slots = 256;
+      while (slots < 2 * max_sum) slots <<= 1;
+      if (slots > SEED_MAX_SLOTS)
+        return pg_fail(ctx, PG_E_CAPACITY, "anim seeding: a reference k-mer group does not fit the LDS table (genome too large or too repetitive)");
+      slot_shift = 0;
+      while ((slots << slot_shift) < (1u << (32 - SEED_GROUP_BITS))) ++slot_shift;
+      n_blks = (uint32_t)blks.size();
+      int rc3;
+      if (n_blks > A->sblk_cap) { if ((rc3 = regrow(ctx, A->sblk_d, n_blks))) return rc3; A->sblk_cap = n_blks; }
+      if (bslots.size() > A->sslot_cap) { if ((rc3 = regrow(ctx, A->sslot_d, bslots.size()))) return rc3; A->sslot_cap = bslots.size(); }
+      if (bqry.size() > A->sbq_cap) { if ((rc3 = regrow(ctx, A->sbq_d, bqry.size()))) return rc3; A->sbq_cap = bqry.size(); }
+      if (bpair.size() > A->spt_cap) { if ((rc3 = regrow(ctx, A->spt_d, bpair.size()))) return rc3; A->spt_cap = bpair.size(); }
+      if (n_blks) {
+        PG_HIP(ctx, hipMemcpyAsync(A->sblk_d, blks.data(), n_blks * sizeof(SeedBlk), hipMemcpyHostToDevice, cur_stream(ctx)));
+        PG_HIP(ctx, hipMemcpyAsync(A->sslot_d, bslots.data(), bslots.size() * sizeof(SeedSlot), hipMemcpyHostToDevice, cur_stream(ctx)));
+        PG_HIP(ctx, hipMemcpyAsync(A->sbq_d, bqry.data(), bqry.size() * sizeof(SeedQry), hipMemcpyHostToDevice, cur_stream(ctx)));
+        PG_HIP(ctx, hipMemcpyAsync(A->spt_d, bpair.data(), bpair.size() * sizeof(int32_t), hipMemcpyHostToDevice, cur_stream(ctx)));
+      }
+      PG_HIP(ctx, hipMemcpyAsync(A->mirror_d, mirror.data(), n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, cur_stream(ctx)));
+      return PG_OK;
+    }
     uint32_t max_group = 1;
     for (int32_t g : seed_refs) if (LSv[g].ref_max > max_group) max_group = LSv[g].ref_max;
     slots = 256;
@@ -668,6 +767,10 @@ int pg_anim_run_batch(pg_ctx* ctx, const int32_t* ref_ids, const int32_t* qry_id
     }
     if (slots > SEED_MAX_SLOTS)
       return pg_fail(ctx, PG_E_CAPACITY, "anim seeding: a reference k-mer group does not fit the LDS table (genome too large or too repetitive)");
+    if (slice_stride > A->slice_pairs) {
+      if ((rc2 = regrow(ctx, A->slice_d, (size_t)slice_stride * SEED_CGROUPS))) return rc2;
+      A->slice_pairs = slice_stride;
+    }
     srefs.clear();   // one entry per reference with seeded pairs: [pair_begin, pair_end) spans them (pairs in between that
                      // are not seeded have empty slices)
     for (uint32_t p = 0; p < n_pairs; ++p) {
@@ -688,6 +791,8 @@ int pg_anim_run_batch(pg_ctx* ctx, const int32_t* ref_ids, const int32_t* qry_id
   };
   if (!A->lds_attr_set) {   // per context = per device (the attribute is a property of the function ON a device)
     PG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(anim_seed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)(SEED_MAX_SLOTS * 8 + SEED_STAGE_BYTES)));
+    PG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(anim_seed_pair_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)(SEED_MAX_SLOTS * 8 + SEED_STAGE_BYTES)));
     A->lds_attr_set = true;
   }
@@ -724,10 +829,14 @@ int pg_anim_run_batch(pg_ctx* ctx, const int32_t* ref_ids, const int32_t* qry_id
     PG_HIP(ctx, hipMemsetAsync(A->seed_total, 0, 8, cur_stream(ctx)));   // [0] matches, [1] hits
     PG_HIP(ctx, hipMemsetAsync(A->hit_count, 0, n_units * 4, cur_stream(ctx)));
     pg_prof_begin(ctx, PG_K_ANIM_SEED);
-    if (n_srefs)
-    hipLaunchKernelGGL(anim_seed_kernel, dim3(n_srefs, SEED_GROUPS), dim3(SEED_BLOCK), (size_t)slots * 8 + SEED_STAGE_BYTES, cur_stream(ctx),
-                       A->refs_d, A->units_d, A->srefs_d, A->sqry_d, A->slice_d, slice_stride, slots - 1, A->hits_d,
-                       (uint32_t)A->hit_cap, A->seed_total + 1, A->hit_count, qstep);
+    if (use_blocks && n_blks)
+      hipLaunchKernelGGL(anim_seed_kernel, dim3(n_blks, SEED_GROUPS), dim3(SEED_BLOCK), (size_t)slots * 8 + SEED_STAGE_BYTES, cur_stream(ctx),
+                         A->sblk_d, A->sslot_d, A->sbq_d, A->spt_d, slots - 1, slot_shift, A->hits_d, (uint32_t)A->hit_cap,
+                         A->seed_total + 1, A->hit_count, qstep);
+    else if (!use_blocks && n_srefs)
+      hipLaunchKernelGGL(anim_seed_pair_kernel, dim3(n_srefs, SEED_CGROUPS), dim3(SEED_BLOCK), (size_t)slots * 8 + SEED_STAGE_BYTES, cur_stream(ctx),
+                         A->srefs_d, A->sqry_d, A->slice_d, slice_stride, slots - 1, A->hits_d, (uint32_t)A->hit_cap, A->seed_total + 1,
+                         A->hit_count, qstep);
     pg_prof_end(ctx);
     PG_HIP(ctx, hipGetLastError());   // a rejected launch (LDS size) must not surface only at the end of the batch
     pg_prof_begin(ctx, PG_K_ANIM_HIT);

@@ -25,29 +25,36 @@ __device__ __forceinline__ bool seed_kmer(const uint32_t* __restrict__ codes, co
   return m == 0xFFFFu;
 }
 
-// Hash of a seed k-mer: the top SEED_GROUP_BITS select the group (partition of the k-mer space shared by all genomes),
-// bits 5.. select the slot inside the group's LDS table.
-constexpr int SEED_GROUP_BITS = 11, SEED_GROUPS = 1 << SEED_GROUP_BITS;
+// Hash of a seed k-mer: the top SEED_GROUP_BITS (14) select the group (partition of the k-mer space shared by all genomes).
+// The per-pair probe kernel works on COARSE groups (the top 11 bits: eight consecutive groups); the block kernel on the
+// groups themselves.  Lists are laid out so that both views are contiguous (below).
+constexpr int SEED_GROUP_BITS = 14, SEED_GROUPS = 1 << SEED_GROUP_BITS;
+constexpr int SEED_CGROUP_BITS = 11, SEED_CGROUPS = 1 << SEED_CGROUP_BITS, SEED_SUB = SEED_GROUPS / SEED_CGROUPS;
 constexpr uint32_t SEED_MAX_SLOTS = 16384;   // 128 KiB of LDS
 __device__ __forceinline__ uint32_t seed_hash(uint32_t k) { return k * 0x9E3779B1u; }
 __device__ __forceinline__ uint32_t seed_group(uint32_t h) { return h >> (32 - SEED_GROUP_BITS); }
 
-// Per-genome seed lists.  role 0 (reference): every stream position, 1 sub-list per group; role 1 (query): every
-// SEED_STEP-th position of both strands, sub-list index = 2 * group + strand.
+// Per-genome seed lists.  role 0 (reference): every stream position, 1 sub-list per group (coarse group c = sub-lists
+// [8 c, 8 c + 8)); role 1 (query): every SEED_STEP-th position of both strands, sub-list index of (group g, strand s) =
+// (2 (g >> 3) + s) * 8 + (g & 7) — coarse group c and strand s = sub-lists [16 c + 8 s, 16 c + 8 s + 8).
 // Entry (64 bit): [63:43] low 21 bits of the k-mer hash (the hash is a bijection of the 32-bit k-mer and its top 11 bits
-// are the group, so these 21 bits identify the k-mer within its group) | [42:33] the SEED_STEP bases to the LEFT of the
-// k-mer, nearest first | [32] 1 = all of them exist and are clean | [31:0] position.  With both flags set, the
-// left-maximality test of a hit needs no memory access at all.
+// are the coarse group, so these 21 bits identify the k-mer within it; the low 18 identify it within its group) | [42:33]
+// the SEED_STEP bases to the LEFT of the k-mer, nearest first | [32] 1 = all of them exist and are clean | [31:0] position.
+// With both flags set, the left-maximality test of a hit needs no memory access at all.
 // pass 0 counts into cnt[], pass 1 writes at goff[] + cursor (cnt[] re-zeroed in between by anim_list_scan_kernel).
 constexpr uint64_t SEED_KEY_SHIFT = 43;
 constexpr int LIST_BLOCK = 1024, LIST_CHUNK = 16384;   // positions (or sampled positions) per workgroup
+__device__ __forceinline__ uint32_t seed_sub(uint32_t g, int role, uint32_t strand) {
+  return role ? ((2u * (g >> 3) + strand) << 3) + (g & 7u) : g;
+}
 __global__ __launch_bounds__(LIST_BLOCK) void anim_list_kernel(const uint32_t* __restrict__ codes, const uint32_t* __restrict__ mask,
                                                                int32_t len, int role, uint32_t* __restrict__ cnt,
                                                                const uint32_t* __restrict__ goff, uint64_t* __restrict__ list, int pass,
                                                                int step) {
-  // Sub-list counters are kept per workgroup in LDS; the global counters see one atomic per (workgroup, non-empty
-  // sub-list) instead of one per k-mer.  pass 1 counts again, reserves a range per sub-list, then writes.
-  __shared__ uint32_t s_cnt[2 * SEED_GROUPS];
+  // Sub-list counters are kept per workgroup in LDS (dynamic: n_sub words, 64 KiB for the reference role, 128 KiB for the
+  // query role); the global counters see one atomic per (workgroup, non-empty sub-list) instead of one per k-mer.  pass 1
+  // counts again, reserves a range per sub-list, then writes.
+  extern __shared__ uint32_t s_cnt[];
   const int32_t strand = role ? (int32_t)blockIdx.y : 0;
   const uint32_t n_sub = role ? 2 * SEED_GROUPS : SEED_GROUPS;
   const int32_t idx0 = blockIdx.x * LIST_CHUNK;
@@ -61,7 +68,7 @@ __global__ __launch_bounds__(LIST_BLOCK) void anim_list_kernel(const uint32_t* _
     h = seed_hash(k);
     return true;
   };
-  auto sub_of = [&](uint32_t h) { const uint32_t g = seed_group(h); return role ? 2 * g + (uint32_t)strand : g; };
+  auto sub_of = [&](uint32_t h) { return seed_sub(seed_group(h), role, (uint32_t)strand); };
   for (int32_t t = threadIdx.x; t < LIST_CHUNK; t += LIST_BLOCK) {
     uint32_t h; int32_t p;
     if (kmer_of(idx0 + t, h, p)) atomicAdd(&s_cnt[sub_of(h)], 1u);
@@ -89,43 +96,83 @@ __global__ __launch_bounds__(LIST_BLOCK) void anim_list_kernel(const uint32_t* _
   }
 }
 
-// goff[0..n] = exclusive prefix of cnt[0..n), goff[n + 1] = max(cnt); cnt re-zeroed.  One wave; n is 2048 or 4096.
-__global__ __launch_bounds__(64) void anim_list_scan_kernel(uint32_t* __restrict__ cnt, uint32_t* __restrict__ goff, uint32_t n) {
-  const uint32_t lane = threadIdx.x;
-  uint32_t run = 0, mx = 0;
-  for (uint32_t base = 0; base < n; base += 64) {
-    const uint32_t c = cnt[base + lane];
-    cnt[base + lane] = 0;
-    uint32_t incl = c;
+// goff[0..n] = exclusive prefix of cnt[0..n), goff[n + 1] = largest sub-list, goff[n + 2] = largest run of SEED_SUB
+// aligned sub-lists (a coarse group of the reference role); cnt re-zeroed.  n = PER * 1024 (SEED_GROUPS or 2 * SEED_GROUPS):
+// each thread owns PER consecutive counters (a multiple of SEED_SUB), loaded and stored as 16-byte vectors.
+constexpr int LIST_SCAN_BLOCK = 1024;
+template <int PER>
+__global__ __launch_bounds__(LIST_SCAN_BLOCK) void anim_list_scan_kernel(uint32_t* __restrict__ cnt, uint32_t* __restrict__ goff) {
+  static_assert(PER % SEED_SUB == 0 && PER % 4 == 0, "a thread owns whole coarse groups");
+  constexpr uint32_t n = PER * LIST_SCAN_BLOCK;
+  __shared__ uint32_t s_sum[LIST_SCAN_BLOCK / 64], s_mx[LIST_SCAN_BLOCK / 64], s_cmx[LIST_SCAN_BLOCK / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  uint4* const c4 = reinterpret_cast<uint4*>(cnt + tid * PER);
+  uint32_t c[PER];
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(incl, o, 64); if ((int)lane >= o) incl += t; }
-    goff[base + lane] = run + incl - c;
-    run += __shfl(incl, 63, 64);
-    mx = c > mx ? c : mx;
+  for (int i = 0; i < PER / 4; ++i) {
+    const uint4 v = c4[i];
+    c[4 * i] = v.x; c[4 * i + 1] = v.y; c[4 * i + 2] = v.z; c[4 * i + 3] = v.w;
+    c4[i] = make_uint4(0, 0, 0, 0);
   }
+  uint32_t sum = 0, mx = 0, cmx = 0;
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const uint32_t t = __shfl_xor(mx, o, 64); mx = t > mx ? t : mx; }
-  if (lane == 0) { goff[n] = run; goff[n + 1] = mx; }
+  for (int i = 0; i < PER; i += SEED_SUB) {
+    uint32_t run8 = 0;
+#pragma unroll
+    for (int j = 0; j < SEED_SUB; ++j) { run8 += c[i + j]; mx = c[i + j] > mx ? c[i + j] : mx; }
+    sum += run8;
+    cmx = run8 > cmx ? run8 : cmx;
+  }
+  uint32_t incl = sum;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(incl, o, 64); if ((int)lane >= o) incl += t; }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    uint32_t t = __shfl_xor(mx, o, 64); mx = t > mx ? t : mx;
+    t = __shfl_xor(cmx, o, 64); cmx = t > cmx ? t : cmx;
+  }
+  if (lane == 63) s_sum[wave] = incl;
+  if (lane == 0) { s_mx[wave] = mx; s_cmx[wave] = cmx; }
+  __syncthreads();
+  uint32_t run = incl - sum;
+  for (uint32_t w = 0; w < wave; ++w) run += s_sum[w];
+  uint4* const g4 = reinterpret_cast<uint4*>(goff + tid * PER);
+#pragma unroll
+  for (int i = 0; i < PER / 4; ++i) {
+    uint4 v;
+    v.x = run; run += c[4 * i];
+    v.y = run; run += c[4 * i + 1];
+    v.z = run; run += c[4 * i + 2];
+    v.w = run; run += c[4 * i + 3];
+    g4[i] = v;
+  }
+  if (tid == LIST_SCAN_BLOCK - 1) {
+    goff[n] = run;
+    uint32_t m = 0, cm = 0;
+    for (uint32_t w = 0; w < LIST_SCAN_BLOCK / 64; ++w) { m = s_mx[w] > m ? s_mx[w] : m; cm = s_cmx[w] > cm ? s_cmx[w] : cm; }
+    goff[n + 1] = m;
+    goff[n + 2] = cm;
+  }
 }
 
-struct SeedRef {            // one per reference of the batch
+struct SeedRef {            // one per reference of the batch (per-pair kernel)
   const uint64_t* list;
-  const uint32_t* goff;     // SEED_GROUPS + 2
+  const uint32_t* goff;     // SEED_GROUPS + 3
   uint32_t pair_begin, pair_end;
 };
 struct SeedQry {            // one per pair of the batch (its query genome)
   const uint64_t* list;
-  const uint32_t* goff;     // 2 * SEED_GROUPS + 2
+  const uint32_t* goff;     // 2 * SEED_GROUPS + 3
 };
-// Per batch, transposed: slice[g * n_pairs + p] = where pair p's query keeps group g.  A wave reads the descriptors of
+// Per batch, transposed: slice[c * n_pairs + p] = where pair p's query keeps coarse group c.  A wave reads the descriptors of
 // 64 of its pairs with ONE coalesced load instead of chasing pair -> offset table -> entries once per pair.
 struct SeedSlice { uint32_t begin, n0, n1; };   // strand-0 entries [begin, begin + n0), strand-1 [begin + n0, begin + n0 + n1)
 __global__ __launch_bounds__(256) void anim_slice_kernel(const SeedQry* __restrict__ sqry, uint32_t n_pairs, SeedSlice* __restrict__ slice) {
   const uint32_t p = blockIdx.x;
   const uint32_t* goff = sqry[p].goff;
-  for (uint32_t g = threadIdx.x; g < SEED_GROUPS; g += 256) {
+  for (uint32_t g = threadIdx.x; g < SEED_CGROUPS; g += 256) {
     if (!goff) { slice[(size_t)g * n_pairs + p] = SeedSlice{0, 0, 0}; continue; }   // not seeded: mirrored from its partner pair
-    const uint32_t o0 = goff[2 * g], o1 = goff[2 * g + 1], o2 = goff[2 * g + 2];
+    const uint32_t o0 = goff[2 * SEED_SUB * g], o1 = goff[2 * SEED_SUB * g + SEED_SUB], o2 = goff[2 * SEED_SUB * (g + 1)];
     slice[(size_t)g * n_pairs + p] = SeedSlice{o0, o1 - o0, o2 - o1};
   }
 }
@@ -167,19 +214,67 @@ __device__ __forceinline__ bool seed_hit(const RefDesc& R, const SeqView& RV, co
   return true;
 }
 
-// Workgroup (g, r): LDS table of reference r's group g, then every query of r streams its group-g entries through it.
+// A hit that may start a match: handed to anim_hit_kernel (verification / extension need the sequences and many registers;
+// keeping them out of the probe kernels doubles their waves per SIMD).  Staged per wave in LDS.
+constexpr int SEED_BLOCK = 1024, SEED_UNROLL = 4;
+constexpr uint32_t SEED_STAGE = 48;    // hits staged in LDS per wave (64 KiB table + staging: two workgroups per CU)
+constexpr size_t SEED_STAGE_BYTES = (SEED_BLOCK / 64) * (SEED_STAGE * sizeof(Match) + 4);
+__device__ __forceinline__ void seed_stage_hit(Match* stage, uint32_t* stage_n, uint32_t wave, const Match& m, Match* __restrict__ buf,
+                                               uint32_t cap, uint32_t* __restrict__ total, uint32_t* __restrict__ hit_count) {
+  const uint32_t at = atomicAdd(&stage_n[wave], 1u);
+  if (at < SEED_STAGE) {
+    stage[wave * SEED_STAGE + at] = m;
+  } else {   // staging buffer full (a burst of hits): straight to the global buffer
+    const uint32_t ga = atomicAdd(total, 1u);
+    atomicAdd(&hit_count[(uint32_t)m.strand], 1u);
+    if (ga < cap) buf[ga] = m;
+  }
+}
+// Uniform point: flush once the buffer is half full (or, `last`, whatever it holds).  Staged hits sit in processing order: every run of
+// one unit adds its length to its unit's hit count (one atomic per run, not per hit).
+__device__ __forceinline__ void seed_stage_flush(Match* stage, uint32_t* stage_n, uint32_t wave, uint32_t lane, bool last,
+                                                 Match* __restrict__ buf, uint32_t cap, uint32_t* __restrict__ total,
+                                                 uint32_t* __restrict__ hit_count) {
+  __builtin_amdgcn_wave_barrier();
+  uint32_t n_st = stage_n[wave];
+  if (n_st > SEED_STAGE) n_st = SEED_STAGE;
+  if (n_st >= SEED_STAGE / 2 || (n_st && last)) {
+    static_assert(SEED_STAGE <= 64, "one staged hit per lane at flush time");
+    uint32_t base = 0;
+    if (lane == 0) {
+      base = atomicAdd(total, n_st);
+      stage_n[wave] = 0;
+    }
+    base = __shfl(base, 0);
+    int32_t mr = 0, mq = 0, ml = 0, mu = -1;   // (field by field: a Match temporary here is kept in scratch)
+    if (lane < n_st) {
+      const Match& st = stage[wave * SEED_STAGE + lane];
+      mr = st.r; mq = st.q; ml = st.len; mu = st.strand;
+    }
+    const int32_t prev_unit = __shfl_up(mu, 1, 64);
+    const bool start = lane < n_st && (lane == 0 || prev_unit != mu);
+    const uint64_t starts = __ballot(start);
+    if (start) {
+      const uint64_t later = starts >> 1 >> lane;   // starts after this lane
+      const uint32_t run = later ? (uint32_t)__ffsll((unsigned long long)later) : n_st - lane;
+      atomicAdd(&hit_count[(uint32_t)mu], run);
+    }
+    if (lane < n_st && base + lane < cap) buf[base + lane] = Match{mr, mq, ml, mu};
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// Per-pair kernel (fragment mode, and PYANI_SEED_PER_PAIR=1): workgroup (c, r): LDS table of reference r's coarse group c,
+// then every query of r streams its group-c entries through it.
 // Each of the 16 WAVES takes every 16th pair and keeps SEED_UNROLL coalesced 512-byte loads in flight, so the stream is
 // bandwidth- rather than latency-bound.  Matches are appended to one batch-wide buffer (the `strand` field carries the
 // unit index until the scatter); unit_count[] is exact even when the buffer overflows, which is what the host uses to
 // size the slices (and to re-run a prefix).
-constexpr int SEED_BLOCK = 1024, SEED_UNROLL = 4;
-constexpr uint32_t SEED_STAGE = 48;    // hits staged in LDS per wave (64 KiB table + staging: two workgroups per CU)
-constexpr size_t SEED_STAGE_BYTES = (SEED_BLOCK / 64) * (SEED_STAGE * sizeof(Match) + 4);
-__global__ __launch_bounds__(SEED_BLOCK) void anim_seed_kernel(const RefDesc* __restrict__ refs, const UnitDesc* __restrict__ units,
-                                                               const SeedRef* __restrict__ srefs, const SeedQry* __restrict__ sqry,
-                                                               const SeedSlice* __restrict__ slice, uint32_t n_pairs,
-                                                               uint32_t slot_mask, Match* __restrict__ buf, uint32_t cap,
-                                                               uint32_t* __restrict__ total, uint32_t* __restrict__ hit_count, int32_t step) {
+__global__ __launch_bounds__(SEED_BLOCK) void anim_seed_pair_kernel(const SeedRef* __restrict__ srefs, const SeedQry* __restrict__ sqry,
+                                                                    const SeedSlice* __restrict__ slice, uint32_t n_pairs,
+                                                                    uint32_t slot_mask, Match* __restrict__ buf, uint32_t cap,
+                                                                    uint32_t* __restrict__ total, uint32_t* __restrict__ hit_count,
+                                                                    int32_t step) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long tab[];
   Match* stage = reinterpret_cast<Match*>(tab + slot_mask + 1);                    // [waves][SEED_STAGE]
   uint32_t* stage_n = reinterpret_cast<uint32_t*>(stage + (SEED_BLOCK / 64) * SEED_STAGE);   // [waves]
@@ -193,7 +288,7 @@ __global__ __launch_bounds__(SEED_BLOCK) void anim_seed_kernel(const RefDesc* __
   for (uint32_t i = tid; i <= slot_mask; i += SEED_BLOCK) tab[i] = SLOT_EMPTY;
   if (tid < SEED_BLOCK / 64) stage_n[tid] = 0;
   __syncthreads();
-  for (uint32_t e = SR.goff[g] + tid; e < SR.goff[g + 1]; e += SEED_BLOCK) {
+  for (uint32_t e = SR.goff[SEED_SUB * g] + tid; e < SR.goff[SEED_SUB * (g + 1)]; e += SEED_BLOCK) {
     const unsigned long long v = SR.list[e];
     uint32_t slot = (uint32_t)(v >> (SEED_KEY_SHIFT + 5)) & slot_mask;   // hash bits 5.. (slot_mask <= 2^14 - 1)
     while (atomicCAS(&tab[slot], SLOT_EMPTY, v) != SLOT_EMPTY) slot = (slot + 1) & slot_mask;
@@ -243,7 +338,7 @@ __global__ __launch_bounds__(SEED_BLOCK) void anim_seed_kernel(const RefDesc* __
         qv[t] = e < c.e_end ? __builtin_nontemporal_load(&c.list[e]) : SLOT_EMPTY;
       }
     };
-    auto process = [&](const Blk& c, const unsigned long long (&qv)[SEED_UNROLL], bool last) {
+    auto process = [&](const Blk& c, const unsigned long long (&qv)[SEED_UNROLL]) {
       const uint32_t unit = 2 * (chunk + c.j) + c.strand;
 #pragma unroll
       for (int t = 0; t < SEED_UNROLL; ++t) {
@@ -271,50 +366,13 @@ __global__ __launch_bounds__(SEED_BLOCK) void anim_seed_kernel(const RefDesc* __
               left = diff ? (__ffs(diff) - 1) >> 1 : SEED_STEP;
               report = left < step;   // inside a longer match: an earlier sampled position (every step-th) reports it
             }
-            if (report) {
-              // a hit that may start a match: handed to anim_hit_kernel (verification / extension need the sequences and
-              // many registers; keeping them out of this kernel doubles its waves per SIMD).  Staged per wave in LDS.
-              const Match m{(int32_t)(uint32_t)v, q, left, (int32_t)unit};
-              const uint32_t at = atomicAdd(&stage_n[wave], 1u);
-              if (at < SEED_STAGE) {
-                stage[wave * SEED_STAGE + at] = m;
-              } else {   // staging buffer full (a burst of hits): straight to the global buffer
-                const uint32_t ga = atomicAdd(total, 1u);
-                atomicAdd(&hit_count[unit], 1u);
-                if (ga < cap) buf[ga] = m;
-              }
-            }
+            if (report) seed_stage_hit(stage, stage_n, wave, Match{(int32_t)(uint32_t)v, q, left, (int32_t)unit}, buf, cap, total, hit_count);
           }
           slot_b = (slot_b + 8u) & byte_mask;
           v = *reinterpret_cast<const unsigned long long*>(tab_b + slot_b);
         }
       }
-      // uniform point: flush once the buffer is half full (or at the very end).  Staged hits sit in processing order,
-      // i.e. in runs of one unit: every run adds its length to its unit's hit count (one atomic per run, not per hit).
-      __builtin_amdgcn_wave_barrier();
-      uint32_t n_st = stage_n[wave];
-      if (n_st > SEED_STAGE) n_st = SEED_STAGE;
-      if (n_st >= SEED_STAGE / 2 || (n_st && last)) {
-        static_assert(SEED_STAGE <= 64, "one staged hit per lane at flush time");
-        uint32_t base = 0;
-        if (lane == 0) {
-          base = atomicAdd(total, n_st);
-          stage_n[wave] = 0;
-        }
-        base = __shfl(base, 0);
-        Match m{0, 0, 0, -1};
-        if (lane < n_st) m = stage[wave * SEED_STAGE + lane];
-        const int32_t prev_unit = __shfl_up(m.strand, 1, 64);
-        const bool start = lane < n_st && (lane == 0 || prev_unit != m.strand);
-        const uint64_t starts = __ballot(start);
-        if (start) {
-          const uint64_t later = starts >> 1 >> lane;   // starts after this lane
-          const uint32_t run = later ? (uint32_t)__ffsll((unsigned long long)later) : n_st - lane;
-          atomicAdd(&hit_count[(uint32_t)m.strand], run);
-        }
-        if (lane < n_st && base + lane < cap) buf[base + lane] = m;
-        __builtin_amdgcn_wave_barrier();
-      }
+      seed_stage_flush(stage, stage_n, wave, lane, false, buf, cap, total, hit_count);
     };
     unsigned long long qa[SEED_UNROLL], qb[SEED_UNROLL];
     Blk A = first_from(0, 0);
@@ -322,13 +380,198 @@ __global__ __launch_bounds__(SEED_BLOCK) void anim_seed_kernel(const RefDesc* __
     while (A.valid) {
       Blk B = next_of(A);
       if (B.valid) load(B, qb);
-      process(A, qa, !B.valid && chunk + 64 >= my_end);
+      process(A, qa);
       if (!B.valid) break;
       A = next_of(B);
       if (A.valid) load(A, qa);
-      process(B, qb, !A.valid && chunk + 64 >= my_end);
+      process(B, qb);
     }
   }
+  seed_stage_flush(stage, stage_n, wave, lane, true, buf, cap, total, hit_count);   // what is still staged (uniform point)
+}
+
+// Unit of a block kernel hit: code = query-in-block << 6 | slot-in-block << 1 | strand; -1 when the pair (slot's reference, query)
+// is not seeded in this direction.  The lookup is made at the key match, before staging: a block holds every query of its
+// slots, so a reference that is also a query of the block (a row of a tiled grid), and the unseeded direction of a mirrored
+// pair, match whole genomes' worth of keys that must be dropped at once (staging them and resolving at the flush made the
+// kernel 1.7 x slower).  n_qry < 2^25 (checked on the host).
+__device__ __forceinline__ int32_t seed_block_unit(const int32_t* __restrict__ ptab, uint32_t n_qry, uint32_t code) {
+  const int32_t pair = ptab[(size_t)((code >> 1) & 31u) * n_qry + (code >> 6)];
+  return pair >= 0 ? 2 * pair + (int32_t)(code & 1u) : -1;
+}
+
+// Block kernel (ANIm): the launch's seeded pairs are cut on the host into BLOCKS of reference SLOTS.  A slot is one reference
+// genome with a set of its seeded pairs whose queries are distinct (a pair listed twice takes a second slot of the same
+// reference); a block holds at most SEED_BLOCK_SLOTS slots whose largest groups sum to at most half the LDS table, and the
+// sorted distinct queries of their pairs.  Workgroup (b, g): ONE LDS table of group g of every slot of block b, then every
+// query of the block streams its group-g entries through it ONCE — each query is read once per block instead of once per
+// pair.  A key match names its slot; pair_of[slot][query] names the pair, or is -1 when the pair (reference, query) is not
+// seeded in this direction (no pair, or mirrored from its partner): such a hit is neither staged nor counted.
+// Table entry: [63:46] hash bits 0..17 (the key within its group) | [45:35] the lists' context bits [42:32] | [34:30] slot in
+// the block | [29:0] reference position.  Positions < 2^30 - 1 (checked on the host), so the low word of an entry is never all
+// ones = SLOT_EMPTY's.
+constexpr int SEED_BLOCK_SLOTS = 32;
+constexpr int SEED_TAB_KEY_SHIFT = 46, SEED_TAB_CTX_SHIFT = 35, SEED_TAB_SLOT_SHIFT = 30;
+constexpr uint32_t SEED_TAB_POS_MASK = (1u << SEED_TAB_SLOT_SHIFT) - 1u, SEED_KEY_MASK = (1u << (32 - SEED_GROUP_BITS)) - 1u;
+static_assert(32 - SEED_GROUP_BITS + 11 + 5 + SEED_TAB_SLOT_SHIFT == 64 && (1 << 5) == SEED_BLOCK_SLOTS, "table entry bit budget");
+struct SeedSlot { const uint64_t* list; const uint32_t* goff; };   // a slot's reference lists
+struct SeedBlk {
+  uint32_t slot_begin, slot_end;   // into the launch's SeedSlot array
+  uint32_t qry_begin, qry_end;     // into the launch's query array (SeedQry, sorted by genome)
+  uint32_t pair_tab;               // pair_of[pair_tab + slot_in_block * n_qry + query_in_block]: pair index or -1
+};
+// Slot of a 18-bit key in a table of slot_mask + 1 = 2^(18 - slot_shift) slots: the key's top bits (hash bits slot_shift ..
+// 17, the best mixed of a multiplicative hash below the group bits).
+__global__ __launch_bounds__(SEED_BLOCK) void anim_seed_kernel(const SeedBlk* __restrict__ blks, const SeedSlot* __restrict__ slots,
+                                                               const SeedQry* __restrict__ bqry, const int32_t* __restrict__ pair_of,
+                                                               uint32_t slot_mask, uint32_t slot_shift, Match* __restrict__ buf,
+                                                               uint32_t cap, uint32_t* __restrict__ total, uint32_t* __restrict__ hit_count,
+                                                               int32_t step) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long tab[];
+  Match* stage = reinterpret_cast<Match*>(tab + slot_mask + 1);                    // [waves][SEED_STAGE]
+  uint32_t* stage_n = reinterpret_cast<uint32_t*>(stage + (SEED_BLOCK / 64) * SEED_STAGE);   // [waves]
+  // Workgroups are numbered block-fastest (as the per-pair kernel's reference-fastest): the workgroups in flight stream the
+  // same few groups of the same queries, which come from L2 / the Infinity Cache for all but the first reader.
+  const uint32_t g = blockIdx.y;
+  const SeedBlk B = blks[blockIdx.x];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  for (uint32_t i = tid; i <= slot_mask; i += SEED_BLOCK) tab[i] = SLOT_EMPTY;
+  if (tid < SEED_BLOCK / 64) stage_n[tid] = 0;
+  __syncthreads();
+  for (uint32_t k = wave; k < B.slot_end - B.slot_begin; k += SEED_BLOCK / 64) {   // one slot per wave at a time
+    const SeedSlot S = slots[B.slot_begin + k];
+    const uint32_t e_end = S.goff[g + 1];
+    for (uint32_t e = S.goff[g] + lane; e < e_end; e += 64) {
+      const unsigned long long v = S.list[e];
+      const unsigned long long t = (((v >> SEED_KEY_SHIFT) & SEED_KEY_MASK) << SEED_TAB_KEY_SHIFT) | (((v >> 32) & 0x7FFull) << SEED_TAB_CTX_SHIFT) |
+                                   ((unsigned long long)k << SEED_TAB_SLOT_SHIFT) | (uint32_t)v;
+      uint32_t slot = (uint32_t)(t >> (SEED_TAB_KEY_SHIFT + slot_shift)) & slot_mask;
+      while (atomicCAS(&tab[slot], SLOT_EMPTY, t) != SLOT_EMPTY) slot = (slot + 1) & slot_mask;
+    }
+  }
+  __syncthreads();
+  // This wave's share of the block's queries: a contiguous range, in chunks of 32 queries = 64 slices (lane i: query i / 2,
+  // strand i & 1), their group-g offsets read straight from the queries' offset tables (strand s: sub-list seed_sub(g, 1, s)).
+  // A chunk's non-empty slices are packed back to back into full rows of 64 entries (a slice holds ~60 entries per strand of a
+  // 5 Mb query: one row per slice would leave a third of the lanes idle and put one memory round trip behind every row).
+  const uint32_t n_qry = B.qry_end - B.qry_begin;
+  const int32_t* __restrict__ ptab = pair_of + B.pair_tab;
+  const uint32_t per_wave = (n_qry + SEED_BLOCK / 64 - 1) / (SEED_BLOCK / 64);
+  const uint32_t my_begin = wave * per_wave;
+  const uint32_t my_end = my_begin + per_wave < n_qry ? my_begin + per_wave : n_qry;
+  const uint32_t sub0 = seed_sub(g, 1, 0), sub1 = seed_sub(g, 1, 1);
+  for (uint32_t chunk = my_begin; chunk < my_end; chunk += 32) {
+    uint32_t n = 0;
+    unsigned long long base = 0;   // address of the slice's entry 0
+    if (chunk + (lane >> 1) < my_end) {
+      const SeedQry Q = bqry[B.qry_begin + chunk + (lane >> 1)];
+      const uint32_t sub = (lane & 1u) ? sub1 : sub0;
+      const uint32_t b = Q.goff[sub];
+      n = Q.goff[sub + 1] - b;
+      base = (unsigned long long)(Q.list + b);
+    }
+    // compaction: lane r takes the r-th non-empty slice (src = its lane above: the slice id)
+    const uint64_t ne = __ballot(n != 0);
+    const uint32_t n_ne = (uint32_t)__popcll(ne);
+    uint32_t src = 0;
+    {
+      uint64_t m = ne;   // select the (lane + 1)-th set bit: binary search on prefix popcounts
+      uint32_t lo = 0;
+#pragma unroll
+      for (uint32_t w = 32; w > 0; w >>= 1) {
+        const uint64_t low = w == 64 ? m : (m & ((1ull << w) - 1ull));
+        const uint32_t c = (uint32_t)__popcll(low);
+        if (lane >= lo + c) { lo += c; m >>= w; src += w; } else { m = low; }
+      }
+    }
+    const uint32_t pulled = (uint32_t)__shfl(n, (int)src, 64);   // (all lanes: a bpermute reads 0 from an inactive lane)
+    const uint32_t cn = lane < n_ne ? pulled : 0u;
+    const unsigned long long cbase = ((unsigned long long)(uint32_t)__shfl((int)(uint32_t)(base >> 32), (int)src, 64) << 32) |
+                                     (uint32_t)__shfl((int)(uint32_t)base, (int)src, 64);
+    uint32_t c = cn;   // exclusive prefix of the packed slice lengths: where slice `lane` starts in the chunk's stream
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(c, o, 64); if ((int)lane >= o) c += t; }
+    const uint32_t T = (uint32_t)__shfl((int)c, 63, 64);
+    c -= cn;
+    const unsigned long long cstart = cbase - (unsigned long long)c * 8ull;   // entry e of the stream (in slice `lane`) at cstart + 8 e
+    // row at E: lane l holds stream entry E + l, of the slice j = (slices starting at or before it) - 1
+    auto load = [&](uint32_t E, unsigned long long (&qv)[SEED_UNROLL], uint32_t (&sid)[SEED_UNROLL]) {
+#pragma unroll
+      for (int t = 0; t < SEED_UNROLL; ++t) {
+        const uint32_t R = E + 64u * (uint32_t)t;
+        qv[t] = SLOT_EMPTY;
+        sid[t] = 0;
+        if (R < T) {
+          const uint32_t before = (uint32_t)__popcll(__ballot(lane < n_ne && c < R));
+          uint64_t in_row = __ballot(lane < n_ne && c >= R && c < R + 64u), S = 0;
+          while (in_row) {   // (one or two slices start inside a row)
+            const int i = __ffsll((unsigned long long)in_row) - 1;
+            S |= 1ull << ((uint32_t)__builtin_amdgcn_readlane((int)c, i) - R);
+            in_row &= in_row - 1ull;
+          }
+          const uint32_t at = before + __builtin_amdgcn_mbcnt_hi((uint32_t)(S >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)S, 0u)) +
+                              (uint32_t)((S >> lane) & 1ull);
+          const int j = (int)at - 1;
+          const unsigned long long st = ((unsigned long long)(uint32_t)__shfl((int)(uint32_t)(cstart >> 32), j, 64) << 32) |
+                                        (uint32_t)__shfl((int)(uint32_t)cstart, j, 64);
+          sid[t] = (uint32_t)__shfl((int)src, j, 64);
+          if (R + lane < T) qv[t] = __builtin_nontemporal_load(reinterpret_cast<const uint64_t*>(st + 8ull * (R + lane)));
+        }
+      }
+    };
+    auto process = [&](const unsigned long long (&qv)[SEED_UNROLL], const uint32_t (&sid)[SEED_UNROLL]) {
+#pragma unroll
+      for (int t = 0; t < SEED_UNROLL; ++t) {
+        if (qv[t] == SLOT_EMPTY) continue;
+        const uint32_t qhi = (uint32_t)(qv[t] >> 32);
+        const uint32_t qkey = (qhi >> (SEED_KEY_SHIFT - 32)) & SEED_KEY_MASK;
+        const uint32_t qctx = qhi & 0x7FFu;   // bit 0: flag, bits 1..10: left bases
+        const int32_t q = (int32_t)(uint32_t)qv[t];
+        const uint32_t qcode = ((chunk + (sid[t] >> 1)) << 6) | (sid[t] & 1u);   // query in block, strand (the slot is or'ed in)
+        uint32_t slot_b = ((qkey >> slot_shift) & slot_mask) << 3;   // byte offset of the slot
+        const uint32_t byte_mask = (slot_mask << 3) | 7u;
+        const char* const tab_b = reinterpret_cast<const char*>(tab);
+        // (single exit, 32-bit tests only: see the per-pair kernel)
+        unsigned long long v = *reinterpret_cast<const unsigned long long*>(tab_b + slot_b);
+        while ((uint32_t)v != 0xFFFFFFFFu) {   // load factor <= 1/2: every probe sequence ends
+          const uint32_t vhi = (uint32_t)(v >> 32);
+          if ((vhi >> (SEED_TAB_KEY_SHIFT - 32)) == qkey) {
+            int32_t left = -1;
+            bool report = true;
+            const uint32_t rctx = (vhi >> (SEED_TAB_CTX_SHIFT - 32)) & 0x7FFu;
+            if (rctx & qctx & 1u) {
+              const uint32_t x = (rctx ^ qctx) >> 1;
+              const uint32_t diff = (x | (x >> 1)) & 0x155u;
+              left = diff ? (__ffs(diff) - 1) >> 1 : SEED_STEP;
+              report = left < step;   // inside a longer match: an earlier sampled position (every step-th) reports it
+            }
+            if (report) {
+              const uint32_t code = qcode | ((vhi & 7u) << 3) | (((uint32_t)v >> (SEED_TAB_SLOT_SHIFT - 1)) & 6u);
+              const int32_t unit = seed_block_unit(ptab, n_qry, code);
+              if (unit >= 0)
+                seed_stage_hit(stage, stage_n, wave, Match{(int32_t)((uint32_t)v & SEED_TAB_POS_MASK), q, left, unit}, buf, cap, total, hit_count);
+            }
+          }
+          slot_b = (slot_b + 8u) & byte_mask;
+          v = *reinterpret_cast<const unsigned long long*>(tab_b + slot_b);
+        }
+      }
+      seed_stage_flush(stage, stage_n, wave, lane, false, buf, cap, total, hit_count);
+    };
+    // software-pipelined: the loads of the next SEED_UNROLL rows are in flight while these are looked up
+    unsigned long long qa[SEED_UNROLL], qb[SEED_UNROLL];
+    uint32_t sa[SEED_UNROLL], sb[SEED_UNROLL];
+    constexpr uint32_t STEP = 64u * SEED_UNROLL;
+    if (T) load(0, qa, sa);
+    for (uint32_t E = 0; E < T; E += 2 * STEP) {
+      if (E + STEP < T) load(E + STEP, qb, sb);
+      process(qa, sa);
+      if (E + STEP >= T) break;
+      if (E + 2 * STEP < T) load(E + 2 * STEP, qa, sa);
+      process(qb, sb);
+    }
+  }
+  seed_stage_flush(stage, stage_n, wave, lane, true, buf, cap, total, hit_count);   // what is still staged (uniform point)
 }
 
 // hoff[0..n] = exclusive prefix of cnt[0..n); cursor[] zeroed.  One workgroup (n <= 2 * pairs of a launch).
