@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the hot path: genome-pairs/s for the ANIm N x N grid (BASELINE.json configs[3] = SURVEY.md
 §8(d) set C4: 1000 synthetic ~5 Mb genomes, 999 000 ordered pairs), the largest configuration that fits one MI355X and the
-one the north-star target is quoted on; with the kernel roofline, the CPU baseline timed on this box's host cores, and the
-C2 TETRA roofline nested as a sub-record.
+one the north-star target is quoted on.  `--full` adds the kernel roofline, the CPU baseline timed on the host's cores, the side
+records, the C2 TETRA roofline nested as a sub-record and the line's checks against committed references.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -24,8 +24,10 @@ whatever N is (strong scaling of that step).
   --workload anib  : C5 (BASELINE.json configs[4]): 500 genomes of 1-12 Mb, pyani's ANIb on the engine's fragment mode
                      (1020-nt fragments against every other genome); steps of 10 fragmented genomes x 499 subjects.
 
-Rank 0 prints ONE JSON line.  `--dump-outputs DIR` also writes what the last timed step returned as DIR/<name>.npy (float64, at most
-64 MB), so that two builds can be compared output for output: the inputs are a fixed function of the arguments.
+A plain run sets up, warms up, times the K steps and prints the line; everything else it could measure or check runs only
+with `--full`, after the timed steps.  Rank 0 prints ONE JSON line.  `--dump-outputs DIR` also writes what the last timed step
+returned as DIR/<name>.npy (float64, at most 64 MB), so that two builds can be compared output for output: the inputs are a
+fixed function of the arguments.
 """
 import argparse
 import hashlib
@@ -76,14 +78,22 @@ def parse_args():
                     "step (56 957 vs 58 657 pairs/s, profiles/r06_pipeline_vs_blocking.txt) — the two calls in flight halve each other's launches, and a step this large "
                     "already overlaps its tails across its own two workers; it pays for family-sized calls (related_only.pipelined_calls)")
     ap.add_argument("--expect-sha", default="auto", help="anim: sha1 the whole N x N result grid must have (checked whenever the timed steps cover the grid): "
-                    "'auto' = the committed hash of the default C4 job (tests/golden/anim_c4_grid_sha1.txt) when the job IS the default C4 job, 'none' = no check; "
+                    "'auto' = the committed hash of the default C4 job (tests/golden/anim_c4_grid_sha1.txt) when the job IS the default C4 job and the run "
+                    "is --full, 'none' = no check; "
                     "a mismatch fails the run loudly (exit code 3) after the line is printed")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (anim / anib: its pair records, tetra: Z and the "
                          "Pearson matrix) as DIR/<name>.npy in float64, at most 64 MB in all (a fixed seeded sample of the records beyond that)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure, after the timed steps: the CPU baselines, the "
+                         "anim roofline pass over every tile, the side records (related_only / unrelated_only / sketch_mode, N > 1: the "
+                         "strong-step series), the nested C2 TETRA record, the grid-hash check (--expect-sha) and the independent-oracle "
+                         "cells.  Off: set-up, warm-up, the timed steps, --dump-outputs and the line (with the grid's hash, unchecked)")
     args = ap.parse_args()
     if args.dump_outputs and args.cold_e2e:
         ap.error("--dump-outputs covers the step loop, not --cold-e2e")
+    if not args.full:      # a plain run: the headline figure alone (the --no-* switches trim a --full run)
+        args.no_cpu_baseline = args.no_tetra = args.no_side_records = True
     w = args.workload
     if args.steps is None:
         args.steps = {"anim": 10, "tetra": 50, "anib": 3}[w]
@@ -418,6 +428,101 @@ def _pmc_profile():
     return json.loads(f.read_text()) if f.exists() else {}
 
 
+def anim_roofline(tile_recs, lens, P, elapsed):
+    """--full: the `roofline` record of the anim line, from the one-worker pass (tile_recs: the HIP-event times of the stages and the
+    engine counters of each tile it ran) and the pairs of the timed steps (P, [M, 2] (reference, query)) over their wall time."""
+    prof_pairs = np.concatenate([t_["pairs"] for t_ in tile_recs])
+    prof_s = sum(t_["seconds"] for t_ in tile_recs)
+    prof = {name: (sum(t_["prof"][name][0] for t_ in tile_recs), sum(t_["prof"][name][1] for t_ in tile_recs)) for name in tile_recs[0]["prof"]}
+    ext_ms = sum(t_["ext_ms"] for t_ in tile_recs)
+    cnt = np.sum([t_["cnt"] for t_ in tile_recs], axis=0)
+    # byte roofline (SURVEY.md §8(d)) of the dominant stage of the one-worker step
+    alg_prof = float(((lens[prof_pairs[:, 0]] + 3) // 4 + (lens[prof_pairs[:, 1]] + 3) // 4 + 32).sum())
+    alg_bytes = float(((lens[P[:, 0]] + 3) // 4 + (lens[P[:, 1]] + 3) // 4 + 32).sum())
+    dom = max(prof, key=lambda name: prof[name][0])
+    dom_ms, dom_n = prof[dom]
+    achieved = alg_prof / (dom_ms * 1e-3) / 1e9 if dom_ms else 0.0
+    pmc = _pmc_profile()
+    traffic = pmc.get(dom, {}).get("hbm_bytes_per_launch")
+    # per tile: the dominant stage's time and byte rate (the tiles differ ~2 x in DP cells: the extremes are printed, `achieved` is the
+    # mean over all of them = total algorithmic bytes / total time of that stage)
+    def _alg(pp):
+        return float(((lens[pp[:, 0]] + 3) // 4 + (lens[pp[:, 1]] + 3) // 4 + 32).sum())
+    per_tile = [{"tile": t_["tile"], "pairs": int(len(t_["pairs"])), "ms": round(t_["prof"][dom][0], 3),
+                 "GBps": round(_alg(t_["pairs"]) / (t_["prof"][dom][0] * 1e-3) / 1e9, 2) if t_["prof"][dom][0] else None,
+                 "dp_cells": int(t_["cnt"][2]) + int(t_["cnt"][5]) + int(t_["cnt"][8]), "kernel_ms_sum": round(sum(v[0] for v in t_["prof"].values()), 1),
+                 "stage_ms": {name_: round(v[0], 1) for name_, v in t_["prof"].items()}}
+                for t_ in tile_recs]
+    # VALU-issue roofline of the extension stage (integer DP in registers: bytes are not its bound): DP cells per second against the
+    # rate at which the chip can issue the vector instructions those cells cost.  MEASURED IN THIS RUN: cells, anti-diagonals and calls
+    # per kernel class (the engines' own counters, pg_anim_counters) and the stages' HIP-event times of the roofline pass.
+    # FROM THE COMMITTED PROFILE (profiles/pmc_anim.json: a rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU pass of the same command on
+    # MI355X, tools/summarize_round_profiles.py): instructions per cell, per kernel class and for the stage as a whole.
+    cells = int(cnt[2]) + int(cnt[5]) + int(cnt[8])
+    vpc, spc = pmc.get("extension_valu_per_cell"), pmc.get("extension_salu_per_cell")
+    kclass = [("gaps", "anim_postnuc_gap_kernels", 128), ("forward", "anim_postnuc_fwd_kernel", 128), ("backward_ahead", "anim_postnuc_rehearse_kernel+anim_postnuc_bwd_kernel", 128),
+              ("walks", "anim_postnuc_kernel", 128), ("forced_narrow", "anim_postnuc_forced_kernels", None), ("forced_512_1024", "anim_postnuc_forced_kernels", None),
+              ("forced_2048", "anim_postnuc_forced_kernels", None), ("forced_group", "anim_postnuc_forced_kernels", None)]
+    per_kernel = {}
+    for kc, (kname, stage_name, slots) in enumerate(kclass):
+        calls, steps_k, cells_k = (int(cnt[32 + 4 * kc + j]) for j in range(3))
+        if not calls:
+            continue
+        rec = {"calls": calls, "anti_diagonals": steps_k, "cells": cells_k, "stage": stage_name, "stage_ms": round(prof.get(stage_name, (0.0, 0))[0], 3)}
+        if slots:      # a trimmed search runs on the 256-diagonal window: 64 lanes x 2 cell slots per anti-diagonal
+            rec["live_slot_fraction"] = round(cells_k / (steps_k * float(slots)), 4) if steps_k else None
+        ipc_k = (pmc.get("valu_per_cell_by_class") or {}).get(kname)
+        if ipc_k:
+            rec["valu_instructions_per_cell"] = ipc_k
+        per_kernel[kname] = rec
+    # instructions per CU and cycle of a stage = its cells (this run) x instructions per cell (committed profile) / its event time (this run)
+    for stage_name in {r_["stage"] for r_ in per_kernel.values()}:
+        ks = [r_ for r_ in per_kernel.values() if r_["stage"] == stage_name and r_.get("valu_instructions_per_cell")]
+        ms_ = prof.get(stage_name, (0.0, 0))[0]
+        if ks and ms_ and len(ks) == sum(1 for r_ in per_kernel.values() if r_["stage"] == stage_name):
+            instr = sum(r_["cells"] * r_["valu_instructions_per_cell"] for r_ in ks)
+            for r_ in ks:
+                r_["stage_valu_per_cu_cycle"] = round(instr / 256.0 / (ms_ * 1e-3 * CLOCK_GHZ * 1e9), 3)
+    valu = None
+    if vpc and ext_ms:
+        # a CU issues one wave64 VALU instruction per cycle (4 SIMDs x 1 per 4 cycles) and one scalar instruction per cycle (ONE scalar
+        # unit per CU): the step loop of the engines spends about as many scalar as vector instructions, so whichever is larger binds
+        ipc = max(vpc, spc or 0.0)
+        peak_cells = SIMDS * CLOCK_GHZ * 1e9 / 4.0 / ipc
+        valu = {"bound": "valu-issue" if ipc == vpc else "salu-issue",
+                "kernels": "anim_postnuc_{gaplane,gapbig,fwd,rehearse,bwd,(walk),forced,forced_wide,forced_huge}_kernel",
+                "achieved": cells / (ext_ms * 1e-3), "peak": peak_cells, "unit": "DP cells/s", "frac": cells / (ext_ms * 1e-3) / peak_cells,
+                "cells": cells, "anti_diagonals": int(cnt[1]), "extension_ms": ext_ms, "valu_instructions_per_cell": vpc,
+                "salu_instructions_per_cell": spc, "instructions_per_cell_replayed": True,
+                "measured_in_this_run": "cells, anti_diagonals, extension_ms, per_kernel.{calls, anti_diagonals, cells, stage_ms, live_slot_fraction} (engine counters + HIP events of the one-worker pass over all tiles)",
+                "from_committed_profile": f"valu / salu instructions per cell, per_kernel.valu_instructions_per_cell ({pmc.get('extension_valu_source', 'profiles/pmc_anim.json')})",
+                "per_kernel": per_kernel,
+                "peak_definition": f"256 CUs x {CLOCK_GHZ} GHz x 1 wave64 VALU instruction per cycle ({SIMDS} SIMDs, 4 cycles each) or 1 scalar "
+                                   f"instruction per cycle (one scalar unit per CU) / instructions per cell of the binding kind"}
+    return {
+        "bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_replayed": True,
+        "traffic_source": "profiles/pmc_anim.json: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command (counters cannot be read inside a timed run); replayed, not measured in this run",
+        "algorithmic_bytes_per_launch": alg_prof / max(dom_n, 1), "avg_launch_ms": dom_ms / max(dom_n, 1),
+        "launches": int(dom_n),
+        "definition": "SURVEY.md §8(d): ceil(Lq/4) + ceil(Ls/4) + 32 B per ordered pair, summed over an untimed pass of EVERY tile of the grid "
+                      "run with a single worker (stage events un-overlapped; rank 0's share of two tiles at N > 1) / the summed HIP-event "
+                      "time of the stage that took longest in it; per_tile has each tile, tile_min / tile_max the extremes",
+        "tiles": len(tile_recs), "per_tile": per_tile,
+        "tile_min_GBps": min((t_["GBps"] for t_ in per_tile if t_["GBps"]), default=None),
+        "tile_max_GBps": max((t_["GBps"] for t_ in per_tile if t_["GBps"]), default=None),
+        "one_worker_step": {"pairs": int(len(prof_pairs)), "seconds": prof_s, "tiles": len(tile_recs),
+                            "stage_ms": {name: round(ms, 3) for name, (ms, _) in prof.items()},
+                            "stage_launches": {name: int(c) for name, (_, c) in prof.items()},
+                            "note": "seconds = wall time of the call, which includes growing the single worker's scratch to the whole "
+                                    "launch budget (it held half of it while two workers ran) and the event synchronisations; the "
+                                    "kernels' own time is the sum of stage_ms"},
+        "pipeline_achieved": alg_bytes / elapsed / 1e9, "pipeline_frac": alg_bytes / elapsed / 1e9 / HBM_PEAK_GBS,
+        "timed_region_ms": round(elapsed * 1e3, 3),
+        "valu_issue": valu,
+    }
+
+
 def run_anim_cold(args, local):
     """ONE cold end-to-end run, one wall clock: FASTA files on disk -> pg_add_fasta_batch (read + parse +
     2-bit pack on the host threads) -> upload -> the whole N x N grid (seed lists built on first use) in steps of R rows ->
@@ -638,39 +743,35 @@ def run_anim(args, rank, world, local, dist, torch):
     # ---- the roofline pass (untimed): ONE worker, so that the stages' HIP events are not timing the other worker's persistent waves
     # (two streams made `anim_finish_kernel` look 379 ms long), over EVERY tile of the grid (one tile is
     # not representative — the ten tiles of C4 hold 1.1 ... 2.5 x 10^12 DP cells), engine counters read around each.  At N > 1 each
-    # rank runs its static share of two tiles; rank 0 reports its own.
+    # rank runs its static share of two tiles; rank 0 reports its own.  --full only.
     k_prof = args.warmup + args.steps
-    n_tiles = max(1, n // R)
-    prof_tiles = list(range(n_tiles)) if world == 1 else [k_prof % n_tiles, (k_prof + 1) % n_tiles]
-    if args.roofline_tiles:
-        prof_tiles = prof_tiles[:args.roofline_tiles]
-    eng.anim_set_workers(1)
-    eng.profile_config(kernel_mask=sum(1 << s_ for s_ in stages), every_n=1)
     tile_recs = []
-    for tno in prof_tiles:
-        pp = parallel.anim_pair_array(n, parallel.anim_row_shard(rows_of(tno), rank, world), symmetric=True)
-        eng.anim_counters(reset=True)
-        eng.profile_reset()
-        eng.profile_enable(True)
-        t1 = time.perf_counter()
-        compute(pp)
-        eng.sync()
-        dt = time.perf_counter() - t1
-        eng.profile_enable(False)
-        tile_recs.append({"tile": tno, "pairs": pp, "seconds": dt, "prof": {eng.kernel_name(s_): eng.profile_get(s_) for s_ in stages},
-                          "ext_ms": sum(eng.profile_get(s_)[0] for s_ in ext_stages), "cnt": eng.anim_counters()})
-    prof_pairs = np.concatenate([t_["pairs"] for t_ in tile_recs])
-    prof_s = sum(t_["seconds"] for t_ in tile_recs)
-    prof = {name: (sum(t_["prof"][name][0] for t_ in tile_recs), sum(t_["prof"][name][1] for t_ in tile_recs)) for name in tile_recs[0]["prof"]}
-    ext_ms = sum(t_["ext_ms"] for t_ in tile_recs)
-    cnt = np.sum([t_["cnt"] for t_ in tile_recs], axis=0)
-    eng.anim_set_workers(2)
-    fence()
+    if args.full:
+        n_tiles = max(1, n // R)
+        prof_tiles = list(range(n_tiles)) if world == 1 else [k_prof % n_tiles, (k_prof + 1) % n_tiles]
+        if args.roofline_tiles:
+            prof_tiles = prof_tiles[:args.roofline_tiles]
+        eng.anim_set_workers(1)
+        eng.profile_config(kernel_mask=sum(1 << s_ for s_ in stages), every_n=1)
+        for tno in prof_tiles:
+            pp = parallel.anim_pair_array(n, parallel.anim_row_shard(rows_of(tno), rank, world), symmetric=True)
+            eng.anim_counters(reset=True)
+            eng.profile_reset()
+            eng.profile_enable(True)
+            t1 = time.perf_counter()
+            compute(pp)
+            eng.sync()
+            dt = time.perf_counter() - t1
+            eng.profile_enable(False)
+            tile_recs.append({"tile": tno, "pairs": pp, "seconds": dt, "prof": {eng.kernel_name(s_): eng.profile_get(s_) for s_ in stages},
+                              "ext_ms": sum(eng.profile_get(s_)[0] for s_ in ext_stages), "cnt": eng.anim_counters()})
+        eng.anim_set_workers(2)
+        fence()
 
     # ---- N > 1: the same tile size as N = 1's step, dealt over all ranks (strong scaling of ONE step: launches shrink with N)
     strong = None
     bare = args.no_side_records or (args.no_cpu_baseline and not args.side_records)      # (tests and profiling runs: the step loop and the roofline step only)
-    if dist is not None and (not bare or REHEARSAL):
+    if dist is not None and args.full and (not bare or REHEARSAL):
         r1 = max(1, n // 10)
         step(k_prof + 1, rows=rows_of(k_prof + 1, r1), key="strong_warm")
         fence()
@@ -702,69 +803,6 @@ def run_anim(args, rank, world, local, dist, torch):
         ok_rel = int(((status == 0) & related_m).sum())
         unrel_aln = int(((status == 0) & ~related_m).sum())
         step_s = elapsed / args.steps
-        # byte roofline of the dominant stage of the one-worker step
-        alg_prof = float(((lens[prof_pairs[:, 0]] + 3) // 4 + (lens[prof_pairs[:, 1]] + 3) // 4 + 32).sum())
-        alg_bytes = float(((lens[P[:, 0]] + 3) // 4 + (lens[P[:, 1]] + 3) // 4 + 32).sum())
-        dom = max(prof, key=lambda name: prof[name][0])
-        dom_ms, dom_n = prof[dom]
-        achieved = alg_prof / (dom_ms * 1e-3) / 1e9 if dom_ms else 0.0
-        pmc = _pmc_profile()
-        traffic = pmc.get(dom, {}).get("hbm_bytes_per_launch")
-        # per tile: the dominant stage's time and byte rate (the tiles differ ~2 x in DP cells: the extremes are printed, `achieved` is the
-        # mean over all of them = total algorithmic bytes / total time of that stage)
-        def _alg(pp):
-            return float(((lens[pp[:, 0]] + 3) // 4 + (lens[pp[:, 1]] + 3) // 4 + 32).sum())
-        per_tile = [{"tile": t_["tile"], "pairs": int(len(t_["pairs"])), "ms": round(t_["prof"][dom][0], 3),
-                     "GBps": round(_alg(t_["pairs"]) / (t_["prof"][dom][0] * 1e-3) / 1e9, 2) if t_["prof"][dom][0] else None,
-                     "dp_cells": int(t_["cnt"][2]) + int(t_["cnt"][5]) + int(t_["cnt"][8]), "kernel_ms_sum": round(sum(v[0] for v in t_["prof"].values()), 1),
-                     "stage_ms": {name_: round(v[0], 1) for name_, v in t_["prof"].items()}}
-                    for t_ in tile_recs]
-        # VALU-issue roofline of the extension stage (integer DP in registers: bytes are not its bound): DP cells per second against the
-        # rate at which the chip can issue the vector instructions those cells cost.  MEASURED IN THIS RUN: cells, anti-diagonals and calls
-        # per kernel class (the engines' own counters, pg_anim_counters) and the stages' HIP-event times of the roofline pass above.
-        # FROM THE COMMITTED PROFILE (profiles/pmc_anim.json: a rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU pass of the same command on
-        # MI355X, tools/summarize_round_profiles.py): instructions per cell, per kernel class and for the stage as a whole.
-        cells = int(cnt[2]) + int(cnt[5]) + int(cnt[8])
-        vpc, spc = pmc.get("extension_valu_per_cell"), pmc.get("extension_salu_per_cell")
-        kclass = [("gaps", "anim_postnuc_gap_kernels", 128), ("forward", "anim_postnuc_fwd_kernel", 128), ("backward_ahead", "anim_postnuc_rehearse_kernel+anim_postnuc_bwd_kernel", 128),
-                  ("walks", "anim_postnuc_kernel", 128), ("forced_narrow", "anim_postnuc_forced_kernels", None), ("forced_512_1024", "anim_postnuc_forced_kernels", None),
-                  ("forced_2048", "anim_postnuc_forced_kernels", None), ("forced_group", "anim_postnuc_forced_kernels", None)]
-        per_kernel = {}
-        for kc, (kname, stage_name, slots) in enumerate(kclass):
-            calls, steps_k, cells_k = (int(cnt[32 + 4 * kc + j]) for j in range(3))
-            if not calls:
-                continue
-            rec = {"calls": calls, "anti_diagonals": steps_k, "cells": cells_k, "stage": stage_name, "stage_ms": round(prof.get(stage_name, (0.0, 0))[0], 3)}
-            if slots:      # a trimmed search runs on the 256-diagonal window: 64 lanes x 2 cell slots per anti-diagonal
-                rec["live_slot_fraction"] = round(cells_k / (steps_k * float(slots)), 4) if steps_k else None
-            ipc_k = (pmc.get("valu_per_cell_by_class") or {}).get(kname)
-            if ipc_k:
-                rec["valu_instructions_per_cell"] = ipc_k
-            per_kernel[kname] = rec
-        # instructions per CU and cycle of a stage = its cells (this run) x instructions per cell (committed profile) / its event time (this run)
-        for stage_name in {r_["stage"] for r_ in per_kernel.values()}:
-            ks = [r_ for r_ in per_kernel.values() if r_["stage"] == stage_name and r_.get("valu_instructions_per_cell")]
-            ms_ = prof.get(stage_name, (0.0, 0))[0]
-            if ks and ms_ and len(ks) == sum(1 for r_ in per_kernel.values() if r_["stage"] == stage_name):
-                instr = sum(r_["cells"] * r_["valu_instructions_per_cell"] for r_ in ks)
-                for r_ in ks:
-                    r_["stage_valu_per_cu_cycle"] = round(instr / 256.0 / (ms_ * 1e-3 * CLOCK_GHZ * 1e9), 3)
-        valu = None
-        if vpc and ext_ms:
-            # a CU issues one wave64 VALU instruction per cycle (4 SIMDs x 1 per 4 cycles) and one scalar instruction per cycle (ONE scalar
-            # unit per CU): the step loop of the engines spends about as many scalar as vector instructions, so whichever is larger binds
-            ipc = max(vpc, spc or 0.0)
-            peak_cells = SIMDS * CLOCK_GHZ * 1e9 / 4.0 / ipc
-            valu = {"bound": "valu-issue" if ipc == vpc else "salu-issue",
-                    "kernels": "anim_postnuc_{gaplane,gapbig,fwd,rehearse,bwd,(walk),forced,forced_wide,forced_huge}_kernel",
-                    "achieved": cells / (ext_ms * 1e-3), "peak": peak_cells, "unit": "DP cells/s", "frac": cells / (ext_ms * 1e-3) / peak_cells,
-                    "cells": cells, "anti_diagonals": int(cnt[1]), "extension_ms": ext_ms, "valu_instructions_per_cell": vpc,
-                    "salu_instructions_per_cell": spc, "instructions_per_cell_replayed": True,
-                    "measured_in_this_run": "cells, anti_diagonals, extension_ms, per_kernel.{calls, anti_diagonals, cells, stage_ms, live_slot_fraction} (engine counters + HIP events of the one-worker pass over all tiles)",
-                    "from_committed_profile": f"valu / salu instructions per cell, per_kernel.valu_instructions_per_cell ({pmc.get('extension_valu_source', 'profiles/pmc_anim.json')})",
-                    "per_kernel": per_kernel,
-                    "peak_definition": f"256 CUs x {CLOCK_GHZ} GHz x 1 wave64 VALU instruction per cycle ({SIMDS} SIMDs, 4 cycles each) or 1 scalar "
-                                       f"instruction per cycle (one scalar unit per CU) / instructions per cell of the binding kind"}
         # hash of one whole N x N result grid (the last occurrence of every cell among the timed steps), if the steps cover it
         dense = np.zeros((n, n, g.shape[1]), dtype=np.int64)
         covered = np.zeros((n, n), dtype=bool)
@@ -775,9 +813,10 @@ def run_anim(args, rank, world, local, dist, torch):
         # ---- the line checks itself: (1) the cells of the grid just computed that are ALSO pairs of the committed goldens of
         # the INDEPENDENT oracle (tests/golden/anim_oracle_family_digests.json.gz: two whole C4 families = 1 200 ordered pairs, made by
         # oracle/nucmer_oracle.cpp + oracle/anim_oracle.py, which share no header with the engine) must hold the oracle's tuple bit for bit;
-        # (2) the whole-grid hash must be the committed one.  Both only read committed DATA (no oracle code runs here).
+        # (2) the whole-grid hash must be the committed one.  Both only read committed DATA (no oracle code runs here).  --full only, but
+        # for an explicit --expect-sha.
         parity_indep, sha_check = None, None
-        if not REHEARSAL:
+        if not REHEARSAL and args.full:
             try:
                 import gzip
                 with gzip.open(ROOT / "tests" / "golden" / "anim_oracle_family_digests.json.gz", "rt") as fh:
@@ -800,11 +839,12 @@ def run_anim(args, rank, world, local, dist, torch):
                                             "independent oracle (oracle/nucmer_oracle.cpp + oracle/anim_oracle.py; tools/make_anim_family_hashes.py)"}
             except Exception as exc:  # noqa: BLE001
                 parity_indep = {"error": repr(exc)}
+        if not REHEARSAL:
             want_sha = args.expect_sha
             if want_sha == "auto":
                 f_ = ROOT / "tests" / "golden" / "anim_c4_grid_sha1.txt"
                 default_job = (n, args.length, args.seed) == (1000, 5_000_000, 20250301)
-                want_sha = f_.read_text().split()[0] if (default_job and f_.exists()) else "none"
+                want_sha = f_.read_text().split()[0] if (args.full and default_job and f_.exists()) else "none"
             if want_sha != "none" and sha is not None:
                 sha_check = {"expected": want_sha, "ok": sha == want_sha}
         measured_cold = None       # (never replayed: `bench.py --cold-e2e` measures it; profiles/ holds the last measurement)
@@ -856,28 +896,7 @@ def run_anim(args, rank, world, local, dist, torch):
                 "note_related_pairs_per_s": "related pairs timed / the same wall time (unrelated pairs of the tile included): a lower "
                                             "bound of the related-only rate; 97.6 % of C4's pairs are unrelated by construction",
             },
-            "roofline": {
-                "bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_replayed": True,
-                "traffic_source": "profiles/pmc_anim.json: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command (counters cannot be read inside a timed run); replayed, not measured in this run",
-                "algorithmic_bytes_per_launch": alg_prof / max(dom_n, 1), "avg_launch_ms": dom_ms / max(dom_n, 1),
-                "launches": int(dom_n),
-                "definition": "SURVEY.md §8(d): ceil(Lq/4) + ceil(Ls/4) + 32 B per ordered pair, summed over an untimed pass of EVERY tile of the grid "
-                              "run with a single worker (stage events un-overlapped; rank 0's share of two tiles at N > 1) / the summed HIP-event "
-                              "time of the stage that took longest in it; per_tile has each tile, tile_min / tile_max the extremes",
-                "tiles": len(tile_recs), "per_tile": per_tile,
-                "tile_min_GBps": min((t_["GBps"] for t_ in per_tile if t_["GBps"]), default=None),
-                "tile_max_GBps": max((t_["GBps"] for t_ in per_tile if t_["GBps"]), default=None),
-                "one_worker_step": {"pairs": int(len(prof_pairs)), "seconds": prof_s, "tiles": len(tile_recs),
-                                    "stage_ms": {name: round(ms, 3) for name, (ms, _) in prof.items()},
-                                    "stage_launches": {name: int(c) for name, (_, c) in prof.items()},
-                                    "note": "seconds = wall time of the call, which includes growing the single worker's scratch to the whole "
-                                            "launch budget (it held half of it while two workers ran) and the event synchronisations; the "
-                                            "kernels' own time is the sum of stage_ms"},
-                "pipeline_achieved": alg_bytes / elapsed / 1e9, "pipeline_frac": alg_bytes / elapsed / 1e9 / HBM_PEAK_GBS,
-                "timed_region_ms": round(elapsed * 1e3, 3),
-                "valu_issue": valu,
-            },
+            "roofline": anim_roofline(tile_recs, lens, P, elapsed) if tile_recs else None,
         }
         if world == 1 and not args.no_cpu_baseline:
             def gpu_lookup(q, s_):

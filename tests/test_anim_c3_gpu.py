@@ -61,10 +61,11 @@ def test_c3_family_equals_cpu_statement_and_properties():
     assert ok >= 0.97 * n_rel
 
 
-def _bench(extra_env, nproc, tmp_path, tag, args=None):
+def _bench(extra_env, nproc, tmp_path, tag, args=None, full=False):
     env = dict(os.environ, **extra_env)
     args = args or ["--genomes", "24", "--length", "300000", "--seed", "11", "--rows-per-step", "8", "--steps", "3", "--warmup", "0",
                     "--no-cpu-baseline", "--no-tetra"]
+    args = args + ["--full"] if full else args
     if nproc == 1:
         cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1"] + args
     else:
@@ -117,8 +118,8 @@ def test_enqueued_calls_overlap_and_equal_the_blocking_call():
 def test_bench_two_ranks_on_one_gpu_equal_single_rank(tmp_path):
     """bench.py's N > 1 path (rows dealt over the ranks, Engine per rank, one all-gather per step) on hardware: two ranks
     sharing GPU 0 over gloo (PYANI_BENCH_DEBUG_ONE_GPU) give the same full-grid result hash as one rank."""
-    one = _bench({}, 1, tmp_path, "one")
-    two = _bench({"PYANI_BENCH_DEBUG_ONE_GPU": "1"}, 2, tmp_path, "two")
+    one = _bench({}, 1, tmp_path, "one", full=True)
+    two = _bench({"PYANI_BENCH_DEBUG_ONE_GPU": "1"}, 2, tmp_path, "two", full=True)
     assert one["config"]["results_sha1_full_grid"] and one["config"]["results_sha1_full_grid"] == two["config"]["results_sha1_full_grid"]
     assert two["n_gpus"] == 2 and two["scaling"] == "strong" and one["config"]["pairs_timed"] == two["config"]["pairs_timed"] == 24 * 23
     assert one["config"]["related_pairs_with_alignment"] == two["config"]["related_pairs_with_alignment"] > 0

@@ -240,7 +240,7 @@ def test_eight_rank_dress_rehearsal_of_the_bench_control_flow():
     # hour of each other — eight sleeping ranks plus a 64 MB gloo all-gather per step on eight cores measure the box, not the deal; what the
     # ratio would show on hardware is in profiles/r05_deal_probe.json and, when an 8-GPU node is available, in the driver's SCALE record)
     assert default["value"] > 0
-    eight = _rehearsal(8, ["--steps", "2", "--warmup", "1", "--dynamic-deal"], slow)
+    eight = _rehearsal(8, ["--steps", "2", "--warmup", "1", "--dynamic-deal", "--full"], slow)      # (--full: the strong-step series)
     assert one["n_gpus"] == 1 and eight["n_gpus"] == 8 and eight["scaling"] == "weak" and "REHEARSAL" in eight["data"]
     assert one["config"]["results_sha1_full_grid"] and one["config"]["results_sha1_full_grid"] == eight["config"]["results_sha1_full_grid"]
     assert eight["config"]["rows_per_step"] == 800 and eight["series"]["weak"]["rows_per_step_per_gpu"] == 100

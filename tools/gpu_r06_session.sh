@@ -10,7 +10,7 @@
 #   tetra    rocprofv3 of the TETRA workload at HEAD (kernel trace + FETCH/WRITE)     anib   C5 bench + kernel trace + SQ pass
 R=$(pwd); O=$R/gpurun_out/r06; mkdir -p $O; export TMPDIR=/tmp
 export PYANI_DEV_KNOBS=1
-B1="python $R/bench.py --gpus 1 --steps 1 --warmup 1 --no-cpu-baseline --no-tetra --no-side-records"      # (+ the one-worker roofline pass over all ten tiles: 12 launches per kernel)
+B1="python $R/bench.py --gpus 1 --steps 1 --warmup 1 --full --no-cpu-baseline --no-tetra --no-side-records"      # (+ the one-worker roofline pass over all ten tiles: 12 launches per kernel)
 for w in "$@"; do
 case $w in
 tests)
@@ -45,7 +45,7 @@ stats4)
   PYANI_PN_STATS=1 PYANI_ANIM_WORKERS=1 timeout -k 10 600 $B1 > $O/bench_c4_stats.log 2> $O/bench_c4_stats.err; echo "stats4 rc=$?"
   grep '^{' $O/bench_c4_stats.log | cut -c1-1500; grep "pn-stats" $O/bench_c4_stats.err | tail -16 ;;
 grid)    # one whole grid timed (10 steps), no CPU leg: the quick comparison with the driver's value
-  timeout -k 10 900 python bench.py --gpus 1 --steps 10 --warmup 2 --no-tetra --no-cpu-baseline --no-side-records > $O/bench_grid.log 2> $O/bench_grid.err; echo "grid rc=$?"
+  timeout -k 10 900 python bench.py --gpus 1 --steps 10 --warmup 2 --full --no-tetra --no-cpu-baseline --no-side-records > $O/bench_grid.log 2> $O/bench_grid.err; echo "grid rc=$?"
   grep '^{' $O/bench_grid.log > $O/bench_grid.json; python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r06/bench_grid.json").read())
@@ -61,7 +61,7 @@ for k, x in (v or {}).get("per_kernel", {}).items():
 PY
   ;;
 c4)
-  timeout -k 10 900 python bench.py --gpus 1 --steps 4 --warmup 1 --no-tetra --no-cpu-baseline > $O/bench_c4.log 2> $O/bench_c4.err; echo "c4 rc=$?"
+  timeout -k 10 900 python bench.py --gpus 1 --steps 4 --warmup 1 --full --no-tetra --no-cpu-baseline > $O/bench_c4.log 2> $O/bench_c4.err; echo "c4 rc=$?"
   grep '^{' $O/bench_c4.log > $O/bench_c4.json; cut -c1-2500 $O/bench_c4.json; tail -5 $O/bench_c4.err ;;
 bench)
   timeout 1500 python bench.py --gpus 1 --steps ${BENCH_STEPS:-20} --warmup ${BENCH_WARMUP:-5} > $O/bench_n1.log 2> $O/bench_n1.err; echo "bench rc=$?"
@@ -77,7 +77,7 @@ tetra)
   f=$(find $O/tetra_kt -name "*kernel_stats.csv" | head -1); cp $f $O/tetra_kernel_stats.csv; head -8 $f | cut -c1-200
   for d in tetra_fetch tetra_write tetra_sq; do python tools/summarize_pmc.py $O/$d $O/${d}_summary.csv 2>&1 | tail -6; done ;;
 anib)    # C5 fragment mode at HEAD: the bench record, a kernel trace and one SQ pass of its steps
-  timeout 900 python bench.py --gpus 1 --workload anib > $O/bench_anib.log 2> $O/bench_anib.err; echo "anib rc=$?"
+  timeout 900 python bench.py --gpus 1 --workload anib --full > $O/bench_anib.log 2> $O/bench_anib.err; echo "anib rc=$?"
   grep '^{' $O/bench_anib.log > $O/bench_anib_C5_n1.json; cut -c1-1500 $O/bench_anib_C5_n1.json
   cd /tmp; rm -rf $O/anib_kt $O/anib_sq
   A="python $R/bench.py --gpus 1 --workload anib --steps 1 --warmup 1 --no-cpu-baseline"

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """gpurun_out/<round> (scratch; default r06) -> profiles/ (tracked): the rocprofv3 summaries of `bench.py --gpus 1 --steps 1 --warmup 1
---no-cpu-baseline --no-tetra` (C4, one step = a tenth of the grid) that bench.py's roofline block reads.
+--full --no-cpu-baseline --no-tetra` (C4, one step = a tenth of the grid) that bench.py's roofline block reads.
 
   profiles/<round>_anim_C4_rocprofv3_kernel_stats_one_worker.csv / ..._two_workers.csv   --kernel-trace --stats
   profiles/<round>_anim_C4_pmc_fetch_summary.csv / _write_summary.csv / _sq_summary.csv     --pmc passes (one worker), per kernel
@@ -52,7 +52,7 @@ if (SRC / "sq_summary.csv").exists():
     shutil.copyfile(SRC / "sq_summary.csv", DST / f"{RND}_anim_C4_pmc_sq_summary.csv")
 fetch, write, sq = rows(SRC / "pmc_fetch_summary.csv"), rows(SRC / "pmc_write_summary.csv"), rows(SRC / "sq_summary.csv")
 out = {"round": RND,
-       "command": "python bench.py --gpus 1 --steps 1 --warmup 1 --no-cpu-baseline --no-tetra under rocprofv3 --pmc <counter> with PYANI_ANIM_WORKERS=1 "
+       "command": "python bench.py --gpus 1 --steps 1 --warmup 1 --full --no-cpu-baseline --no-tetra under rocprofv3 --pmc <counter> with PYANI_ANIM_WORKERS=1 "
                   "(C4, a step = a tenth of the grid: 99 900 ordered pairs; 12 launches per kernel: the warm-up step, the timed one and the one-worker roofline pass over all ten tiles)",
        "correction": "FETCH_SIZE doubled (gfx950 rocprofv3 tallies 128-B read requests at 64 B, MI355X_MICROARCH.md §HBM; exact for wide coalesced streams, "
                      "an upper bound for narrower accesses); WRITE_SIZE as reported (uncalibrated)"}
