@@ -270,6 +270,35 @@ typedef struct {
 int pg_sketch_pairs(pg_ctx* ctx, const int32_t* qry_ids, const int32_t* ref_ids, uint64_t n_pairs, int32_t frag_len, int32_t scale,
                     double min_fraction, pg_sketch_result* out);
 
+/* ---- classify: clique sweep over identity thresholds ------------------------------------------------------------------
+ * The compute of `pyani classify`.  These calls read caller matrices only: they touch no genome, seed list or ANIm worker slot, so
+ * they need no interlock with the pg_anim_pairs_enqueue / _fetch lanes and may run while enqueued ANIm calls are in flight (own
+ * kernels on the context's own stream; among themselves they are serialised by the caller, as every call on a context).
+ *
+ * pg_classify_edges replaces the pair loop of build_graph_from_results (pyani/pyani_classify.py:90-111).  identity / coverage: n x n
+ * row-major fp64 (host), rows and columns in the same label order.  For every i < j: a = M[row j, col i], b = M[row i, col j],
+ * weight = b if b < a else a (Python's min(a, b), its NaN order included), for both matrices; (i, j) is an edge iff
+ * identity weight > id_min and coverage weight > cov_min.  *n_nodes_out = size of the reference's node set: every edge endpoint plus
+ * every label except the last (pyani_classify.py:108), i.e. n, or n - 1 when the last genome has no edge.  The edge state (weights)
+ * stays resident in the context until the next pg_classify_edges, pg_classify_release or pg_destroy.  n <= 8192 (PG_E_ARG beyond);
+ * PG_E_NOMEM when the tables do not fit. */
+int pg_classify_edges(pg_ctx* ctx, const double* identity, const double* coverage, uint32_t n, double id_min, double cov_min,
+                      uint64_t* n_edges_out, uint32_t* n_nodes_out);
+/* The identities of the resident edges, in no particular order (the caller sorts them: the edge list remove_low_weight_edges sorts,
+ * pyani_classify.py:160, from which the thresholds of trimmed_graph_sequence follow, subcmd_classify.py:144-157).  cap >= n_edges. */
+int pg_classify_edge_identities(pg_ctx* ctx, double* out, uint64_t cap);
+/* The sweep of trimmed_graph_sequence (subcmd_classify.py:159-171) with analyse_cliques (pyani_classify.py:115-148) at every step.
+ * theta[n_steps]: non-decreasing; step k sees exactly the resident edges with identity > theta[k] (the reference's step-by-step
+ * removal of edges <= threshold, restated per step: the steps are independent).  Per step: n_subgraphs_out = number of connected
+ * components over the node set, complete_out = 1 iff every node's degree equals its component's size - 1 (all_components_k_complete);
+ * labels_out (may be NULL): n_steps x n int32, the smallest member index of the node's component, -1 for a genome outside the node
+ * set.  Labels cost n_steps * n * 4 bytes of device and host memory per call: callers slice long threshold lists (any sub-list of a
+ * sweep's thetas gives the same per-step answers).  PG_E_ARG without edge state or for a decreasing / NaN theta. */
+int pg_classify_sweep(pg_ctx* ctx, const double* theta, uint64_t n_steps, int32_t* n_subgraphs_out, uint8_t* complete_out,
+                      int32_t* labels_out);
+/* Frees the edge state now (otherwise: the next pg_classify_edges or pg_destroy). */
+int pg_classify_release(pg_ctx* ctx);
+
 /* ---- measurement ---------------------------------------------------------------------------------------- */
 /* When enabled, every kernel launch is bracketed by HIP events on the context's stream. */
 int pg_profile_enable(pg_ctx* ctx, int on);
@@ -295,7 +324,9 @@ int pg_profile_reset(pg_ctx* ctx);
 #define PG_K_ANIM_FWD 13     /* anim_postnuc_fwd_kernel: the forward extension off every cluster, ahead of the units' walks */
 #define PG_K_ANIM_BWD 14     /* anim_postnuc_rehearse_kernel + anim_postnuc_bwd_kernel: the walks rehearsed, their backward searches run ahead */
 #define PG_K_SKETCH_PAIRS 15 /* sketch_pairs_kernel: the sketch mode's containment pass (pg_sketch_pairs) */
-#define PG_K__COUNT 16
+#define PG_K_CLASSIFY_EDGE 16  /* classify_edge_kernel: ordered minima, floors, edge list (pg_classify_edges) */
+#define PG_K_CLASSIFY_SWEEP 17 /* classify_death_kernel + classify_sweep_kernel: one workgroup per threshold step (pg_classify_sweep) */
+#define PG_K__COUNT 18
 /* total milliseconds and number of launches of kernel `which` since the last reset (synchronises). */
 int pg_profile_get(pg_ctx* ctx, int which, double* total_ms_out, uint64_t* launches_out);
 const char* pg_kernel_name(int which);

@@ -27,7 +27,8 @@ K_TETRA_COUNT, K_TETRA_FINALIZE, K_TETRA_STATS, K_TETRA_PAIRS = 0, 1, 2, 3
 K_ANIB_BUCKET, K_ANIB_FRAG = 11, 12
 K_ANIM_FWD, K_ANIM_BWD = 13, 14
 K_SKETCH_PAIRS = 15
-K_COUNT = 16
+K_CLASSIFY_EDGE, K_CLASSIFY_SWEEP = 16, 17
+K_COUNT = 18
 PG_SKETCH_NO_RESULT = 1
 
 # every symbol declared in include/pyani_gpu.h: (name, restype, argtypes)
@@ -70,6 +71,10 @@ SIGNATURES = {
     "pg_anib_pairs": (_int, [_vp, _vp, _vp, _u64, _u32, _vp]),
     "pg_anib_pair_rows": (_int, [_vp, _i32, _i32, _u32, _vp, _u32, _P(_u32)]),
     "pg_sketch_pairs": (_int, [_vp, _vp, _vp, _u64, _i32, _i32, ctypes.c_double, _vp]),
+    "pg_classify_edges": (_int, [_vp, _vp, _vp, _u32, ctypes.c_double, ctypes.c_double, _P(_u64), _P(_u32)]),
+    "pg_classify_edge_identities": (_int, [_vp, _vp, _u64]),
+    "pg_classify_sweep": (_int, [_vp, _vp, _u64, _vp, _vp, _vp]),
+    "pg_classify_release": (_int, [_vp]),
     "pg_profile_enable": (_int, [_vp, _int]),
     "pg_profile_config": (_int, [_vp, _u32, _u32]),
     "pg_profile_reset": (_int, [_vp]),

@@ -21,7 +21,7 @@ static const char* const KERNEL_NAMES[PG_K__COUNT] = {"tetra_count_kernel", "tet
                                                       "anim_postnuc_gap_kernels", "anim_postnuc_forced_kernels",
                                                       "anim_postnuc_kernel", "anim_finish_kernel", "anib_bucket_kernel",
                                                       "anib_frag_kernel", "anim_postnuc_fwd_kernel", "anim_postnuc_rehearse_kernel+anim_postnuc_bwd_kernel",
-                                                      "sketch_pairs_kernel"};
+                                                      "sketch_pairs_kernel", "classify_edge_kernel", "classify_death_kernel+classify_sweep_kernel"};
 
 // ---- profiling ----------------------------------------------------------------------------------------------
 thread_local hipStream_t pg_tls_stream = nullptr;
@@ -353,6 +353,7 @@ void pg_destroy(pg_ctx* ctx) {
   for (int w = 1; w < pg_ctx::MAX_WORKERS; ++w) (void)hipStreamSynchronize(ctx->stream_w[w]);
   pg_anim_free_scratch(ctx);
   pg_sketch_drop(ctx);
+  pg_classify_drop(ctx);
   prof_drain(ctx);
   void* dev[] = {ctx->d_codes, ctx->d_mask, ctx->d_quirk, ctx->d_seg_tile0, ctx->d_seg_prefix, ctx->d_batch_gid, ctx->d_acc,
                  ctx->d_counts, ctx->d_z, ctx->d_present, ctx->d_dev, ctx->d_ss, ctx->d_flags, ctx->d_corr};

@@ -96,6 +96,7 @@ struct pg_ctx {
   hipStream_t stream_w[MAX_WORKERS] = {nullptr, nullptr, nullptr, nullptr};   // workers 1.. (index 0 unused: worker 0 = stream)
   void* anim_lists = nullptr;      // per-genome seed lists, shared by the workers (guarded by anim_mu)
   void* sketch_store = nullptr;    // per-genome k-mer sketches of the sketch mode (pg_sketch.hip), built on first use
+  void* classify_state = nullptr;  // resident edge state of the classify sweep (pg_classify.hip), replaced by every pg_classify_edges
   std::mutex anim_mu, err_mu, prof_mu;
   int anib_word_tier = 1;      // fragment mode: search failed fragments again with blastn-sized (11-mer) seeds
   int anim_pn_window_max = 2048;   // forced runs: the widest single-wave window (development: smaller values push runs on to the group kernel)
@@ -180,6 +181,7 @@ int pg_anim_counters_read(pg_ctx* ctx, uint64_t* out /*[64]*/, int reset);
 void pg_anim_set_sink(PgAlnSink* sink);           // thread-local; nullptr = none
 void pg_anim_drop_lists(pg_ctx* ctx);   // per-genome seed lists: must go when the genome store is cleared
 void pg_sketch_drop(pg_ctx* ctx);       // ... and the sketches of the sketch mode (pg_sketch.hip)
+void pg_classify_drop(pg_ctx* ctx);     // ... the classify sweep's edge state (pg_classify.hip): goes with the context or on request
 int pg_anib_reduce_run(pg_ctx* ctx, uint32_t n_pairs, const uint64_t* offsets, const uint32_t* n_frags, const int32_t* frag,
                        const int32_t* length, const int32_t* mismatch, const int32_t* gaps, const int32_t* qlen,
                        const double* pident, int64_t* aln_out, int64_t* err_out, double* pid_out);

@@ -311,6 +311,40 @@ class Engine:
                                              out.ctypes.data))
         return out
 
+    # -- classify: clique sweep over identity thresholds (pyani_amd.classify drives these) -------------------------------------
+    def classify_edges(self, identity: np.ndarray, coverage: np.ndarray, id_min: float = 0.8, cov_min: float = 0.5) -> Tuple[int, int]:
+        """pg_classify_edges: the edges of build_graph_from_results (pyani_classify.py:90-111) from two n x n float64 matrices in one
+        label order; they stay resident for classify_sweep.  Returns (number of edges, size of the reference's node set)."""
+        i = np.ascontiguousarray(identity, dtype=np.float64)
+        c = np.ascontiguousarray(coverage, dtype=np.float64)
+        if i.ndim != 2 or i.shape[0] != i.shape[1] or i.shape != c.shape:
+            raise ValueError("identity and coverage must be square matrices of one size")
+        ne, nn = ctypes.c_uint64(0), ctypes.c_uint32(0)
+        self._check(self.lib.pg_classify_edges(self._h, i.ctypes.data, c.ctypes.data, i.shape[0], float(id_min), float(cov_min),
+                                               ctypes.byref(ne), ctypes.byref(nn)))
+        self._classify_n = i.shape[0]
+        return int(ne.value), int(nn.value)
+
+    def classify_edge_identities(self, n_edges: int) -> np.ndarray:
+        """The resident edges' identities, unordered (float64[n_edges])."""
+        out = np.zeros(int(n_edges), dtype=np.float64)
+        self._check(self.lib.pg_classify_edge_identities(self._h, out.ctypes.data if len(out) else None, len(out)))
+        return out
+
+    def classify_sweep(self, theta, labels: bool = False) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
+        """pg_classify_sweep over the resident edges: step k sees the edges with identity > theta[k] (theta non-decreasing).  Returns
+        (components int32[steps], all-cliques bool[steps], labels int32[steps, n] or None: the smallest member index of every node's
+        component, -1 outside the node set)."""
+        t = np.ascontiguousarray(theta, dtype=np.float64).reshape(-1)
+        n_sub = np.zeros(len(t), dtype=np.int32)
+        comp = np.zeros(len(t), dtype=np.uint8)
+        lab = np.zeros((len(t), getattr(self, "_classify_n", 0)), dtype=np.int32) if labels else None
+        self._check(self.lib.pg_classify_sweep(self._h, t.ctypes.data, len(t), n_sub.ctypes.data, comp.ctypes.data, _ptr(lab)))
+        return n_sub, comp.astype(bool), lab
+
+    def classify_release(self) -> None:
+        self._check(self.lib.pg_classify_release(self._h))
+
     def profile_enable(self, on: bool = True):
         self._check(self.lib.pg_profile_enable(self._h, int(on)))
 
