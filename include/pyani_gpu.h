@@ -33,6 +33,7 @@ extern "C" {
 #define PG_E_RNA (-8)      /* sequence contains U/u: Biopython complements it asymmetrically (U->A); unsupported */
 #define PG_E_CAPACITY (-9) /* a per-pair work buffer overflowed (pg_anim_result.status; pg_anim_alignments_batch) */
 #define PG_E_INTERNAL (-10) /* an internal consistency check failed (traceback pass), see pg_last_error */
+#define PG_E_NONFINITE (-11) /* cluster calls: a distance is NaN or infinite; scipy's linkage raises ValueError on it */
 
 typedef struct pg_ctx pg_ctx;
 
@@ -299,6 +300,37 @@ int pg_classify_sweep(pg_ctx* ctx, const double* theta, uint64_t n_steps, int32_
 /* Frees the edge state now (otherwise: the next pg_classify_edges or pg_destroy). */
 int pg_classify_release(pg_ctx* ctx);
 
+/* ---- heatmap clustering: distance matrix and linkage --------------------------------------------------------------------
+ * The arithmetic that orders every heatmap of `pyani plot`.  Like the classify calls these read caller matrices only: they touch
+ * no genome, seed list or ANIm worker slot, and keep nothing resident.  x: rows x cols float64, row-major.  columns = 0: the n = rows
+ * rows are the observations (length cols); columns != 0: the n = cols columns are (length rows), read in place, no transposed copy.
+ * Results EQUAL scipy's bit for bit (every operation rounded on its own, sums in k order).  n <= 8192 (PG_E_ARG beyond; the
+ * observation length is unbounded); PG_E_NOMEM when a working matrix (8 n^2 bytes per problem) does not fit; PG_E_NONFINITE when any
+ * distance is NaN or infinite (a NaN cell, an overflow), where scipy raises ValueError.
+ *
+ * pg_cluster_pdist replaces scipy.spatial.distance.pdist(dfr) / pdist(dfr.T), Euclidean (pyani/pyani_graphics/mpl/__init__.py:101
+ * and :107): out holds the n (n - 1) / 2 distances in condensed order (0,1), (0,2), ..., (n-2,n-1).  n = 1 writes nothing. */
+int pg_cluster_pdist(pg_ctx* ctx, const double* x, uint32_t rows, uint32_t cols, int columns, double* out);
+#define PG_CLUSTER_COMPLETE 0 /* linkage(dists, method="complete"): pyani_graphics/mpl/__init__.py:128 */
+#define PG_CLUSTER_AVERAGE 1  /* method="average": what sns.clustermap computes, pyani_graphics/sns/__init__.py:130 */
+/* pg_cluster_linkage replaces pdist + scipy.cluster.hierarchy.linkage of add_dendrogram (pyani_graphics/mpl/__init__.py:100-128).
+ * merges_out: (n - 1) x 4 float64, the nearest-neighbour chain's merge records (lower cluster slot, higher slot, height, size) in
+ * MERGE order; a stable sort by height and the union-find relabelling (host, pyani_amd.graphics) turn them into scipy's Z.
+ * n >= 2 (PG_E_ARG below: scipy raises ValueError on an empty distance vector). */
+int pg_cluster_linkage(pg_ctx* ctx, const double* x, uint32_t rows, uint32_t cols, int columns, int method, double* merges_out);
+/* The clusterings of a run in one call (pyani/scripts/subcommands/subcmd_plot.py:130-139: five matrices, rows and columns each):
+ * distances per problem, then ONE linkage launch with a workgroup per problem.  Problems naming the same x / rows / cols share one
+ * upload.  status: PG_OK or PG_E_NONFINITE per problem (merges untouched then); the call itself fails only for bad arguments, memory
+ * or the runtime. */
+typedef struct {
+  const double* x;
+  uint32_t rows, cols;
+  int32_t columns, method;
+  double* merges;      /* (n - 1) x 4 */
+  int32_t status, reserved;
+} pg_cluster_problem;
+int pg_cluster_linkage_batch(pg_ctx* ctx, pg_cluster_problem* problems, uint32_t n_problems);
+
 /* ---- measurement ---------------------------------------------------------------------------------------- */
 /* When enabled, every kernel launch is bracketed by HIP events on the context's stream. */
 int pg_profile_enable(pg_ctx* ctx, int on);
@@ -326,7 +358,9 @@ int pg_profile_reset(pg_ctx* ctx);
 #define PG_K_SKETCH_PAIRS 15 /* sketch_pairs_kernel: the sketch mode's containment pass (pg_sketch_pairs) */
 #define PG_K_CLASSIFY_EDGE 16  /* classify_edge_kernel: ordered minima, floors, edge list (pg_classify_edges) */
 #define PG_K_CLASSIFY_SWEEP 17 /* classify_death_kernel + classify_sweep_kernel: one workgroup per threshold step (pg_classify_sweep) */
-#define PG_K__COUNT 18
+#define PG_K_CLUSTER_PDIST 18   /* cluster_pdist_kernel: Euclidean distances, upper-triangle tiles (pg_cluster_pdist, pg_cluster_linkage*) */
+#define PG_K_CLUSTER_LINKAGE 19 /* cluster_linkage_kernel: nearest-neighbour chain, one workgroup per problem (pg_cluster_linkage*) */
+#define PG_K__COUNT 20
 /* total milliseconds and number of launches of kernel `which` since the last reset (synchronises). */
 int pg_profile_get(pg_ctx* ctx, int which, double* total_ms_out, uint64_t* launches_out);
 const char* pg_kernel_name(int which);

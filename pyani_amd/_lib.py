@@ -22,13 +22,17 @@ LIB_PATH = Path(__file__).resolve().parent / "libpyani_gpu.so"
 
 PG_OK, PG_E_ARG, PG_E_NODEVICE, PG_E_HIP, PG_E_IO, PG_E_NOMEM, PG_E_KEYSET, PG_E_EMPTY, PG_E_RNA = 0, -1, -2, -3, -4, -5, -6, -7, -8
 PG_E_CAPACITY, PG_ANIM_NO_ALIGNMENT = -9, 1
+PG_E_NONFINITE = -11
+PG_CLUSTER_COMPLETE, PG_CLUSTER_AVERAGE = 0, 1
 K_TETRA_COUNT, K_TETRA_FINALIZE, K_TETRA_STATS, K_TETRA_PAIRS = 0, 1, 2, 3
 (K_ANIM_SEED, K_ANIM_HIT, K_ANIM_CLUSTER, K_ANIM_GAPS, K_ANIM_EXTLANE, K_ANIM_EXTEND, K_ANIM_FINISH) = 4, 5, 6, 7, 8, 9, 10
 K_ANIB_BUCKET, K_ANIB_FRAG = 11, 12
 K_ANIM_FWD, K_ANIM_BWD = 13, 14
 K_SKETCH_PAIRS = 15
 K_CLASSIFY_EDGE, K_CLASSIFY_SWEEP = 16, 17
-K_COUNT = 18
+K_COUNT = 18      # the slots of the comparison and classify stages, 0 .. 17: the value callers have seen so far stays as it is
+K_CLUSTER_PDIST, K_CLUSTER_LINKAGE = 18, 19
+K_TOTAL = 20      # PG_K__COUNT of the header: every slot, the two cluster slots included
 PG_SKETCH_NO_RESULT = 1
 
 # every symbol declared in include/pyani_gpu.h: (name, restype, argtypes)
@@ -75,12 +79,23 @@ SIGNATURES = {
     "pg_classify_edge_identities": (_int, [_vp, _vp, _u64]),
     "pg_classify_sweep": (_int, [_vp, _vp, _u64, _vp, _vp, _vp]),
     "pg_classify_release": (_int, [_vp]),
+    "pg_cluster_pdist": (_int, [_vp, _vp, _u32, _u32, _int, _vp]),
+    "pg_cluster_linkage": (_int, [_vp, _vp, _u32, _u32, _int, _int, _vp]),
+    "pg_cluster_linkage_batch": (_int, [_vp, _vp, _u32]),
     "pg_profile_enable": (_int, [_vp, _int]),
     "pg_profile_config": (_int, [_vp, _u32, _u32]),
     "pg_profile_reset": (_int, [_vp]),
     "pg_profile_get": (_int, [_vp, _int, _P(ctypes.c_double), _P(_u64)]),
     "pg_kernel_name": (ctypes.c_char_p, [_int]),
 }
+
+
+
+class ClusterProblem(ctypes.Structure):
+    """pg_cluster_problem (include/pyani_gpu.h)."""
+    _fields_ = [("x", _vp), ("rows", _u32), ("cols", _u32), ("columns", _i32), ("method", _i32), ("merges", _vp), ("status", _i32),
+                ("reserved", _i32)]
+
 
 _lib = None
 

@@ -21,7 +21,8 @@ static const char* const KERNEL_NAMES[PG_K__COUNT] = {"tetra_count_kernel", "tet
                                                       "anim_postnuc_gap_kernels", "anim_postnuc_forced_kernels",
                                                       "anim_postnuc_kernel", "anim_finish_kernel", "anib_bucket_kernel",
                                                       "anib_frag_kernel", "anim_postnuc_fwd_kernel", "anim_postnuc_rehearse_kernel+anim_postnuc_bwd_kernel",
-                                                      "sketch_pairs_kernel", "classify_edge_kernel", "classify_death_kernel+classify_sweep_kernel"};
+                                                      "sketch_pairs_kernel", "classify_edge_kernel", "classify_death_kernel+classify_sweep_kernel",
+                                                      "cluster_pdist_kernel", "cluster_linkage_kernel"};
 
 // ---- profiling ----------------------------------------------------------------------------------------------
 thread_local hipStream_t pg_tls_stream = nullptr;

@@ -345,6 +345,51 @@ class Engine:
     def classify_release(self) -> None:
         self._check(self.lib.pg_classify_release(self._h))
 
+    # -- heatmap clustering: distances and linkage (pyani_amd.graphics drives these) ---------------------------------------------
+    @staticmethod
+    def _cluster_matrix(x) -> np.ndarray:
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim != 2 or x.shape[0] == 0 or x.shape[1] == 0:
+            raise ValueError(f"a non-empty two-dimensional matrix is needed, not shape {x.shape}")
+        return x
+
+    def cluster_pdist(self, x, columns: bool = False) -> np.ndarray:
+        """pg_cluster_pdist: scipy's pdist(x) (columns: pdist(x.T), without a transposed copy), Euclidean, condensed order, bit for bit
+        (pyani_graphics/mpl/__init__.py:101, :107).  PyaniGpuError with code PG_E_NONFINITE if any distance is NaN or infinite."""
+        x = self._cluster_matrix(x)
+        n = x.shape[1] if columns else x.shape[0]
+        out = np.zeros(n * (n - 1) // 2, dtype=np.float64)
+        self._check(self.lib.pg_cluster_pdist(self._h, x.ctypes.data, x.shape[0], x.shape[1], int(bool(columns)), out.ctypes.data if len(out) else None))
+        return out
+
+    def cluster_linkage(self, x, method: int = _lib.PG_CLUSTER_COMPLETE, columns: bool = False) -> np.ndarray:
+        """pg_cluster_linkage: the (n - 1) x 4 merge records of the nearest-neighbour chain in MERGE order (not yet scipy's Z: see
+        pyani_amd.graphics.merges_to_linkage).  Replaces pdist + linkage of add_dendrogram (pyani_graphics/mpl/__init__.py:100-128)."""
+        x = self._cluster_matrix(x)
+        n = x.shape[1] if columns else x.shape[0]
+        out = np.zeros((max(n - 1, 0), 4), dtype=np.float64)
+        self._check(self.lib.pg_cluster_linkage(self._h, x.ctypes.data, x.shape[0], x.shape[1], int(bool(columns)), int(method), out.ctypes.data))
+        return out
+
+    def cluster_linkage_batch(self, problems) -> List[Optional[np.ndarray]]:
+        """pg_cluster_linkage_batch over [(x, columns, method)]: one linkage launch, a workgroup per problem (the ten clusterings of a
+        run, subcmd_plot.py:130-139).  Problems that pass the SAME array object share one upload.  Per problem the merge records, or
+        None where a distance was not finite."""
+        mats = {}
+        arr = (_lib.ClusterProblem * len(problems))()
+        outs = []
+        for k, (x, columns, method) in enumerate(problems):
+            if id(x) not in mats:
+                mats[id(x)] = self._cluster_matrix(x)
+            m = mats[id(x)]
+            n = m.shape[1] if columns else m.shape[0]
+            out = np.zeros((max(n - 1, 0), 4), dtype=np.float64)
+            outs.append(out)
+            arr[k].x, arr[k].rows, arr[k].cols = m.ctypes.data, m.shape[0], m.shape[1]
+            arr[k].columns, arr[k].method, arr[k].merges = int(bool(columns)), int(method), out.ctypes.data
+        self._check(self.lib.pg_cluster_linkage_batch(self._h, ctypes.cast(arr, ctypes.c_void_p), len(problems)))
+        return [None if arr[k].status == _lib.PG_E_NONFINITE else outs[k] for k in range(len(problems))]
+
     def profile_enable(self, on: bool = True):
         self._check(self.lib.pg_profile_enable(self._h, int(on)))
 

@@ -129,6 +129,16 @@ class MultiEngine:
     def genome_length(self, gid: int):
         return self.engines[0].genome_length(gid)
 
+    # heatmap clustering reads caller matrices only: one device is enough
+    def cluster_pdist(self, x, columns: bool = False):
+        return self.engines[0].cluster_pdist(x, columns)
+
+    def cluster_linkage(self, x, method: int = 0, columns: bool = False):
+        return self.engines[0].cluster_linkage(x, method, columns)
+
+    def cluster_linkage_batch(self, problems):
+        return self.engines[0].cluster_linkage_batch(problems)
+
     def clear_genomes(self):
         self._all(lambda e: e.clear_genomes())
 
