@@ -19,6 +19,8 @@
 // The kernels live in include files, in pipeline order: pga_seed.inc (A1/A2), pga_cluster.inc (A3), pga_postnuc.inc +
 // pga_postnuc_diag.inc (A4x), pga_finish.inc (A5), pga_frag.inc (fragment mode); this file holds the shared descriptors and
 // the host driver.  (The fixed-band "banded64" extender of rounds 1-2 was retired in round 5: it was not exact.)
+// Host driver: a worker's device scratch is an AnimScratch of owning buffers (PgDevBuf, pg_devbuf.h: each knows its size, the
+// scratch is freed by deleting it); pg_anim_run_batch is a sequence of stage functions over one Batch struct, in launch order.
 //
 // Every kernel has a scalar statement in pg_anim_core.h that compiles for the host (tools/anim_debug); the two are kept
 // in lock-step and compared on the GPU by tests/test_anim_gpu.py.  Limits: genomes up to ~14 Mb (a reference k-mer
@@ -26,6 +28,7 @@
 #include <tuple>
 #include <unordered_map>
 #include "pg_internal.h"
+#include "pg_devbuf.h"
 #include "pg_anim_core.h"
 #include "pg_nucmer_core.h"
 #include "pg_nucmer_diag.h"
@@ -117,89 +120,87 @@ struct AnimLists { std::vector<GenomeIdx> gidx; };
 thread_local PgAlnSink* tls_sink = nullptr;      // set by pg_anim_alignments_batch around its run_batch calls
 thread_local int tls_worker = 0;   // which of the context's two (stream, scratch) sets the calling thread drives
 
+// A worker's launch scratch.  Every array owns its block and knows its size (pg_devbuf.h); arrays that grow together are
+// grown by one reserve_all.  It lives in the context and only grows; deleting it frees everything.
 struct AnimScratch {
-  size_t units = 0, pairs = 0, refs = 0, recs = 0, wl = 0, matches = 0;
-  uint32_t* list_cnt = nullptr;   // 2 * SEED_GROUPS counters used by this worker's list builds
-  SeedRef* srefs_d = nullptr;
-  SeedQry* sqry_d = nullptr;
-  SeedSlice* slice_d = nullptr;   // [SEED_CGROUPS][pairs of the batch] (per-pair kernel)
-  size_t slice_pairs = 0;
-  SeedBlk* sblk_d = nullptr;      // block kernel: blocks, slots, block queries, pair tables
-  SeedSlot* sslot_d = nullptr;
-  SeedQry* sbq_d = nullptr;
-  int32_t* spt_d = nullptr;
-  size_t sblk_cap = 0, sslot_cap = 0, sbq_cap = 0, spt_cap = 0;
-  int32_t* recs_d = nullptr;
-  RefDesc* refs_d = nullptr;
-  UnitDesc* units_d = nullptr;
-  uint32_t *mem_count = nullptr, *moff = nullptr, *choff_d = nullptr;
-  int32_t *nch = nullptr, *status = nullptr;
-  pg_anim_result* out = nullptr;
+  PgDevBuf<uint32_t> list_cnt;      // 2 * SEED_GROUPS counters used by this worker's list builds
+  PgDevBuf<SeedRef> srefs_d;
+  PgDevBuf<SeedQry> sqry_d;
+  PgDevBuf<SeedSlice> slice_d;      // [SEED_CGROUPS][pairs of the batch] (per-pair kernel)
+  PgDevBuf<SeedBlk> sblk_d;         // block kernel: blocks, slots, block queries, pair tables
+  PgDevBuf<SeedSlot> sslot_d;
+  PgDevBuf<SeedQry> sbq_d;
+  PgDevBuf<int32_t> spt_d;
+  PgDevBuf<int32_t> recs_d;
+  PgDevBuf<RefDesc> refs_d;
+  PgDevBuf<UnitDesc> units_d;
+  PgDevBuf<uint32_t> mem_count, moff, choff_d;
+  PgDevBuf<int32_t> nch, status;
+  PgDevBuf<pg_anim_result> out;
   // per-match arrays (sliced by moff)
-  Match *mem = nullptr, *cm = nullptr;
-  int32_t *iscratch = nullptr, *order = nullptr;
-  Chain* chains = nullptr;
-  FinishScratch S{};
-  uint2* wl_d = nullptr;
-  Match* seedbuf = nullptr;   // batch-wide append buffer of the seed pass
-  size_t seed_cap = 0;
-  uint32_t* seed_total = nullptr;   // [0] matches appended, [1] hits recorded
-  Match* hits_d = nullptr;          // hits recorded by the probe kernel for anim_hit_kernel
-  Match* hits_sorted = nullptr;     // the same, dealt into per-unit slices (hoff)
-  uint32_t *hit_count = nullptr, *hoff = nullptr, *hit_cursor = nullptr;   // per unit
-  size_t hit_cap = 0;
-  int32_t* mirror_d = nullptr;      // per pair: the partner pair (roles swapped) that receives this pair's matches transposed, or -1
-  BigUnit* big_d = nullptr;         // cluster stage: units whose chains are extracted by ranges, the range work items, their counts
-  uint2* ranges_d = nullptr;
-  RangeOut* range_out = nullptr;
-  size_t big_cap = 0, range_cap = 0;
+  PgDevBuf<Match> mem, cm;
+  PgDevBuf<int32_t> iscratch, order;
+  PgDevBuf<Chain> chains;
+  struct {   // the finish kernel's per-alignment arrays; it takes them as a FinishScratch
+    PgDevBuf<Aln> alns;
+    PgDevBuf<int32_t> a_rrec, a_qrec, idx, from;
+    PgDevBuf<double> sc;
+    FinishScratch view() const { return FinishScratch{alns, a_rrec, a_qrec, idx, from, sc}; }
+  } S;
+  PgDevBuf<uint2> wl_d;
+  PgDevBuf<Match> seedbuf;          // batch-wide append buffer of the seed pass
+  PgDevBuf<uint32_t> seed_total;    // [0] matches appended, [1] hits recorded
+  PgDevBuf<Match> hits_d;           // hits recorded by the probe kernel for anim_hit_kernel
+  PgDevBuf<Match> hits_sorted;      // the same, dealt into per-unit slices (hoff)
+  PgDevBuf<uint32_t> hit_count, hoff, hit_cursor;   // per unit
+  PgDevBuf<int32_t> mirror_d;       // per pair: the partner pair (roles swapped) that receives this pair's matches transposed, or -1
+  PgDevBuf<BigUnit> big_d;          // cluster stage: units whose chains are extracted by ranges, the range work items, their counts
+  PgDevBuf<uint2> ranges_d;
+  PgDevBuf<RangeOut> range_out;
   bool lds_attr_set = false;        // the probe kernels' dynamic-LDS limit has been raised on this context's device
   // A4x, the postnuc extension stage (pga_postnuc.inc)
-  pgn::PnAln* pn = nullptr;         // per-unit alignment lists, sliced by moff like the per-match arrays
-  uint8_t* pn_fused = nullptr;      // per chain: already extended / fused / shadowed
-  int32_t* pn_n = nullptr;          // per unit: alignments (< 0: capacity)
-  uint32_t* pn_cursor = nullptr;    // unit hand-out counter of the persistent waves
-  uint32_t* pn_gscratch = nullptr;  // [waves][PN_GLOBAL_WORDS] anti-diagonals too wide for LDS
-  uint32_t* pn_wide = nullptr;      // request slots handed from the narrow forced kernel to the wide one
-  PnForcedReq* pn_reqs = nullptr;   // the launch's deferred forced runs (at most one per alignment started: <= chains)
-  pgn::PnGap* pn_gaps = nullptr;    // match-to-match alignments by match slot
-  pgn::PnFwd* pn_fwd = nullptr;     // forward extensions by cluster (moff-relative position in the unit's order)
-  pgn::PnBwd* pn_bwd = nullptr;      // backward searches run ahead of the walks, by cluster (as pn_fwd)
-  pgn::PnTurn* pn_tlog = nullptr;    // the walks' turn logs (pgn::PnPairSync), sliced by moff: at most one turn per cluster
-  int32_t* pn_born = nullptr;        // per alignment: the key of the turn that pushed it
-  uint32_t* pn_porder = nullptr;     // pairs by descending cluster count of their larger strand
-  pgn::PnPiece* pn_pieces = nullptr; // traceback runs: the walks' pieces (pn_piece_base)
-  uint32_t* pn_npieces = nullptr;    // per unit
-  size_t pn_piece_cap = 0, pn_npieces_cap = 0;
-  uint8_t* tr_arena = nullptr;       // traceback pass: the jobs' slabs
-  uint32_t* tr_out = nullptr;        // ... their paths (run-length coded)
-  PnTraceJob* tr_jobs = nullptr;
-  unsigned long long *tr_off = nullptr, *tr_cursor = nullptr;
-  int32_t* tr_cnt = nullptr;
-  size_t tr_arena_cap = 0, tr_out_cap = 0, tr_jobs_cap = 0;
-  PnGapTask* pn_tasks = nullptr;    // [3 size classes][pn_cap] small gaps for the lane kernel
-  uint32_t* pn_order = nullptr;     // units by descending cluster count
-  size_t pn_cap = 0, pn_units = 0, pn_waves = 0, pn_req_cap = 0, pn_req_n = 0;   // pn_req_n: slots of pn_reqs the latest launch used (its req_cap)
+  PgDevBuf<pgn::PnAln> pn;          // per-unit alignment lists, sliced by moff like the per-match arrays
+  PgDevBuf<uint8_t> pn_fused;       // per chain: already extended / fused / shadowed
+  PgDevBuf<int32_t> pn_n;           // per unit: alignments (< 0: capacity)
+  PgDevBuf<uint32_t> pn_cursor;     // the persistent waves' hand-out counters (PnCursor)
+  PgDevBuf<uint32_t> pn_gscratch;   // [waves][PN_GLOBAL_WORDS] anti-diagonals too wide for LDS
+  PgDevBuf<uint32_t> pn_wide;       // request slots handed from the narrow forced kernel to the wide one
+  PgDevBuf<PnForcedReq> pn_reqs;    // the launch's deferred forced runs (at most one per alignment started: <= chains)
+  PgDevBuf<pgn::PnGap> pn_gaps;     // match-to-match alignments by match slot
+  PgDevBuf<pgn::PnFwd> pn_fwd;      // forward extensions by cluster (moff-relative position in the unit's order)
+  PgDevBuf<pgn::PnBwd> pn_bwd;      // backward searches run ahead of the walks, by cluster (as pn_fwd)
+  PgDevBuf<pgn::PnTurn> pn_tlog;    // the walks' turn logs (pgn::PnPairSync), sliced by moff: at most one turn per cluster
+  PgDevBuf<int32_t> pn_born;        // per alignment: the key of the turn that pushed it
+  PgDevBuf<uint32_t> pn_porder;     // pairs by descending cluster count of their larger strand
+  PgDevBuf<pgn::PnPiece> pn_pieces; // traceback runs: the walks' pieces (pn_piece_base)
+  PgDevBuf<uint32_t> pn_npieces;    // per unit
+  PgDevBuf<uint8_t> tr_arena;       // traceback pass: the jobs' slabs
+  PgDevBuf<uint32_t> tr_out;        // ... their paths (run-length coded)
+  PgDevBuf<PnTraceJob> tr_jobs;
+  PgDevBuf<unsigned long long> tr_off, tr_cursor;
+  PgDevBuf<int32_t> tr_cnt;
+  PgDevBuf<PnGapTask> pn_tasks;     // [4][pn.cap]: small gaps for the lane kernel by size class, then the wave engine's list
+  PgDevBuf<uint32_t> pn_order;      // units by descending cluster count
+  size_t pn_req_n = 0;              // slots of pn_reqs the latest launch used (its req_cap)
   // fragment mode (ANIb)
-  int32_t* fr_tables = nullptr;     // frag_pos | frag_len | rec_frag0 of every distinct query genome of the batch
-  FragPair* fr_pairs = nullptr;
-  uint32_t *fr_slot_pair = nullptr, *fr_off = nullptr, *fr_nrows = nullptr;
-  uint64_t* fr_ebase = nullptr;
-  FragSeed* fr_entries = nullptr;
-  FragRow* fr_rows = nullptr;
-  pg_anib_result* fr_out = nullptr;
-  uint32_t *fr_list = nullptr, *fr_nlist = nullptr, *fr_wtmp = nullptr;   // word tier: slots to search again, their number, scan scratch
-  WordIdx* fr_widx = nullptr;
-  size_t fr_list_cap = 0, fr_widx_cap = 0;
-  size_t fr_tables_cap = 0, fr_pairs_cap = 0, fr_slots_cap = 0, fr_off_cap = 0, fr_units_cap = 0, fr_entries_cap = 0;
+  PgDevBuf<int32_t> fr_tables;      // frag_pos | frag_len | rec_frag0 of every distinct query genome of the batch
+  PgDevBuf<FragPair> fr_pairs;
+  PgDevBuf<uint32_t> fr_slot_pair, fr_off, fr_nrows;
+  PgDevBuf<uint64_t> fr_ebase;
+  PgDevBuf<FragSeed> fr_entries;
+  PgDevBuf<FragRow> fr_rows;
+  PgDevBuf<pg_anib_result> fr_out;
+  PgDevBuf<uint32_t> fr_list, fr_nlist, fr_wtmp;   // word tier: slots to search again, their number, scan scratch
+  PgDevBuf<WordIdx> fr_widx;
 };
 
-template <typename T>
-int regrow(pg_ctx* ctx, T*& p, size_t n) {
-  if (p) PG_HIP(ctx, hipFree(p));
-  p = nullptr;
-  PG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&p), (n ? n : 1) * sizeof(T)));
-  return PG_OK;
+// Room for `need` elements in every buffer of a group, each grown to `alloc` if it is short.  Every buffer is tested by its own
+// size, so a group that an allocation failure left half-grown is completed by the next call.
+template <typename... B>
+hipError_t reserve_all(size_t need, size_t alloc, B&... bufs) {
+  hipError_t e = hipSuccess;
+  ((e = e == hipSuccess ? bufs.reserve(need, alloc) : e), ...);
+  return e;
 }
 }  // namespace
 
@@ -253,10 +254,9 @@ static int anim_ensure_lists(pg_ctx* ctx, AnimScratch* A, const std::vector<int3
   // allocated is taken back if anything after the allocation fails, so that no later call seeds from a half-built list.
   std::vector<std::pair<uint64_t**, uint32_t**>> mine;
   const int rc_all = [&]() -> int {
-  int rc;
   bool built = false;
   if (!A->list_cnt) {
-    if ((rc = regrow(ctx, A->list_cnt, (size_t)2 * SEED_GROUPS))) return rc;
+    PG_HIP(ctx, A->list_cnt.reserve((size_t)2 * SEED_GROUPS));
     PG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(anim_list_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)(2 * SEED_GROUPS * 4)));
   }
@@ -274,8 +274,8 @@ static int anim_ensure_lists(pg_ctx* ctx, AnimScratch* A, const std::vector<int3
       uint64_t*& list = role ? qlist : X.ref_list;
       uint32_t*& goff = role ? qgoff : X.ref_goff;
       mine.emplace_back(&list, &goff);
-      if ((rc = regrow(ctx, list, bound))) return rc;
-      if ((rc = regrow(ctx, goff, (size_t)n_sub + 3))) return rc;
+      PG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&list), bound * sizeof(uint64_t)));      // (both are null here, bound >= 1)
+      PG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&goff), ((size_t)n_sub + 3) * sizeof(uint32_t)));
       const uint32_t* codes = ctx->d_codes + G.arena_start / 16;
       const uint32_t* mask = ctx->d_mask + G.arena_start / 32;
       const int32_t n_idx = role ? len / qstep + 1 : len;
@@ -315,40 +315,27 @@ static int anim_ensure_lists(pg_ctx* ctx, AnimScratch* A, const std::vector<int3
   return rc_all;
 }
 
-static void anim_free_one(pg_ctx* ctx, void*& slot);
+static void anim_free_one(void*& slot) {
+  delete static_cast<AnimScratch*>(slot);
+  slot = nullptr;
+}
 // the workers' launch scratch only (the per-genome seed lists stay): the context must be idle
 void pg_anim_release_worker_scratch(pg_ctx* ctx) {
   (void)hipStreamSynchronize(ctx->stream);
   for (int w = 1; w < pg_ctx::MAX_WORKERS; ++w) (void)hipStreamSynchronize(ctx->stream_w[w]);
-  anim_free_one(ctx, ctx->anim_scratch);
-  for (int w = 1; w < pg_ctx::MAX_WORKERS; ++w) anim_free_one(ctx, ctx->anim_scratch_w[w]);
+  anim_free_one(ctx->anim_scratch);
+  for (int w = 1; w < pg_ctx::MAX_WORKERS; ++w) anim_free_one(ctx->anim_scratch_w[w]);
   ctx->anim_scratch_matches_held = 0;
 }
 void pg_anim_free_scratch(pg_ctx* ctx) {
   pg_anim_drop_lists(ctx);
   delete static_cast<AnimLists*>(ctx->anim_lists);
   ctx->anim_lists = nullptr;
-  anim_free_one(ctx, ctx->anim_scratch);
-  for (int w = 1; w < pg_ctx::MAX_WORKERS; ++w) anim_free_one(ctx, ctx->anim_scratch_w[w]);
+  anim_free_one(ctx->anim_scratch);
+  for (int w = 1; w < pg_ctx::MAX_WORKERS; ++w) anim_free_one(ctx->anim_scratch_w[w]);
   ctx->anim_scratch_matches_held = 0;
 }
-static void anim_free_one(pg_ctx* ctx, void*& slot) {
-  AnimScratch* A = static_cast<AnimScratch*>(slot);
-  if (!A) return;
-  void* ptrs[] = {A->mirror_d, A->big_d, A->ranges_d, A->range_out, A->hits_sorted, A->hit_count, A->hoff, A->hit_cursor, A->hits_d, A->slice_d, A->sblk_d, A->sslot_d, A->sbq_d, A->spt_d, A->choff_d, A->list_cnt, A->srefs_d, A->sqry_d, A->recs_d, A->refs_d, A->units_d, A->mem_count, A->moff, A->nch, A->status, A->out, A->mem, A->cm,
-                  A->iscratch, A->order, A->chains, A->S.alns, A->S.a_rrec,
-                  A->S.a_qrec, A->S.idx, A->S.from, A->S.sc, A->wl_d, A->seedbuf, A->seed_total, A->fr_tables, A->fr_pairs,
-                  A->fr_slot_pair, A->fr_off, A->fr_nrows, A->fr_ebase, A->fr_entries, A->fr_rows, A->fr_out, A->fr_list, A->fr_nlist, A->fr_wtmp, A->fr_widx,
-                  A->pn, A->pn_fused, A->pn_n, A->pn_cursor, A->pn_gscratch, A->pn_reqs, A->pn_wide, A->pn_gaps, A->pn_fwd, A->pn_bwd, A->pn_tlog, A->pn_born, A->pn_porder, A->pn_tasks, A->pn_order, A->pn_pieces, A->pn_npieces, A->tr_arena, A->tr_out, A->tr_jobs, A->tr_off, A->tr_cursor, A->tr_cnt};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  delete A;
-  slot = nullptr;
-}
 
-// One batch of ordered pairs (ref_ids grouped).  The seed pass appends every unit's matches to one buffer and counts them
-// per (pair, strand) unit; a scatter then gives every per-match array exactly the slice it needs, which is what lets
-// thousands of units be in flight at once within the HBM budget.
-// If the batch needs more than max_matches, only its first n_done pairs are processed (the caller continues from there).
 static_assert(sizeof(FragRow) == sizeof(pg_anib_row), "FragRow is pg_anib_row");
 static int anib_frag_stage(pg_ctx* ctx, AnimScratch* A, const int32_t* qry_ids, uint32_t n_pairs, const std::vector<uint32_t>& cnt,
                            const PgFragArgs& F, const std::vector<int32_t>& ref_list, const std::vector<uint32_t>& ref_of_pair);
@@ -357,10 +344,23 @@ static int anib_frag_stage(pg_ctx* ctx, AnimScratch* A, const int32_t* qry_ids, 
 // search / forced piece of the walks per thread, the scalar engine with its backpointer store) and the .delta lists
 // (pg_anim_trace.h).  Host work here is list management: sizing the jobs' slabs from the wave engine's own bookkeeping,
 // batching them into the arena, stitching the pieces' paths.
+static int anim_collect_indels(pg_ctx* ctx, AnimScratch* A, uint32_t n_pairs, const std::vector<uint32_t>& moff, const std::vector<uint32_t>& choff,
+                               const std::vector<size_t>& pair_first, PgAlnSink& sink);
+
+// an alignment in forward stream coordinates, half-open -> MUMmer's 1-based closed coordinates within its records, which start
+// at the stream positions ro (reference) and qo (query)
+static pg_anim_alignment to_record(const Aln& a, int32_t ro, int32_t qo) {
+  pg_anim_alignment x;
+  x.rs = a.rs - ro + 1; x.re = a.re - ro;
+  x.qs = a.strand ? a.qe - qo : a.qs - qo + 1;
+  x.qe = a.strand ? a.qs - qo + 1 : a.qe - qo;
+  x.errors = a.errors; x.kept = a.keep;
+  return x;
+}
+
 static int anim_collect(pg_ctx* ctx, AnimScratch* A, const int32_t* ref_ids, const int32_t* qry_ids, uint32_t n_pairs, const pg_anim_result* res,
                         const std::vector<uint32_t>& choff, PgAlnSink& sink) {
   const uint32_t n_units = 2 * n_pairs;
-  int rc;
   std::vector<uint32_t> moff((size_t)n_units + 1);
   PG_HIP(ctx, hipMemcpy(moff.data(), A->moff, moff.size() * 4, hipMemcpyDeviceToHost));
   const size_t total = moff[n_units];
@@ -371,7 +371,6 @@ static int anim_collect(pg_ctx* ctx, AnimScratch* A, const int32_t* ref_ids, con
     PG_HIP(ctx, hipMemcpy(rr.data(), A->S.a_rrec, total * 4, hipMemcpyDeviceToHost));
     PG_HIP(ctx, hipMemcpy(qr.data(), A->S.a_qrec, total * 4, hipMemcpyDeviceToHost));
   }
-  const size_t first_aln = sink.alns.size();
   std::vector<size_t> pair_first(n_pairs);
   for (uint32_t p = 0; p < n_pairs; ++p) {
     if (res[p].status == PG_E_CAPACITY) return pg_fail(ctx, PG_E_CAPACITY, "anim: work buffers overflowed for a pair of the batch");
@@ -380,22 +379,24 @@ static int anim_collect(pg_ctx* ctx, AnimScratch* A, const int32_t* ref_ids, con
     const uint32_t n = (uint32_t)res[p].reserved;
     pair_first[p] = sink.alns.size();
     for (uint32_t i = 0; i < n; ++i) {
-      const Aln& a = al[moff[2 * p] + i];            // forward stream coordinates, half-open
-      const int32_t r_ = rr[moff[2 * p] + i], q_ = qr[moff[2 * p] + i], ro = G.rec_start[r_], qo = H.rec_start[q_];
-      pg_anim_alignment x;
+      const int32_t r_ = rr[moff[2 * p] + i], q_ = qr[moff[2 * p] + i];
+      pg_anim_alignment x = to_record(al[moff[2 * p] + i], G.rec_start[r_], H.rec_start[q_]);
       x.ref_rec = r_; x.qry_rec = q_;
-      x.rs = a.rs - ro + 1; x.re = a.re - ro;
-      x.qs = a.strand ? a.qe - qo : a.qs - qo + 1;
-      x.qe = a.strand ? a.qs - qo + 1 : a.qe - qo;
-      x.errors = a.errors; x.kept = a.keep;
       sink.alns.push_back(x);
     }
     sink.pair_count.push_back(n);
   }
   if (!sink.with_indels) return PG_OK;
   sink.indels.resize(sink.alns.size());
-  const size_t n_wl = choff[n_units];
-  if (!total || !n_wl) return PG_OK;      // no clusters at all: no alignments, nothing to trace
+  if (!total || !choff[n_units]) return PG_OK;      // no clusters at all: no alignments, nothing to trace
+  return anim_collect_indels(ctx, A, n_pairs, moff, choff, pair_first, sink);
+}
+
+// The traceback pass of anim_collect: the .delta list of every record the sink has just received (pair p's start at pair_first[p]).
+static int anim_collect_indels(pg_ctx* ctx, AnimScratch* A, uint32_t n_pairs, const std::vector<uint32_t>& moff, const std::vector<uint32_t>& choff,
+                               const std::vector<size_t>& pair_first, PgAlnSink& sink) {
+  const uint32_t n_units = 2 * n_pairs;
+  const size_t total = moff[n_units], n_wl = choff[n_units];
   // ---- the walks' pieces
   std::vector<pgn::PnAln> pn(total);
   std::vector<int32_t> pn_n(n_units);
@@ -452,7 +453,7 @@ static int anim_collect(pg_ctx* ctx, AnimScratch* A, const int32_t* ref_ids, con
   std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return refs_[a].bytes > refs_[b].bytes; });
   std::vector<std::vector<uint32_t>> rle(jobs.size());
   const uint64_t ARENA = 6ull << 30, OUT_MAX = 192ull << 20;      // bytes of slabs / path entries per launch
-  if (!A->tr_cursor && (rc = regrow(ctx, A->tr_cursor, 2))) return rc;
+  PG_HIP(ctx, A->tr_cursor.reserve(2));
   for (size_t b0 = 0; b0 < order.size();) {
     uint64_t bytes = 0, outs = 0;
     size_t b1 = b0;
@@ -463,14 +464,11 @@ static int anim_collect(pg_ctx* ctx, AnimScratch* A, const int32_t* ref_ids, con
     std::vector<PnTraceJob> hj(nb);
     uint64_t at = 0;
     for (size_t k = 0; k < nb; ++k) { hj[k] = jobs[order[b0 + k]]; hj[k].slab = at; at += refs_[order[b0 + k]].bytes; }
-    if (bytes > A->tr_arena_cap) { if ((rc = regrow(ctx, A->tr_arena, (size_t)bytes))) return rc; A->tr_arena_cap = (size_t)bytes; }
-    if (outs > A->tr_out_cap) { if ((rc = regrow(ctx, A->tr_out, (size_t)outs))) return rc; A->tr_out_cap = (size_t)outs; }
-    if (nb > A->tr_jobs_cap) {
-      if ((rc = regrow(ctx, A->tr_jobs, nb))) return rc;
-      if ((rc = regrow(ctx, A->tr_off, nb))) return rc;
-      if ((rc = regrow(ctx, A->tr_cnt, nb))) return rc;
-      A->tr_jobs_cap = nb;
-    }
+    PG_HIP(ctx, A->tr_arena.reserve((size_t)bytes));
+    PG_HIP(ctx, A->tr_out.reserve((size_t)outs));
+    PG_HIP(ctx, A->tr_jobs.reserve(nb));
+    PG_HIP(ctx, A->tr_off.reserve(nb));
+    PG_HIP(ctx, A->tr_cnt.reserve(nb));
     PG_HIP(ctx, hipMemcpyAsync(A->tr_jobs, hj.data(), nb * sizeof(PnTraceJob), hipMemcpyHostToDevice, cur_stream(ctx)));
     PG_HIP(ctx, hipMemsetAsync(A->tr_cursor, 0, 8, cur_stream(ctx)));
     hipLaunchKernelGGL(anim_trace_kernel, dim3((uint32_t)((nb + 63) / 64)), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, A->tr_jobs, (uint32_t)nb,
@@ -521,87 +519,124 @@ static int anim_collect(pg_ctx* ctx, AnimScratch* A, const int32_t* ref_ids, con
     for (size_t i = 0; i < n_rec; ++i) recs[i] = sink.alns[pair_first[p] + perm[i]];
     for (size_t i = 0; i < n_rec; ++i) { sink.alns[pair_first[p] + i] = recs[i]; sink.indels[pair_first[p] + i] = std::move(lists[perm[i]]); }
   }
-  (void)first_aln;
   return PG_OK;
 }
 
-int pg_anim_run_batch(pg_ctx* ctx, const int32_t* ref_ids, const int32_t* qry_ids, uint32_t n_pairs, int filter_1to1, int maxmatch,
-                      uint64_t max_matches, pg_anim_result* out_host, uint32_t* n_done, const PgFragArgs* frag) {
-  AnimScratch* A = anim_scratch(ctx);
-  int rc;
-  (void)hipGetLastError();   // launch checks below must only see this batch's errors
-  if (frag) {   // fragment mode: a launch holds at most max_slots (pair, fragment) slots
-    uint64_t slots = 0;
-    uint32_t fit = 0;
-    for (uint32_t p = 0; p < n_pairs; ++p) {
-      const PgGenome& Q = ctx->genomes[qry_ids[p]];
-      uint64_t nf = 0;
-      for (uint32_t r = 0; r < Q.n_rec; ++r) nf += ((uint64_t)(Q.rec_start[r + 1] - 1 - Q.rec_start[r]) + frag->fragsize - 1) / frag->fragsize;
-      if (p > 0 && slots + nf > frag->max_slots) break;
-      slots += nf;
-      fit = p + 1;
-    }
-    n_pairs = fit;
-  }
-  uint32_t n_units = 2 * n_pairs;
-  const int qstep = frag ? FRAG_QSTEP : SEED_STEP;   // query-strand sampling of the seed lists
-  std::vector<int32_t> ref_list;
-  std::vector<uint32_t> ref_of_pair(n_pairs);
-  for (uint32_t p = 0; p < n_pairs; ++p) {
-    if (ref_list.empty() || ref_list.back() != ref_ids[p]) ref_list.push_back(ref_ids[p]);
-    ref_of_pair[p] = (uint32_t)ref_list.size() - 1;
-  }
-  const uint32_t n_refs = (uint32_t)ref_list.size();
-  std::vector<RefDesc> refs(n_refs);
+// ---- the batch driver: pg_anim_run_batch and its stages, in launch order --------------------------------------------------
+namespace {
+// What the stages of one call share on the host.  Every vector that is uploaded with an asynchronous copy lives here, so that
+// it outlives the copy.
+struct Batch {
+  pg_ctx* ctx;
+  AnimScratch* A;
+  const int32_t *ref_ids, *qry_ids;   // the call's pairs; the launch processes the first n_pairs of them
+  const PgFragArgs* frag;
+  int filter_1to1, maxmatch;
+  uint64_t max_matches;
+  uint32_t n_pairs = 0, n_units = 0;
+  void set_pairs(uint32_t n) { n_pairs = n; n_units = 2 * n; }   // (frag_limit_pairs and seed_stage shorten the launch)
+  int qstep = SEED_STEP;               // query-strand sampling of the seed lists
+  bool use_mirror = false, use_blocks = false, trace = false;
+  uint32_t blk_slots = SEED_MAX_SLOTS;
+  // descriptors
+  std::vector<int32_t> ref_list;       // distinct references, in the order of ref_ids
+  std::vector<uint32_t> ref_of_pair;
+  std::vector<RefDesc> refs;
+  std::vector<UnitDesc> units;
   std::vector<int32_t> recs;
+  // the seed plan, made again by every attempt of seed_stage
+  std::vector<int32_t> mirror;
+  std::vector<uint8_t> seeded;
+  std::vector<GenomeIdx> LSv;          // snapshot of the genomes' seed lists
+  std::vector<SeedRef> srefs;
+  std::vector<SeedQry> sqry, bqry;
+  std::vector<SeedBlk> blks;
+  std::vector<SeedSlot> bslots;
+  std::vector<int32_t> bpair;
+  uint32_t slots = 256, n_srefs = 0, n_blks = 0, slot_shift = 0;
+  uint32_t slice_stride = 0;           // the slice table is laid out for the whole batch even if only a prefix is seeded again
+  // what the stages leave for the next ones
+  std::vector<uint32_t> cnt, moff, choff;   // per unit: matches, slice offsets (moff.back() = M), cluster offsets
+  std::vector<int32_t> nch;
+  uint32_t total = 0;                  // matches in the append buffer
+  ClusterOut O{};
+};
+
+// the counters of AnimScratch::pn_cursor, zeroed before every extension stage
+enum PnCursor : uint32_t {
+  PNC_UNIT = 0,            // unit cursor of the walks
+  PNC_FORCED_N = 1,        // forced runs recorded ...
+  PNC_FORCED_CUR = 2,      // ... and their cursor
+  PNC_GAP_BIG = 3,         // chain / big-gap cursor
+  PNC_GAP_LANE = 4,        // 4, 5, 6: small gaps by size class
+  PNC_FORCED_LONG = 7,     // forced runs recorded: the long ones
+  PNC_FWD = 8,             // cluster cursor of the forward extensions
+  PNC_REHEARSE = 9,        // unit cursor of the rehearsal
+  PNC_BWD = 10,            // cluster cursor of the backward searches
+  PNC_GAP_WAVE = 11,       // gaps left to the wave engine
+  PNC_WIDE_N = 12, PNC_WIDE_CUR = 13,       // wide forced runs: count / cursor
+  PNC_HUGE_N = 14, PNC_HUGE_CUR = 15,       // huge ones
+  PNC_STRIPS_N = 16, PNC_STRIPS_CUR = 17,   // the strips' list
+  PNC_WORDS = 24
+};
+}  // namespace
+
+// fragment mode: a launch holds at most max_slots (pair, fragment) slots
+static void frag_limit_pairs(Batch& B) {
+  pg_ctx* ctx = B.ctx;
+  uint64_t slots = 0;
+  uint32_t fit = 0;
+  for (uint32_t p = 0; p < B.n_pairs; ++p) {
+    const PgGenome& Q = ctx->genomes[B.qry_ids[p]];
+    uint64_t nf = 0;
+    for (uint32_t r = 0; r < Q.n_rec; ++r) nf += ((uint64_t)(Q.rec_start[r + 1] - 1 - Q.rec_start[r]) + B.frag->fragsize - 1) / B.frag->fragsize;
+    if (p > 0 && slots + nf > B.frag->max_slots) break;
+    slots += nf;
+    fit = p + 1;
+  }
+  B.set_pairs(fit);
+}
+
+// RefDesc per distinct reference, UnitDesc per (pair, strand), the records table behind both; grows what is sized by them; uploads
+static int build_descriptors(Batch& B) {
+  pg_ctx* ctx = B.ctx;
+  AnimScratch* A = B.A;
+  const uint32_t n_pairs = B.n_pairs, n_units = B.n_units;
+  B.ref_of_pair.resize(n_pairs);
+  for (uint32_t p = 0; p < n_pairs; ++p) {
+    if (B.ref_list.empty() || B.ref_list.back() != B.ref_ids[p]) B.ref_list.push_back(B.ref_ids[p]);
+    B.ref_of_pair[p] = (uint32_t)B.ref_list.size() - 1;
+  }
+  const uint32_t n_refs = (uint32_t)B.ref_list.size();
+  std::vector<RefDesc>& refs = B.refs;
+  std::vector<int32_t>& recs = B.recs;
+  refs.resize(n_refs);
   std::vector<uint32_t> ref_rec_off(n_refs), qry_rec_off(n_pairs);
-  int32_t max_rlen = 0, max_qlen = 0;
   for (uint32_t r = 0; r < n_refs; ++r) {
-    const PgGenome& G = ctx->genomes[ref_list[r]];
+    const PgGenome& G = ctx->genomes[B.ref_list[r]];
     refs[r].codes = ctx->d_codes + G.arena_start / 16;
     refs[r].mask = ctx->d_mask + G.arena_start / 32;
     refs[r].len = (int32_t)G.stream_len;
     refs[r].n_rec = (int32_t)G.n_rec;
     ref_rec_off[r] = (uint32_t)recs.size();
     recs.insert(recs.end(), G.rec_start.begin(), G.rec_start.end());
-    if ((int32_t)G.stream_len > max_rlen) max_rlen = (int32_t)G.stream_len;
   }
   for (uint32_t p = 0; p < n_pairs; ++p) {
-    const PgGenome& Q = ctx->genomes[qry_ids[p]];
+    const PgGenome& Q = ctx->genomes[B.qry_ids[p]];
     qry_rec_off[p] = (uint32_t)recs.size();
     recs.insert(recs.end(), Q.rec_start.begin(), Q.rec_start.end());
-    if ((int32_t)Q.stream_len > max_qlen) max_qlen = (int32_t)Q.stream_len;
   }
-  if (recs.size() > A->recs) { if ((rc = regrow(ctx, A->recs_d, recs.size()))) return rc; A->recs = recs.size(); }
-  if (n_refs > A->refs) {
-    if ((rc = regrow(ctx, A->refs_d, n_refs))) return rc;
-    if ((rc = regrow(ctx, A->srefs_d, n_refs))) return rc;
-    A->refs = n_refs;
-  }
-  if (n_units > A->units) {
-    if ((rc = regrow(ctx, A->units_d, n_units))) return rc;
-    if ((rc = regrow(ctx, A->mem_count, n_units))) return rc;
-    if ((rc = regrow(ctx, A->moff, (size_t)n_units + 1))) return rc;
-    if ((rc = regrow(ctx, A->choff_d, (size_t)n_units + 1))) return rc;
-    if ((rc = regrow(ctx, A->hit_count, n_units))) return rc;
-    if ((rc = regrow(ctx, A->hoff, (size_t)n_units + 1))) return rc;
-    if ((rc = regrow(ctx, A->hit_cursor, n_units))) return rc;
-    if ((rc = regrow(ctx, A->nch, n_units))) return rc;
-    A->units = n_units;
-  }
-  if (n_pairs > A->pairs) {
-    if ((rc = regrow(ctx, A->status, n_pairs))) return rc;
-    if ((rc = regrow(ctx, A->sqry_d, n_pairs))) return rc;
-    if ((rc = regrow(ctx, A->out, n_pairs))) return rc;
-    if ((rc = regrow(ctx, A->mirror_d, n_pairs))) return rc;
-    A->pairs = n_pairs;
-  }
+  PG_HIP(ctx, A->recs_d.reserve(recs.size()));
+  PG_HIP(ctx, reserve_all(n_refs, n_refs, A->refs_d, A->srefs_d));
+  PG_HIP(ctx, reserve_all(n_units, n_units, A->units_d, A->mem_count, A->hit_count, A->hit_cursor, A->nch));
+  PG_HIP(ctx, reserve_all((size_t)n_units + 1, (size_t)n_units + 1, A->moff, A->choff_d, A->hoff));
+  PG_HIP(ctx, reserve_all(n_pairs, n_pairs, A->status, A->sqry_d, A->out, A->mirror_d));
   for (uint32_t r = 0; r < n_refs; ++r) refs[r].rec_start = A->recs_d + ref_rec_off[r];
-  std::vector<UnitDesc> units(n_units);
+  B.units.resize(n_units);
   for (uint32_t p = 0; p < n_pairs; ++p) {
-    const PgGenome& Q = ctx->genomes[qry_ids[p]];
+    const PgGenome& Q = ctx->genomes[B.qry_ids[p]];
     for (int s = 0; s < 2; ++s) {
-      UnitDesc& U = units[2 * p + s];
+      UnitDesc& U = B.units[2 * p + s];
       U.codes = ctx->d_codes + Q.arena_start / 16;
       U.mask = ctx->d_mask + Q.arena_start / 32;
       U.len = (int32_t)Q.stream_len;
@@ -609,186 +644,198 @@ int pg_anim_run_batch(pg_ctx* ctx, const int32_t* ref_ids, const int32_t* qry_id
       U.n_rec = (int32_t)Q.n_rec;
       U.strand = s;
       U.pair = (int32_t)p;
-      U.ref = (int32_t)ref_of_pair[p];
+      U.ref = (int32_t)B.ref_of_pair[p];
     }
   }
   PG_HIP(ctx, hipMemcpyAsync(A->recs_d, recs.data(), recs.size() * 4, hipMemcpyHostToDevice, cur_stream(ctx)));
   PG_HIP(ctx, hipMemcpyAsync(A->refs_d, refs.data(), n_refs * sizeof(RefDesc), hipMemcpyHostToDevice, cur_stream(ctx)));
-  PG_HIP(ctx, hipMemcpyAsync(A->units_d, units.data(), n_units * sizeof(UnitDesc), hipMemcpyHostToDevice, cur_stream(ctx)));
-  // seeding: LDS-resident reference groups, streamed query groups; one pass appends (unit, match) records and the
-  // per-unit counts it leaves are exact even if the buffer overflowed.
-  // Roles: when the launch holds a pair in BOTH directions, (A, B) and (B, A), only one of them is seeded — the maximal exact
-  // matches of the two are the same set, and anim_hit_kernel appends each match a second time, transposed, for the partner
-  // (`mirror`).  The seeded direction is the one whose reference has more pairs in the launch (longer query streams per LDS
-  // table); equal counts: decided by the ids' parity, so that every genome is the table for half of its partners.
-  std::vector<int32_t> mirror(n_pairs);
-  std::vector<uint8_t> seeded(n_pairs);
-  std::vector<SeedRef> srefs;
-  std::vector<SeedQry> sqry(n_pairs);
-  std::vector<GenomeIdx> LSv;
-  uint32_t slots = 256, n_srefs = 0, n_blks = 0, slot_shift = 0;
-  const uint32_t slice_stride = n_pairs;   // the table is laid out for the whole batch even if only a prefix is seeded again
-  const bool use_mirror = !frag && !pg_dev_env("PYANI_ANIM_NO_MIRROR");
-  // Seeding kernel: ANIm uses the block kernel (anim_seed_kernel); fragment mode — and ANIm under the development switch
-  // PYANI_SEED_PER_PAIR=1, which tests hold against it — the per-pair kernel (anim_seed_pair_kernel).  PYANI_SEED_BLOCK_SLOTS
-  // (development): the table size a block is planned for (default SEED_MAX_SLOTS).
-  const bool use_blocks = !frag && !(pg_dev_env("PYANI_SEED_PER_PAIR") && atoi(pg_dev_env("PYANI_SEED_PER_PAIR")) == 1);
-  uint32_t blk_slots = SEED_MAX_SLOTS;
-  if (pg_dev_env("PYANI_SEED_BLOCK_SLOTS")) {
-    const int want = atoi(pg_dev_env("PYANI_SEED_BLOCK_SLOTS"));
-    blk_slots = want >= 512 && want <= (int)SEED_MAX_SLOTS ? (uint32_t)want : SEED_MAX_SLOTS;
-  }
-  std::vector<SeedBlk> blks;
-  std::vector<SeedSlot> bslots;
-  std::vector<SeedQry> bqry;
-  std::vector<int32_t> bpair;
-  auto prepare = [&](uint32_t limit) -> int {   // roles, seed lists and descriptors for the pairs [0, limit)
-    std::fill(mirror.begin(), mirror.end(), -1);
-    std::fill(seeded.begin(), seeded.end(), (uint8_t)0);
-    std::fill(seeded.begin(), seeded.begin() + limit, (uint8_t)1);
-    if (use_mirror && limit > 1) {
-      std::vector<uint32_t> deg(ctx->genomes.size(), 0);
-      for (uint32_t p = 0; p < limit; ++p) ++deg[ref_ids[p]];
-      std::vector<uint32_t> idx(limit);
-      for (uint32_t p = 0; p < limit; ++p) idx[p] = p;
-      auto key = [&](uint32_t p) {   // unordered pair, then direction, then position: partners end up next to each other
-        const uint32_t a = (uint32_t)ref_ids[p], b = (uint32_t)qry_ids[p];
-        return std::make_tuple(a < b ? a : b, a < b ? b : a, a < b ? 0 : 1, p);
-      };
-      std::sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) { return key(x) < key(y); });
-      for (uint32_t i = 0; i < limit;) {
-        uint32_t j = i;
-        while (j < limit && std::get<0>(key(idx[j])) == std::get<0>(key(idx[i])) && std::get<1>(key(idx[j])) == std::get<1>(key(idx[i]))) ++j;
-        uint32_t m = i;   // [i, m): direction min -> max, [m, j): the other direction (a pair listed twice pairs up once)
-        while (m < j && std::get<2>(key(idx[m])) == 0) ++m;
-        if (ref_ids[idx[i]] != qry_ids[idx[i]])
-          for (uint32_t k = 0; i + k < m && m + k < j; ++k) {
-            const uint32_t p = idx[i + k], p2 = idx[m + k];
-            const uint32_t a = (uint32_t)ref_ids[p], b = (uint32_t)qry_ids[p];
-            const bool first = deg[a] != deg[b] ? deg[a] > deg[b] : ((a < b) != (((a + b) & 1u) != 0));
-            if (first) { mirror[p] = (int32_t)p2; seeded[p2] = 0; } else { mirror[p2] = (int32_t)p; seeded[p] = 0; }
-          }
-        i = j;
-      }
-    }
-    std::vector<int32_t> seed_refs, seed_qrys;
-    for (uint32_t p = 0; p < limit; ++p)
-      if (seeded[p]) {
-        if (seed_refs.empty() || seed_refs.back() != ref_ids[p]) seed_refs.push_back(ref_ids[p]);
-        seed_qrys.push_back(qry_ids[p]);
-      }
-    std::sort(seed_qrys.begin(), seed_qrys.end());
-    seed_qrys.erase(std::unique(seed_qrys.begin(), seed_qrys.end()), seed_qrys.end());
-    int rc2;
-    if ((rc2 = anim_ensure_lists(ctx, A, seed_refs, seed_qrys, qstep))) return rc2;
-    {   // (entries of genomes this batch uses are complete and never change while the genomes are resident; the vector itself
-        // may be resized by another worker, so take the pointers under the lock)
-      std::lock_guard<std::mutex> lk(ctx->anim_mu);
-      LSv = anim_lists(ctx)->gidx;
-    }
-    if (use_blocks) {
-      // Slots: per run of seeded pairs with one reference, a pair listed k times goes to the run's k-th slot (a slot's queries are
-      // distinct).  Blocks: consecutive slots while their largest groups sum to at most half the table and there are at most
-      // SEED_BLOCK_SLOTS of them; per block, its distinct queries (sorted) and the [slot][query] -> pair table.
-      std::vector<int32_t> slot_ref;
-      std::vector<std::vector<uint32_t>> slot_pairs;
-      std::unordered_map<int32_t, uint32_t> occ;
-      uint32_t run_first = 0;
-      int32_t run_ref = -1;
-      for (uint32_t p = 0; p < limit; ++p) {
-        if (!seeded[p]) continue;
-        if (ref_ids[p] != run_ref) { run_ref = ref_ids[p]; run_first = (uint32_t)slot_ref.size(); occ.clear(); }
-        const uint32_t k = occ[qry_ids[p]]++;
-        if (run_first + k == slot_ref.size()) { slot_ref.push_back(run_ref); slot_pairs.emplace_back(); }
-        slot_pairs[run_first + k].push_back(p);
-      }
-      blks.clear(); bslots.clear(); bqry.clear(); bpair.clear();
-      uint32_t max_sum = 1;
-      for (uint32_t s0 = 0; s0 < slot_ref.size();) {
-        uint32_t s1 = s0, sum = 0;
-        while (s1 < slot_ref.size() && s1 - s0 < (uint32_t)SEED_BLOCK_SLOTS) {
-          const uint32_t w = LSv[slot_ref[s1]].ref_max_fine;
-          if (s1 > s0 && 2 * (sum + w) > blk_slots) break;
-          sum += w;
-          ++s1;
-        }
-        max_sum = sum > max_sum ? sum : max_sum;
-        std::vector<int32_t> qs;
-        for (uint32_t t = s0; t < s1; ++t) {
-          const PgGenome& G = ctx->genomes[slot_ref[t]];
-          if (G.stream_len >= SEED_TAB_POS_MASK)
-            return pg_fail(ctx, PG_E_CAPACITY, "anim seeding: a reference position does not fit the block table's 30 bits");
-          bslots.push_back(SeedSlot{LSv[slot_ref[t]].ref_list, LSv[slot_ref[t]].ref_goff});
-          for (uint32_t p : slot_pairs[t]) qs.push_back(qry_ids[p]);
-        }
-        std::sort(qs.begin(), qs.end());
-        qs.erase(std::unique(qs.begin(), qs.end()), qs.end());
-        if (qs.size() >= (1u << 25)) return pg_fail(ctx, PG_E_CAPACITY, "anim seeding: more than 2^25 queries in a block");
-        const SeedBlk Bk{s0, s1, (uint32_t)bqry.size(), (uint32_t)(bqry.size() + qs.size()), (uint32_t)bpair.size()};
-        for (int32_t qg : qs) bqry.push_back(SeedQry{LSv[qg].qry_list, LSv[qg].qry_goff});
-        bpair.resize(bpair.size() + (size_t)(s1 - s0) * qs.size(), -1);
-        for (uint32_t t = s0; t < s1; ++t)
-          for (uint32_t p : slot_pairs[t]) {
-            const size_t qi = (size_t)(std::lower_bound(qs.begin(), qs.end(), qry_ids[p]) - qs.begin());
-            bpair[Bk.pair_tab + (size_t)(t - s0) * qs.size() + qi] = (int32_t)p;
-          }
-        blks.push_back(Bk);
-        s0 = s1;
-      }
-      if (bpair.size() > (size_t)0x7FFFFFFF) return pg_fail(ctx, PG_E_CAPACITY, "anim seeding: block pair tables too large");
-      slots = 256;
-      while (slots < 2 * max_sum) slots <<= 1;
-      if (slots > SEED_MAX_SLOTS)
-        return pg_fail(ctx, PG_E_CAPACITY, "anim seeding: a reference k-mer group does not fit the LDS table (genome too large or too repetitive)");
-      slot_shift = 0;
-      while ((slots << slot_shift) < (1u << (32 - SEED_GROUP_BITS))) ++slot_shift;
-      n_blks = (uint32_t)blks.size();
-      int rc3;
-      if (n_blks > A->sblk_cap) { if ((rc3 = regrow(ctx, A->sblk_d, n_blks))) return rc3; A->sblk_cap = n_blks; }
-      if (bslots.size() > A->sslot_cap) { if ((rc3 = regrow(ctx, A->sslot_d, bslots.size()))) return rc3; A->sslot_cap = bslots.size(); }
-      if (bqry.size() > A->sbq_cap) { if ((rc3 = regrow(ctx, A->sbq_d, bqry.size()))) return rc3; A->sbq_cap = bqry.size(); }
-      if (bpair.size() > A->spt_cap) { if ((rc3 = regrow(ctx, A->spt_d, bpair.size()))) return rc3; A->spt_cap = bpair.size(); }
-      if (n_blks) {
-        PG_HIP(ctx, hipMemcpyAsync(A->sblk_d, blks.data(), n_blks * sizeof(SeedBlk), hipMemcpyHostToDevice, cur_stream(ctx)));
-        PG_HIP(ctx, hipMemcpyAsync(A->sslot_d, bslots.data(), bslots.size() * sizeof(SeedSlot), hipMemcpyHostToDevice, cur_stream(ctx)));
-        PG_HIP(ctx, hipMemcpyAsync(A->sbq_d, bqry.data(), bqry.size() * sizeof(SeedQry), hipMemcpyHostToDevice, cur_stream(ctx)));
-        PG_HIP(ctx, hipMemcpyAsync(A->spt_d, bpair.data(), bpair.size() * sizeof(int32_t), hipMemcpyHostToDevice, cur_stream(ctx)));
-      }
-      PG_HIP(ctx, hipMemcpyAsync(A->mirror_d, mirror.data(), n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, cur_stream(ctx)));
-      return PG_OK;
-    }
-    uint32_t max_group = 1;
-    for (int32_t g : seed_refs) if (LSv[g].ref_max > max_group) max_group = LSv[g].ref_max;
-    slots = 256;
-    while (slots < 2 * max_group) slots <<= 1;
-    if (pg_dev_env("PYANI_SEED_SLOTS_MIN")) {   // development: a larger LDS table (lower load, shorter probe sequences, fewer workgroups per CU)
-      const uint32_t want = (uint32_t)atoi(pg_dev_env("PYANI_SEED_SLOTS_MIN"));
-      while (slots < want && slots < SEED_MAX_SLOTS) slots <<= 1;
-    }
-    if (slots > SEED_MAX_SLOTS)
-      return pg_fail(ctx, PG_E_CAPACITY, "anim seeding: a reference k-mer group does not fit the LDS table (genome too large or too repetitive)");
-    if (slice_stride > A->slice_pairs) {
-      if ((rc2 = regrow(ctx, A->slice_d, (size_t)slice_stride * SEED_CGROUPS))) return rc2;
-      A->slice_pairs = slice_stride;
-    }
-    srefs.clear();   // one entry per reference with seeded pairs: [pair_begin, pair_end) spans them (pairs in between that
-                     // are not seeded have empty slices)
-    for (uint32_t p = 0; p < n_pairs; ++p) {
-      sqry[p] = SeedQry{nullptr, nullptr};
-      if (p >= limit || !seeded[p]) continue;
-      const GenomeIdx& X = LSv[qry_ids[p]];
-      sqry[p] = qstep == 1 ? SeedQry{X.qry_list1, X.qry_goff1} : SeedQry{X.qry_list, X.qry_goff};
-      if (srefs.empty() || srefs.back().list != LSv[ref_ids[p]].ref_list)
-        srefs.push_back(SeedRef{LSv[ref_ids[p]].ref_list, LSv[ref_ids[p]].ref_goff, p, p + 1});
-      srefs.back().pair_end = p + 1;
-    }
-    n_srefs = (uint32_t)srefs.size();
-    PG_HIP(ctx, hipMemcpyAsync(A->sqry_d, sqry.data(), n_pairs * sizeof(SeedQry), hipMemcpyHostToDevice, cur_stream(ctx)));
-    PG_HIP(ctx, hipMemcpyAsync(A->mirror_d, mirror.data(), n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, cur_stream(ctx)));
-    if (n_srefs) PG_HIP(ctx, hipMemcpyAsync(A->srefs_d, srefs.data(), n_srefs * sizeof(SeedRef), hipMemcpyHostToDevice, cur_stream(ctx)));
-    hipLaunchKernelGGL(anim_slice_kernel, dim3(n_pairs), dim3(256), 0, cur_stream(ctx), A->sqry_d, slice_stride, A->slice_d);
-    return PG_OK;
+  PG_HIP(ctx, hipMemcpyAsync(A->units_d, B.units.data(), n_units * sizeof(UnitDesc), hipMemcpyHostToDevice, cur_stream(ctx)));
+  return PG_OK;
+}
+
+// Roles: when the launch holds a pair in BOTH directions, (A, B) and (B, A), only one of them is seeded — the maximal exact
+// matches of the two are the same set, and anim_hit_kernel appends each match a second time, transposed, for the partner
+// (`mirror`).  The seeded direction is the one whose reference has more pairs in the launch (longer query streams per LDS
+// table); equal counts: decided by the ids' parity, so that every genome is the table for half of its partners.
+static void assign_mirrors(Batch& B, uint32_t limit) {
+  const int32_t *ref_ids = B.ref_ids, *qry_ids = B.qry_ids;
+  std::vector<int32_t>& mirror = B.mirror;
+  std::vector<uint8_t>& seeded = B.seeded;
+  std::fill(mirror.begin(), mirror.end(), -1);
+  std::fill(seeded.begin(), seeded.end(), (uint8_t)0);
+  std::fill(seeded.begin(), seeded.begin() + limit, (uint8_t)1);
+  if (!B.use_mirror || limit <= 1) return;
+  std::vector<uint32_t> deg(B.ctx->genomes.size(), 0);
+  for (uint32_t p = 0; p < limit; ++p) ++deg[ref_ids[p]];
+  std::vector<uint32_t> idx(limit);
+  for (uint32_t p = 0; p < limit; ++p) idx[p] = p;
+  auto key = [&](uint32_t p) {   // unordered pair, then direction, then position: partners end up next to each other
+    const uint32_t a = (uint32_t)ref_ids[p], b = (uint32_t)qry_ids[p];
+    return std::make_tuple(a < b ? a : b, a < b ? b : a, a < b ? 0 : 1, p);
   };
+  std::sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) { return key(x) < key(y); });
+  for (uint32_t i = 0; i < limit;) {
+    uint32_t j = i;
+    while (j < limit && std::get<0>(key(idx[j])) == std::get<0>(key(idx[i])) && std::get<1>(key(idx[j])) == std::get<1>(key(idx[i]))) ++j;
+    uint32_t m = i;   // [i, m): direction min -> max, [m, j): the other direction (a pair listed twice pairs up once)
+    while (m < j && std::get<2>(key(idx[m])) == 0) ++m;
+    if (ref_ids[idx[i]] != qry_ids[idx[i]])
+      for (uint32_t k = 0; i + k < m && m + k < j; ++k) {
+        const uint32_t p = idx[i + k], p2 = idx[m + k];
+        const uint32_t a = (uint32_t)ref_ids[p], b = (uint32_t)qry_ids[p];
+        const bool first = deg[a] != deg[b] ? deg[a] > deg[b] : ((a < b) != (((a + b) & 1u) != 0));
+        if (first) { mirror[p] = (int32_t)p2; seeded[p2] = 0; } else { mirror[p2] = (int32_t)p; seeded[p] = 0; }
+      }
+    i = j;
+  }
+}
+
+// The block kernel's plan for the seeded pairs of [0, limit), and its upload.
+// Slots: per run of seeded pairs with one reference, a pair listed k times goes to the run's k-th slot (a slot's queries are
+// distinct).  Blocks: consecutive slots while their largest groups sum to at most half the table and there are at most
+// SEED_BLOCK_SLOTS of them; per block, its distinct queries (sorted) and the [slot][query] -> pair table.
+static int plan_seed_blocks(Batch& B, uint32_t limit) {
+  pg_ctx* ctx = B.ctx;
+  AnimScratch* A = B.A;
+  const int32_t *ref_ids = B.ref_ids, *qry_ids = B.qry_ids;
+  const std::vector<GenomeIdx>& LSv = B.LSv;
+  std::vector<int32_t> slot_ref;
+  std::vector<std::vector<uint32_t>> slot_pairs;
+  std::unordered_map<int32_t, uint32_t> occ;
+  uint32_t run_first = 0;
+  int32_t run_ref = -1;
+  for (uint32_t p = 0; p < limit; ++p) {
+    if (!B.seeded[p]) continue;
+    if (ref_ids[p] != run_ref) { run_ref = ref_ids[p]; run_first = (uint32_t)slot_ref.size(); occ.clear(); }
+    const uint32_t k = occ[qry_ids[p]]++;
+    if (run_first + k == slot_ref.size()) { slot_ref.push_back(run_ref); slot_pairs.emplace_back(); }
+    slot_pairs[run_first + k].push_back(p);
+  }
+  std::vector<SeedBlk>& blks = B.blks;
+  std::vector<SeedSlot>& bslots = B.bslots;
+  std::vector<SeedQry>& bqry = B.bqry;
+  std::vector<int32_t>& bpair = B.bpair;
+  blks.clear(); bslots.clear(); bqry.clear(); bpair.clear();
+  uint32_t max_sum = 1;
+  for (uint32_t s0 = 0; s0 < slot_ref.size();) {
+    uint32_t s1 = s0, sum = 0;
+    while (s1 < slot_ref.size() && s1 - s0 < (uint32_t)SEED_BLOCK_SLOTS) {
+      const uint32_t w = LSv[slot_ref[s1]].ref_max_fine;
+      if (s1 > s0 && 2 * (sum + w) > B.blk_slots) break;
+      sum += w;
+      ++s1;
+    }
+    max_sum = sum > max_sum ? sum : max_sum;
+    std::vector<int32_t> qs;
+    for (uint32_t t = s0; t < s1; ++t) {
+      const PgGenome& G = ctx->genomes[slot_ref[t]];
+      if (G.stream_len >= SEED_TAB_POS_MASK)
+        return pg_fail(ctx, PG_E_CAPACITY, "anim seeding: a reference position does not fit the block table's 30 bits");
+      bslots.push_back(SeedSlot{LSv[slot_ref[t]].ref_list, LSv[slot_ref[t]].ref_goff});
+      for (uint32_t p : slot_pairs[t]) qs.push_back(qry_ids[p]);
+    }
+    std::sort(qs.begin(), qs.end());
+    qs.erase(std::unique(qs.begin(), qs.end()), qs.end());
+    if (qs.size() >= (1u << 25)) return pg_fail(ctx, PG_E_CAPACITY, "anim seeding: more than 2^25 queries in a block");
+    const SeedBlk Bk{s0, s1, (uint32_t)bqry.size(), (uint32_t)(bqry.size() + qs.size()), (uint32_t)bpair.size()};
+    for (int32_t qg : qs) bqry.push_back(SeedQry{LSv[qg].qry_list, LSv[qg].qry_goff});
+    bpair.resize(bpair.size() + (size_t)(s1 - s0) * qs.size(), -1);
+    for (uint32_t t = s0; t < s1; ++t)
+      for (uint32_t p : slot_pairs[t]) {
+        const size_t qi = (size_t)(std::lower_bound(qs.begin(), qs.end(), qry_ids[p]) - qs.begin());
+        bpair[Bk.pair_tab + (size_t)(t - s0) * qs.size() + qi] = (int32_t)p;
+      }
+    blks.push_back(Bk);
+    s0 = s1;
+  }
+  if (bpair.size() > (size_t)0x7FFFFFFF) return pg_fail(ctx, PG_E_CAPACITY, "anim seeding: block pair tables too large");
+  B.slots = 256;
+  while (B.slots < 2 * max_sum) B.slots <<= 1;
+  if (B.slots > SEED_MAX_SLOTS)
+    return pg_fail(ctx, PG_E_CAPACITY, "anim seeding: a reference k-mer group does not fit the LDS table (genome too large or too repetitive)");
+  B.slot_shift = 0;
+  while ((B.slots << B.slot_shift) < (1u << (32 - SEED_GROUP_BITS))) ++B.slot_shift;
+  const uint32_t n_blks = B.n_blks = (uint32_t)blks.size();
+  PG_HIP(ctx, A->sblk_d.reserve(n_blks));
+  PG_HIP(ctx, A->sslot_d.reserve(bslots.size()));
+  PG_HIP(ctx, A->sbq_d.reserve(bqry.size()));
+  PG_HIP(ctx, A->spt_d.reserve(bpair.size()));
+  if (n_blks) {
+    PG_HIP(ctx, hipMemcpyAsync(A->sblk_d, blks.data(), n_blks * sizeof(SeedBlk), hipMemcpyHostToDevice, cur_stream(ctx)));
+    PG_HIP(ctx, hipMemcpyAsync(A->sslot_d, bslots.data(), bslots.size() * sizeof(SeedSlot), hipMemcpyHostToDevice, cur_stream(ctx)));
+    PG_HIP(ctx, hipMemcpyAsync(A->sbq_d, bqry.data(), bqry.size() * sizeof(SeedQry), hipMemcpyHostToDevice, cur_stream(ctx)));
+    PG_HIP(ctx, hipMemcpyAsync(A->spt_d, bpair.data(), bpair.size() * sizeof(int32_t), hipMemcpyHostToDevice, cur_stream(ctx)));
+  }
+  PG_HIP(ctx, hipMemcpyAsync(A->mirror_d, B.mirror.data(), B.n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, cur_stream(ctx)));
+  return PG_OK;
+}
+
+// The per-pair kernel's plan for the seeded pairs of [0, limit): table size, one SeedRef per reference of seed_refs, the slice table.
+static int plan_seed_pairs(Batch& B, uint32_t limit, const std::vector<int32_t>& seed_refs) {
+  pg_ctx* ctx = B.ctx;
+  AnimScratch* A = B.A;
+  const std::vector<GenomeIdx>& LSv = B.LSv;
+  const uint32_t n_pairs = B.n_pairs;
+  uint32_t max_group = 1;
+  for (int32_t g : seed_refs) if (LSv[g].ref_max > max_group) max_group = LSv[g].ref_max;
+  B.slots = 256;
+  while (B.slots < 2 * max_group) B.slots <<= 1;
+  if (B.slots > SEED_MAX_SLOTS)
+    return pg_fail(ctx, PG_E_CAPACITY, "anim seeding: a reference k-mer group does not fit the LDS table (genome too large or too repetitive)");
+  PG_HIP(ctx, A->slice_d.reserve((size_t)B.slice_stride * SEED_CGROUPS));
+  B.srefs.clear();   // one entry per reference with seeded pairs: [pair_begin, pair_end) spans them (pairs in between that
+                     // are not seeded have empty slices)
+  for (uint32_t p = 0; p < n_pairs; ++p) {
+    B.sqry[p] = SeedQry{nullptr, nullptr};
+    if (p >= limit || !B.seeded[p]) continue;
+    const GenomeIdx& X = LSv[B.qry_ids[p]];
+    B.sqry[p] = B.qstep == 1 ? SeedQry{X.qry_list1, X.qry_goff1} : SeedQry{X.qry_list, X.qry_goff};
+    if (B.srefs.empty() || B.srefs.back().list != LSv[B.ref_ids[p]].ref_list)
+      B.srefs.push_back(SeedRef{LSv[B.ref_ids[p]].ref_list, LSv[B.ref_ids[p]].ref_goff, p, p + 1});
+    B.srefs.back().pair_end = p + 1;
+  }
+  B.n_srefs = (uint32_t)B.srefs.size();
+  PG_HIP(ctx, hipMemcpyAsync(A->sqry_d, B.sqry.data(), n_pairs * sizeof(SeedQry), hipMemcpyHostToDevice, cur_stream(ctx)));
+  PG_HIP(ctx, hipMemcpyAsync(A->mirror_d, B.mirror.data(), n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, cur_stream(ctx)));
+  if (B.n_srefs) PG_HIP(ctx, hipMemcpyAsync(A->srefs_d, B.srefs.data(), B.n_srefs * sizeof(SeedRef), hipMemcpyHostToDevice, cur_stream(ctx)));
+  hipLaunchKernelGGL(anim_slice_kernel, dim3(n_pairs), dim3(256), 0, cur_stream(ctx), A->sqry_d, B.slice_stride, A->slice_d);
+  return PG_OK;
+}
+
+// roles, seed lists and the seeding kernel's plan for the pairs [0, limit)
+static int plan_seeding(Batch& B, uint32_t limit) {
+  pg_ctx* ctx = B.ctx;
+  assign_mirrors(B, limit);
+  std::vector<int32_t> seed_refs, seed_qrys;
+  for (uint32_t p = 0; p < limit; ++p)
+    if (B.seeded[p]) {
+      if (seed_refs.empty() || seed_refs.back() != B.ref_ids[p]) seed_refs.push_back(B.ref_ids[p]);
+      seed_qrys.push_back(B.qry_ids[p]);
+    }
+  std::sort(seed_qrys.begin(), seed_qrys.end());
+  seed_qrys.erase(std::unique(seed_qrys.begin(), seed_qrys.end()), seed_qrys.end());
+  int rc;
+  if ((rc = anim_ensure_lists(ctx, B.A, seed_refs, seed_qrys, B.qstep))) return rc;
+  {   // (entries of genomes this batch uses are complete and never change while the genomes are resident; the vector itself
+      // may be resized by another worker, so take the pointers under the lock)
+    std::lock_guard<std::mutex> lk(ctx->anim_mu);
+    B.LSv = anim_lists(ctx)->gidx;
+  }
+  return B.use_blocks ? plan_seed_blocks(B, limit) : plan_seed_pairs(B, limit, seed_refs);
+}
+
+// Seeding: LDS-resident reference groups, streamed query groups; one pass appends (unit, match) records and the per-unit
+// counts it leaves are exact even if the buffer overflowed.  Leaves B.cnt and B.total, and the launch cut down to the pairs
+// whose matches fit max_matches.
+static int seed_stage(Batch& B) {
+  pg_ctx* ctx = B.ctx;
+  AnimScratch* A = B.A;
+  const PgFragArgs* frag = B.frag;
+  const int qstep = B.qstep;
+  B.mirror.resize(B.n_pairs);
+  B.seeded.resize(B.n_pairs);
+  B.sqry.resize(B.n_pairs);
+  B.slice_stride = B.n_pairs;
   if (!A->lds_attr_set) {   // per context = per device (the attribute is a property of the function ON a device)
     PG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(anim_seed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)(SEED_MAX_SLOTS * 8 + SEED_STAGE_BYTES)));
@@ -800,42 +847,35 @@ int pg_anim_run_batch(pg_ctx* ctx, const int32_t* ref_ids, const int32_t* qry_id
   // than the call can produce: a pair of genomes cannot have more maximal matches than a quarter of its bases (a one-pair call
   // — smoke(), pg_anim_pair_alignments — used to reserve 3 x 8 GB for a few MB of matches).  Both grow on overflow (below).
   size_t call_bound = 0;
-  for (uint32_t p = 0; p < n_pairs && call_bound <= max_matches; ++p)
-    call_bound += (size_t)(ctx->genomes[ref_ids[p]].stream_len + ctx->genomes[qry_ids[p]].stream_len) / 4 + 8192;
-  const size_t budget = call_bound < max_matches ? call_bound : (size_t)max_matches;
-  if (!A->seed_total) {
-    if ((rc = regrow(ctx, A->seed_total, 2))) return rc;
-  }
-  if (budget + 1024 > A->seed_cap) {
-    A->seed_cap = budget + 1024;
-    if ((rc = regrow(ctx, A->seedbuf, A->seed_cap))) return rc;
-  }
-  std::vector<uint32_t> cnt(n_units), moff;
-  uint32_t total = 0, pairs_fit = 0;
-  // hit buffer: the matches of the budget plus the chance 16-mer hits of unrelated pairs (~1200 per 5 Mb unit)
-  {
-    const size_t want = budget + (size_t)(frag ? 8 * 4096 : 4096) * n_units + 1024;   // (every position sampled: 5 x the chance hits)
-    if (want > A->hit_cap) {
-      if ((rc = regrow(ctx, A->hits_d, want))) return rc;
-      if ((rc = regrow(ctx, A->hits_sorted, want))) return rc;
-      A->hit_cap = want;
-    }
+  for (uint32_t p = 0; p < B.n_pairs && call_bound <= B.max_matches; ++p)
+    call_bound += (size_t)(ctx->genomes[B.ref_ids[p]].stream_len + ctx->genomes[B.qry_ids[p]].stream_len) / 4 + 8192;
+  const size_t budget = call_bound < B.max_matches ? call_bound : (size_t)B.max_matches;
+  PG_HIP(ctx, A->seed_total.reserve(2));
+  PG_HIP(ctx, A->seedbuf.reserve(budget + 1024));
+  B.cnt.resize(B.n_units);
+  {   // hit buffer: the matches of the budget plus the chance 16-mer hits of unrelated pairs (~1200 per 5 Mb unit)
+    const size_t want = budget + (size_t)(frag ? 8 * 4096 : 4096) * B.n_units + 1024;   // (every position sampled: 5 x the chance hits)
+    PG_HIP(ctx, reserve_all(want, want, A->hits_d, A->hits_sorted));
   }
   for (int attempt = 0;; ++attempt) {
     if (attempt == 8) return pg_fail(ctx, PG_E_CAPACITY, "anim seeding: buffers still overflow after repeated splitting");
+    const uint32_t n_pairs = B.n_pairs, n_units = B.n_units;
+    const size_t hit_room = std::min(A->hits_d.cap, A->hits_sorted.cap);   // (one size: the two grow together)
+    const uint32_t hit_cap = (uint32_t)hit_room, seed_cap = (uint32_t)A->seedbuf.cap;
     uint32_t counts[2] = {0, 0};   // matches appended, hits recorded
-    if ((rc = prepare(n_pairs))) return rc;   // (again after a split: a pair whose partner left the launch is seeded itself)
+    int rc;
+    if ((rc = plan_seeding(B, n_pairs))) return rc;   // (again after a split: a pair whose partner left the launch is seeded itself)
     PG_HIP(ctx, hipMemsetAsync(A->mem_count, 0, n_units * 4, cur_stream(ctx)));
     PG_HIP(ctx, hipMemsetAsync(A->seed_total, 0, 8, cur_stream(ctx)));   // [0] matches, [1] hits
     PG_HIP(ctx, hipMemsetAsync(A->hit_count, 0, n_units * 4, cur_stream(ctx)));
     pg_prof_begin(ctx, PG_K_ANIM_SEED);
-    if (use_blocks && n_blks)
-      hipLaunchKernelGGL(anim_seed_kernel, dim3(n_blks, SEED_GROUPS), dim3(SEED_BLOCK), (size_t)slots * 8 + SEED_STAGE_BYTES, cur_stream(ctx),
-                         A->sblk_d, A->sslot_d, A->sbq_d, A->spt_d, slots - 1, slot_shift, A->hits_d, (uint32_t)A->hit_cap,
+    if (B.use_blocks && B.n_blks)
+      hipLaunchKernelGGL(anim_seed_kernel, dim3(B.n_blks, SEED_GROUPS), dim3(SEED_BLOCK), (size_t)B.slots * 8 + SEED_STAGE_BYTES, cur_stream(ctx),
+                         A->sblk_d, A->sslot_d, A->sbq_d, A->spt_d, B.slots - 1, B.slot_shift, A->hits_d, hit_cap,
                          A->seed_total + 1, A->hit_count, qstep);
-    else if (!use_blocks && n_srefs)
-      hipLaunchKernelGGL(anim_seed_pair_kernel, dim3(n_srefs, SEED_CGROUPS), dim3(SEED_BLOCK), (size_t)slots * 8 + SEED_STAGE_BYTES, cur_stream(ctx),
-                         A->srefs_d, A->sqry_d, A->slice_d, slice_stride, slots - 1, A->hits_d, (uint32_t)A->hit_cap, A->seed_total + 1,
+    else if (!B.use_blocks && B.n_srefs)
+      hipLaunchKernelGGL(anim_seed_pair_kernel, dim3(B.n_srefs, SEED_CGROUPS), dim3(SEED_BLOCK), (size_t)B.slots * 8 + SEED_STAGE_BYTES, cur_stream(ctx),
+                         A->srefs_d, A->sqry_d, A->slice_d, B.slice_stride, B.slots - 1, A->hits_d, hit_cap, A->seed_total + 1,
                          A->hit_count, qstep);
     pg_prof_end(ctx);
     PG_HIP(ctx, hipGetLastError());   // a rejected launch (LDS size) must not surface only at the end of the batch
@@ -843,280 +883,305 @@ int pg_anim_run_batch(pg_ctx* ctx, const int32_t* ref_ids, const int32_t* qry_id
     // hits -> per-unit slices, then one workgroup per unit verifies / extends them
     hipLaunchKernelGGL(anim_hoff_kernel, dim3(1), dim3(1024), 0, cur_stream(ctx), A->hit_count, n_units, A->hoff, A->hit_cursor);
     hipLaunchKernelGGL(anim_hit_scatter_kernel, dim3((uint32_t)ctx->num_cu * 8u), dim3(256), 0, cur_stream(ctx), A->hits_d, A->seed_total + 1,
-                       (uint32_t)A->hit_cap, A->hoff, A->hit_cursor, A->hits_sorted);
+                       hit_cap, A->hoff, A->hit_cursor, A->hits_sorted);
     hipLaunchKernelGGL(anim_hit_kernel, dim3(n_units), dim3(256), 0, cur_stream(ctx), A->refs_d, A->units_d, A->hits_sorted, A->hoff,
-                       A->seed_total + 1, (uint32_t)A->hit_cap, A->seedbuf, (uint32_t)A->seed_cap, A->seed_total, A->mem_count,
-                       frag ? FRAG_SEED_MIN : MIN_MATCH, qstep, use_mirror ? A->mirror_d : (const int32_t*)nullptr);
+                       A->seed_total + 1, hit_cap, A->seedbuf, seed_cap, A->seed_total, A->mem_count,
+                       frag ? FRAG_SEED_MIN : MIN_MATCH, qstep, B.use_mirror ? A->mirror_d.p : (const int32_t*)nullptr);
     pg_prof_end(ctx);
-    PG_HIP(ctx, hipMemcpyAsync(cnt.data(), A->mem_count, n_units * 4, hipMemcpyDeviceToHost, cur_stream(ctx)));
+    PG_HIP(ctx, hipMemcpyAsync(B.cnt.data(), A->mem_count, n_units * 4, hipMemcpyDeviceToHost, cur_stream(ctx)));
     PG_HIP(ctx, hipMemcpyAsync(counts, A->seed_total, 8, hipMemcpyDeviceToHost, cur_stream(ctx)));
     PG_HIP(ctx, hipStreamSynchronize(cur_stream(ctx)));
-    total = counts[0];
-    if (counts[1] > A->hit_cap) {   // hits were dropped: the counts are incomplete -> seed half as many pairs
-      if (n_pairs == 1) {
-        A->hit_cap = (size_t)counts[1] + 1024;
-        if ((rc = regrow(ctx, A->hits_d, A->hit_cap))) return rc;
-        if ((rc = regrow(ctx, A->hits_sorted, A->hit_cap))) return rc;
-      } else {
-        n_pairs = (n_pairs + 1) / 2;
-        n_units = 2 * n_pairs;
-      }
+    B.total = counts[0];
+    if (counts[1] > hit_room) {   // hits were dropped: the counts are incomplete -> seed half as many pairs
+      if (n_pairs == 1) PG_HIP(ctx, reserve_all((size_t)counts[1] + 1024, (size_t)counts[1] + 1024, A->hits_d, A->hits_sorted));
+      else B.set_pairs((n_pairs + 1) / 2);
       continue;
     }
     uint64_t tot = 0, raw = 0;
-    pairs_fit = 0;
+    uint32_t pairs_fit = 0;
     for (uint32_t p = 0; p < n_pairs; ++p) {
-      const uint64_t need = (uint64_t)cnt[2 * p] + cnt[2 * p + 1] + 4;   // per unit: count + 1 (never empty), rounded up to even
-      if (p > 0 && tot + need > max_matches) break;
+      const uint64_t need = (uint64_t)B.cnt[2 * p] + B.cnt[2 * p + 1] + 4;   // per unit: count + 1 (never empty), rounded up to even
+      if (p > 0 && tot + need > B.max_matches) break;
       tot += need;
       raw += need - 4;
       pairs_fit = p + 1;
     }
-    n_pairs = pairs_fit;
-    n_units = 2 * n_pairs;
-    if (total <= A->seed_cap) break;
-    // overflow: make room for the prefix of pairs that fits the batch budget and seed that prefix again
-    A->seed_cap = (size_t)(raw + raw / 8 + 1024);
-    if ((rc = regrow(ctx, A->seedbuf, A->seed_cap))) return rc;
+    B.set_pairs(pairs_fit);
+    if (B.total <= A->seedbuf.cap) break;
+    // overflow: make room for the prefix of pairs that fits the batch budget (the buffer is made anew at that size, smaller or
+    // larger) and seed that prefix again
+    A->seedbuf.release();
+    PG_HIP(ctx, A->seedbuf.reserve((size_t)(raw + raw / 8 + 1024)));
   }
-  *n_done = n_pairs;
-  moff.assign((size_t)n_units + 1, 0);
-  for (uint32_t u = 0; u < n_units; ++u) moff[u + 1] = moff[u] + ((cnt[u] + 2) & ~1u);   // even slice sizes: 8-byte aligned sub-slices
-  const size_t M = moff[n_units];
-  if (M > A->matches) {
-    const size_t cap = M + M / 4;
-    if ((rc = regrow(ctx, A->mem, cap))) return rc;
-    if ((rc = regrow(ctx, A->cm, cap))) return rc;
-    if ((rc = regrow(ctx, A->iscratch, cap * 8))) return rc;
-    if ((rc = regrow(ctx, A->chains, cap))) return rc;
-    if ((rc = regrow(ctx, A->order, cap))) return rc;
-    if ((rc = regrow(ctx, A->S.alns, cap))) return rc;
-    if ((rc = regrow(ctx, A->S.a_rrec, cap))) return rc;
-    if ((rc = regrow(ctx, A->S.a_qrec, cap))) return rc;
-    if ((rc = regrow(ctx, A->S.idx, cap))) return rc;
-    if ((rc = regrow(ctx, A->S.from, cap))) return rc;
-    if ((rc = regrow(ctx, A->S.sc, cap))) return rc;
-    __atomic_fetch_add(&ctx->anim_scratch_matches_held, (uint64_t)(cap - A->matches), __ATOMIC_RELAXED);      // (what pg_api.cpp's anim_match_budget may count as available)
-    A->matches = cap;
-  }
-  PG_HIP(ctx, hipMemcpyAsync(A->moff, moff.data(), ((size_t)n_units + 1) * 4, hipMemcpyHostToDevice, cur_stream(ctx)));
+  return PG_OK;
+}
+
+// Every per-match array gets exactly the slice it needs (B.moff: even slice sizes), then the append buffer is dealt into them.
+static int scatter_matches(Batch& B) {
+  pg_ctx* ctx = B.ctx;
+  AnimScratch* A = B.A;
+  const uint32_t n_pairs = B.n_pairs, n_units = B.n_units;
+  B.moff.assign((size_t)n_units + 1, 0);
+  for (uint32_t u = 0; u < n_units; ++u) B.moff[u + 1] = B.moff[u] + ((B.cnt[u] + 2) & ~1u);   // even slice sizes: 8-byte aligned sub-slices
+  const size_t M = B.moff[n_units], cap = M + M / 4, held = A->mem.cap;
+  PG_HIP(ctx, reserve_all(M, cap, A->mem, A->cm, A->chains, A->order, A->S.alns, A->S.a_rrec, A->S.a_qrec, A->S.idx, A->S.from, A->S.sc));
+  PG_HIP(ctx, A->iscratch.reserve(M * 8, cap * 8));
+  if (A->mem.cap > held)      // (what pg_api.cpp's anim_match_budget may count as available)
+    __atomic_fetch_add(&ctx->anim_scratch_matches_held, (uint64_t)(A->mem.cap - held), __ATOMIC_RELAXED);
+  PG_HIP(ctx, hipMemcpyAsync(A->moff, B.moff.data(), ((size_t)n_units + 1) * 4, hipMemcpyHostToDevice, cur_stream(ctx)));
   PG_HIP(ctx, hipMemsetAsync(A->mem_count, 0, n_units * 4, cur_stream(ctx)));
   PG_HIP(ctx, hipMemsetAsync(A->status, 0, n_pairs * 4, cur_stream(ctx)));
-  ClusterOut O{A->moff, A->cm, A->chains, A->nch, A->order, A->status};
+  B.O = ClusterOut{A->moff, A->cm, A->chains, A->nch, A->order, A->status};
   pg_prof_begin(ctx, PG_K_ANIM_HIT);
-  if (total)
-    hipLaunchKernelGGL(anim_scatter_kernel, dim3((total + 255) / 256), dim3(256), 0, cur_stream(ctx), A->seedbuf, total, A->moff, n_units,
+  if (B.total)
+    hipLaunchKernelGGL(anim_scatter_kernel, dim3((B.total + 255) / 256), dim3(256), 0, cur_stream(ctx), A->seedbuf, B.total, A->moff, n_units,
                        A->mem_count, A->mem);
   pg_prof_end(ctx);
-  if (frag) {   // fragment mode: the matches of every unit are in place; the rest of the batch is the fragment kernels
-    PG_HIP(ctx, hipGetLastError());
-    return anib_frag_stage(ctx, A, qry_ids, n_pairs, cnt, *frag, ref_list, ref_of_pair);
-  }
-  // Units with >= split_min matches ("big": pairs of related genomes) get their chains from many waves (pga_cluster.inc,
-  // anim_chain_range_kernel); every other unit is finished by the one wave that filters and clusters it.
+  return PG_OK;
+}
+
+// A3.  Units with >= split_min matches ("big": pairs of related genomes) get their chains from many waves (pga_cluster.inc,
+// anim_chain_range_kernel); every other unit is finished by the one wave that filters and clusters it.  Leaves B.nch / B.choff.
+static int cluster_stage(Batch& B) {
+  pg_ctx* ctx = B.ctx;
+  AnimScratch* A = B.A;
+  const ClusterOut& O = B.O;
+  const uint32_t n_units = B.n_units;
   const int split_min = pg_dev_env("PYANI_ANIM_SPLIT_MIN") ? atoi(pg_dev_env("PYANI_ANIM_SPLIT_MIN")) : 2048;   // (<= 0: never split)
   const int range_entries = pg_dev_env("PYANI_ANIM_RANGE_ENTRIES") && atoi(pg_dev_env("PYANI_ANIM_RANGE_ENTRIES")) > 0
                                 ? atoi(pg_dev_env("PYANI_ANIM_RANGE_ENTRIES")) : CHAIN_RANGE_ENTRIES;
   std::vector<BigUnit> big;
   std::vector<uint2> ranges;
-  if (split_min > 0 && !pg_dev_env("PYANI_ANIM_SCALAR_CLUSTER"))
+  if (split_min > 0)
     for (uint32_t u = 0; u < n_units; ++u)
-      if (cnt[u] >= (uint32_t)split_min) {
-        uint32_t R = cnt[u] / (uint32_t)range_entries;
+      if (B.cnt[u] >= (uint32_t)split_min) {
+        uint32_t R = B.cnt[u] / (uint32_t)range_entries;
         R = R < 1 ? 1 : (R > (uint32_t)CHAIN_RANGES_MAX ? (uint32_t)CHAIN_RANGES_MAX : R);
         for (uint32_t r = 0; r < R; ++r) ranges.push_back(make_uint2((uint32_t)big.size(), r));
         big.push_back(BigUnit{u, (uint32_t)(ranges.size() - R), R, 0});
       }
   if (!big.empty()) {
-    if (big.size() > A->big_cap) { if ((rc = regrow(ctx, A->big_d, big.size() + big.size() / 4))) return rc; A->big_cap = big.size() + big.size() / 4; }
-    if (ranges.size() > A->range_cap) {
-      const size_t c = ranges.size() + ranges.size() / 4;
-      if ((rc = regrow(ctx, A->ranges_d, c))) return rc;
-      if ((rc = regrow(ctx, A->range_out, c))) return rc;
-      A->range_cap = c;
-    }
+    PG_HIP(ctx, A->big_d.reserve(big.size(), big.size() + big.size() / 4));
+    PG_HIP(ctx, reserve_all(ranges.size(), ranges.size() + ranges.size() / 4, A->ranges_d, A->range_out));
     PG_HIP(ctx, hipMemcpyAsync(A->big_d, big.data(), big.size() * sizeof(BigUnit), hipMemcpyHostToDevice, cur_stream(ctx)));
     PG_HIP(ctx, hipMemcpyAsync(A->ranges_d, ranges.data(), ranges.size() * sizeof(uint2), hipMemcpyHostToDevice, cur_stream(ctx)));
   }
   const int split_arg = big.empty() ? 0x7fffffff : split_min;
   pg_prof_begin(ctx, PG_K_ANIM_CLUSTER);
-  if (pg_dev_env("PYANI_ANIM_SCALAR_CLUSTER") && !maxmatch)   // debugging aid: the one-thread-per-unit statement of the same algorithm
-    hipLaunchKernelGGL(anim_cluster_kernel, dim3((n_units + 63) / 64), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, n_units,
-                       A->mem, A->mem_count, A->iscratch, O);
-  else {
-    // the front half (MUM filter, union-find, grouping) of a big unit is shared by the PREP_WAVES waves of one workgroup: a
-    // single wave needs ~10 ms for the sorts of 50 000 matches, and the launch would wait for the slowest of them (measured
-    // on C4, cluster stage per grid: one wave per big unit 1.95 s, workgroup 0.51 s; PYANI_ANIM_WAVE_PREP=1 forces the former)
-    const bool prep = !big.empty() && !pg_dev_env("PYANI_ANIM_WAVE_PREP");
-    if (prep)
-      hipLaunchKernelGGL(anim_cluster_prep_kernel, dim3((uint32_t)big.size()), dim3(PREP_THREADS), 0, cur_stream(ctx), A->refs_d, A->units_d,
-                         A->mem, A->mem_count, A->iscratch, O, maxmatch, A->big_d);
-    hipLaunchKernelGGL(anim_cluster_wave_kernel, dim3(n_units), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, A->mem,
-                       A->mem_count, A->iscratch, O, prep ? 1 : 0, maxmatch, split_arg);
-    if (!big.empty()) {
-      hipLaunchKernelGGL(anim_chain_range_kernel, dim3((uint32_t)ranges.size()), dim3(64), 0, cur_stream(ctx), A->units_d, A->mem, A->iscratch,
-                         O, A->big_d, A->ranges_d, A->range_out);
-      hipLaunchKernelGGL(anim_chain_merge_kernel, dim3((uint32_t)big.size()), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, A->iscratch, O,
-                         A->big_d, A->range_out);
-    }
+  // the front half (MUM filter, union-find, grouping) of a big unit is shared by the PREP_WAVES waves of one workgroup: a
+  // single wave needs ~10 ms for the sorts of 50 000 matches, and the launch would wait for the slowest of them (measured
+  // on C4, cluster stage per grid: one wave per big unit 1.95 s, workgroup 0.51 s; PYANI_ANIM_WAVE_PREP=1 forces the former)
+  const bool prep = !big.empty() && !pg_dev_env("PYANI_ANIM_WAVE_PREP");
+  if (prep)
+    hipLaunchKernelGGL(anim_cluster_prep_kernel, dim3((uint32_t)big.size()), dim3(PREP_THREADS), 0, cur_stream(ctx), A->refs_d, A->units_d,
+                       A->mem, A->mem_count, A->iscratch, O, B.maxmatch, A->big_d);
+  hipLaunchKernelGGL(anim_cluster_wave_kernel, dim3(n_units), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, A->mem,
+                     A->mem_count, A->iscratch, O, prep ? 1 : 0, B.maxmatch, split_arg);
+  if (!big.empty()) {
+    hipLaunchKernelGGL(anim_chain_range_kernel, dim3((uint32_t)ranges.size()), dim3(64), 0, cur_stream(ctx), A->units_d, A->mem, A->iscratch,
+                       O, A->big_d, A->ranges_d, A->range_out);
+    hipLaunchKernelGGL(anim_chain_merge_kernel, dim3((uint32_t)big.size()), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, A->iscratch, O,
+                       A->big_d, A->range_out);
   }
   pg_prof_end(ctx);
-  // work list of (unit, chain): one wave each
-  std::vector<int32_t> nch(n_units);
-  PG_HIP(ctx, hipMemcpyAsync(nch.data(), A->nch, n_units * 4, hipMemcpyDeviceToHost, cur_stream(ctx)));
+  B.nch.resize(n_units);
+  PG_HIP(ctx, hipMemcpyAsync(B.nch.data(), A->nch, n_units * 4, hipMemcpyDeviceToHost, cur_stream(ctx)));
   PG_HIP(ctx, hipStreamSynchronize(cur_stream(ctx)));
   // (unit, chain) work list, one wave each: offsets by a host prefix over the per-unit chain counts, entries on device
-  std::vector<uint32_t> choff((size_t)n_units + 1, 0);
-  for (uint32_t u = 0; u < n_units; ++u) choff[u + 1] = choff[u] + (uint32_t)nch[u];
-  const size_t n_wl = choff[n_units];
+  B.choff.assign((size_t)n_units + 1, 0);
+  for (uint32_t u = 0; u < n_units; ++u) B.choff[u + 1] = B.choff[u] + (uint32_t)B.nch[u];
+  return PG_OK;
+}
+
+// A4x: MUMmer's own extension algorithm — the (unit, chain) work list, the pre-passes over it (match-to-match gaps, forward
+// extensions, backward searches), the pairs' walks on persistent waves, then the forced re-alignments the walks deferred.
+static int extend_stage(Batch& B) {
+  pg_ctx* ctx = B.ctx;
+  AnimScratch* A = B.A;
+  const ClusterOut& O = B.O;
+  const uint32_t n_pairs = B.n_pairs, n_units = B.n_units;
+  const std::vector<int32_t>& nch = B.nch;
+  const size_t M = B.moff[n_units], n_wl = B.choff[n_units];
+  const size_t Mp = (M + 15) & ~(size_t)15;
+  PG_HIP(ctx, reserve_all(Mp, Mp, A->pn, A->pn_fused, A->pn_gaps, A->pn_fwd, A->pn_bwd, A->pn_tlog, A->pn_born));
+  PG_HIP(ctx, A->pn_tasks.reserve(4 * Mp));      // three lane classes + the wave engine's list
+  const size_t task_cap = A->pn_tasks.cap / 4;
+  PG_HIP(ctx, reserve_all(n_units, (size_t)n_units + n_units / 2, A->pn_n, A->pn_order, A->pn_porder));
   {
-    // A4x: MUMmer's own extension algorithm, one wave per unit (persistent waves, units handed out longest first would be
-    // better still: a unit's time is ~ its clusters; the cursor takes them in batch order)
-    const size_t Mp = (M + 15) & ~(size_t)15;
-    if (Mp > A->pn_cap) {
-      if ((rc = regrow(ctx, A->pn, Mp))) return rc;
-      if ((rc = regrow(ctx, A->pn_fused, Mp))) return rc;
-      if ((rc = regrow(ctx, A->pn_gaps, Mp))) return rc;
-      if ((rc = regrow(ctx, A->pn_fwd, Mp))) return rc;
-      if ((rc = regrow(ctx, A->pn_bwd, Mp))) return rc;
-      if ((rc = regrow(ctx, A->pn_tlog, Mp))) return rc;
-      if ((rc = regrow(ctx, A->pn_born, Mp))) return rc;
-      if ((rc = regrow(ctx, A->pn_tasks, 4 * Mp))) return rc;      // three lane classes + the wave engine's list
-      A->pn_cap = Mp;
-    }
-    if (n_units > A->pn_units) {
-      if ((rc = regrow(ctx, A->pn_n, (size_t)n_units + n_units / 2))) return rc;
-      if ((rc = regrow(ctx, A->pn_order, (size_t)n_units + n_units / 2))) return rc;
-      if ((rc = regrow(ctx, A->pn_porder, (size_t)n_units + n_units / 2))) return rc;
-      A->pn_units = (size_t)n_units + n_units / 2;
-    }
-    {
-      std::vector<uint32_t> uorder(n_units);
-      for (uint32_t u = 0; u < n_units; ++u) uorder[u] = u;
-      std::stable_sort(uorder.begin(), uorder.end(), [&](uint32_t a, uint32_t b) { return nch[a] > nch[b]; });
-      PG_HIP(ctx, hipMemcpyAsync(A->pn_order, uorder.data(), (size_t)n_units * 4, hipMemcpyHostToDevice, cur_stream(ctx)));
-      std::vector<uint32_t> porder(n_pairs);      // the walk kernel takes PAIRS (one wave per strand): by the larger strand's cluster count
-      for (uint32_t p = 0; p < n_pairs; ++p) porder[p] = p;
-      std::stable_sort(porder.begin(), porder.end(), [&](uint32_t a, uint32_t b) { return std::max(nch[2 * a], nch[2 * a + 1]) > std::max(nch[2 * b], nch[2 * b + 1]); });
-      PG_HIP(ctx, hipMemcpyAsync(A->pn_porder, porder.data(), (size_t)n_pairs * 4, hipMemcpyHostToDevice, cur_stream(ctx)));
-      PG_HIP(ctx, hipStreamSynchronize(cur_stream(ctx)));     // (uorder / porder are locals)
-    }
-    if (!A->pn_cursor && (rc = regrow(ctx, A->pn_cursor, 24))) return rc;
-    const uint32_t pn_waves = (uint32_t)ctx->num_cu * 12u;   // forced kernels with the LDS store: 12 KiB of LDS each: 12 per CU
-    const uint32_t pn_walk_waves = (uint32_t)ctx->num_cu * 8u;   // the walk / rehearsal kernels: 219 / 173 VGPRs, two waves per SIMD — one persistent wave per resident slot
-    const uint32_t pn_waves_pre = (uint32_t)ctx->num_cu * 32u;   // gap / forward / backward pre-passes and the narrow forced kernel: no LDS, diagonal engine only, <= 64 registers: 8 per SIMD
-    const uint32_t pn_waves_scr = ctx->anim_gap_lanes ? (pn_waves > pn_walk_waves ? pn_waves : pn_walk_waves) : pn_waves_pre;      // (only the walks, the wide forced kernel and the all-gaps form of the gap kernel use the global scratch)
-    if (pn_waves_scr > A->pn_waves) { if ((rc = regrow(ctx, A->pn_gscratch, (size_t)pn_waves_scr * PN_GLOBAL_WORDS))) return rc; A->pn_waves = pn_waves_scr; }
-    const bool trace = tls_sink && tls_sink->with_indels;      // the walks list their pieces and align everything themselves
-    const bool bwd_ahead = ctx->anim_bwd_ahead != 0;
-    if (trace) {
-      const size_t need = pn_piece_base(Mp, (uint32_t)n_wl, n_units) + 16;
-      if (need > A->pn_piece_cap) { if ((rc = regrow(ctx, A->pn_pieces, need))) return rc; A->pn_piece_cap = need; }
-      if (n_units > A->pn_npieces_cap) { if ((rc = regrow(ctx, A->pn_npieces, (size_t)n_units + 16))) return rc; A->pn_npieces_cap = (size_t)n_units + 16; }
-      PG_HIP(ctx, hipMemsetAsync(A->pn_npieces, 0, (size_t)n_units * 4, cur_stream(ctx)));
-    }
-    const size_t req_cap = Mp + 16;      // one slot per match slot: a walk records at most one forced run per alignment it starts, and starts at most one per match
-    A->pn_req_n = req_cap;
-    if (req_cap > A->pn_req_cap) { if ((rc = regrow(ctx, A->pn_reqs, req_cap + req_cap / 2))) return rc; if ((rc = regrow(ctx, A->pn_wide, 3 * (req_cap + req_cap / 2)))) return rc; A->pn_req_cap = req_cap + req_cap / 2; }
-    PG_HIP(ctx, hipMemsetAsync(A->pn_cursor, 0, 96, cur_stream(ctx)));   // [0] unit cursor, [1] forced runs recorded ([7]: the long ones), [2] forced-run cursor, [3] chain / big-gap cursor, [4..6] small gaps by class ([11]: gaps left to the wave engine), [8] cluster cursor of the forward extensions, [9] unit cursor of the rehearsal, [10] cluster cursor of the backward searches, [12] / [13] wide forced runs: count / cursor, [14] / [15] huge ones, [16] / [17] the strips' list
-    if (n_wl && trace) PG_HIP(ctx, hipMemcpyAsync(A->choff_d, choff.data(), choff.size() * 4, hipMemcpyHostToDevice, cur_stream(ctx)));
-    if (n_wl && !trace) {     // the (unit, chain) work list, then every cluster's match-to-match alignments
-      if (n_wl > A->wl) { if ((rc = regrow(ctx, A->wl_d, n_wl + n_wl / 2))) return rc; A->wl = n_wl + n_wl / 2; }
-      PG_HIP(ctx, hipMemcpyAsync(A->choff_d, choff.data(), choff.size() * 4, hipMemcpyHostToDevice, cur_stream(ctx)));
-      hipLaunchKernelGGL(anim_wl_kernel, dim3(n_units), dim3(64), 0, cur_stream(ctx), A->choff_d, A->wl_d);
-      pg_prof_begin(ctx, PG_K_ANIM_GAPS);
-      const int lane_small = ctx->anim_gap_lanes;
-      if (lane_small) {     // small gaps: one LANE each, by size class
-        hipLaunchKernelGGL(anim_postnuc_gaplist_kernel, dim3((uint32_t)((n_wl + 255) / 256)), dim3(256), 0, cur_stream(ctx), A->units_d, O, A->wl_d,
-                           (uint32_t)n_wl, A->pn_tasks, A->pn_cap, A->pn_cursor + 4);
-        const dim3 lg((uint32_t)ctx->num_cu * 8u);
-        hipLaunchKernelGGL((anim_postnuc_gaplane_kernel<16>), lg, dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, O, A->pn_tasks, A->pn_cursor + 4, A->pn_gaps);
-        hipLaunchKernelGGL((anim_postnuc_gaplane_kernel<32>), lg, dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, O, A->pn_tasks + A->pn_cap, A->pn_cursor + 5, A->pn_gaps);
-        hipLaunchKernelGGL((anim_postnuc_gaplane_kernel<PN_SMALL>), lg, dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, O, A->pn_tasks + 2 * A->pn_cap, A->pn_cursor + 6, A->pn_gaps);
-      }
-      if (lane_small)
-        hipLaunchKernelGGL(anim_postnuc_gapbig_kernel, dim3(pn_waves_pre), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, O, A->pn_cursor + 3,
-                           A->pn_gaps, A->pn_tasks + 3 * A->pn_cap, A->pn_cursor + 11);
-      else
-        hipLaunchKernelGGL(anim_postnuc_gap_kernel, dim3(pn_waves_pre), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, O, A->wl_d, (uint32_t)n_wl,
-                           A->pn_cursor + 3, A->pn_gaps, A->pn_gscratch);
-      pg_prof_end(ctx);
-      pg_prof_begin(ctx, PG_K_ANIM_FWD);
-      hipLaunchKernelGGL(anim_postnuc_fwd_kernel, dim3(pn_waves_pre), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, O, A->wl_d, (uint32_t)n_wl,
-                         A->pn_cursor + 8, A->pn_fwd, A->pn_gscratch);
-      pg_prof_end(ctx);
-      pg_prof_begin(ctx, PG_K_ANIM_BWD);
-      if (bwd_ahead) {     // the walks rehearsed without their backward searches, then the searches they predict, one wave each
-        PG_HIP(ctx, hipMemsetAsync(A->pn_bwd, 0, (size_t)M * sizeof(pgn::PnBwd), cur_stream(ctx)));
-        hipLaunchKernelGGL(anim_postnuc_rehearse_kernel, dim3(pn_walk_waves < n_units ? pn_walk_waves : n_units), dim3(64), 0, cur_stream(ctx), A->refs_d,
-                           A->units_d, n_units, O, A->pn_cursor + 9, A->pn, A->pn_fused, A->pn_gscratch, A->pn_gaps, A->pn_fwd, A->pn_order, A->pn_bwd);
-        hipLaunchKernelGGL(anim_postnuc_bwd_kernel, dim3(pn_waves_pre), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, O, A->wl_d, (uint32_t)n_wl,
-                           A->pn_cursor + 10, A->pn_bwd, A->pn_gscratch);
-      }
-      pg_prof_end(ctx);
-    }
-    pg_prof_begin(ctx, PG_K_ANIM_EXTEND);
-    if (n_wl)
-      hipLaunchKernelGGL(anim_postnuc_kernel, dim3(pn_walk_waves / 2 < n_pairs ? pn_walk_waves / 2 : n_pairs), dim3(128), 0, cur_stream(ctx), A->refs_d, A->units_d,
-                         n_pairs, O, A->pn_cursor, A->pn, A->pn_fused, A->pn_n, A->pn_gscratch, A->pn_reqs, A->pn_cursor + 1, (uint32_t)req_cap,
-                         trace ? nullptr : A->pn_gaps, trace ? nullptr : A->pn_fwd, A->pn_porder, trace ? A->pn_pieces : nullptr, A->pn_npieces, A->choff_d,
-                         bwd_ahead && !trace ? A->pn_bwd : nullptr, A->pn_tlog, A->pn_born);
-    else
-      PG_HIP(ctx, hipMemsetAsync(A->pn_n, 0, (size_t)n_units * 4, cur_stream(ctx)));
-    pg_prof_end(ctx);
-    pg_prof_begin(ctx, PG_K_ANIM_EXTLANE);     // (the forced re-alignments, deferred: pga_postnuc.inc)
-    if (n_wl) {      // narrow bands first (five waves per SIMD), then the runs that asked for a wide one (pga_postnuc.inc, pn_forced_wave)
-      const uint32_t win_max = (uint32_t)ctx->anim_pn_window_max, group_max = (uint32_t)ctx->anim_pn_group_max;
-      hipLaunchKernelGGL(anim_postnuc_forced_kernel, dim3(pn_waves_pre), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, A->pn_reqs,
-                         A->pn_cursor + 1, (uint32_t)req_cap, A->pn_cursor + 2, A->pn_n, A->pn_wide, A->pn_cursor + 12, win_max);
-      hipLaunchKernelGGL(anim_postnuc_forced_wide_kernel, dim3(pn_waves), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, A->pn_reqs,
-                         A->pn_cursor + 1, (uint32_t)req_cap, A->pn_cursor + 13, A->pn_n, A->pn_gscratch, A->pn_wide, A->pn_cursor + 12,
-                         A->pn_wide + req_cap, A->pn_cursor + 14, win_max);
-      // runs whose band spans more than one wave's 2048 diagonals: a workgroup of four waves each (2 workgroups per CU: the 8192-diagonal form holds 242 VGPRs); what the group
-      // cannot hold either: the column strips, one wave per run (a list that is empty on every workload seen so far)
-      hipLaunchKernelGGL(anim_postnuc_forced_huge_kernel, dim3((uint32_t)ctx->num_cu * 2u), dim3(64 * PN_HUGE_WAVES), 0, cur_stream(ctx), A->refs_d,
-                         A->units_d, A->pn_reqs, A->pn_cursor + 15, A->pn_n, A->pn_wide + req_cap, A->pn_cursor + 14, A->pn_wide + 2 * req_cap,
-                         A->pn_cursor + 16, group_max);
-      hipLaunchKernelGGL(anim_postnuc_forced_strips_kernel, dim3(pn_waves), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, A->pn_reqs,
-                         A->pn_cursor + 17, A->pn_n, A->pn_gscratch, A->pn_wide + 2 * req_cap, A->pn_cursor + 16);
-    }
-    pg_prof_end(ctx);
-    if (pg_dev_env("PYANI_PN_STATS")) {   // development: what the engines did in this launch
-      PG_HIP(ctx, hipStreamSynchronize(cur_stream(ctx)));
-      unsigned long long st[32], zero[32] = {0};
-      PG_HIP(ctx, hipMemcpyFromSymbol(st, HIP_SYMBOL(g_pn_stats), sizeof(st)));
-      PG_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_pn_stats), zero, sizeof(zero)));
-      fprintf(stderr, "[pn-stats] units %llu clusters %llu | regs: calls %llu steps %llu cells %llu moves %llu overflows %llu | lds: calls %llu steps %llu cells %llu | "
-                      "global: calls %llu steps %llu cells %llu\n", st[11], st[12], st[0], st[1], st[2], st[9], st[10], st[3], st[4], st[5], st[6], st[7], st[8]);
-      fprintf(stderr, "[pn-stats] searches of the gap + units kernels: %llu calls, %.1f ms inside the engine (summed over waves); shadow tests that asked for the synteny's current alignment: %llu\n", st[22], st[21] / 1e5, st[31]);
-      fprintf(stderr, "[pn-stats] forced passes by engine (127 / 255 / 511 cells / strips): %llu %llu %llu %llu passes, %.1f %.1f %.1f %.1f ms summed over waves\n",
-              st[27], st[28], st[29], st[30], st[23] / 1e5, st[24] / 1e5, st[25] / 1e5, st[26] / 1e5);
-      {
-        unsigned long long ks[32], kz[32] = {0};
-        PG_HIP(ctx, hipMemcpyFromSymbol(ks, HIP_SYMBOL(g_pn_kstats), sizeof(ks)));
-        PG_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_pn_kstats), kz, sizeof(kz)));
-        const char* kn[8] = {"gaps", "forward", "backward-ahead", "walks", "forced narrow", "forced 512-1024", "forced 2048", "forced group 8192"};
-        for (int k = 0; k < 8; ++k)
-          fprintf(stderr, "[pn-stats] diagonal engine in %-16s: %llu calls, %llu anti-diagonals, %llu cells\n", kn[k], ks[4 * k], ks[4 * k + 1], ks[4 * k + 2]);
-        fprintf(stderr, "[pn-stats] walk kernel scans: shadow test %.1f ms over %llu rows of 64 alignments, reverse-target search %.1f ms in %llu calls (summed over waves)\n",
-                ks[3] / 1e5, ks[7], ks[11] / 1e5, ks[15]);
-        fprintf(stderr, "[pn-stats] run-ahead results the walk took: forward %llu of %llu computed (%.4f), backward %llu found ready of %llu searches run ahead; %llu searches left to the walk itself\n",
-                ks[19], ks[4], ks[4] ? (double)ks[19] / (double)ks[4] : 0.0, ks[23], ks[8], ks[12]);
-      }
-      for (int k = 13; k <= 17; k += 4)      // ticks of the 100 MHz wall clock -> ms
-        fprintf(stderr, "[pn-stats] %s: busy %.1f ms summed over waves, span %.1f ms, longest item %.1f ms (size %llu)\n", k == 13 ? "units" : "forced",
-                st[k] / 1e5, st[k + 2] ? (st[k + 2] - ~st[k + 3]) / 1e5 : 0.0, (st[k + 1] >> 20) / 1e5, st[k + 1] & 0xFFFFFull);
-    }
+    std::vector<uint32_t> uorder(n_units);
+    for (uint32_t u = 0; u < n_units; ++u) uorder[u] = u;
+    std::stable_sort(uorder.begin(), uorder.end(), [&](uint32_t a, uint32_t b) { return nch[a] > nch[b]; });
+    PG_HIP(ctx, hipMemcpyAsync(A->pn_order, uorder.data(), (size_t)n_units * 4, hipMemcpyHostToDevice, cur_stream(ctx)));
+    std::vector<uint32_t> porder(n_pairs);      // the walk kernel takes PAIRS (one wave per strand): by the larger strand's cluster count
+    for (uint32_t p = 0; p < n_pairs; ++p) porder[p] = p;
+    std::stable_sort(porder.begin(), porder.end(), [&](uint32_t a, uint32_t b) { return std::max(nch[2 * a], nch[2 * a + 1]) > std::max(nch[2 * b], nch[2 * b + 1]); });
+    PG_HIP(ctx, hipMemcpyAsync(A->pn_porder, porder.data(), (size_t)n_pairs * 4, hipMemcpyHostToDevice, cur_stream(ctx)));
+    PG_HIP(ctx, hipStreamSynchronize(cur_stream(ctx)));     // (uorder / porder are locals)
   }
+  PG_HIP(ctx, A->pn_cursor.reserve(PNC_WORDS));
+  uint32_t* const cur = A->pn_cursor;
+  const uint32_t pn_waves = (uint32_t)ctx->num_cu * 12u;   // forced kernels with the LDS store: 12 KiB of LDS each: 12 per CU
+  const uint32_t pn_walk_waves = (uint32_t)ctx->num_cu * 8u;   // the walk / rehearsal kernels: 219 / 173 VGPRs, two waves per SIMD — one persistent wave per resident slot
+  const uint32_t pn_waves_pre = (uint32_t)ctx->num_cu * 32u;   // gap / forward / backward pre-passes and the narrow forced kernel: no LDS, diagonal engine only, <= 64 registers: 8 per SIMD
+  const uint32_t pn_waves_scr = ctx->anim_gap_lanes ? (pn_waves > pn_walk_waves ? pn_waves : pn_walk_waves) : pn_waves_pre;      // (only the walks, the wide forced kernel and the all-gaps form of the gap kernel use the global scratch)
+  PG_HIP(ctx, A->pn_gscratch.reserve((size_t)pn_waves_scr * PN_GLOBAL_WORDS));
+  const bool trace = B.trace;      // the walks list their pieces and align everything themselves
+  const bool bwd_ahead = ctx->anim_bwd_ahead != 0;
+  if (trace) {
+    const size_t need = pn_piece_base(Mp, (uint32_t)n_wl, n_units) + 16;
+    PG_HIP(ctx, A->pn_pieces.reserve(need));
+    PG_HIP(ctx, A->pn_npieces.reserve(n_units, (size_t)n_units + 16));
+    PG_HIP(ctx, hipMemsetAsync(A->pn_npieces, 0, (size_t)n_units * 4, cur_stream(ctx)));
+  }
+  const size_t req_cap = Mp + 16;      // one slot per match slot: a walk records at most one forced run per alignment it starts, and starts at most one per match
+  A->pn_req_n = req_cap;
+  PG_HIP(ctx, A->pn_reqs.reserve(req_cap, req_cap + req_cap / 2));
+  PG_HIP(ctx, A->pn_wide.reserve(3 * req_cap, 3 * (req_cap + req_cap / 2)));
+  PG_HIP(ctx, hipMemsetAsync(cur, 0, PNC_WORDS * 4, cur_stream(ctx)));
+  if (n_wl && trace) PG_HIP(ctx, hipMemcpyAsync(A->choff_d, B.choff.data(), B.choff.size() * 4, hipMemcpyHostToDevice, cur_stream(ctx)));
+  if (n_wl && !trace) {     // the (unit, chain) work list, then every cluster's match-to-match alignments
+    PG_HIP(ctx, A->wl_d.reserve(n_wl, n_wl + n_wl / 2));
+    PG_HIP(ctx, hipMemcpyAsync(A->choff_d, B.choff.data(), B.choff.size() * 4, hipMemcpyHostToDevice, cur_stream(ctx)));
+    hipLaunchKernelGGL(anim_wl_kernel, dim3(n_units), dim3(64), 0, cur_stream(ctx), A->choff_d, A->wl_d);
+    pg_prof_begin(ctx, PG_K_ANIM_GAPS);
+    const int lane_small = ctx->anim_gap_lanes;
+    if (lane_small) {     // small gaps: one LANE each, by size class
+      hipLaunchKernelGGL(anim_postnuc_gaplist_kernel, dim3((uint32_t)((n_wl + 255) / 256)), dim3(256), 0, cur_stream(ctx), A->units_d, O, A->wl_d,
+                         (uint32_t)n_wl, A->pn_tasks, task_cap, cur + PNC_GAP_LANE);
+      const dim3 lg((uint32_t)ctx->num_cu * 8u);
+      hipLaunchKernelGGL((anim_postnuc_gaplane_kernel<16>), lg, dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, O, A->pn_tasks, cur + PNC_GAP_LANE, A->pn_gaps);
+      hipLaunchKernelGGL((anim_postnuc_gaplane_kernel<32>), lg, dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, O, A->pn_tasks + task_cap, cur + PNC_GAP_LANE + 1, A->pn_gaps);
+      hipLaunchKernelGGL((anim_postnuc_gaplane_kernel<PN_SMALL>), lg, dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, O, A->pn_tasks + 2 * task_cap, cur + PNC_GAP_LANE + 2, A->pn_gaps);
+    }
+    if (lane_small)
+      hipLaunchKernelGGL(anim_postnuc_gapbig_kernel, dim3(pn_waves_pre), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, O, cur + PNC_GAP_BIG,
+                         A->pn_gaps, A->pn_tasks + 3 * task_cap, cur + PNC_GAP_WAVE);
+    else
+      hipLaunchKernelGGL(anim_postnuc_gap_kernel, dim3(pn_waves_pre), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, O, A->wl_d, (uint32_t)n_wl,
+                         cur + PNC_GAP_BIG, A->pn_gaps, A->pn_gscratch);
+    pg_prof_end(ctx);
+    pg_prof_begin(ctx, PG_K_ANIM_FWD);
+    hipLaunchKernelGGL(anim_postnuc_fwd_kernel, dim3(pn_waves_pre), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, O, A->wl_d, (uint32_t)n_wl,
+                       cur + PNC_FWD, A->pn_fwd, A->pn_gscratch);
+    pg_prof_end(ctx);
+    pg_prof_begin(ctx, PG_K_ANIM_BWD);
+    if (bwd_ahead) {     // the walks rehearsed without their backward searches, then the searches they predict, one wave each
+      PG_HIP(ctx, hipMemsetAsync(A->pn_bwd, 0, (size_t)M * sizeof(pgn::PnBwd), cur_stream(ctx)));
+      hipLaunchKernelGGL(anim_postnuc_rehearse_kernel, dim3(pn_walk_waves < n_units ? pn_walk_waves : n_units), dim3(64), 0, cur_stream(ctx), A->refs_d,
+                         A->units_d, n_units, O, cur + PNC_REHEARSE, A->pn, A->pn_fused, A->pn_gscratch, A->pn_gaps, A->pn_fwd, A->pn_order, A->pn_bwd);
+      hipLaunchKernelGGL(anim_postnuc_bwd_kernel, dim3(pn_waves_pre), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, O, A->wl_d, (uint32_t)n_wl,
+                         cur + PNC_BWD, A->pn_bwd, A->pn_gscratch);
+    }
+    pg_prof_end(ctx);
+  }
+  pg_prof_begin(ctx, PG_K_ANIM_EXTEND);
+  if (n_wl)
+    hipLaunchKernelGGL(anim_postnuc_kernel, dim3(pn_walk_waves / 2 < n_pairs ? pn_walk_waves / 2 : n_pairs), dim3(128), 0, cur_stream(ctx), A->refs_d, A->units_d,
+                       n_pairs, O, cur + PNC_UNIT, A->pn, A->pn_fused, A->pn_n, A->pn_gscratch, A->pn_reqs, cur + PNC_FORCED_N, (uint32_t)req_cap,
+                       trace ? nullptr : A->pn_gaps.p, trace ? nullptr : A->pn_fwd.p, A->pn_porder, trace ? A->pn_pieces.p : nullptr, A->pn_npieces, A->choff_d,
+                       bwd_ahead && !trace ? A->pn_bwd.p : nullptr, A->pn_tlog, A->pn_born);
+  else
+    PG_HIP(ctx, hipMemsetAsync(A->pn_n, 0, (size_t)n_units * 4, cur_stream(ctx)));
+  pg_prof_end(ctx);
+  pg_prof_begin(ctx, PG_K_ANIM_EXTLANE);     // (the forced re-alignments, deferred: pga_postnuc.inc)
+  if (n_wl) {      // narrow bands first (five waves per SIMD), then the runs that asked for a wide one (pga_postnuc.inc, pn_forced_wave)
+    const uint32_t win_max = (uint32_t)ctx->anim_pn_window_max, group_max = (uint32_t)ctx->anim_pn_group_max;
+    hipLaunchKernelGGL(anim_postnuc_forced_kernel, dim3(pn_waves_pre), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, A->pn_reqs,
+                       cur + PNC_FORCED_N, (uint32_t)req_cap, cur + PNC_FORCED_CUR, A->pn_n, A->pn_wide, cur + PNC_WIDE_N, win_max);
+    hipLaunchKernelGGL(anim_postnuc_forced_wide_kernel, dim3(pn_waves), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, A->pn_reqs,
+                       cur + PNC_FORCED_N, (uint32_t)req_cap, cur + PNC_WIDE_CUR, A->pn_n, A->pn_gscratch, A->pn_wide, cur + PNC_WIDE_N,
+                       A->pn_wide + req_cap, cur + PNC_HUGE_N, win_max);
+    // runs whose band spans more than one wave's 2048 diagonals: a workgroup of four waves each (2 workgroups per CU: the 8192-diagonal form holds 242 VGPRs); what the group
+    // cannot hold either: the column strips, one wave per run (a list that is empty on every workload seen so far)
+    hipLaunchKernelGGL(anim_postnuc_forced_huge_kernel, dim3((uint32_t)ctx->num_cu * 2u), dim3(64 * PN_HUGE_WAVES), 0, cur_stream(ctx), A->refs_d,
+                       A->units_d, A->pn_reqs, cur + PNC_HUGE_CUR, A->pn_n, A->pn_wide + req_cap, cur + PNC_HUGE_N, A->pn_wide + 2 * req_cap,
+                       cur + PNC_STRIPS_N, group_max);
+    hipLaunchKernelGGL(anim_postnuc_forced_strips_kernel, dim3(pn_waves), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, A->pn_reqs,
+                       cur + PNC_STRIPS_CUR, A->pn_n, A->pn_gscratch, A->pn_wide + 2 * req_cap, cur + PNC_STRIPS_N);
+  }
+  pg_prof_end(ctx);
+  return PG_OK;
+}
+
+// PYANI_PN_STATS (development): what the engines did in this launch
+static int print_pn_stats(pg_ctx* ctx) {
+  PG_HIP(ctx, hipStreamSynchronize(cur_stream(ctx)));
+  unsigned long long st[32], zero[32] = {0};
+  PG_HIP(ctx, hipMemcpyFromSymbol(st, HIP_SYMBOL(g_pn_stats), sizeof(st)));
+  PG_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_pn_stats), zero, sizeof(zero)));
+  fprintf(stderr, "[pn-stats] units %llu clusters %llu | regs: calls %llu steps %llu cells %llu moves %llu overflows %llu | lds: calls %llu steps %llu cells %llu | "
+                  "global: calls %llu steps %llu cells %llu\n", st[11], st[12], st[0], st[1], st[2], st[9], st[10], st[3], st[4], st[5], st[6], st[7], st[8]);
+  fprintf(stderr, "[pn-stats] searches of the gap + units kernels: %llu calls, %.1f ms inside the engine (summed over waves); shadow tests that asked for the synteny's current alignment: %llu\n", st[22], st[21] / 1e5, st[31]);
+  fprintf(stderr, "[pn-stats] forced passes by engine (127 / 255 / 511 cells / strips): %llu %llu %llu %llu passes, %.1f %.1f %.1f %.1f ms summed over waves\n",
+          st[27], st[28], st[29], st[30], st[23] / 1e5, st[24] / 1e5, st[25] / 1e5, st[26] / 1e5);
+  {
+    unsigned long long ks[32], kz[32] = {0};
+    PG_HIP(ctx, hipMemcpyFromSymbol(ks, HIP_SYMBOL(g_pn_kstats), sizeof(ks)));
+    PG_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_pn_kstats), kz, sizeof(kz)));
+    const char* kn[8] = {"gaps", "forward", "backward-ahead", "walks", "forced narrow", "forced 512-1024", "forced 2048", "forced group 8192"};
+    for (int k = 0; k < 8; ++k)
+      fprintf(stderr, "[pn-stats] diagonal engine in %-16s: %llu calls, %llu anti-diagonals, %llu cells\n", kn[k], ks[4 * k], ks[4 * k + 1], ks[4 * k + 2]);
+    fprintf(stderr, "[pn-stats] walk kernel scans: shadow test %.1f ms over %llu rows of 64 alignments, reverse-target search %.1f ms in %llu calls (summed over waves)\n",
+            ks[3] / 1e5, ks[7], ks[11] / 1e5, ks[15]);
+    fprintf(stderr, "[pn-stats] run-ahead results the walk took: forward %llu of %llu computed (%.4f), backward %llu found ready of %llu searches run ahead; %llu searches left to the walk itself\n",
+            ks[19], ks[4], ks[4] ? (double)ks[19] / (double)ks[4] : 0.0, ks[23], ks[8], ks[12]);
+  }
+  for (int k = 13; k <= 17; k += 4)      // ticks of the 100 MHz wall clock -> ms
+    fprintf(stderr, "[pn-stats] %s: busy %.1f ms summed over waves, span %.1f ms, longest item %.1f ms (size %llu)\n", k == 13 ? "units" : "forced",
+            st[k] / 1e5, st[k + 2] ? (st[k + 2] - ~st[k + 3]) / 1e5 : 0.0, (st[k + 1] >> 20) / 1e5, st[k + 1] & 0xFFFFFull);
+  return PG_OK;
+}
+
+// A5 and the results: the pairs' pg_anim_result, and their alignment records when the calling thread has set a sink
+static int finish_stage(Batch& B, pg_anim_result* out_host) {
+  pg_ctx* ctx = B.ctx;
+  AnimScratch* A = B.A;
+  int rc;
   pg_prof_begin(ctx, PG_K_ANIM_FINISH);
-  hipLaunchKernelGGL(anim_finish_kernel, dim3(n_pairs), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, n_pairs,
-                     O, A->pn, A->pn_n, A->S, filter_1to1, A->out);
+  hipLaunchKernelGGL(anim_finish_kernel, dim3(B.n_pairs), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, B.n_pairs,
+                     B.O, A->pn, A->pn_n, A->S.view(), B.filter_1to1, A->out);
   pg_prof_end(ctx);
   PG_HIP(ctx, hipGetLastError());
-  PG_HIP(ctx, hipMemcpyAsync(out_host, A->out, n_pairs * sizeof(pg_anim_result), hipMemcpyDeviceToHost, cur_stream(ctx)));
+  PG_HIP(ctx, hipMemcpyAsync(out_host, A->out, B.n_pairs * sizeof(pg_anim_result), hipMemcpyDeviceToHost, cur_stream(ctx)));
   PG_HIP(ctx, hipStreamSynchronize(cur_stream(ctx)));
-  if (tls_sink && (rc = anim_collect(ctx, A, ref_ids, qry_ids, n_pairs, out_host, choff, *tls_sink))) return rc;
+  if (tls_sink && (rc = anim_collect(ctx, A, B.ref_ids, B.qry_ids, B.n_pairs, out_host, B.choff, *tls_sink))) return rc;
   return PG_OK;
+}
+
+// One batch of ordered pairs (ref_ids grouped).  The seed pass appends every unit's matches to one buffer and counts them
+// per (pair, strand) unit; a scatter then gives every per-match array exactly the slice it needs, which is what lets
+// thousands of units be in flight at once within the HBM budget.
+// If the batch needs more than max_matches, only its first n_done pairs are processed (the caller continues from there).
+int pg_anim_run_batch(pg_ctx* ctx, const int32_t* ref_ids, const int32_t* qry_ids, uint32_t n_pairs, int filter_1to1, int maxmatch,
+                      uint64_t max_matches, pg_anim_result* out_host, uint32_t* n_done, const PgFragArgs* frag) {
+  Batch B{ctx, anim_scratch(ctx), ref_ids, qry_ids, frag, filter_1to1, maxmatch, max_matches};
+  int rc;
+  (void)hipGetLastError();   // launch checks below must only see this batch's errors
+  B.set_pairs(n_pairs);
+  if (frag) frag_limit_pairs(B);
+  B.qstep = frag ? FRAG_QSTEP : SEED_STEP;
+  B.use_mirror = !frag && !pg_dev_env("PYANI_ANIM_NO_MIRROR");
+  // Seeding kernel: ANIm uses the block kernel (anim_seed_kernel); fragment mode — and ANIm under the development switch
+  // PYANI_SEED_PER_PAIR=1, which tests hold against it — the per-pair kernel (anim_seed_pair_kernel).  PYANI_SEED_BLOCK_SLOTS
+  // (development): the table size a block is planned for (default SEED_MAX_SLOTS).
+  B.use_blocks = !frag && !(pg_dev_env("PYANI_SEED_PER_PAIR") && atoi(pg_dev_env("PYANI_SEED_PER_PAIR")) == 1);
+  if (pg_dev_env("PYANI_SEED_BLOCK_SLOTS")) {
+    const int want = atoi(pg_dev_env("PYANI_SEED_BLOCK_SLOTS"));
+    B.blk_slots = want >= 512 && want <= (int)SEED_MAX_SLOTS ? (uint32_t)want : SEED_MAX_SLOTS;
+  }
+  B.trace = tls_sink && tls_sink->with_indels;
+  if ((rc = build_descriptors(B))) return rc;
+  if ((rc = seed_stage(B))) return rc;
+  *n_done = B.n_pairs;
+  if ((rc = scatter_matches(B))) return rc;
+  if (frag) {   // fragment mode: the matches of every unit are in place; the rest of the batch is the fragment kernels
+    PG_HIP(ctx, hipGetLastError());
+    return anib_frag_stage(ctx, B.A, qry_ids, B.n_pairs, B.cnt, *frag, B.ref_list, B.ref_of_pair);
+  }
+  if ((rc = cluster_stage(B))) return rc;
+  if ((rc = extend_stage(B))) return rc;
+  if (pg_dev_env("PYANI_PN_STATS") && (rc = print_pn_stats(ctx))) return rc;
+  return finish_stage(B, out_host);
 }
 
 // Fragment mode after seeding: A->mem / A->moff / A->mem_count hold every unit's exact matches (>= 16, sampled), A->units_d /
@@ -1124,7 +1189,6 @@ int pg_anim_run_batch(pg_ctx* ctx, const int32_t* ref_ids, const int32_t* qry_id
 // the pair results (and, optionally, the rows of pair 0).
 // The word index of one genome (pga_frag.inc), built once and kept with its seed lists.
 static int anib_ensure_word_index(pg_ctx* ctx, AnimScratch* A, int32_t gid) {
-  int rc;
   std::lock_guard<std::mutex> lk(ctx->anim_mu);
   AnimLists* LS = anim_lists(ctx);
   if (LS->gidx.size() < ctx->genomes.size()) LS->gidx.resize(ctx->genomes.size());
@@ -1136,9 +1200,12 @@ static int anib_ensure_word_index(pg_ctx* ctx, AnimScratch* A, int32_t gid) {
   const uint32_t* mask = ctx->d_mask + G.arena_start / 32;
   uint32_t* start = nullptr;
   int32_t* pos = nullptr;
-  if (!A->fr_wtmp && (rc = regrow(ctx, A->fr_wtmp, (size_t)WORD_BUCKETS + 1024 + 16))) return rc;   // fill cursors | block sums
-  if ((rc = regrow(ctx, start, (size_t)WORD_BUCKETS + 1))) return rc;
-  if ((rc = regrow(ctx, pos, (size_t)(len > 0 ? len : 1)))) { (void)hipFree(start); return rc; }
+  PG_HIP(ctx, A->fr_wtmp.reserve((size_t)WORD_BUCKETS + 1024 + 16));   // fill cursors | block sums
+  PG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&start), ((size_t)WORD_BUCKETS + 1) * sizeof(uint32_t)));
+  if (hipError_t e0 = hipMalloc(reinterpret_cast<void**>(&pos), (size_t)(len > 0 ? len : 1) * sizeof(int32_t))) {
+    (void)hipFree(start);
+    PG_HIP(ctx, e0);
+  }
   hipStream_t st = cur_stream(ctx);
   const uint32_t grid = (uint32_t)((len + 255) / 256);
   hipError_t e = hipMemsetAsync(start, 0, ((size_t)WORD_BUCKETS + 1) * 4, st);
@@ -1188,25 +1255,20 @@ static int anib_frag_stage(pg_ctx* ctx, AnimScratch* A, const int32_t* qry_ids, 
     slots += (uint64_t)T.n_frags;
   }
   if (slots >= (1ull << 31)) return pg_fail(ctx, PG_E_CAPACITY, "fragment mode: too many (pair, fragment) slots in one launch");
-  if (tables.size() + 1 > A->fr_tables_cap) { if ((rc = regrow(ctx, A->fr_tables, tables.size() + 1024))) return rc; A->fr_tables_cap = tables.size() + 1024; }
+  PG_HIP(ctx, A->fr_tables.reserve(tables.size() + 1, tables.size() + 1024));
   for (uint32_t p = 0; p < n_pairs; ++p) {
     const Tab& T = tab_of[qry_ids[p]];
     fp[p].frag_pos = A->fr_tables + T.pos; fp[p].frag_len = A->fr_tables + T.len; fp[p].rec_frag0 = A->fr_tables + T.rec0;
   }
-  if (n_pairs > A->fr_pairs_cap) {
-    if ((rc = regrow(ctx, A->fr_pairs, n_pairs))) return rc;
-    if ((rc = regrow(ctx, A->fr_out, n_pairs))) return rc;
-    A->fr_pairs_cap = n_pairs;
-  }
-  if (n_units > A->fr_units_cap) { if ((rc = regrow(ctx, A->fr_ebase, n_units))) return rc; A->fr_units_cap = n_units; }
+  PG_HIP(ctx, A->fr_pairs.reserve(n_pairs));
+  PG_HIP(ctx, A->fr_out.reserve(n_pairs));
+  PG_HIP(ctx, A->fr_ebase.reserve(n_units));
   const size_t n_off = 2 * (size_t)slots + 2 * (size_t)n_pairs;
-  if (n_off > A->fr_off_cap) { if ((rc = regrow(ctx, A->fr_off, n_off + n_off / 4))) return rc; A->fr_off_cap = n_off + n_off / 4; }
-  if (slots > A->fr_slots_cap) {
+  PG_HIP(ctx, A->fr_off.reserve(n_off, n_off + n_off / 4));
+  {
     const size_t cap = (size_t)slots + (size_t)slots / 4;
-    if ((rc = regrow(ctx, A->fr_slot_pair, cap))) return rc;
-    if ((rc = regrow(ctx, A->fr_nrows, cap))) return rc;
-    if ((rc = regrow(ctx, A->fr_rows, cap * FRAG_ROWS))) return rc;
-    A->fr_slots_cap = cap;
+    PG_HIP(ctx, reserve_all((size_t)slots, cap, A->fr_slot_pair, A->fr_nrows));
+    PG_HIP(ctx, A->fr_rows.reserve((size_t)slots * FRAG_ROWS, cap * FRAG_ROWS));
   }
   std::vector<uint32_t> slot_pair((size_t)slots);
   for (uint32_t p = 0; p < n_pairs; ++p) std::fill(slot_pair.begin() + fp[p].slot0, slot_pair.begin() + fp[p].slot0 + fp[p].n_frags, p);
@@ -1214,7 +1276,7 @@ static int anib_frag_stage(pg_ctx* ctx, AnimScratch* A, const int32_t* qry_ids, 
   std::vector<uint64_t> ebase(n_units);
   uint64_t n_entries = 0;
   for (uint32_t u = 0; u < n_units; ++u) { ebase[u] = n_entries; n_entries += (uint64_t)cnt[u] + (uint64_t)fp[u / 2].n_frags; }
-  if (n_entries > A->fr_entries_cap) { if ((rc = regrow(ctx, A->fr_entries, (size_t)n_entries + (size_t)n_entries / 4))) return rc; A->fr_entries_cap = (size_t)n_entries + (size_t)n_entries / 4; }
+  PG_HIP(ctx, A->fr_entries.reserve((size_t)n_entries, (size_t)n_entries + (size_t)n_entries / 4));
   if (!tables.empty()) PG_HIP(ctx, hipMemcpyAsync(A->fr_tables, tables.data(), tables.size() * 4, hipMemcpyHostToDevice, cur_stream(ctx)));
   PG_HIP(ctx, hipMemcpyAsync(A->fr_pairs, fp.data(), n_pairs * sizeof(FragPair), hipMemcpyHostToDevice, cur_stream(ctx)));
   if (slots) PG_HIP(ctx, hipMemcpyAsync(A->fr_slot_pair, slot_pair.data(), (size_t)slots * 4, hipMemcpyHostToDevice, cur_stream(ctx)));
@@ -1248,9 +1310,9 @@ static int anib_frag_stage(pg_ctx* ctx, AnimScratch* A, const int32_t* qry_ids, 
       any = true;
     }
     if (any) {
-      if (widx.size() > A->fr_widx_cap) { if ((rc = regrow(ctx, A->fr_widx, widx.size() + 16))) return rc; A->fr_widx_cap = widx.size() + 16; }
-      if ((size_t)slots > A->fr_list_cap) { if ((rc = regrow(ctx, A->fr_list, (size_t)slots + (size_t)slots / 4))) return rc; A->fr_list_cap = (size_t)slots + (size_t)slots / 4; }
-      if (!A->fr_nlist && (rc = regrow(ctx, A->fr_nlist, 4))) return rc;
+      PG_HIP(ctx, A->fr_widx.reserve(widx.size(), widx.size() + 16));
+      PG_HIP(ctx, A->fr_list.reserve((size_t)slots, (size_t)slots + (size_t)slots / 4));
+      PG_HIP(ctx, A->fr_nlist.reserve(4));
       PG_HIP(ctx, hipMemcpyAsync(A->fr_widx, widx.data(), widx.size() * sizeof(WordIdx), hipMemcpyHostToDevice, cur_stream(ctx)));
       PG_HIP(ctx, hipMemsetAsync(A->fr_nlist, 0, 4, cur_stream(ctx)));
       hipLaunchKernelGGL(anib_failed_kernel, dim3((uint32_t)((slots + 255) / 256)), dim3(256), 0, cur_stream(ctx), A->fr_pairs, A->fr_slot_pair,
@@ -1302,15 +1364,8 @@ int pg_anim_fetch_alignments(pg_ctx* ctx, int32_t ref_id, int32_t qry_id, uint32
   const PgGenome& G = ctx->genomes[ref_id];
   const PgGenome& H = ctx->genomes[qry_id];
   for (uint32_t i = 0; i < n; ++i) {
-    const Aln& a = al[i];            // forward stream coordinates, half-open
-    const int32_t ro = G.rec_start[rr[i]], qo = H.rec_start[qr[i]];
-    pg_anim_alignment x;
-    x.ref_rec = rr[i]; x.qry_rec = qr[i];
-    x.rs = a.rs - ro + 1; x.re = a.re - ro;
-    x.qs = a.strand ? a.qe - qo : a.qs - qo + 1;
-    x.qe = a.strand ? a.qs - qo + 1 : a.qe - qo;
-    x.errors = a.errors; x.kept = a.keep;
-    out[i] = x;
+    out[i] = to_record(al[i], G.rec_start[rr[i]], H.rec_start[qr[i]]);
+    out[i].ref_rec = rr[i]; out[i].qry_rec = qr[i];
   }
   return PG_OK;
 }
@@ -1329,28 +1384,25 @@ int pg_anim_reduce_run(pg_ctx* ctx, uint32_t n_pairs, const uint64_t* offsets, c
     a.keep = apply_filter ? 0 : 3;
     h[i] = a;
   }
-  uint64_t* d_off = nullptr; Aln* d_a = nullptr; int32_t *d_rg = nullptr, *d_qg = nullptr, *d_idx = nullptr, *d_from = nullptr;
-  double* d_sc = nullptr; pg_anim_result* d_out = nullptr;
-  std::vector<void*> to_free;
-  auto cleanup = [&]() { for (void* p : to_free) if (p) (void)hipFree(p); };
-  int rc;
-#define AA(ptr, cnt) do { if ((rc = anim_alloc(ctx, ptr, (cnt)))) { cleanup(); return rc; } to_free.push_back(ptr); } while (0)
-  AA(d_off, n_pairs + 1); AA(d_a, n + 1); AA(d_rg, n + 1); AA(d_qg, n + 1); AA(d_idx, n + 1); AA(d_from, n + 1); AA(d_sc, n + 1);
-  AA(d_out, n_pairs + 1);
-#undef AA
-  hipError_t e = hipMemcpyAsync(d_off, offsets, (n_pairs + 1) * 8, hipMemcpyHostToDevice, cur_stream(ctx));
-  if (e == hipSuccess && n) e = hipMemcpyAsync(d_a, h.data(), n * sizeof(Aln), hipMemcpyHostToDevice, cur_stream(ctx));
-  if (e == hipSuccess && n) e = hipMemcpyAsync(d_rg, rseq, n * 4, hipMemcpyHostToDevice, cur_stream(ctx));
-  if (e == hipSuccess && n) e = hipMemcpyAsync(d_qg, qseq, n * 4, hipMemcpyHostToDevice, cur_stream(ctx));
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(anim_reduce_kernel, dim3((n_pairs + 63) / 64), dim3(64), 0, cur_stream(ctx), n_pairs, d_off, d_a, d_rg, d_qg,
-                       d_idx, d_from, d_sc, apply_filter, d_out);
-    e = hipGetLastError();
+  const hipStream_t st = cur_stream(ctx);
+  PgDevBuf<uint64_t> d_off;
+  PgDevBuf<Aln> d_a;
+  PgDevBuf<int32_t> d_rg, d_qg, d_idx, d_from;
+  PgDevBuf<double> d_sc;
+  PgDevBuf<pg_anim_result> d_out;
+  PG_HIP(ctx, reserve_all(n_pairs + 1, n_pairs + 1, d_off, d_out));
+  PG_HIP(ctx, reserve_all(n + 1, n + 1, d_a, d_rg, d_qg, d_idx, d_from, d_sc));
+  PG_HIP_MSG(ctx, "anim reduce: ", hipMemcpyAsync(d_off, offsets, (n_pairs + 1) * 8, hipMemcpyHostToDevice, st));
+  if (n) {
+    PG_HIP_MSG(ctx, "anim reduce: ", hipMemcpyAsync(d_a, h.data(), n * sizeof(Aln), hipMemcpyHostToDevice, st));
+    PG_HIP_MSG(ctx, "anim reduce: ", hipMemcpyAsync(d_rg, rseq, n * 4, hipMemcpyHostToDevice, st));
+    PG_HIP_MSG(ctx, "anim reduce: ", hipMemcpyAsync(d_qg, qseq, n * 4, hipMemcpyHostToDevice, st));
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n_pairs * sizeof(pg_anim_result), hipMemcpyDeviceToHost, cur_stream(ctx));
-  if (e == hipSuccess) e = hipStreamSynchronize(cur_stream(ctx));
-  cleanup();
-  if (e != hipSuccess) return pg_fail(ctx, PG_E_HIP, std::string("anim reduce: ") + hipGetErrorString(e));
+  hipLaunchKernelGGL(anim_reduce_kernel, dim3((n_pairs + 63) / 64), dim3(64), 0, st, n_pairs, d_off, d_a, d_rg, d_qg,
+                     d_idx, d_from, d_sc, apply_filter, d_out);
+  PG_HIP_MSG(ctx, "anim reduce: ", hipGetLastError());
+  PG_HIP_MSG(ctx, "anim reduce: ", hipMemcpyAsync(out, d_out, n_pairs * sizeof(pg_anim_result), hipMemcpyDeviceToHost, st));
+  PG_HIP_MSG(ctx, "anim reduce: ", hipStreamSynchronize(st));
   return PG_OK;
 }
 
@@ -1395,33 +1447,27 @@ int pg_anib_reduce_run(pg_ctx* ctx, uint32_t n_pairs, const uint64_t* offsets, c
   const uint64_t n = offsets[n_pairs];
   std::vector<uint64_t> foff(n_pairs + 1, 0);
   for (uint32_t p = 0; p < n_pairs; ++p) foff[p + 1] = foff[p] + n_frags[p];
-  std::vector<void*> to_free;
-  auto cleanup = [&]() { for (void* q : to_free) if (q) (void)hipFree(q); };
-  uint64_t *d_off = nullptr, *d_foff = nullptr;
-  int32_t *d_frag = nullptr, *d_len = nullptr, *d_mm = nullptr, *d_gap = nullptr, *d_ql = nullptr;
-  double *d_pid = nullptr, *d_pout = nullptr;
-  int64_t *d_first = nullptr, *d_aln = nullptr, *d_err = nullptr;
-  int rc;
-#define AA(ptr, cnt) do { if ((rc = anim_alloc(ctx, ptr, (cnt)))) { cleanup(); return rc; } to_free.push_back(ptr); } while (0)
-  AA(d_off, n_pairs + 1); AA(d_foff, n_pairs + 1); AA(d_frag, n + 1); AA(d_len, n + 1); AA(d_mm, n + 1); AA(d_gap, n + 1);
-  AA(d_ql, n + 1); AA(d_pid, n + 1); AA(d_first, foff[n_pairs] + 1); AA(d_aln, n_pairs); AA(d_err, n_pairs); AA(d_pout, n_pairs);
-#undef AA
-  hipError_t e = hipMemcpyAsync(d_off, offsets, (n_pairs + 1) * 8, hipMemcpyHostToDevice, cur_stream(ctx));
-  if (e == hipSuccess) e = hipMemcpyAsync(d_foff, foff.data(), (n_pairs + 1) * 8, hipMemcpyHostToDevice, cur_stream(ctx));
+  const hipStream_t st = cur_stream(ctx);
+  PgDevBuf<uint64_t> d_off, d_foff;
+  PgDevBuf<int32_t> d_frag, d_len, d_mm, d_gap, d_ql;
+  PgDevBuf<double> d_pid, d_pout;
+  PgDevBuf<int64_t> d_first, d_aln, d_err;
+  PG_HIP(ctx, reserve_all(n_pairs + 1, n_pairs + 1, d_off, d_foff));
+  PG_HIP(ctx, reserve_all(n + 1, n + 1, d_frag, d_len, d_mm, d_gap, d_ql, d_pid));
+  PG_HIP(ctx, d_first.reserve(foff[n_pairs] + 1));
+  PG_HIP(ctx, reserve_all(n_pairs, n_pairs, d_aln, d_err, d_pout));
+  PG_HIP_MSG(ctx, "anib reduce: ", hipMemcpyAsync(d_off, offsets, (n_pairs + 1) * 8, hipMemcpyHostToDevice, st));
+  PG_HIP_MSG(ctx, "anib reduce: ", hipMemcpyAsync(d_foff, foff.data(), (n_pairs + 1) * 8, hipMemcpyHostToDevice, st));
   const struct { void* d; const void* h; size_t b; } cp[] = {{d_frag, frag, n * 4}, {d_len, length, n * 4}, {d_mm, mismatch, n * 4},
                                                            {d_gap, gaps, n * 4}, {d_ql, qlen, n * 4}, {d_pid, pident, n * 8}};
   for (const auto& c : cp)
-    if (e == hipSuccess && c.b) e = hipMemcpyAsync(c.d, c.h, c.b, hipMemcpyHostToDevice, cur_stream(ctx));
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(anib_reduce_kernel, dim3((n_pairs + 63) / 64), dim3(64), 0, cur_stream(ctx), n_pairs, d_off, d_foff, d_frag, d_len,
-                       d_mm, d_gap, d_ql, d_pid, d_first, d_aln, d_err, d_pout);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(aln_out, d_aln, n_pairs * 8, hipMemcpyDeviceToHost, cur_stream(ctx));
-  if (e == hipSuccess) e = hipMemcpyAsync(err_out, d_err, n_pairs * 8, hipMemcpyDeviceToHost, cur_stream(ctx));
-  if (e == hipSuccess) e = hipMemcpyAsync(pid_out, d_pout, n_pairs * 8, hipMemcpyDeviceToHost, cur_stream(ctx));
-  if (e == hipSuccess) e = hipStreamSynchronize(cur_stream(ctx));
-  cleanup();
-  if (e != hipSuccess) return pg_fail(ctx, PG_E_HIP, std::string("anib reduce: ") + hipGetErrorString(e));
+    if (c.b) PG_HIP_MSG(ctx, "anib reduce: ", hipMemcpyAsync(c.d, c.h, c.b, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(anib_reduce_kernel, dim3((n_pairs + 63) / 64), dim3(64), 0, st, n_pairs, d_off, d_foff, d_frag, d_len,
+                     d_mm, d_gap, d_ql, d_pid, d_first, d_aln, d_err, d_pout);
+  PG_HIP_MSG(ctx, "anib reduce: ", hipGetLastError());
+  PG_HIP_MSG(ctx, "anib reduce: ", hipMemcpyAsync(aln_out, d_aln, n_pairs * 8, hipMemcpyDeviceToHost, st));
+  PG_HIP_MSG(ctx, "anib reduce: ", hipMemcpyAsync(err_out, d_err, n_pairs * 8, hipMemcpyDeviceToHost, st));
+  PG_HIP_MSG(ctx, "anib reduce: ", hipMemcpyAsync(pid_out, d_pout, n_pairs * 8, hipMemcpyDeviceToHost, st));
+  PG_HIP_MSG(ctx, "anib reduce: ", hipStreamSynchronize(st));
   return PG_OK;
 }

@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "pg_internal.h"
+#include "pg_devbuf.h"
 
 namespace {
 
@@ -33,15 +34,10 @@ constexpr size_t CL_LDS_LIMIT = 160 * 1024;
 struct ClassifyState {
   uint32_t n = 0, n_nodes = 0;
   uint64_t n_edges = 0;
-  double* d_w = nullptr;           // n x n: identity of the pair's edge at [i * n + j], i < j (NaN: no edge)
-  double* d_edges = nullptr;       // n_edges identities, unordered
-  uint32_t* d_death = nullptr;     // n x n, made by every sweep call
+  PgDevBuf<double> d_w;            // n x n: identity of the pair's edge at [i * n + j], i < j (NaN: no edge)
+  PgDevBuf<double> d_edges;        // n_edges identities, unordered
+  PgDevBuf<uint32_t> d_death;      // n x n, made by every sweep call
 };
-
-void free_state(ClassifyState* S) {
-  for (void* p : {(void*)S->d_w, (void*)S->d_edges, (void*)S->d_death}) if (p) (void)hipFree(p);
-  *S = ClassifyState{};
-}
 
 // counters: [0] number of edges (the append cursor), [1] != 0: the last genome has an edge
 __global__ __launch_bounds__(256) void classify_edge_kernel(const double* __restrict__ ident, const double* __restrict__ cov, uint32_t n, double id_min,
@@ -166,18 +162,11 @@ __global__ __launch_bounds__(1024) void classify_sweep_kernel(const uint32_t* __
 }
 
 template <typename T>
-int cl_malloc(pg_ctx* ctx, T*& p, size_t count, const char* what) {
-  p = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T)) == hipSuccess) return PG_OK;
+int cl_malloc(pg_ctx* ctx, PgDevBuf<T>& b, size_t count, const char* what) {      // an empty buffer gets count (at least 1) elements
+  if (b.reserve(std::max<size_t>(count, 1)) == hipSuccess) return PG_OK;
   (void)hipGetLastError();
-  p = nullptr;
   return pg_fail(ctx, PG_E_NOMEM, std::string("classify: no device memory for ") + what);
 }
-
-struct DevBuf {      // freed on every exit path
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-};
 
 ClassifyState* state_of(pg_ctx* ctx) { return static_cast<ClassifyState*>(ctx->classify_state); }
 
@@ -185,9 +174,7 @@ ClassifyState* state_of(pg_ctx* ctx) { return static_cast<ClassifyState*>(ctx->c
 
 void pg_classify_drop(pg_ctx* ctx) {
   if (!ctx->classify_state) return;
-  ClassifyState* S = state_of(ctx);
-  free_state(S);
-  delete S;
+  delete state_of(ctx);
   ctx->classify_state = nullptr;
 }
 
@@ -209,17 +196,12 @@ extern "C" int pg_classify_edges(pg_ctx* ctx, const double* identity, const doub
   ClassifyState* S = new ClassifyState();
   ctx->classify_state = S;
   const size_t nn = (size_t)n * n;
-  DevBuf d_id, d_cov, d_cnt;
-  double *pi = nullptr, *pc = nullptr;
-  unsigned long long* pk = nullptr;
+  PgDevBuf<double> pi, pc;
+  PgDevBuf<unsigned long long> pk;
   int rc;
-  if ((rc = cl_malloc(ctx, pi, nn, "the identity matrix"))) { pg_classify_drop(ctx); return rc; }
-  d_id.p = pi;
-  if ((rc = cl_malloc(ctx, pc, nn, "the coverage matrix"))) { pg_classify_drop(ctx); return rc; }
-  d_cov.p = pc;
-  if ((rc = cl_malloc(ctx, pk, 2, "the edge counters"))) { pg_classify_drop(ctx); return rc; }
-  d_cnt.p = pk;
-  if ((rc = cl_malloc(ctx, S->d_w, nn, "the edge weight table")) || (rc = cl_malloc(ctx, S->d_edges, nn / 2, "the edge list"))) {
+  if ((rc = cl_malloc(ctx, pi, nn, "the identity matrix")) || (rc = cl_malloc(ctx, pc, nn, "the coverage matrix")) ||
+      (rc = cl_malloc(ctx, pk, 2, "the edge counters")) || (rc = cl_malloc(ctx, S->d_w, nn, "the edge weight table")) ||
+      (rc = cl_malloc(ctx, S->d_edges, nn / 2, "the edge list"))) {
     pg_classify_drop(ctx);
     return rc;
   }
@@ -281,25 +263,15 @@ extern "C" int pg_classify_sweep(pg_ctx* ctx, const double* theta, uint64_t n_st
   const uint32_t grid = (uint32_t)std::min<uint64_t>(steps, (uint64_t)ctx->num_cu * (lds_adj ? per_cu : 1u));
   int rc;
   if (!S->d_death && (rc = cl_malloc(ctx, S->d_death, nn, "the death-index table"))) return rc;
-  DevBuf b_theta, b_sub, b_comp, b_lab, b_scr;
-  double* d_theta = nullptr;
-  int32_t *d_sub = nullptr, *d_lab = nullptr;
-  uint8_t* d_comp = nullptr;
-  unsigned long long* d_scr = nullptr;
+  PgDevBuf<double> d_theta;
+  PgDevBuf<int32_t> d_sub, d_lab;
+  PgDevBuf<uint8_t> d_comp;
+  PgDevBuf<unsigned long long> d_scr;
   if ((rc = cl_malloc(ctx, d_theta, steps, "the thresholds"))) return rc;
-  b_theta.p = d_theta;
   if ((rc = cl_malloc(ctx, d_sub, steps, "the component counts"))) return rc;
-  b_sub.p = d_sub;
   if ((rc = cl_malloc(ctx, d_comp, steps, "the completeness flags"))) return rc;
-  b_comp.p = d_comp;
-  if (labels_out) {
-    if ((rc = cl_malloc(ctx, d_lab, (size_t)steps * n, "the per-step labels (ask for fewer steps per call)"))) return rc;
-    b_lab.p = d_lab;
-  }
-  if (!lds_adj) {
-    if ((rc = cl_malloc(ctx, d_scr, (size_t)grid * n * n_words, "the adjacency scratch"))) return rc;
-    b_scr.p = d_scr;
-  }
+  if (labels_out && (rc = cl_malloc(ctx, d_lab, (size_t)steps * n, "the per-step labels (ask for fewer steps per call)"))) return rc;
+  if (!lds_adj && (rc = cl_malloc(ctx, d_scr, (size_t)grid * n * n_words, "the adjacency scratch"))) return rc;
   const void* fn = lds_adj ? reinterpret_cast<const void*>(classify_sweep_kernel<true>) : reinterpret_cast<const void*>(classify_sweep_kernel<false>);
   if (lds_bytes > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) {
     (void)hipGetLastError();

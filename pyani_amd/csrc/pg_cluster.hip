@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "pg_internal.h"
+#include "pg_devbuf.h"
 
 namespace {
 
@@ -245,20 +246,10 @@ __global__ __launch_bounds__(1024) void cluster_linkage_kernel(const ClusterProb
   }
 }
 
-struct DevBuf {      // freed on every exit path
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
 template <typename T>
-int clu_malloc(pg_ctx* ctx, DevBuf& b, T*& p, size_t count, const char* what) {
-  p = nullptr;
-  if (hipMalloc(&b.p, std::max<size_t>(count, 1) * sizeof(T)) == hipSuccess) {
-    p = static_cast<T*>(b.p);
-    return PG_OK;
-  }
+int clu_malloc(pg_ctx* ctx, PgDevBuf<T>& b, size_t count, const char* what) {      // an empty buffer gets count (at least 1) elements
+  if (b.reserve(std::max<size_t>(count, 1)) == hipSuccess) return PG_OK;
   (void)hipGetLastError();
-  b.p = nullptr;
   return pg_fail(ctx, PG_E_NOMEM, std::string("cluster: no device memory for ") + what);
 }
 
@@ -293,11 +284,10 @@ extern "C" int pg_cluster_pdist(pg_ctx* ctx, const double* x, uint32_t rows, uin
   if (n_pairs == 0) return PG_OK;
   if (!out) return pg_fail(ctx, PG_E_ARG, "cluster: bad argument");
   PG_HIP(ctx, hipSetDevice(ctx->device));
-  DevBuf b_x, b_c, b_f;
-  double *d_x, *d_c;
-  int* d_f;
-  if ((rc = clu_malloc(ctx, b_x, d_x, (size_t)rows * cols, "the matrix")) || (rc = clu_malloc(ctx, b_c, d_c, n_pairs, "the distances")) ||
-      (rc = clu_malloc(ctx, b_f, d_f, 1, "the flag")))
+  PgDevBuf<double> d_x, d_c;
+  PgDevBuf<int> d_f;
+  if ((rc = clu_malloc(ctx, d_x, (size_t)rows * cols, "the matrix")) || (rc = clu_malloc(ctx, d_c, n_pairs, "the distances")) ||
+      (rc = clu_malloc(ctx, d_f, 1, "the flag")))
     return rc;
   int h_flag = 0;
   hipError_t e = hipMemcpyAsync(d_x, x, (size_t)rows * cols * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
@@ -330,13 +320,13 @@ extern "C" int pg_cluster_linkage_batch(pg_ctx* ctx, pg_cluster_problem* problem
   }
   PG_HIP(ctx, hipSetDevice(ctx->device));
   // device buffers: one copy of every distinct caller matrix, a working matrix and the records per problem, the flags, the descriptors
-  std::vector<DevBuf> bufs(3 * (size_t)n_problems + 2);
+  std::vector<PgDevBuf<double>> bufs(3 * (size_t)n_problems);
   size_t nb = 0;
   std::vector<double*> d_x(n_problems, nullptr);
   std::vector<ClusterProblem> h_prob(n_problems);
-  int* d_flags;
-  ClusterProblem* d_prob;
-  if ((rc = clu_malloc(ctx, bufs[nb++], d_flags, n_problems, "the flags")) || (rc = clu_malloc(ctx, bufs[nb++], d_prob, n_problems, "the problem table")))
+  PgDevBuf<int> d_flags;
+  PgDevBuf<ClusterProblem> d_prob;
+  if ((rc = clu_malloc(ctx, d_flags, n_problems, "the flags")) || (rc = clu_malloc(ctx, d_prob, n_problems, "the problem table")))
     return rc;
   hipError_t e = hipMemsetAsync(d_flags, 0, n_problems * sizeof(int), ctx->stream);
   for (uint32_t p = 0; p < n_problems && e == hipSuccess; ++p) {
@@ -344,13 +334,15 @@ extern "C" int pg_cluster_linkage_batch(pg_ctx* ctx, pg_cluster_problem* problem
     for (uint32_t o = 0; o < p; ++o)      // both orientations of one matrix share its upload
       if (problems[o].x == q.x && problems[o].rows == q.rows && problems[o].cols == q.cols) { d_x[p] = d_x[o]; break; }
     if (!d_x[p]) {
-      if ((rc = clu_malloc(ctx, bufs[nb++], d_x[p], (size_t)q.rows * q.cols, "a matrix"))) return rc;
+      if ((rc = clu_malloc(ctx, bufs[nb], (size_t)q.rows * q.cols, "a matrix"))) return rc;
+      d_x[p] = bufs[nb++];
       e = hipMemcpyAsync(d_x[p], q.x, (size_t)q.rows * q.cols * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
     }
     const uint32_t n = ns[p];
-    if ((rc = clu_malloc(ctx, bufs[nb++], h_prob[p].work, (size_t)n * n, "a working matrix")) ||
-        (rc = clu_malloc(ctx, bufs[nb++], h_prob[p].merges, (size_t)(n - 1) * 4, "the merge records")))
+    if ((rc = clu_malloc(ctx, bufs[nb], (size_t)n * n, "a working matrix")) || (rc = clu_malloc(ctx, bufs[nb + 1], (size_t)(n - 1) * 4, "the merge records")))
       return rc;
+    h_prob[p].work = bufs[nb++];
+    h_prob[p].merges = bufs[nb++];
     h_prob[p].flag = d_flags + p;
     h_prob[p].n = n;
     h_prob[p].method = q.method;

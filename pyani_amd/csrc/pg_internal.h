@@ -127,6 +127,12 @@ int pg_fail(pg_ctx* ctx, int code, const std::string& msg);
     if (_e != hipSuccess)                                                                                     \
       return pg_fail((ctx), PG_E_HIP, std::string(#call) + ": " + hipGetErrorString(_e));                     \
   } while (0)
+// the same with the caller's message prefix in place of the call's text
+#define PG_HIP_MSG(ctx, prefix, call)                                                                         \
+  do {                                                                                                        \
+    hipError_t _e = (call);                                                                                   \
+    if (_e != hipSuccess) return pg_fail((ctx), PG_E_HIP, std::string(prefix) + hipGetErrorString(_e));       \
+  } while (0)
 
 // profiling helpers (pg_api.cpp).  Events are recorded on the calling thread's stream: pg_tls_stream when set (the ANIm
 // workers), else the context's.

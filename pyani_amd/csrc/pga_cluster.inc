@@ -1,5 +1,5 @@
 // pga_cluster.inc — part of pg_anim.hip (included inside its anonymous namespace; not a translation unit of its own):
-// A3: MUM filter, mgaps clustering, chain extraction (scalar debug kernel, wave primitives, prep kernel, wave kernel).
+// A3: MUM filter, mgaps clustering, chain extraction (wave primitives, prep kernel, wave kernel).
 
 constexpr int CHAIN_RANGES_MAX = 64;
 constexpr int CHAIN_RANGE_ENTRIES = 1024;   // nominal range length (host: ranges of a unit = matches / this, 1..CHAIN_RANGES_MAX)
@@ -19,40 +19,6 @@ struct ClusterOut {   // per-match arrays are sliced by moff[] (a chain has >= 1
 __device__ __forceinline__ int32_t unit_qrec(const UnitDesc& U, int32_t q) {
   if (U.n_rec <= 1) return 0;
   return record_of(U.rec_start, U.n_rec, U.strand ? U.len - 1 - q : q);
-}
-
-__global__ __launch_bounds__(64) void anim_cluster_kernel(const RefDesc* __restrict__ refs, const UnitDesc* __restrict__ units, uint32_t n_units,
-                                                          Match* __restrict__ mem, const uint32_t* __restrict__ mem_count,
-                                                          int32_t* __restrict__ iscratch, ClusterOut O) {
-  const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
-  if (u >= n_units) return;
-  const UnitDesc U = units[u];
-  const RefDesc R = refs[U.ref];
-  O.n_chains[u] = 0;
-  const size_t off = O.moff[u];
-  const uint32_t cap = O.moff[u + 1] - O.moff[u];
-  uint32_t n0 = mem_count[u];
-  if (n0 > cap) { atomicOr(&O.status[U.pair], 1); n0 = cap; }
-  if (n0 == 0) return;
-  Match* m = mem + off;
-  const int n = mum_filter(m, (int)n0, U.strand, [&](int32_t q) { return unit_qrec(U, q); });
-  int32_t* s = iscratch + off * 7;
-  int32_t *rrec = s, *qrec = s + cap, *parent = s + 2 * (size_t)cap, *score = s + 3 * (size_t)cap, *from = s + 4 * (size_t)cap,
-          *adj = s + 5 * (size_t)cap, *order = s + 6 * (size_t)cap;
-  for (int i = 0; i < n; ++i) {
-    rrec[i] = record_of(R.rec_start, R.n_rec, m[i].r);
-    const int32_t qf = U.strand ? U.len - 1 - m[i].q : m[i].q;
-    qrec[i] = record_of(U.rec_start, U.n_rec, qf);
-  }
-  int n_chains = 0, n_cm = 0;
-  Chain* chains = O.chains + off;
-  Match* cm = O.cm + off;
-  mgaps_strand(m, n, U.strand, rrec, qrec, parent, score, from, adj, order, chains, n_chains, (int)cap, cm, n_cm, (int)cap);
-  n_chains = split_chains_by_ref_record(chains, n_chains, cm, [&](int32_t r) { return record_of(R.rec_start, R.n_rec, r); });
-  int32_t* co = O.order + off;
-  for (int i = 0; i < n_chains; ++i) co[i] = i;
-  heapsort(co, n_chains, [&](int a, int b) { return chain_before(chains, cm, a, b); });
-  O.n_chains[u] = n_chains;
 }
 
 __device__ __forceinline__ int32_t from_lane_below(int32_t v, int32_t fill) {  // lane l <- lane l-1 (lane 0 <- fill)
@@ -90,7 +56,7 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return ~wave_max_
 
 // =====================================================================================================================
 // A3, wave-cooperative: one WAVE per (pair, strand) unit.  Same results as the scalar statement (pga::mum_filter +
-// pga::mgaps_strand, which the one-thread kernel above runs): stable LSD radix sorts instead of heapsorts, wave scans
+// pga::mgaps_strand in pg_anim_core.h): stable LSD radix sorts instead of heapsorts, wave scans
 // for the containment flags, a lock-free union-find, and a chain DP whose 64-deep look-back lives in the 64 lanes.
 // =====================================================================================================================
 __device__ __forceinline__ uint64_t lanemask_lt() { return (1ull << (threadIdx.x & 63)) - 1ull; }

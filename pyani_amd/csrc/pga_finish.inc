@@ -143,9 +143,3 @@ __global__ __launch_bounds__(64) void anim_reduce_kernel(uint32_t n_pairs, const
   res.reserved = 0;
   out[p] = res;
 }
-
-template <typename T>
-int anim_alloc(pg_ctx* ctx, T*& p, size_t n) {
-  PG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T)));
-  return PG_OK;
-}
