@@ -331,6 +331,39 @@ typedef struct {
 } pg_cluster_problem;
 int pg_cluster_linkage_batch(pg_ctx* ctx, pg_cluster_problem* problems, uint32_t n_problems);
 
+/* ---- distribution plots: histogram and Gaussian kernel density estimate -------------------------------------------------
+ * The arithmetic of `pyani plot`'s distribution plots over all cells of a result matrix (five matrices per run,
+ * pyani/scripts/subcommands/subcmd_plot.py:141-153).  Like the classify and cluster calls these read caller arrays only and may be
+ * used on any context.  The values stay resident in the context from pg_dist_load until the next pg_dist_load, pg_dist_release or
+ * pg_destroy.  Minimum, maximum and all counts are exact; the density sums are deterministic (their order is fixed at compile time:
+ * two calls give the same bits on any launch).  The host owns what fixes floats: bin edges, grid, bandwidth, normalisation
+ * (pyani_amd.graphics.distribution_data). */
+typedef struct {
+  double min, max;        /* over the non-NaN values, +-inf included (+inf, -inf when every value is NaN) */
+  uint64_t n_nan, n_inf;  /* NaN cells; +inf and -inf cells */
+} pg_dist_stats;
+/* pg_dist_load replaces `data = dfr.values.flatten()` with `min(data)`, `max(data)` (pyani_graphics/mpl/__init__.py:149-150) and the
+ * range scan of np.histogram: uploads the n float64 values and makes one pass over them.  n <= 8192 * 8192 (PG_E_ARG beyond);
+ * PG_E_NOMEM when the values do not fit. */
+int pg_dist_load(pg_ctx* ctx, const double* x, uint64_t n, pg_dist_stats* stats_out);
+/* pg_dist_hist replaces the counting of `axes[0].hist(data, bins=50)` (pyani_graphics/mpl/__init__.py:152) and of histplot
+ * (pyani_graphics/sns/__init__.py:204-211), i.e. np.histogram(data, edges)[0]: edges are n_bins + 1 ascending float64 (equal
+ * neighbours allowed, not necessarily evenly spaced); value x is counted in the largest i with edges[i] <= x, x == edges[n_bins] in
+ * the last bin; NaN and values outside [edges[0], edges[n_bins]] are not counted.  counts_out: n_bins uint64.  PG_E_ARG when nothing
+ * is loaded, when an edge is NaN or below its predecessor, or for n_bins > 4096. */
+int pg_dist_hist(pg_ctx* ctx, const double* edges, uint32_t n_bins, uint64_t* counts_out);
+/* pg_dist_kde replaces the sum inside `density(xvals)` of scipy.stats.gaussian_kde (pyani_graphics/mpl/__init__.py:154-156; kdeplot,
+ * pyani_graphics/sns/__init__.py:213): sums_out[j] = sum over the non-NaN values x of exp(-((points[j] - x) / bandwidth)^2 / 2), fp64;
+ * the caller applies the normalisation.  PG_E_ARG when nothing is loaded, when the bandwidth is not finite and positive, or for
+ * n_points > 1024. */
+int pg_dist_kde(pg_ctx* ctx, const double* points, uint32_t n_points, double bandwidth, double* sums_out);
+/* Frees the resident values now (otherwise: the next pg_dist_load or pg_destroy). */
+int pg_dist_release(pg_ctx* ctx);
+/* Kernel milliseconds of the latest pg_dist_load (the stats pass), pg_dist_hist and pg_dist_kde, in this order: HIP events on the
+ * context's stream round the call's kernels, taken while pg_profile_enable is on; zeros when it is off.  (These kernels have no
+ * PG_K_* slot: the slot count is published.) */
+int pg_dist_last_ms(pg_ctx* ctx, double* out3);
+
 /* ---- measurement ---------------------------------------------------------------------------------------- */
 /* When enabled, every kernel launch is bracketed by HIP events on the context's stream. */
 int pg_profile_enable(pg_ctx* ctx, int on);

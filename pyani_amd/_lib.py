@@ -82,6 +82,11 @@ SIGNATURES = {
     "pg_cluster_pdist": (_int, [_vp, _vp, _u32, _u32, _int, _vp]),
     "pg_cluster_linkage": (_int, [_vp, _vp, _u32, _u32, _int, _int, _vp]),
     "pg_cluster_linkage_batch": (_int, [_vp, _vp, _u32]),
+    "pg_dist_load": (_int, [_vp, _vp, _u64, _vp]),
+    "pg_dist_hist": (_int, [_vp, _vp, _u32, _vp]),
+    "pg_dist_kde": (_int, [_vp, _vp, _u32, ctypes.c_double, _vp]),
+    "pg_dist_release": (_int, [_vp]),
+    "pg_dist_last_ms": (_int, [_vp, _vp]),
     "pg_profile_enable": (_int, [_vp, _int]),
     "pg_profile_config": (_int, [_vp, _u32, _u32]),
     "pg_profile_reset": (_int, [_vp]),
@@ -95,6 +100,11 @@ class ClusterProblem(ctypes.Structure):
     """pg_cluster_problem (include/pyani_gpu.h)."""
     _fields_ = [("x", _vp), ("rows", _u32), ("cols", _u32), ("columns", _i32), ("method", _i32), ("merges", _vp), ("status", _i32),
                 ("reserved", _i32)]
+
+
+class DistStats(ctypes.Structure):
+    """pg_dist_stats (include/pyani_gpu.h)."""
+    _fields_ = [("min", ctypes.c_double), ("max", ctypes.c_double), ("n_nan", _u64), ("n_inf", _u64)]
 
 
 _lib = None

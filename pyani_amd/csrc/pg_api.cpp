@@ -355,6 +355,7 @@ void pg_destroy(pg_ctx* ctx) {
   pg_anim_free_scratch(ctx);
   pg_sketch_drop(ctx);
   pg_classify_drop(ctx);
+  pg_dist_drop(ctx);
   prof_drain(ctx);
   void* dev[] = {ctx->d_codes, ctx->d_mask, ctx->d_quirk, ctx->d_seg_tile0, ctx->d_seg_prefix, ctx->d_batch_gid, ctx->d_acc,
                  ctx->d_counts, ctx->d_z, ctx->d_present, ctx->d_dev, ctx->d_ss, ctx->d_flags, ctx->d_corr};

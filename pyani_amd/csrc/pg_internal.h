@@ -97,6 +97,8 @@ struct pg_ctx {
   void* anim_lists = nullptr;      // per-genome seed lists, shared by the workers (guarded by anim_mu)
   void* sketch_store = nullptr;    // per-genome k-mer sketches of the sketch mode (pg_sketch.hip), built on first use
   void* classify_state = nullptr;  // resident edge state of the classify sweep (pg_classify.hip), replaced by every pg_classify_edges
+  void* dist_state = nullptr;      // resident values of the distribution calls (pg_dist.hip), replaced by every pg_dist_load
+  double dist_ms[3] = {0.0, 0.0, 0.0};   // kernel milliseconds of the latest pg_dist_load / _hist / _kde while profiling is on (pg_dist_last_ms)
   std::mutex anim_mu, err_mu, prof_mu;
   int anib_word_tier = 1;      // fragment mode: search failed fragments again with blastn-sized (11-mer) seeds
   int anim_pn_window_max = 2048;   // forced runs: the widest single-wave window (development: smaller values push runs on to the group kernel)
@@ -188,6 +190,7 @@ void pg_anim_set_sink(PgAlnSink* sink);           // thread-local; nullptr = non
 void pg_anim_drop_lists(pg_ctx* ctx);   // per-genome seed lists: must go when the genome store is cleared
 void pg_sketch_drop(pg_ctx* ctx);       // ... and the sketches of the sketch mode (pg_sketch.hip)
 void pg_classify_drop(pg_ctx* ctx);     // ... the classify sweep's edge state (pg_classify.hip): goes with the context or on request
+void pg_dist_drop(pg_ctx* ctx);         // ... the distribution calls' resident values (pg_dist.hip): the same
 int pg_anib_reduce_run(pg_ctx* ctx, uint32_t n_pairs, const uint64_t* offsets, const uint32_t* n_frags, const int32_t* frag,
                        const int32_t* length, const int32_t* mismatch, const int32_t* gaps, const int32_t* qlen,
                        const double* pident, int64_t* aln_out, int64_t* err_out, double* pid_out);

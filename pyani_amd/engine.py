@@ -390,6 +390,39 @@ class Engine:
         self._check(self.lib.pg_cluster_linkage_batch(self._h, ctypes.cast(arr, ctypes.c_void_p), len(problems)))
         return [None if arr[k].status == _lib.PG_E_NONFINITE else outs[k] for k in range(len(problems))]
 
+    # -- distribution plots: histogram and kernel density estimate (pyani_amd.graphics drives these) ------------------------------
+    def dist_load(self, x) -> Tuple[float, float, int, int]:
+        """pg_dist_load: uploads the values (any shape, taken in C order) and keeps them resident for dist_hist / dist_kde.  Returns
+        (min, max, NaN cells, +-inf cells); min and max are over the non-NaN values (pyani_graphics/mpl/__init__.py:149-150)."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        st = _lib.DistStats()
+        self._check(self.lib.pg_dist_load(self._h, x.ctypes.data if len(x) else None, len(x), ctypes.addressof(st)))
+        return float(st.min), float(st.max), int(st.n_nan), int(st.n_inf)
+
+    def dist_hist(self, edges) -> np.ndarray:
+        """pg_dist_hist over the resident values: np.histogram(values, edges)[0] as int64, exactly (pyani_graphics/mpl/__init__.py:152)."""
+        e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        counts = np.zeros(max(len(e) - 1, 0), dtype=np.uint64)
+        self._check(self.lib.pg_dist_hist(self._h, e.ctypes.data, len(counts), counts.ctypes.data if len(counts) else None))
+        return counts.astype(np.int64)
+
+    def dist_kde(self, points, bandwidth: float) -> np.ndarray:
+        """pg_dist_kde over the resident values: sum_i exp(-((p_j - x_i) / bandwidth)^2 / 2) per point, float64, NOT normalised (the sum
+        inside scipy's gaussian_kde.evaluate, pyani_graphics/mpl/__init__.py:154-156)."""
+        p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1)
+        out = np.zeros(len(p), dtype=np.float64)
+        self._check(self.lib.pg_dist_kde(self._h, p.ctypes.data if len(p) else None, len(p), float(bandwidth), out.ctypes.data if len(p) else None))
+        return out
+
+    def dist_release(self) -> None:
+        self._check(self.lib.pg_dist_release(self._h))
+
+    def dist_last_ms(self) -> Tuple[float, float, float]:
+        """Kernel milliseconds of the latest dist_load (stats pass), dist_hist and dist_kde; zeros unless profile_enable() is on."""
+        out = (ctypes.c_double * 3)()
+        self._check(self.lib.pg_dist_last_ms(self._h, ctypes.addressof(out)))
+        return out[0], out[1], out[2]
+
     def profile_enable(self, on: bool = True):
         self._check(self.lib.pg_profile_enable(self._h, int(on)))
 

@@ -9,8 +9,12 @@ pg_cluster_linkage_batch); the host does what fixes order: the stable sort of th
 relabelling, the leaf traversal, the labels and the frame handling.  Results EQUAL scipy's: distances and linkage matrices bit for
 bit, leaves and labels element for element.
 
+The distribution plots (pyani_graphics/mpl/__init__.py:139-175, pyani_graphics/sns/__init__.py:192-233) are arithmetic too: a histogram
+and a Gaussian kernel density estimate over all cells of a matrix.  The device scans, counts and sums (pg_dist_load / pg_dist_hist /
+pg_dist_kde); the host fixes bin edges, grid, bandwidth and normalisation (distribution_data, run_distributions, at the end of this file).
+
 Rendering stays out: this module returns what a drawing layer needs (leaf orders, labels in leaf order, linkage matrices, the
-re-ordered frame) and needs neither scipy nor matplotlib nor seaborn.  There is no CPU fallback for the device part;
+re-ordered frame, bars and curves) and needs neither scipy nor matplotlib nor seaborn.  There is no CPU fallback for the device part;
 `merges_to_linkage`, `dendrogram_leaves` and `dendrogram_labels` are host-only and need no GPU."""
 import io
 from typing import Dict, List, Mapping, NamedTuple, Optional, Sequence, Union
@@ -150,11 +154,16 @@ def linkage(x, method: str = "complete", columns: bool = False, engine: Optional
         _refuse_nonfinite(err)
 
 
-def _frame(dfr) -> pd.DataFrame:
+def _read_frame(dfr) -> pd.DataFrame:
     if isinstance(dfr, str):
         dfr = pd.read_json(io.StringIO(dfr))      # as write_run_plots reads the Run row's strings (subcmd_plot.py:133-137)
     elif not isinstance(dfr, pd.DataFrame):
         dfr = pd.DataFrame(np.asarray(dfr))
+    return dfr
+
+
+def _frame(dfr) -> pd.DataFrame:
+    dfr = _read_frame(dfr)
     # rows only, as heatmap() does (pyani_graphics/mpl/__init__.py:309); an index already in order needs no copy of the frame
     return dfr if dfr.index.is_monotonic_increasing else dfr.sort_index()
 
@@ -205,3 +214,116 @@ def run_heatmap_orders(mats: Mapping[str, Union[pd.DataFrame, str]], method: str
     name), or any other name -> frame / string mapping.  The result is keyed like the input."""
     names = list(mats)
     return dict(zip(names, _orders([_frame(mats[k]) for k in names], method, labels, engine)))
+
+
+# ---- distribution plots: histogram and Gaussian kernel density estimate ---------------------------------------------------------
+# The reference's distribution() (pyani_graphics/mpl/__init__.py:139-175: hist(data, bins=50), gaussian_kde(data) on a 200-point grid;
+# pyani_graphics/sns/__init__.py:192-233: histplot and kdeplot with their defaults) computes, per matrix, a histogram and a density over
+# all cells.  The device scans, counts and sums (pg_dist_load / pg_dist_hist / pg_dist_kde); the host fixes the floats: bin edges,
+# grid, bandwidth and normalisation, with the numpy calls the reference's libraries make, so that they carry the reference's bits.
+DIST_METHODS = ("mpl", "seaborn")
+DIST_BINS = 50          # hist(data, bins=50)
+DIST_GRID = 200         # np.linspace(min, max, 200); seaborn's gridsize
+DIST_CUT = 3            # seaborn's cut: the grid reaches 3 bandwidths past the extremes
+NOT_FINITE = "array must not contain infs or NaNs"      # scipy's text (gaussian_kde's Cholesky step checks its input)
+TOO_FEW_VALUES = "`dataset` input should have multiple elements."      # gaussian_kde's
+SINGULAR = ("The data appears to lie in a lower-dimensional subspace of the space in which it is expressed. This has resulted in a "
+            "singular data covariance matrix, which cannot be treated using the algorithms implemented in `gaussian_kde`.")
+
+
+class DistributionData(NamedTuple):
+    """What distribution() computes before it draws: the bars of the left panel and the curve of the right one."""
+    bin_edges: np.ndarray      # float64[bins + 1]
+    counts: np.ndarray         # int64[bins]: np.histogram's
+    support: np.ndarray        # float64[200]: the grid of the density
+    density: np.ndarray        # float64[200]: gaussian_kde(data)(support)
+    bandwidth: float           # the kernel's standard deviation: gaussian_kde's cho_cov[0, 0]
+
+
+def _dist_method(method: str) -> str:
+    if method not in DIST_METHODS:
+        raise ValueError(f'method must be "mpl" or "seaborn", not {method!r}')
+    return method
+
+
+def _flat_values(dfr) -> np.ndarray:
+    """`dfr.values.flatten()` as float64 (pyani_graphics/mpl/__init__.py:149): row-major, the frame NOT sorted.  The order is part of
+    the contract: the bandwidth's sums run in it."""
+    if isinstance(dfr, (str, pd.DataFrame)):
+        return np.ascontiguousarray(_read_frame(dfr).values.flatten(), dtype=np.float64)
+    return np.array(dfr, dtype=np.float64).reshape(-1)
+
+
+def scott_bandwidth(x: np.ndarray):
+    """(bandwidth, sqrt of the kernel covariance) of scipy.stats.gaussian_kde(x) with its default, Scott's factor, by the numpy calls
+    scipy makes (_kde.py: weights = ones(n) / n; neff = 1 / sum(weights ** 2); factor = power(neff, -1 / 5); the data covariance
+    cov(dataset, rowvar=1, bias=False, aweights=weights); cho_cov = cholesky(covariance) * factor, for one dimension a square root).
+    The first is the kernel's standard deviation and enters every exponent; the second is what seaborn spaces its grid by
+    (sqrt(covariance), covariance = data covariance * factor ** 2) and may differ from the first in the last bit.
+    ValueError for fewer than two values or non-finite ones, LinAlgError for a singular covariance, as gaussian_kde raises them."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    n = x.size
+    if not n > 1:
+        raise ValueError(TOO_FEW_VALUES)
+    weights = np.ones(n) / n
+    neff = 1 / np.sum(weights ** 2)
+    factor = np.power(neff, -1.0 / 5)
+    data_cov = np.atleast_2d(np.cov(x[None, :], rowvar=1, bias=False, aweights=weights))
+    if not np.isfinite(data_cov[0, 0]):
+        raise ValueError(NOT_FINITE)
+    if not data_cov[0, 0] > 0.0:
+        raise np.linalg.LinAlgError(SINGULAR)
+    cho_cov = (np.sqrt(data_cov) * factor).astype(np.float64)
+    return float(cho_cov[0, 0]), float(np.sqrt((data_cov * factor ** 2).squeeze()))
+
+
+def _distribution(x: np.ndarray, method: str, eng) -> DistributionData:
+    if x.size == 0:
+        raise ValueError("min() arg is an empty sequence")
+    lo, hi, n_nan, n_inf = eng.dist_load(x)
+    lo, hi = lo + 0.0, hi + 0.0      # a zero extreme is +0.0 whichever of the equal zeros the scan met first
+    if n_inf or (n_nan and method == "mpl"):
+        # mpl: hist() skips NaN (nanmin / nanmax) and refuses an infinite range; gaussian_kde refuses both.  seaborn drops NaN only.
+        raise ValueError(NOT_FINITE)
+    used = x[~np.isnan(x)] if n_nan else x
+    if used.size == 0:
+        raise ValueError(TOO_FEW_VALUES)
+    bw, grid_bw = scott_bandwidth(used)
+    if method == "mpl":
+        edges = np.histogram_bin_edges(np.empty(0), bins=DIST_BINS, range=(lo, hi))      # +-0.5 when lo == hi, then linspace
+        support = np.linspace(lo, hi, DIST_GRID)
+    else:
+        edges = np.histogram_bin_edges(used, "auto", range=(lo, hi))
+        support = np.linspace(lo - grid_bw * DIST_CUT, hi + grid_bw * DIST_CUT, DIST_GRID)
+    counts = eng.dist_hist(edges)
+    sums = eng.dist_kde(support, bw)
+    # gaussian_kde.evaluate: every term is weighted 1 / n and scaled by (2 pi) ** (-d / 2) / cho_cov[0, 0]
+    norm = np.power(2 * np.pi, -1 / 2) / bw
+    return DistributionData(edges, counts, support, sums * norm * (1.0 / used.size), bw)
+
+
+def distribution_data(dfr, method: str = "mpl", engine: Optional[Engine] = None) -> DistributionData:
+    """Everything distribution() computes before it draws, over all cells of the matrix.  method="mpl" is the reference's matplotlib
+    backend (pyani_graphics/mpl/__init__.py:149-156): 50 even bins over (min, max), the density on np.linspace(min, max, 200);
+    method="seaborn" what histplot and kdeplot compute with their defaults (pyani_graphics/sns/__init__.py:204-213): NaN cells dropped,
+    np.histogram_bin_edges(x, "auto"), the grid from min - 3 bw to max + 3 bw.  dfr: a DataFrame, a DataFrame.to_json() string or an
+    array.  Raises what the reference raises: ValueError for a NaN or infinite cell (mpl) or fewer than two values,
+    numpy.linalg.LinAlgError when all values are equal."""
+    _dist_method(method)
+    eng = engine or default_engine()
+    try:
+        return _distribution(_flat_values(dfr), method, eng)
+    finally:
+        eng.dist_release()
+
+
+def run_distributions(mats: Mapping[str, Union[pd.DataFrame, str]], method: str = "mpl",
+                      engine: Optional[Engine] = None) -> Dict[str, DistributionData]:
+    """distribution_data for all matrices of a run (subcmd_plot.py:141-153), each uploaded once.  mats: as for run_heatmap_orders.  The
+    result is keyed like the input."""
+    _dist_method(method)
+    eng = engine or default_engine()
+    try:
+        return {k: _distribution(_flat_values(mats[k]), method, eng) for k in mats}
+    finally:
+        eng.dist_release()

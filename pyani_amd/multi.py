@@ -139,6 +139,19 @@ class MultiEngine:
     def cluster_linkage_batch(self, problems):
         return self.engines[0].cluster_linkage_batch(problems)
 
+    # ... and so do the distribution calls
+    def dist_load(self, x):
+        return self.engines[0].dist_load(x)
+
+    def dist_hist(self, edges):
+        return self.engines[0].dist_hist(edges)
+
+    def dist_kde(self, points, bandwidth: float):
+        return self.engines[0].dist_kde(points, bandwidth)
+
+    def dist_release(self):
+        return self.engines[0].dist_release()
+
     def clear_genomes(self):
         self._all(lambda e: e.clear_genomes())
 
