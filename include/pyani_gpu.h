@@ -102,7 +102,9 @@ int pg_tetra_matrix_fetch(pg_ctx* ctx, uint32_t n, double* z_out, uint8_t* prese
  * layer on these device buffers — SURVEY.md §8(e)).  d_* are DEVICE pointers owned by the caller.
  * Both calls return after their work has completed on the device. */
 int pg_tetra_zscores_dev(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, double* d_z, uint8_t* d_present);
-/* rows [row0, row0+nrows) of the n x n matrix from the full (all-gathered) d_z / d_present; d_out: nrows x n */
+/* rows [row0, row0+nrows) of the n x n matrix from the full (all-gathered) d_z / d_present; d_out: nrows x n.
+ * PG_E_KEYSET / PG_E_EMPTY as pg_tetra_corr, over all n genomes whichever rows are asked for; nrows == 0 computes
+ * and checks nothing (PG_OK). */
 int pg_tetra_corr_rows_dev(pg_ctx* ctx, const double* d_z, const uint8_t* d_present, uint32_t n, uint32_t row0,
                            uint32_t nrows, double* d_out);
 

@@ -679,11 +679,13 @@ int pg_tetra_corr_rows_dev(pg_ctx* ctx, const double* d_z, const uint8_t* d_pres
                            uint32_t nrows, double* d_out) {
   if (!ctx || (n && (!d_z || !d_present)) || row0 + (uint64_t)nrows > n || (nrows && !d_out))
     return pg_fail(ctx, PG_E_ARG, "bad argument");
+  // An empty slice (a rank without rows: more ranks than genomes) computes nothing.  The key-set and empty-set flags are raised by the
+  // pairs kernel, which does not run then: checking them would read what an earlier call left (on a fresh context: zeros, PG_E_EMPTY).
+  if (n == 0 || nrows == 0) return PG_OK;
   PG_HIP(ctx, hipSetDevice(ctx->device));
   int rc;
   if ((rc = ensure_batch_scratch(ctx, n))) return rc;
   if ((rc = ensure_result(ctx, 1, false))) return rc;  // only the flags words are used
-  if (n == 0) return PG_OK;
   ctx->batch_ids.clear();  // d_dev / d_ss no longer describe the cached batch
   if ((rc = pg_launch_tetra_stats(ctx, d_z, d_present, n))) return rc;
   if ((rc = pg_launch_tetra_pairs(ctx, n, row0, nrows, d_out, false))) return rc;
