@@ -116,7 +116,22 @@ struct GenomeIdx {
   uint32_t* word_start = nullptr;   // fragment mode, word tier: 4^11 + 1 bucket offsets of the genome's 11-mers ...
   int32_t* word_pos = nullptr;      // ... and their positions
 };
-struct AnimLists { std::vector<GenomeIdx> gidx; };
+// gidx holds views (a batch works on a copy of them); the memory behind them is `blocks`, which goes all at once (pg_anim_drop_lists)
+// or, for the blocks of a call that failed, at that call's end
+struct AnimLists {
+  std::vector<GenomeIdx> gidx;
+  std::vector<PgDevBuf<uint8_t>> blocks;
+  template <typename T>
+  T* adopt(PgDevBuf<T>& b) {      // takes the block over from the buffer that allocated it; returns the view
+    blocks.emplace_back();
+    blocks.back().p = reinterpret_cast<uint8_t*>(b.p);
+    blocks.back().cap = b.cap * sizeof(T);
+    T* const view = b.p;
+    b.p = nullptr;
+    b.cap = 0;
+    return view;
+  }
+};
 thread_local PgAlnSink* tls_sink = nullptr;      // set by pg_anim_alignments_batch around its run_batch calls
 thread_local int tls_worker = 0;   // which of the context's two (stream, scratch) sets the calling thread drives
 
@@ -237,11 +252,8 @@ void pg_anim_drop_lists(pg_ctx* ctx) {
   std::lock_guard<std::mutex> lk(ctx->anim_mu);
   AnimLists* A = static_cast<AnimLists*>(ctx->anim_lists);
   if (!A) return;
-  for (auto& g : A->gidx) {
-    void* ptrs[] = {g.ref_list, g.qry_list, g.ref_goff, g.qry_goff, g.qry_list1, g.qry_goff1, g.word_start, g.word_pos};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-  }
   A->gidx.clear();
+  A->blocks.clear();
 }
 
 // Build the seed lists the batch needs and does not have yet: reference role for `ref_genomes`, query role for `qry_genomes`.
@@ -253,6 +265,7 @@ static int anim_ensure_lists(pg_ctx* ctx, AnimScratch* A, const std::vector<int3
   // A list counts as built when its pointer is set, and it outlives this call (shared by the workers): whatever this call
   // allocated is taken back if anything after the allocation fails, so that no later call seeds from a half-built list.
   std::vector<std::pair<uint64_t**, uint32_t**>> mine;
+  const size_t blocks0 = LS->blocks.size();
   const int rc_all = [&]() -> int {
   bool built = false;
   if (!A->list_cnt) {
@@ -274,8 +287,12 @@ static int anim_ensure_lists(pg_ctx* ctx, AnimScratch* A, const std::vector<int3
       uint64_t*& list = role ? qlist : X.ref_list;
       uint32_t*& goff = role ? qgoff : X.ref_goff;
       mine.emplace_back(&list, &goff);
-      PG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&list), bound * sizeof(uint64_t)));      // (both are null here, bound >= 1)
-      PG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&goff), ((size_t)n_sub + 3) * sizeof(uint32_t)));
+      PgDevBuf<uint64_t> new_list;
+      PgDevBuf<uint32_t> new_goff;
+      PG_HIP(ctx, new_list.reserve(bound));      // (bound >= 1)
+      PG_HIP(ctx, new_goff.reserve((size_t)n_sub + 3));
+      list = LS->adopt(new_list);
+      goff = LS->adopt(new_goff);
       const uint32_t* codes = ctx->d_codes + G.arena_start / 16;
       const uint32_t* mask = ctx->d_mask + G.arena_start / 32;
       const int32_t n_idx = role ? len / qstep + 1 : len;
@@ -307,10 +324,8 @@ static int anim_ensure_lists(pg_ctx* ctx, AnimScratch* A, const std::vector<int3
   }();
   if (rc_all != PG_OK) {
     (void)hipStreamSynchronize(cur_stream(ctx));      // nothing of this call may still be writing into them
-    for (auto& pr : mine) {
-      if (*pr.first) { (void)hipFree(*pr.first); *pr.first = nullptr; }
-      if (*pr.second) { (void)hipFree(*pr.second); *pr.second = nullptr; }
-    }
+    for (auto& pr : mine) *pr.first = nullptr, *pr.second = nullptr;
+    LS->blocks.erase(LS->blocks.begin() + blocks0, LS->blocks.end());      // (the lock is held: every block past blocks0 is this call's)
   }
   return rc_all;
 }
@@ -1198,14 +1213,11 @@ static int anib_ensure_word_index(pg_ctx* ctx, AnimScratch* A, int32_t gid) {
   const int32_t len = (int32_t)G.stream_len;
   const uint32_t* codes = ctx->d_codes + G.arena_start / 16;
   const uint32_t* mask = ctx->d_mask + G.arena_start / 32;
-  uint32_t* start = nullptr;
-  int32_t* pos = nullptr;
+  PgDevBuf<uint32_t> start;      // locals until the index is complete: every earlier exit frees them
+  PgDevBuf<int32_t> pos;
   PG_HIP(ctx, A->fr_wtmp.reserve((size_t)WORD_BUCKETS + 1024 + 16));   // fill cursors | block sums
-  PG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&start), ((size_t)WORD_BUCKETS + 1) * sizeof(uint32_t)));
-  if (hipError_t e0 = hipMalloc(reinterpret_cast<void**>(&pos), (size_t)(len > 0 ? len : 1) * sizeof(int32_t))) {
-    (void)hipFree(start);
-    PG_HIP(ctx, e0);
-  }
+  PG_HIP(ctx, start.reserve((size_t)WORD_BUCKETS + 1));
+  PG_HIP(ctx, pos.reserve((size_t)(len > 0 ? len : 1)));
   hipStream_t st = cur_stream(ctx);
   const uint32_t grid = (uint32_t)((len + 255) / 256);
   hipError_t e = hipMemsetAsync(start, 0, ((size_t)WORD_BUCKETS + 1) * 4, st);
@@ -1218,8 +1230,8 @@ static int anib_ensure_word_index(pg_ctx* ctx, AnimScratch* A, int32_t gid) {
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { (void)hipFree(start); (void)hipFree(pos); return pg_fail(ctx, PG_E_HIP, hipGetErrorString(e)); }
-  X.word_start = start; X.word_pos = pos;     // published complete
+  if (e != hipSuccess) return pg_fail(ctx, PG_E_HIP, hipGetErrorString(e));
+  X.word_start = LS->adopt(start); X.word_pos = LS->adopt(pos);     // published complete
   return PG_OK;
 }
 

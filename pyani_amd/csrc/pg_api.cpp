@@ -200,43 +200,30 @@ int add_packed(pg_ctx* ctx, PgGenome&& g, int32_t* id_out) {
   return PG_OK;
 }
 
-template <typename T>
-int dev_realloc(pg_ctx* ctx, T*& p, size_t n_new) {
-  if (p) PG_HIP(ctx, hipFree(p));
-  p = nullptr;
-  PG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&p), n_new * sizeof(T)));
-  return PG_OK;
-}
-template <typename T>
-int host_realloc(pg_ctx* ctx, T*& p, size_t n_new) {
-  if (p) PG_HIP(ctx, hipHostFree(p));
-  p = nullptr;
-  PG_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&p), n_new * sizeof(T), hipHostMallocDefault));
-  return PG_OK;
-}
-
+// Room for a batch of n genomes in the batch arrays.  They grow as a group, every member tested by its own size and grown to
+// max(n, 2 x the genomes it held): a group that an allocation failure left half-grown is completed (or fails again) by the next call,
+// whatever its n, and no launch sees an array smaller than its batch.
 int ensure_batch_scratch(pg_ctx* ctx, uint32_t n) {
-  if (n > ctx->batch_cap) {
-    const uint32_t cap = std::max<uint32_t>(n, ctx->batch_cap * 2);
-    int rc;
-    if ((rc = dev_realloc(ctx, ctx->d_batch_gid, cap))) return rc;
-    if ((rc = dev_realloc(ctx, ctx->d_seg_tile0, cap))) return rc;
-    if ((rc = dev_realloc(ctx, ctx->d_seg_prefix, (size_t)cap + 1))) return rc;
-    if ((rc = dev_realloc(ctx, ctx->d_acc, (size_t)cap * PG_ACC_WORDS))) return rc;
-    PG_HIP(ctx, hipMemsetAsync(ctx->d_acc, 0, (size_t)cap * PG_ACC_WORDS * 8, ctx->stream));
-    if ((rc = dev_realloc(ctx, ctx->d_counts, (size_t)cap * PG_ACC_WORDS))) return rc;
-    if ((rc = dev_realloc(ctx, ctx->d_dev, (size_t)cap * 256))) return rc;
-    if ((rc = dev_realloc(ctx, ctx->d_ss, (size_t)cap))) return rc;
-    if ((rc = dev_realloc(ctx, ctx->d_keybits, (size_t)cap * 4))) return rc;
-    ctx->batch_cap = cap;
-    ctx->batch_ids.clear();
-  }
-  if (n > ctx->h_batch_cap) {
-    const uint32_t cap = std::max<uint32_t>(n, ctx->h_batch_cap * 2);
-    int rc;
-    if ((rc = host_realloc(ctx, ctx->h_counts, (size_t)cap * PG_ACC_WORDS))) return rc;
-    ctx->h_batch_cap = cap;
-  }
+  hipError_t e = hipSuccess;
+  bool replaced = false;
+  auto grow = [&](auto& b, size_t per, size_t extra = 0) {   // true: b has a new block
+    if (e != hipSuccess) return false;
+    const auto* const old = b.p;
+    e = b.reserve_items(n, per, extra);
+    replaced |= b.p != old;
+    return e == hipSuccess && b.p != old;
+  };
+  grow(ctx->d_batch_gid, 1);
+  grow(ctx->d_seg_tile0, 1);
+  grow(ctx->d_seg_prefix, 1, 1);
+  if (grow(ctx->d_acc, PG_ACC_WORDS)) e = hipMemsetAsync(ctx->d_acc, 0, ctx->d_acc.cap * 8, ctx->stream);
+  grow(ctx->d_counts, PG_ACC_WORDS);
+  grow(ctx->d_dev, 256);
+  grow(ctx->d_ss, 1);
+  grow(ctx->d_keybits, 4);
+  if (replaced) ctx->batch_ids.clear();   // the cached work list lay in the arrays that went
+  grow(ctx->h_counts, PG_ACC_WORDS);
+  PG_HIP_MSG(ctx, "TETRA batch scratch: ", e);
   return PG_OK;
 }
 
@@ -252,18 +239,20 @@ struct ResultLayout {
   }
 };
 
+uint64_t result_bytes_held(const pg_ctx* ctx) { return std::min(ctx->d_result.cap, ctx->h_result.cap); }
+
 int ensure_result(pg_ctx* ctx, uint32_t n, bool corr) {
   const ResultLayout L(n, corr);
-  if (L.bytes > ctx->result_cap) {
-    const uint64_t cap = std::max<uint64_t>(L.bytes, ctx->result_cap + ctx->result_cap / 2);
-    int rc;
+  ctx->d_flags = nullptr;   // the views are set again below: a call that fails leaves none behind
+  ctx->d_z = ctx->d_corr = nullptr;
+  ctx->d_present = nullptr;
+  if (L.bytes > result_bytes_held(ctx)) {
     PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if ((rc = dev_realloc(ctx, ctx->d_result, cap))) return rc;
-    if ((rc = host_realloc(ctx, ctx->h_result, cap))) return rc;
+    PG_HIP_MSG(ctx, "TETRA result block (device): ", ctx->d_result.reserve(L.bytes, ctx->d_result.cap + ctx->d_result.cap / 2));
+    PG_HIP_MSG(ctx, "TETRA result block (pinned host): ", ctx->h_result.reserve(L.bytes, ctx->h_result.cap + ctx->h_result.cap / 2));
     PG_HIP(ctx, hipMemsetAsync(ctx->d_result, 0, 16, ctx->stream));
-    ctx->result_cap = cap;
   }
-  ctx->d_flags = reinterpret_cast<int32_t*>(ctx->d_result);
+  ctx->d_flags = reinterpret_cast<int32_t*>(ctx->d_result.p);
   ctx->d_z = reinterpret_cast<double*>(ctx->d_result + L.off_z);
   ctx->d_corr = reinterpret_cast<double*>(ctx->d_result + L.off_corr);
   ctx->d_present = ctx->d_result + L.off_present;
@@ -297,7 +286,7 @@ int ensure_batch(pg_ctx* ctx, const int32_t* ids, uint32_t n) {
 }
 
 int check_flags(pg_ctx* ctx, uint32_t n) {
-  const int32_t* h_flags = reinterpret_cast<const int32_t*>(ctx->h_result);
+  const int32_t* h_flags = reinterpret_cast<const int32_t*>(ctx->h_result.p);
   if (n >= 2) {
     if (h_flags[0] & 1) return pg_fail(ctx, PG_E_KEYSET, "genomes have different observed-tetranucleotide key sets");
     if (h_flags[1] == 0) return pg_fail(ctx, PG_E_EMPTY, "no tetranucleotide observed in any genome");
@@ -308,6 +297,12 @@ int check_flags(pg_ctx* ctx, uint32_t n) {
 }  // namespace
 
 // ---- context ------------------------------------------------------------------------------------------------
+// (pg_create's failure paths and pg_destroy both end in `delete ctx`: no path leaks a stream)
+pg_ctx::~pg_ctx() {
+  if (stream) (void)hipStreamDestroy(stream);
+  for (hipStream_t s : stream_w) if (s) (void)hipStreamDestroy(s);
+}
+
 extern "C" {
 
 const char* pg_version(void) { return "pyani_gpu 0.1.0 (gfx950)"; }
@@ -324,7 +319,7 @@ int pg_create(pg_ctx** out, int device) {
   if (!ctx) return PG_E_NOMEM;
   ctx->device = device;
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
-    delete ctx;
+    delete ctx;      // (~pg_ctx destroys the streams that exist)
     return PG_E_HIP;
   }
   for (int w = 1; w < pg_ctx::MAX_WORKERS; ++w)
@@ -357,17 +352,8 @@ void pg_destroy(pg_ctx* ctx) {
   pg_classify_drop(ctx);
   pg_dist_drop(ctx);
   prof_drain(ctx);
-  void* dev[] = {ctx->d_codes, ctx->d_mask, ctx->d_quirk, ctx->d_seg_tile0, ctx->d_seg_prefix, ctx->d_batch_gid, ctx->d_acc,
-                 ctx->d_counts, ctx->d_z, ctx->d_present, ctx->d_dev, ctx->d_ss, ctx->d_flags, ctx->d_corr};
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
-  void* host[] = {ctx->h_result, ctx->h_counts};
-  for (void* p : host)
-    if (p) (void)hipHostFree(p);
-  (void)hipStreamDestroy(ctx->stream);
-  for (int w = 1; w < pg_ctx::MAX_WORKERS; ++w) (void)hipStreamDestroy(ctx->stream_w[w]);
+  delete ctx;                // the buffers and the streams go here, on the context's device
   (void)hipGetLastError();   // teardown errors must not surface in a later context's launch checks
-  delete ctx;
 }
 
 const char* pg_last_error(const pg_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -483,13 +469,15 @@ int pg_upload(pg_ctx* ctx) {
   const uint32_t ng = (uint32_t)ctx->genomes.size();
   if (ctx->n_resident == ng) return PG_OK;
   // arena (+ one zero guard super-tile so look-ahead loads past the last genome stay in bounds and read "dirty")
+  // A new block is a local until the resident part has been copied across: every exit before that frees it and leaves the context as it was.
   if (ctx->arena_used > ctx->arena_cap) {
     const uint64_t cap = std::max<uint64_t>(ctx->arena_used, ctx->arena_cap + ctx->arena_cap / 2);
-    uint32_t *nc = nullptr, *nm = nullptr;
-    PG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&nc), (cap + PG_SUPER) / 4));
-    PG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&nm), (cap + PG_SUPER) / 8));
-    PG_HIP(ctx, hipMemsetAsync(nc, 0, (cap + PG_SUPER) / 4, ctx->stream));
-    PG_HIP(ctx, hipMemsetAsync(nm, 0, (cap + PG_SUPER) / 8, ctx->stream));
+    const size_t codes_bytes = (cap + PG_SUPER) / 4, mask_bytes = (cap + PG_SUPER) / 8;
+    PgDevBuf<uint32_t> nc, nm;
+    PG_HIP_MSG(ctx, "genome arena (codes): ", nc.reserve((codes_bytes + 3) / 4));
+    PG_HIP_MSG(ctx, "genome arena (mask): ", nm.reserve((mask_bytes + 3) / 4));
+    PG_HIP(ctx, hipMemsetAsync(nc, 0, codes_bytes, ctx->stream));
+    PG_HIP(ctx, hipMemsetAsync(nm, 0, mask_bytes, ctx->stream));
     uint64_t res_bases = 0;
     for (uint32_t i = 0; i < ctx->n_resident; ++i) res_bases = ctx->genomes[i].arena_start + ctx->genomes[i].padded_len;
     if (res_bases && ctx->d_codes) {
@@ -497,21 +485,16 @@ int pg_upload(pg_ctx* ctx) {
       PG_HIP(ctx, hipMemcpyAsync(nm, ctx->d_mask, res_bases / 8, hipMemcpyDeviceToDevice, ctx->stream));
     }
     PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_codes) PG_HIP(ctx, hipFree(ctx->d_codes));
-    if (ctx->d_mask) PG_HIP(ctx, hipFree(ctx->d_mask));
-    ctx->d_codes = nc;
-    ctx->d_mask = nm;
+    ctx->d_codes = std::move(nc);
+    ctx->d_mask = std::move(nm);
     ctx->arena_cap = cap;
   }
-  if (ng > ctx->quirk_cap) {
-    const uint32_t cap = std::max<uint32_t>(ng, ctx->quirk_cap * 2);
-    uint32_t* nq = nullptr;
-    PG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&nq), (size_t)cap * 256 * 4));
+  if ((size_t)ng * 256 > ctx->d_quirk.cap) {
+    PgDevBuf<uint32_t> nq;
+    PG_HIP_MSG(ctx, "quirk table: ", nq.reserve((size_t)ng * 256, 2 * ctx->d_quirk.cap));
     if (ctx->n_resident && ctx->d_quirk)
       PG_HIP(ctx, hipMemcpy(nq, ctx->d_quirk, (size_t)ctx->n_resident * 256 * 4, hipMemcpyDeviceToDevice));
-    if (ctx->d_quirk) PG_HIP(ctx, hipFree(ctx->d_quirk));
-    ctx->d_quirk = nq;
-    ctx->quirk_cap = cap;
+    ctx->d_quirk = std::move(nq);
   }
   for (uint32_t i = ctx->n_resident; i < ng; ++i) {
     PgGenome& g = ctx->genomes[i];
@@ -643,7 +626,7 @@ int pg_tetra_matrix_fetch(pg_ctx* ctx, uint32_t n, double* z_out, uint8_t* prese
   PG_HIP(ctx, hipSetDevice(ctx->device));
   PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const ResultLayout L(n, true);
-  if (L.bytes > ctx->result_cap) return pg_fail(ctx, PG_E_ARG, "fetch larger than last batch");
+  if (L.bytes > result_bytes_held(ctx)) return pg_fail(ctx, PG_E_ARG, "fetch larger than last batch");
   if (z_out) std::memcpy(z_out, ctx->h_result + L.off_z, (size_t)n * 256 * 8);
   if (present_out) std::memcpy(present_out, ctx->h_result + L.off_present, (size_t)n * 256);
   if (corr_out) {

@@ -161,13 +161,6 @@ __global__ __launch_bounds__(1024) void classify_sweep_kernel(const uint32_t* __
   }
 }
 
-template <typename T>
-int cl_malloc(pg_ctx* ctx, PgDevBuf<T>& b, size_t count, const char* what) {      // an empty buffer gets count (at least 1) elements
-  if (b.reserve(std::max<size_t>(count, 1)) == hipSuccess) return PG_OK;
-  (void)hipGetLastError();
-  return pg_fail(ctx, PG_E_NOMEM, std::string("classify: no device memory for ") + what);
-}
-
 ClassifyState* state_of(pg_ctx* ctx) { return static_cast<ClassifyState*>(ctx->classify_state); }
 
 }  // namespace
@@ -199,9 +192,9 @@ extern "C" int pg_classify_edges(pg_ctx* ctx, const double* identity, const doub
   PgDevBuf<double> pi, pc;
   PgDevBuf<unsigned long long> pk;
   int rc;
-  if ((rc = cl_malloc(ctx, pi, nn, "the identity matrix")) || (rc = cl_malloc(ctx, pc, nn, "the coverage matrix")) ||
-      (rc = cl_malloc(ctx, pk, 2, "the edge counters")) || (rc = cl_malloc(ctx, S->d_w, nn, "the edge weight table")) ||
-      (rc = cl_malloc(ctx, S->d_edges, nn / 2, "the edge list"))) {
+  if ((rc = pg_dev_alloc(ctx, "classify", pi, nn, "the identity matrix")) || (rc = pg_dev_alloc(ctx, "classify", pc, nn, "the coverage matrix")) ||
+      (rc = pg_dev_alloc(ctx, "classify", pk, 2, "the edge counters")) || (rc = pg_dev_alloc(ctx, "classify", S->d_w, nn, "the edge weight table")) ||
+      (rc = pg_dev_alloc(ctx, "classify", S->d_edges, nn / 2, "the edge list"))) {
     pg_classify_drop(ctx);
     return rc;
   }
@@ -262,16 +255,16 @@ extern "C" int pg_classify_sweep(pg_ctx* ctx, const double* theta, uint64_t n_st
   const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(8, 2048 / threads), CL_LDS_LIMIT / lds_bytes));
   const uint32_t grid = (uint32_t)std::min<uint64_t>(steps, (uint64_t)ctx->num_cu * (lds_adj ? per_cu : 1u));
   int rc;
-  if (!S->d_death && (rc = cl_malloc(ctx, S->d_death, nn, "the death-index table"))) return rc;
+  if (!S->d_death && (rc = pg_dev_alloc(ctx, "classify", S->d_death, nn, "the death-index table"))) return rc;
   PgDevBuf<double> d_theta;
   PgDevBuf<int32_t> d_sub, d_lab;
   PgDevBuf<uint8_t> d_comp;
   PgDevBuf<unsigned long long> d_scr;
-  if ((rc = cl_malloc(ctx, d_theta, steps, "the thresholds"))) return rc;
-  if ((rc = cl_malloc(ctx, d_sub, steps, "the component counts"))) return rc;
-  if ((rc = cl_malloc(ctx, d_comp, steps, "the completeness flags"))) return rc;
-  if (labels_out && (rc = cl_malloc(ctx, d_lab, (size_t)steps * n, "the per-step labels (ask for fewer steps per call)"))) return rc;
-  if (!lds_adj && (rc = cl_malloc(ctx, d_scr, (size_t)grid * n * n_words, "the adjacency scratch"))) return rc;
+  if ((rc = pg_dev_alloc(ctx, "classify", d_theta, steps, "the thresholds"))) return rc;
+  if ((rc = pg_dev_alloc(ctx, "classify", d_sub, steps, "the component counts"))) return rc;
+  if ((rc = pg_dev_alloc(ctx, "classify", d_comp, steps, "the completeness flags"))) return rc;
+  if (labels_out && (rc = pg_dev_alloc(ctx, "classify", d_lab, (size_t)steps * n, "the per-step labels (ask for fewer steps per call)"))) return rc;
+  if (!lds_adj && (rc = pg_dev_alloc(ctx, "classify", d_scr, (size_t)grid * n * n_words, "the adjacency scratch"))) return rc;
   const void* fn = lds_adj ? reinterpret_cast<const void*>(classify_sweep_kernel<true>) : reinterpret_cast<const void*>(classify_sweep_kernel<false>);
   if (lds_bytes > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) {
     (void)hipGetLastError();

@@ -246,13 +246,6 @@ __global__ __launch_bounds__(1024) void cluster_linkage_kernel(const ClusterProb
   }
 }
 
-template <typename T>
-int clu_malloc(pg_ctx* ctx, PgDevBuf<T>& b, size_t count, const char* what) {      // an empty buffer gets count (at least 1) elements
-  if (b.reserve(std::max<size_t>(count, 1)) == hipSuccess) return PG_OK;
-  (void)hipGetLastError();
-  return pg_fail(ctx, PG_E_NOMEM, std::string("cluster: no device memory for ") + what);
-}
-
 int clu_check_shape(pg_ctx* ctx, const double* x, uint32_t rows, uint32_t cols, uint32_t min_obs, int columns, uint32_t* n, uint32_t* m) {
   if (!x || rows == 0 || cols == 0) return pg_fail(ctx, PG_E_ARG, "cluster: bad argument");
   *n = columns ? cols : rows;
@@ -286,8 +279,8 @@ extern "C" int pg_cluster_pdist(pg_ctx* ctx, const double* x, uint32_t rows, uin
   PG_HIP(ctx, hipSetDevice(ctx->device));
   PgDevBuf<double> d_x, d_c;
   PgDevBuf<int> d_f;
-  if ((rc = clu_malloc(ctx, d_x, (size_t)rows * cols, "the matrix")) || (rc = clu_malloc(ctx, d_c, n_pairs, "the distances")) ||
-      (rc = clu_malloc(ctx, d_f, 1, "the flag")))
+  if ((rc = pg_dev_alloc(ctx, "cluster", d_x, (size_t)rows * cols, "the matrix")) || (rc = pg_dev_alloc(ctx, "cluster", d_c, n_pairs, "the distances")) ||
+      (rc = pg_dev_alloc(ctx, "cluster", d_f, 1, "the flag")))
     return rc;
   int h_flag = 0;
   hipError_t e = hipMemcpyAsync(d_x, x, (size_t)rows * cols * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
@@ -326,7 +319,7 @@ extern "C" int pg_cluster_linkage_batch(pg_ctx* ctx, pg_cluster_problem* problem
   std::vector<ClusterProblem> h_prob(n_problems);
   PgDevBuf<int> d_flags;
   PgDevBuf<ClusterProblem> d_prob;
-  if ((rc = clu_malloc(ctx, d_flags, n_problems, "the flags")) || (rc = clu_malloc(ctx, d_prob, n_problems, "the problem table")))
+  if ((rc = pg_dev_alloc(ctx, "cluster", d_flags, n_problems, "the flags")) || (rc = pg_dev_alloc(ctx, "cluster", d_prob, n_problems, "the problem table")))
     return rc;
   hipError_t e = hipMemsetAsync(d_flags, 0, n_problems * sizeof(int), ctx->stream);
   for (uint32_t p = 0; p < n_problems && e == hipSuccess; ++p) {
@@ -334,12 +327,12 @@ extern "C" int pg_cluster_linkage_batch(pg_ctx* ctx, pg_cluster_problem* problem
     for (uint32_t o = 0; o < p; ++o)      // both orientations of one matrix share its upload
       if (problems[o].x == q.x && problems[o].rows == q.rows && problems[o].cols == q.cols) { d_x[p] = d_x[o]; break; }
     if (!d_x[p]) {
-      if ((rc = clu_malloc(ctx, bufs[nb], (size_t)q.rows * q.cols, "a matrix"))) return rc;
+      if ((rc = pg_dev_alloc(ctx, "cluster", bufs[nb], (size_t)q.rows * q.cols, "a matrix"))) return rc;
       d_x[p] = bufs[nb++];
       e = hipMemcpyAsync(d_x[p], q.x, (size_t)q.rows * q.cols * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
     }
     const uint32_t n = ns[p];
-    if ((rc = clu_malloc(ctx, bufs[nb], (size_t)n * n, "a working matrix")) || (rc = clu_malloc(ctx, bufs[nb + 1], (size_t)(n - 1) * 4, "the merge records")))
+    if ((rc = pg_dev_alloc(ctx, "cluster", bufs[nb], (size_t)n * n, "a working matrix")) || (rc = pg_dev_alloc(ctx, "cluster", bufs[nb + 1], (size_t)(n - 1) * 4, "the merge records")))
       return rc;
     h_prob[p].work = bufs[nb++];
     h_prob[p].merges = bufs[nb++];

@@ -151,13 +151,6 @@ __global__ __launch_bounds__(64) void dist_kde_sum_kernel(const double* __restri
   sums[j] = s;
 }
 
-template <typename T>
-int dist_malloc(pg_ctx* ctx, PgDevBuf<T>& b, size_t count, const char* what) {
-  if (b.reserve(std::max<size_t>(count, 1)) == hipSuccess) return PG_OK;
-  (void)hipGetLastError();
-  return pg_fail(ctx, PG_E_NOMEM, std::string("dist: no device memory for ") + what);
-}
-
 DistState* state_of(pg_ctx* ctx) { return static_cast<DistState*>(ctx->dist_state); }
 
 // Kernel time of one call, outside the profile slots (their count is published): with pg_profile_enable on, a pair of events round the
@@ -213,7 +206,7 @@ extern "C" int pg_dist_load(pg_ctx* ctx, const double* x, uint64_t n, pg_dist_st
   PgDevBuf<DistPartial> d_part;
   const uint32_t blocks = (uint32_t)std::min<uint64_t>(DIST_STATS_BLOCKS, (n + DIST_THREADS - 1) / DIST_THREADS);
   int rc;
-  if ((rc = dist_malloc(ctx, S->d_x, n, "the values")) || (rc = dist_malloc(ctx, d_part, blocks + 1, "the partial records"))) {
+  if ((rc = pg_dev_alloc(ctx, "dist", S->d_x, n, "the values")) || (rc = pg_dev_alloc(ctx, "dist", d_part, blocks + 1, "the partial records"))) {
     pg_dist_drop(ctx);
     return rc;
   }
@@ -264,7 +257,7 @@ extern "C" int pg_dist_hist(pg_ctx* ctx, const double* edges, uint32_t n_bins, u
   PgDevBuf<double> d_edges;
   PgDevBuf<unsigned long long> d_counts;
   int rc;
-  if ((rc = dist_malloc(ctx, d_edges, n_bins + 1, "the bin edges")) || (rc = dist_malloc(ctx, d_counts, n_bins, "the counts"))) return rc;
+  if ((rc = pg_dev_alloc(ctx, "dist", d_edges, n_bins + 1, "the bin edges")) || (rc = pg_dev_alloc(ctx, "dist", d_counts, n_bins, "the counts"))) return rc;
   // every value is counted once whatever the grid; enough workgroups to fill the device, few enough to keep the flushes small
   const uint32_t blocks = (uint32_t)std::min<uint64_t>((uint64_t)ctx->num_cu * 8, (S->n + 4 * DIST_THREADS - 1) / (4 * DIST_THREADS));
   static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "counts are copied out as they lie");
@@ -300,8 +293,8 @@ extern "C" int pg_dist_kde(pg_ctx* ctx, const double* points, uint32_t n_points,
   const uint32_t threads = (n_points + 63u) & ~63u;
   PgDevBuf<double> d_points, d_partial, d_sums;
   int rc;
-  if ((rc = dist_malloc(ctx, d_points, n_points, "the grid")) || (rc = dist_malloc(ctx, d_partial, (size_t)n_slices * n_points, "the partial sums")) ||
-      (rc = dist_malloc(ctx, d_sums, n_points, "the sums")))
+  if ((rc = pg_dev_alloc(ctx, "dist", d_points, n_points, "the grid")) || (rc = pg_dev_alloc(ctx, "dist", d_partial, (size_t)n_slices * n_points, "the partial sums")) ||
+      (rc = pg_dev_alloc(ctx, "dist", d_sums, n_points, "the sums")))
     return rc;
   DistTimer timer(ctx, 2);
   hipError_t e = hipMemcpyAsync(d_points, points, (size_t)n_points * sizeof(double), hipMemcpyHostToDevice, ctx->stream);

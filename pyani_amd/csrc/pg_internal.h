@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "pyani_gpu.h"
+#include "pg_devbuf.h"
 
 // ---- HBM layout of the genome store -------------------------------------------------------------------------
 // One "base stream" per genome: its records back to back with ONE dirty separator base between records, then
@@ -40,6 +41,7 @@ struct PgEventPair {
 };
 
 struct pg_ctx {
+  ~pg_ctx();   // destroys the streams (pg_api.cpp); the buffers below free themselves
   int device = 0;
   hipStream_t stream = nullptr;
   std::string err;
@@ -47,39 +49,35 @@ struct pg_ctx {
   std::vector<PgGenome> genomes;
   uint64_t arena_used = 0;  // bases
   // device arena
-  uint32_t* d_codes = nullptr;
-  uint32_t* d_mask = nullptr;
-  uint64_t arena_cap = 0;  // bases (device), excludes the trailing guard super-tile
-  uint32_t* d_quirk = nullptr;
-  uint32_t quirk_cap = 0;  // genomes
+  PgDevBuf<uint32_t> d_codes, d_mask;
+  uint64_t arena_cap = 0;  // bases both arena blocks hold, excluding the trailing guard super-tile (written once both exist)
+  PgDevBuf<uint32_t> d_quirk;   // genomes x 256
   uint32_t n_resident = 0;
-  // batch scratch (device)
+  // batch scratch (device): grown as a group by ensure_batch_scratch, every member tested by its own size
   std::vector<int32_t> batch_ids;  // ids of the cached work list
-  uint32_t* d_seg_tile0 = nullptr;   // batch: first arena super-tile of each genome
-  uint32_t* d_seg_prefix = nullptr;  // batch + 1: cumulative super-tile counts
-  uint32_t* d_batch_gid = nullptr;
-  uint32_t n_work = 0, batch_cap = 0;
-  unsigned long long* d_acc = nullptr;      // batch x PG_ACC_WORDS (zero between passes)
-  unsigned long long* d_counts = nullptr;   // batch x (16+64+256): c2 | c3 | c4
-  double* d_dev = nullptr;                  // batch x 256 compacted deviations
-  double* d_ss = nullptr;                   // batch
-  unsigned long long* d_keybits = nullptr;  // batch x 4: bitmap of observed tetramers
+  PgDevBuf<uint32_t> d_seg_tile0;    // batch: first arena super-tile of each genome
+  PgDevBuf<uint32_t> d_seg_prefix;   // batch + 1: cumulative super-tile counts
+  PgDevBuf<uint32_t> d_batch_gid;
+  uint32_t n_work = 0;
+  PgDevBuf<unsigned long long> d_acc;      // batch x PG_ACC_WORDS (zero between passes)
+  PgDevBuf<unsigned long long> d_counts;   // batch x (16+64+256): c2 | c3 | c4
+  PgDevBuf<double> d_dev;                  // batch x 256 compacted deviations
+  PgDevBuf<double> d_ss;                   // batch
+  PgDevBuf<unsigned long long> d_keybits;  // batch x 4: bitmap of observed tetramers
   // One result block per pass so that ONE device-to-host copy returns everything:
   //   [ flags: 4 x int32 ] [ z: n x 256 f64 ] [ corr: n x n f64 ] [ present: n x 256 u8 ]
-  uint8_t* d_result = nullptr;
-  uint8_t* h_result = nullptr;  // pinned
-  uint64_t result_cap = 0;      // bytes
-  int32_t* d_flags = nullptr;   // [0]=keyset mismatch, [1]=n present keys      (pointers into d_result)
+  PgDevBuf<uint8_t> d_result;
+  PgPinnedBuf<uint8_t> h_result;
+  // views into d_result, not owned: set by every ensure_result, null after a failed one
+  int32_t* d_flags = nullptr;   // [0]=keyset mismatch, [1]=n present keys
   double* d_z = nullptr;
   double* d_corr = nullptr;
   uint8_t* d_present = nullptr;
-  unsigned long long* h_counts = nullptr;  // pinned
-  uint32_t h_batch_cap = 0;
+  PgPinnedBuf<unsigned long long> h_counts;   // batch x PG_ACC_WORDS
   // profiling
   bool profiling = false;
   uint32_t prof_mask = 0xFFFFFFFFu, prof_every = 1;
   uint64_t prof_seen[PG_K__COUNT] = {};
-  bool prof_open = false;
   std::vector<PgEventPair> events;
   double prof_ms[PG_K__COUNT] = {};
   uint64_t prof_n[PG_K__COUNT] = {};
@@ -135,6 +133,14 @@ int pg_fail(pg_ctx* ctx, int code, const std::string& msg);
     hipError_t _e = (call);                                                                                   \
     if (_e != hipSuccess) return pg_fail((ctx), PG_E_HIP, std::string(prefix) + hipGetErrorString(_e));       \
   } while (0)
+
+// `count` (at least 1) elements for a buffer of one of the modes; a refusal is PG_E_NOMEM, "<mode>: no device memory for <what>"
+template <typename T>
+int pg_dev_alloc(pg_ctx* ctx, const char* mode, PgDevBuf<T>& b, size_t count, const char* what) {
+  if (b.reserve(count ? count : 1) == hipSuccess) return PG_OK;
+  (void)hipGetLastError();
+  return pg_fail(ctx, PG_E_NOMEM, std::string(mode) + ": no device memory for " + what);
+}
 
 // profiling helpers (pg_api.cpp).  Events are recorded on the calling thread's stream: pg_tls_stream when set (the ANIm
 // workers), else the context's.

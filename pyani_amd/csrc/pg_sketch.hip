@@ -27,25 +27,19 @@ struct SketchGenome {
   bool built = false;
   int32_t frag_len = 0, scale = 0;
   uint32_t n_frags = 0, n_occ = 0, cap_mask = 0;
-  uint32_t *occ_kmer = nullptr, *occ_frag = nullptr, *frag_n = nullptr, *tab = nullptr;
-  int32_t* rec_tab = nullptr;      // [2 (n_rec + 1)]: rec_start | frag_base (device)
+  PgDevBuf<uint32_t> occ_kmer, occ_frag, frag_n, tab;
+  PgDevBuf<int32_t> rec_tab;       // [2 (n_rec + 1)]: rec_start | frag_base (device)
 };
-struct SketchStore { std::vector<SketchGenome> g; uint32_t* counters = nullptr; };
-
-void free_genome(SketchGenome& S) {
-  for (void* p : {(void*)S.occ_kmer, (void*)S.occ_frag, (void*)S.frag_n, (void*)S.tab, (void*)S.rec_tab}) if (p) (void)hipFree(p);
-  S = SketchGenome{};
-}
+struct SketchStore { std::vector<SketchGenome> g; PgDevBuf<uint32_t> counters; };
 
 // Device memory for a sketch.  The ANIm engine keeps its per-launch scratch and per-genome seed lists for reuse (after a 1000-genome
 // grid: ~200 GB of the 288); a sketch that does not fit beside them takes their place — they are rebuilt on the next ANIm call.
 template <typename T>
-int sk_malloc(pg_ctx* ctx, T*& p, size_t n) {
+int sk_malloc(pg_ctx* ctx, PgDevBuf<T>& b, size_t n) {      // an empty buffer gets n elements
   // (PYANI_SKETCH_ALLOC_FAIL under PYANI_DEV_KNOBS=1: every first attempt counts as failed, so that a test can walk the fallback)
   static const bool fail_first = pg_dev_env("PYANI_SKETCH_ALLOC_FAIL") != nullptr;
-  if (!fail_first && hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T)) == hipSuccess) return PG_OK;
+  if (!fail_first && b.reserve(n) == hipSuccess) return PG_OK;
   (void)hipGetLastError();
-  p = nullptr;
   // The ANIm launch scratch takes the sketches' place — only on an IDLE context: never under an enqueued ANIm call (its thread is using
   // that scratch), and only after everything the worker streams were given has finished.
   {
@@ -55,7 +49,7 @@ int sk_malloc(pg_ctx* ctx, T*& p, size_t n) {
   }
   PG_HIP(ctx, hipDeviceSynchronize());
   pg_anim_free_scratch(ctx);
-  PG_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T)));
+  PG_HIP_MSG(ctx, "sketch: no device memory, the ANIm scratch released: ", b.reserve(n));
   return PG_OK;
 }
 
@@ -181,7 +175,7 @@ SketchStore* store_of(pg_ctx* ctx) {
 int build_sketch(pg_ctx* ctx, SketchStore* ST, int32_t gid, int32_t frag_len, int32_t scale, uint32_t log2_scale) {
   SketchGenome& S = ST->g[gid];
   if (S.built && S.frag_len == frag_len && S.scale == scale) return PG_OK;
-  free_genome(S);
+  S = SketchGenome{};
   const PgGenome& G = ctx->genomes[gid];
   std::vector<int32_t> rec_tab(2 * (G.n_rec + 1));
   uint32_t nf = 0;
@@ -200,6 +194,7 @@ int build_sketch(pg_ctx* ctx, SketchStore* ST, int32_t gid, int32_t frag_len, in
   const dim3 grid((uint32_t)std::min<uint64_t>((G.stream_len / 32 + 255) / 256 + 1, (uint64_t)ctx->num_cu * 8));
   hipLaunchKernelGGL((sketch_scan_kernel<false>), grid, dim3(256), 0, ctx->stream, codes, mask, (int64_t)G.stream_len, S.rec_tab, (int)G.n_rec, frag_len,
                      (uint32_t)scale, log2_scale, ST->counters, nullptr, nullptr, nullptr, nullptr, 0u);
+  PG_HIP(ctx, hipGetLastError());
   uint32_t cnt[2];
   PG_HIP(ctx, hipMemcpyAsync(cnt, ST->counters, 8, hipMemcpyDeviceToHost, ctx->stream));
   PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -223,11 +218,7 @@ int build_sketch(pg_ctx* ctx, SketchStore* ST, int32_t gid, int32_t frag_len, in
 }  // namespace
 
 void pg_sketch_drop(pg_ctx* ctx) {
-  if (!ctx->sketch_store) return;
-  SketchStore* ST = static_cast<SketchStore*>(ctx->sketch_store);
-  for (auto& s : ST->g) free_genome(s);
-  if (ST->counters) (void)hipFree(ST->counters);
-  delete ST;
+  delete static_cast<SketchStore*>(ctx->sketch_store);
   ctx->sketch_store = nullptr;
 }
 
@@ -275,9 +266,8 @@ extern "C" int pg_sketch_pairs(pg_ctx* ctx, const int32_t* qry_ids, const int32_
     lds_max = std::max(lds_max, per_ref * g);
     jobs.push_back(J);
   }
-  SketchJob* d_jobs = nullptr;
-  pg_sketch_result* d_out = nullptr;
-  struct Guard { SketchJob*& j; pg_sketch_result*& o; ~Guard() { if (j) (void)hipFree(j); if (o) (void)hipFree(o); } } guard{d_jobs, d_out};   // every exit path
+  PgDevBuf<SketchJob> d_jobs;
+  PgDevBuf<pg_sketch_result> d_out;
   if ((rc = sk_malloc(ctx, d_jobs, jobs.size()))) return rc;
   if ((rc = sk_malloc(ctx, d_out, (size_t)n_pairs))) return rc;
   PG_HIP(ctx, hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(SketchJob), hipMemcpyHostToDevice, ctx->stream));

@@ -1,5 +1,5 @@
-// A fake of the HIP runtime header for tests/test_devbuf_cpu.py: hipMalloc / hipFree on the host heap that count what they
-// do and can be told to fail the k-th allocation from now.
+// A fake of the HIP runtime header for tests/test_devbuf_cpu.py: hipMalloc / hipFree and hipHostMalloc / hipHostFree on the host
+// heap that count what they do (in the same counters) and can be told to fail the k-th allocation from now.
 #pragma once
 #include <cstddef>
 #include <cstdlib>
@@ -26,3 +26,6 @@ inline hipError_t hipFree(void* p) {
   if (p) { std::free(p); --f.live; ++f.frees; }
   return hipSuccess;
 }
+constexpr unsigned hipHostMallocDefault = 0;
+inline hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) { return hipMalloc(p, bytes); }
+inline hipError_t hipHostFree(void* p) { return hipFree(p); }

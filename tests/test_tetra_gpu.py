@@ -160,6 +160,36 @@ def test_synthetic_vs_oracle_ragged_batch(eng, oracle):
     _assert_bits(corr, ocorr)
 
 
+def test_buffers_grow_are_reused_and_go_with_the_engine(oracle):
+    """The lifetime of the context's own buffers on ONE engine: 3 genomes of one super-tile each; then 9 (the batch scratch and the
+    result block grow, the arena grows with the 3 resident genomes copied across); then the first 3 again (smaller than what the
+    buffers hold, a different batch).  The engine is destroyed and a fresh one in the same process gives the 3-genome result again.
+    Every result bit for bit equal to oracle/tetra_oracle.c."""
+    from pyani_amd import synth
+    from pyani_amd.engine import Engine
+    data = [synth.genome(20250228, 9, g, 40_000) for g in range(9)]
+    assert all(len(s_) + len(o_) - 2 < 65535 for s_, o_ in data)      # one super-tile each (65 536 bases, at least one of them padding)
+    cs = [oracle.counts(*d) for d in data]
+
+    def check(got, ks):
+        oz, op = oracle.zscores(*(np.array([cs[k][j] for k in ks]) for j in range(3)))
+        rc, ocorr = oracle.corr(oz, op)
+        assert rc == 0
+        z, present, corr = got
+        assert (present == op).all()
+        _assert_bits(z, oz)
+        _assert_bits(corr, ocorr)
+
+    with Engine(0) as e:
+        ids = [e.add_genome(*d) for d in data[:3]]
+        check(e.tetra_matrix(ids), range(3))
+        ids += [e.add_genome(*d) for d in data[3:]]
+        check(e.tetra_matrix(ids), range(9))
+        check(e.tetra_matrix(ids[:3]), range(3))
+    with Engine(0) as e:
+        check(e.tetra_matrix([e.add_genome(*d) for d in data[:3]]), range(3))
+
+
 def test_empty_and_degenerate_inputs(eng, oracle):
     eng.clear_genomes()
     g_empty = eng.add_genome(np.zeros(0, dtype=np.uint8), [0])              # no records at all
