@@ -253,6 +253,21 @@ typedef struct {
 } pg_anib_row;
 int pg_anib_pair_rows(pg_ctx* ctx, int32_t qry_id, int32_t sbj_id, uint32_t fragsize, pg_anib_row* out, uint32_t cap, uint32_t* n_out);
 
+/* The tables of MANY ordered pairs in one call — what pyani's blastn jobs leave on disk for a whole run (one
+ * `<query>_vs_<subject>.blast_tab` per ordered pair under blastn_output/, pyani/anib.py:383-471) — without running the launch chain
+ * once per pair.  out[i] is what pg_anib_pairs returns for pair i, and pair i owns rows [row_offsets[i], row_offsets[i + 1]) of the
+ * result, exactly the rows pg_anib_pair_rows gives for it and in its order (fragments in order, a fragment's rows best score
+ * first), in the CALLER's pair order: how the call sorts its pairs by subject, cuts them into launches and deals those to the
+ * context's workers does not show.  Every launch compacts its rows on the device (an exclusive scan over the per-fragment row
+ * counts, then a pack pass) and reads back the live rows and one count per pair, not the padded per-fragment scratch.
+ * row_offsets: n_pairs + 1 entries.  A pair whose status is PG_E_CAPACITY owns no rows; the call goes on with the others.
+ * n_pairs == 0 is PG_OK with row_offsets[0] = 0.  Argument checks as pg_anib_pairs (fragsize 1 ... 1020, ids in range: PG_E_ARG).
+ * The result stays in the context until the next pg_anib_rows_batch; pg_anib_rows_read copies it out: out[row_offsets[n_pairs]]
+ * (may be NULL when there is no row).  PG_E_ARG before any pg_anib_rows_batch has succeeded on the context. */
+int pg_anib_rows_batch(pg_ctx* ctx, const int32_t* qry_ids, const int32_t* sbj_ids, uint64_t n_pairs, uint32_t fragsize,
+                       pg_anib_result* out, uint64_t* row_offsets);
+int pg_anib_rows_read(pg_ctx* ctx, pg_anib_row* out);
+
 /* ---- sketch mode: an opt-in ESTIMATE in the shape of pyani's fastANI wrapper -------------------------
  * Replaces the `fastANI -q <query> -r <ref> --fragLen 3000 -k 16 --minFraction 0.2` job of pyani/fastani.py:193-229
  * (construct_fastani_cmdline) and the line parse_fastani_file reads back (fastani.py:231-270): ANI estimate, matching fragments,
@@ -396,6 +411,12 @@ int pg_profile_reset(pg_ctx* ctx);
 #define PG_K_CLUSTER_PDIST 18   /* cluster_pdist_kernel: Euclidean distances, upper-triangle tiles (pg_cluster_pdist, pg_cluster_linkage*) */
 #define PG_K_CLUSTER_LINKAGE 19 /* cluster_linkage_kernel: nearest-neighbour chain, one workgroup per problem (pg_cluster_linkage*) */
 #define PG_K__COUNT 20
+/* PG_K__COUNT is a published value (slots 0 ... 19, the numbering callers were built against) and stays 20; index 20 itself is no slot
+ * (pg_kernel_name(20) is ""), and slots added since carry on after it.  PG_K__END is one past the last slot: pg_profile_get and
+ * pg_kernel_name accept 0 ... PG_K__END - 1, bit i of pg_profile_config's mask is slot i as before. */
+#define PG_K_ANIB_ROWS_SCAN 21 /* anib_rows_scan1 / 2 / 3 kernels: exclusive scan of a launch's per-slot row counts (pg_anib_rows_batch) */
+#define PG_K_ANIB_ROWS_PACK 22 /* anib_rows_pack_kernel: the live rows of a launch copied back to back, the pairs' row counts */
+#define PG_K__END 23
 /* total milliseconds and number of launches of kernel `which` since the last reset (synchronises). */
 int pg_profile_get(pg_ctx* ctx, int which, double* total_ms_out, uint64_t* launches_out);
 const char* pg_kernel_name(int which);

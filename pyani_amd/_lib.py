@@ -33,6 +33,8 @@ K_CLASSIFY_EDGE, K_CLASSIFY_SWEEP = 16, 17
 K_COUNT = 18      # the slots of the comparison and classify stages, 0 .. 17: the value callers have seen so far stays as it is
 K_CLUSTER_PDIST, K_CLUSTER_LINKAGE = 18, 19
 K_TOTAL = 20      # PG_K__COUNT of the header: every slot, the two cluster slots included
+K_ANIB_ROWS_SCAN, K_ANIB_ROWS_PACK = 21, 22      # (20 is no slot: K_TOTAL is a published value)
+K_END = 23        # PG_K__END of the header: one past the last slot
 PG_SKETCH_NO_RESULT = 1
 
 # every symbol declared in include/pyani_gpu.h: (name, restype, argtypes)
@@ -74,6 +76,8 @@ SIGNATURES = {
     "pg_anib_reduce": (_int, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pg_anib_pairs": (_int, [_vp, _vp, _vp, _u64, _u32, _vp]),
     "pg_anib_pair_rows": (_int, [_vp, _i32, _i32, _u32, _vp, _u32, _P(_u32)]),
+    "pg_anib_rows_batch": (_int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp]),
+    "pg_anib_rows_read": (_int, [_vp, _vp]),
     "pg_sketch_pairs": (_int, [_vp, _vp, _vp, _u64, _i32, _i32, ctypes.c_double, _vp]),
     "pg_classify_edges": (_int, [_vp, _vp, _vp, _u32, ctypes.c_double, ctypes.c_double, _P(_u64), _P(_u32)]),
     "pg_classify_edge_identities": (_int, [_vp, _vp, _u64]),

@@ -207,6 +207,8 @@ struct AnimScratch {
   PgDevBuf<pg_anib_result> fr_out;
   PgDevBuf<uint32_t> fr_list, fr_nlist, fr_wtmp;   // word tier: slots to search again, their number, scan scratch
   PgDevBuf<WordIdx> fr_widx;
+  PgDevBuf<uint32_t> fr_roff, fr_rsum, fr_prows;   // packed rows: slot offsets (+ the total), the scan's block sums, rows per pair
+  PgDevBuf<FragRow> fr_packed;                     // ... and the launch's rows back to back
 };
 
 // Room for `need` elements in every buffer of a group, each grown to `alloc` if it is short.  Every buffer is tested by its own
@@ -1201,7 +1203,7 @@ int pg_anim_run_batch(pg_ctx* ctx, const int32_t* ref_ids, const int32_t* qry_id
 
 // Fragment mode after seeding: A->mem / A->moff / A->mem_count hold every unit's exact matches (>= 16, sampled), A->units_d /
 // A->refs_d the descriptors.  Builds the fragment tables of the batch's query genomes, runs F1-F3 (pga_frag.inc), returns
-// the pair results (and, optionally, the rows of pair 0).
+// the pair results (and, optionally, the rows of pair 0, or — with a sink — the rows of every pair, packed on the device).
 // The word index of one genome (pga_frag.inc), built once and kept with its seed lists.
 static int anib_ensure_word_index(pg_ctx* ctx, AnimScratch* A, int32_t gid) {
   std::lock_guard<std::mutex> lk(ctx->anim_mu);
@@ -1344,6 +1346,41 @@ static int anib_frag_stage(pg_ctx* ctx, AnimScratch* A, const int32_t* qry_ids, 
         PG_HIP(ctx, hipStreamSynchronize(cur_stream(ctx)));
       }
     }
+  }
+  if (F.sink) {   // the tables of every pair, packed on the device: one read-back of the live rows and the pairs' counts
+    PgRowSink& S = *F.sink;
+    std::vector<uint32_t> pair_rows(n_pairs, 0);
+    if (slots) {
+      const uint32_t n_slots = (uint32_t)slots, n_blocks = (n_slots + ROWS_SCAN_TILE - 1) / ROWS_SCAN_TILE;
+      if (n_blocks > ROWS_SCAN_MAX_BLOCKS) return pg_fail(ctx, PG_E_CAPACITY, "fragment mode: too many (pair, fragment) slots in one launch to pack their rows");
+      PG_HIP(ctx, A->fr_roff.reserve((size_t)slots + 1, (size_t)slots + (size_t)slots / 4 + 1));
+      PG_HIP(ctx, A->fr_rsum.reserve(ROWS_SCAN_MAX_BLOCKS));
+      PG_HIP(ctx, A->fr_prows.reserve(n_pairs, (size_t)n_pairs + n_pairs / 4));
+      pg_prof_begin(ctx, PG_K_ANIB_ROWS_SCAN);
+      hipLaunchKernelGGL(anib_rows_scan1_kernel, dim3(n_blocks), dim3(1024), 0, cur_stream(ctx), A->fr_nrows, n_slots, A->fr_roff, A->fr_rsum);
+      hipLaunchKernelGGL(anib_rows_scan2_kernel, dim3(1), dim3(1024), 0, cur_stream(ctx), A->fr_rsum, n_blocks, A->fr_roff + n_slots);
+      hipLaunchKernelGGL(anib_rows_scan3_kernel, dim3((n_slots + 1023) / 1024), dim3(1024), 0, cur_stream(ctx), A->fr_roff, n_slots, A->fr_rsum);
+      pg_prof_end(ctx);
+      PG_HIP(ctx, hipGetLastError());
+      uint32_t total = 0;
+      PG_HIP(ctx, hipMemcpyAsync(&total, A->fr_roff + n_slots, 4, hipMemcpyDeviceToHost, cur_stream(ctx)));
+      PG_HIP(ctx, hipStreamSynchronize(cur_stream(ctx)));
+      if ((uint64_t)total > slots * FRAG_ROWS) return pg_fail(ctx, PG_E_INTERNAL, "fragment mode: the row scan counted more rows than the slots hold");
+      PG_HIP(ctx, A->fr_packed.reserve((size_t)total + 1, (size_t)total + (size_t)total / 4 + 1));
+      const uint64_t n_threads = std::max<uint64_t>(slots * FRAG_ROWS, n_pairs);
+      pg_prof_begin(ctx, PG_K_ANIB_ROWS_PACK);
+      hipLaunchKernelGGL(anib_rows_pack_kernel, dim3((uint32_t)((n_threads + 255) / 256)), dim3(256), 0, cur_stream(ctx), A->fr_rows, A->fr_nrows,
+                         A->fr_roff, n_slots, A->fr_pairs, n_pairs, A->fr_packed, A->fr_prows);
+      pg_prof_end(ctx);
+      PG_HIP(ctx, hipGetLastError());
+      const size_t at = S.rows.size();
+      S.rows.resize(at + total);
+      static_assert(sizeof(pg_anib_row) == sizeof(FragRow), "FragRow is pg_anib_row");
+      if (total) PG_HIP(ctx, hipMemcpyAsync(S.rows.data() + at, A->fr_packed, (size_t)total * sizeof(FragRow), hipMemcpyDeviceToHost, cur_stream(ctx)));
+      PG_HIP(ctx, hipMemcpyAsync(pair_rows.data(), A->fr_prows, (size_t)n_pairs * 4, hipMemcpyDeviceToHost, cur_stream(ctx)));
+      PG_HIP(ctx, hipStreamSynchronize(cur_stream(ctx)));
+    }
+    S.pair_count.insert(S.pair_count.end(), pair_rows.begin(), pair_rows.end());
   }
   if (F.n_rows_out) {   // the table of pair 0
     const uint32_t nf = (uint32_t)fp[0].n_frags;

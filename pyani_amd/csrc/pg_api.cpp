@@ -9,20 +9,22 @@
 #include <thread>
 
 #include "pg_internal.h"
+#include "pg_anib_rows.h"
 
 int pg_fail(pg_ctx* ctx, int code, const std::string& msg) {
   if (ctx) { std::lock_guard<std::mutex> lk(ctx->err_mu); ctx->err = msg; }
   return code;
 }
 
-static const char* const KERNEL_NAMES[PG_K__COUNT] = {"tetra_count_kernel", "tetra_finalize_kernel", "tetra_stats_kernel",
+static const char* const KERNEL_NAMES[PG_K__END] = {"tetra_count_kernel", "tetra_finalize_kernel", "tetra_stats_kernel",
                                                       "tetra_pairs_kernel", "anim_seed_kernel", "anim_hit_kernels",
                                                       "anim_cluster_wave_kernel",
                                                       "anim_postnuc_gap_kernels", "anim_postnuc_forced_kernels",
                                                       "anim_postnuc_kernel", "anim_finish_kernel", "anib_bucket_kernel",
                                                       "anib_frag_kernel", "anim_postnuc_fwd_kernel", "anim_postnuc_rehearse_kernel+anim_postnuc_bwd_kernel",
                                                       "sketch_pairs_kernel", "classify_edge_kernel", "classify_death_kernel+classify_sweep_kernel",
-                                                      "cluster_pdist_kernel", "cluster_linkage_kernel"};
+                                                      "cluster_pdist_kernel", "cluster_linkage_kernel",
+                                                      "" /* 20 = PG_K__COUNT: not a slot */, "anib_rows_scan_kernels", "anib_rows_pack_kernel"};
 
 // ---- profiling ----------------------------------------------------------------------------------------------
 thread_local hipStream_t pg_tls_stream = nullptr;
@@ -307,7 +309,7 @@ extern "C" {
 
 const char* pg_version(void) { return "pyani_gpu 0.1.0 (gfx950)"; }
 
-const char* pg_kernel_name(int which) { return (which >= 0 && which < PG_K__COUNT) ? KERNEL_NAMES[which] : ""; }
+const char* pg_kernel_name(int which) { return (which >= 0 && which < PG_K__END) ? KERNEL_NAMES[which] : ""; }
 
 int pg_create(pg_ctx** out, int device) {
   if (!out) return PG_E_ARG;
@@ -1059,7 +1061,16 @@ int pg_anib_reduce(pg_ctx* ctx, uint32_t n_pairs, const uint64_t* offsets, const
 // ---- ANIb fragment mode ----------------------------------------------------------------------------------------
 static constexpr uint64_t ANIB_MAX_SLOTS = 4ull << 20;   // (pair, fragment) slots per launch: 192 B of rows each
 
+static int anib_pairs_body(pg_ctx* ctx, const int32_t* qry_ids, const int32_t* sbj_ids, uint64_t n_pairs, uint32_t fragsize, pg_anib_result* out,
+                           PgAnibRowParts* rows);
+
 int pg_anib_pairs(pg_ctx* ctx, const int32_t* qry_ids, const int32_t* sbj_ids, uint64_t n_pairs, uint32_t fragsize, pg_anib_result* out) {
+  return anib_pairs_body(ctx, qry_ids, sbj_ids, n_pairs, fragsize, out, nullptr);
+}
+
+// rows == nullptr: pg_anib_pairs as it always was; else every launch also packs its tables (PgFragArgs::sink) and they are filed by pair
+static int anib_pairs_body(pg_ctx* ctx, const int32_t* qry_ids, const int32_t* sbj_ids, uint64_t n_pairs, uint32_t fragsize, pg_anib_result* out,
+                           PgAnibRowParts* rows) {
   if (!ctx || fragsize == 0 || fragsize > 1020 || (n_pairs && (!qry_ids || !sbj_ids || !out)))
     return pg_fail(ctx, PG_E_ARG, "bad argument (fragment sizes up to pyani's 1020 are supported)");
   PG_HIP(ctx, hipSetDevice(ctx->device));
@@ -1103,15 +1114,46 @@ int pg_anib_pairs(pg_ctx* ctx, const int32_t* qry_ids, const int32_t* sbj_ids, u
       s.clear(); q.clear();
       for (uint64_t k = i; k < j; ++k) { s.push_back(sbj_ids[order[k]]); q.push_back(qry_ids[order[k]]); }
       res.assign(j - i, pg_anib_result{});
-      PgFragArgs F{(int32_t)fragsize, res.data(), nullptr, 0, nullptr, max_slots};
+      PgRowSink sink;
+      PgFragArgs F{(int32_t)fragsize, res.data(), nullptr, 0, nullptr, max_slots, rows ? &sink : nullptr};
       uint32_t done = 0;
       const int rc2 = pg_anim_run_batch(ctx, s.data(), q.data(), (uint32_t)(j - i), 0, 1, max_matches, nullptr, &done, &F);
       if (rc2) return rc2;
       for (uint64_t k = i; k < i + done; ++k) out[order[k]] = res[k - i];
+      if (rows) {
+        if (sink.pair_count.size() != done || !rows->file(std::move(sink.rows), sink.pair_count.data(), order.data() + i, done))
+          return pg_fail(ctx, PG_E_INTERNAL, "pg_anib_rows_batch: a launch's row counts do not match its rows");
+      }
       i += done;
     }
     return PG_OK;
   });
+}
+
+static int anib_rows_batch_body(pg_ctx* ctx, const int32_t* qry_ids, const int32_t* sbj_ids, uint64_t n_pairs, uint32_t fragsize, pg_anib_result* out,
+                                uint64_t* row_offsets) {
+  if (!ctx || !row_offsets) return pg_fail(ctx, PG_E_ARG, "bad argument");
+  PgAnibRowParts parts(n_pairs);      // (a PG_E_CAPACITY pair is never launched: 0 rows)
+  const int rc = anib_pairs_body(ctx, qry_ids, sbj_ids, n_pairs, fragsize, out, &parts);
+  if (rc) return rc;
+  parts.assemble(row_offsets, ctx->anib_rows_store);      // back to the caller's order
+  ctx->anib_rows_valid = true;
+  return PG_OK;
+}
+// No exception may cross the C ABI (the call grows host vectors: the launches' parts, the stored result).
+int pg_anib_rows_batch(pg_ctx* ctx, const int32_t* qry_ids, const int32_t* sbj_ids, uint64_t n_pairs, uint32_t fragsize, pg_anib_result* out,
+                       uint64_t* row_offsets) {
+  try { return anib_rows_batch_body(ctx, qry_ids, sbj_ids, n_pairs, fragsize, out, row_offsets); }
+  catch (const std::bad_alloc&) { return pg_fail(ctx, PG_E_NOMEM, "out of host memory while collecting the pairs' rows"); }
+  catch (const std::exception& e) { return pg_fail(ctx, PG_E_INTERNAL, std::string("pg_anib_rows_batch: ") + e.what()); }
+}
+
+int pg_anib_rows_read(pg_ctx* ctx, pg_anib_row* out) {
+  if (!ctx) return PG_E_ARG;
+  if (!ctx->anib_rows_valid) return pg_fail(ctx, PG_E_ARG, "pg_anib_rows_read: no pg_anib_rows_batch result is stored");
+  if (!out && !ctx->anib_rows_store.empty()) return pg_fail(ctx, PG_E_ARG, "bad argument");
+  if (!ctx->anib_rows_store.empty()) memcpy(out, ctx->anib_rows_store.data(), ctx->anib_rows_store.size() * sizeof(pg_anib_row));
+  return PG_OK;
 }
 
 int pg_anib_pair_rows(pg_ctx* ctx, int32_t qry_id, int32_t sbj_id, uint32_t fragsize, pg_anib_row* out, uint32_t cap, uint32_t* n_out) {
@@ -1144,11 +1186,11 @@ int pg_profile_reset(pg_ctx* ctx) {
   PG_HIP(ctx, hipSetDevice(ctx->device));
   PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
   prof_drain(ctx);
-  for (int i = 0; i < PG_K__COUNT; ++i) { ctx->prof_ms[i] = 0; ctx->prof_n[i] = 0; ctx->prof_seen[i] = 0; }
+  for (int i = 0; i < PG_K__END; ++i) { ctx->prof_ms[i] = 0; ctx->prof_n[i] = 0; ctx->prof_seen[i] = 0; }
   return PG_OK;
 }
 int pg_profile_get(pg_ctx* ctx, int which, double* total_ms_out, uint64_t* launches_out) {
-  if (!ctx || which < 0 || which >= PG_K__COUNT) return PG_E_ARG;
+  if (!ctx || which < 0 || which >= PG_K__END) return PG_E_ARG;
   PG_HIP(ctx, hipSetDevice(ctx->device));
   PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
   prof_drain(ctx);

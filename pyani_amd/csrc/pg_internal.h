@@ -77,10 +77,10 @@ struct pg_ctx {
   // profiling
   bool profiling = false;
   uint32_t prof_mask = 0xFFFFFFFFu, prof_every = 1;
-  uint64_t prof_seen[PG_K__COUNT] = {};
+  uint64_t prof_seen[PG_K__END] = {};
   std::vector<PgEventPair> events;
-  double prof_ms[PG_K__COUNT] = {};
-  uint64_t prof_n[PG_K__COUNT] = {};
+  double prof_ms[PG_K__END] = {};
+  uint64_t prof_n[PG_K__END] = {};
   int num_cu = 256;
   void* anim_scratch = nullptr;  // AnimScratch (pg_anim.hip) of worker 0, grows on demand
   // ANIm / fragment-mode calls are split over two host workers, each with its own stream and scratch: while one worker's
@@ -89,6 +89,9 @@ struct pg_ctx {
   std::vector<pg_anim_alignment> aln_store;
   std::vector<uint64_t> aln_indel_off;
   std::vector<int64_t> aln_indels;
+  // result of the latest pg_anib_rows_batch (caller's pair order); anib_rows_valid: there has been one
+  std::vector<pg_anib_row> anib_rows_store;
+  bool anib_rows_valid = false;
   static constexpr int MAX_WORKERS = 4;
   void* anim_scratch_w[MAX_WORKERS] = {nullptr, nullptr, nullptr, nullptr};   // workers 1.. (index 0 unused: worker 0 = anim_scratch)
   hipStream_t stream_w[MAX_WORKERS] = {nullptr, nullptr, nullptr, nullptr};   // workers 1.. (index 0 unused: worker 0 = stream)
@@ -167,6 +170,13 @@ struct PgFragArgs {
   uint32_t rows_cap;
   uint32_t* n_rows_out;
   uint64_t max_slots;         // (pair, fragment) slots per launch
+  struct PgRowSink* sink = nullptr;   // optional: the rows of EVERY pair of the launch, packed on the device (pg_anib_rows_batch)
+};
+// Where a fragment-mode launch leaves its tables when PgFragArgs::sink is set: the rows of its pairs back to back in launch order
+// (fragments in order, a fragment's rows best score first), and how many each pair owns.  One sink per launch chain: the caller's.
+struct PgRowSink {
+  std::vector<pg_anib_row> rows;
+  std::vector<uint32_t> pair_count;
 };
 int pg_anim_run_batch(pg_ctx* ctx, const int32_t* ref_ids, const int32_t* qry_ids, uint32_t n_pairs, int filter_1to1, int maxmatch,
                       uint64_t max_matches, pg_anim_result* out_host, uint32_t* n_done,

@@ -791,3 +791,89 @@ __global__ __launch_bounds__(64) void anib_reduce_pairs_kernel(const FragPair* _
   o.aln_length = aln; o.sim_errors = err; o.pid = kept ? sum / (double)kept : 0.0; o.n_frags = P.n_frags; o.n_kept = kept; o.status = 0; o.reserved = 0;
   out[p] = o;
 }
+
+// ---- packed rows of a launch (pg_anib_rows_batch) ---------------------------------------------------------------------------
+// The tables of every pair of a launch, compacted on the device: an exclusive scan over the per-slot row counts gives every slot
+// its place (off[slot]; off[n_slots] = the launch's rows), a pack pass copies the live rows there.  Slots in launch order are pairs
+// in launch order and fragments in fragment order, rows of a slot keep their stored order (best score first): what the host loop
+// over the padded scratch of pair 0 produces (anib_frag_stage), for every pair at once, with no atomics.  Launched after the word
+// tier, so the rows are final.  The scan is the word scan's three passes with a bound (n_slots is no multiple of the tile) and
+// wave shuffles in place of the LDS ladder: 4096 slots per block, then the <= 1024 block sums, then the add.
+constexpr uint32_t ROWS_SCAN_TILE = 4096;         // slots per block: 1024 threads x 4
+constexpr uint32_t ROWS_SCAN_MAX_BLOCKS = 1024;   // block sums one workgroup scans: 4 Mi slots per launch (ANIB_MAX_SLOTS)
+static_assert(FRAG_ROWS == 4, "anib_rows_pack_kernel: one thread per (slot, row), four to a slot");
+static_assert(sizeof(FragRow) == 48, "a row is three 16-byte accesses");
+
+// inclusive scan of one value per thread over a workgroup of 1024 (16 waves); s_wave: 16 words of LDS
+__device__ __forceinline__ uint32_t rows_block_scan(uint32_t v, uint32_t* s_wave) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(v, o, 64); if (lane >= (uint32_t)o) v += u; }
+  if (lane == 63) s_wave[wave] = v;
+  __syncthreads();
+  if (wave == 0) {
+    uint32_t w = lane < 16 ? s_wave[lane] : 0u;
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) { const uint32_t u = __shfl_up(w, o, 64); if (lane >= (uint32_t)o) w += u; }
+    if (lane < 16) s_wave[lane] = w;
+  }
+  __syncthreads();
+  return v + (wave ? s_wave[wave - 1] : 0u);
+}
+__device__ __forceinline__ uint32_t rows_live(uint32_t n) { return n < (uint32_t)FRAG_ROWS ? n : (uint32_t)FRAG_ROWS; }
+
+__global__ __launch_bounds__(1024) void anib_rows_scan1_kernel(const uint32_t* __restrict__ n_rows, uint32_t n_slots, uint32_t* __restrict__ off,
+                                                               uint32_t* __restrict__ bsum) {
+  __shared__ uint32_t s_wave[16];
+  const uint32_t t = threadIdx.x, base = blockIdx.x * ROWS_SCAN_TILE + t * 4u;
+  uint32_t a = 0, b = 0, c = 0, d = 0;
+  if (base + 3u < n_slots) {
+    const uint4 x = *reinterpret_cast<const uint4*>(n_rows + base);
+    a = rows_live(x.x); b = rows_live(x.y); c = rows_live(x.z); d = rows_live(x.w);
+  } else {
+    if (base < n_slots) a = rows_live(n_rows[base]);
+    if (base + 1u < n_slots) b = rows_live(n_rows[base + 1]);
+    if (base + 2u < n_slots) c = rows_live(n_rows[base + 2]);
+  }
+  const uint32_t incl = rows_block_scan(a + b + c + d, s_wave), excl = incl - (a + b + c + d);
+  if (base + 3u < n_slots) {
+    *reinterpret_cast<uint4*>(off + base) = make_uint4(excl, excl + a, excl + a + b, excl + a + b + c);
+  } else {
+    if (base < n_slots) off[base] = excl;
+    if (base + 1u < n_slots) off[base + 1] = excl + a;
+    if (base + 2u < n_slots) off[base + 2] = excl + a + b;
+  }
+  if (t == 1023) bsum[blockIdx.x] = incl;
+}
+// n_blocks <= ROWS_SCAN_MAX_BLOCKS; *total = off[n_slots]
+__global__ __launch_bounds__(1024) void anib_rows_scan2_kernel(uint32_t* __restrict__ bsum, uint32_t n_blocks, uint32_t* __restrict__ total) {
+  __shared__ uint32_t s_wave[16];
+  const uint32_t t = threadIdx.x;
+  const uint32_t v0 = t < n_blocks ? bsum[t] : 0u;
+  const uint32_t incl = rows_block_scan(v0, s_wave);
+  if (t < n_blocks) bsum[t] = incl - v0;
+  if (t == 1023) *total = incl;
+}
+__global__ __launch_bounds__(1024) void anib_rows_scan3_kernel(uint32_t* __restrict__ off, uint32_t n_slots, const uint32_t* __restrict__ bsum) {
+  const uint32_t i = blockIdx.x * 1024u + threadIdx.x;
+  if (i < n_slots) off[i] += bsum[i / ROWS_SCAN_TILE];
+}
+
+// One thread per (slot, row): the live rows of a slot go to packed[off[slot] + i].  The live lanes of a wave write consecutive
+// 48-byte rows (three 16-byte stores each), so a wave's stores cover one contiguous span.  The first n_pairs threads also leave
+// their pair's row count (off is complete: off[n_slots] = total).
+__global__ __launch_bounds__(256) void anib_rows_pack_kernel(const FragRow* __restrict__ rows, const uint32_t* __restrict__ n_rows,
+                                                             const uint32_t* __restrict__ off, uint32_t n_slots, const FragPair* __restrict__ pairs,
+                                                             uint32_t n_pairs, FragRow* __restrict__ packed, uint32_t* __restrict__ pair_rows) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t < n_pairs) {
+    const FragPair P = pairs[t];
+    pair_rows[t] = off[P.slot0 + (uint32_t)P.n_frags] - off[P.slot0];
+  }
+  const uint32_t slot = t >> 2, i = t & 3u;
+  if (slot >= n_slots || i >= rows_live(n_rows[slot])) return;
+  const uint4* src = reinterpret_cast<const uint4*>(rows + (size_t)slot * FRAG_ROWS + i);
+  uint4* dst = reinterpret_cast<uint4*>(packed + (size_t)off[slot] + i);
+  const uint4 x0 = src[0], x1 = src[1], x2 = src[2];
+  dst[0] = x0; dst[1] = x1; dst[2] = x2;
+}

@@ -296,6 +296,27 @@ class Engine:
             self._check(self.lib.pg_anib_pair_rows(self._h, int(qry_id), int(sbj_id), int(fragsize), out.ctypes.data, len(out), ctypes.byref(n)))
         return out[:n.value].copy()
 
+    def anib_rows_batch(self, qry_ids, sbj_ids, fragsize: int = 1020) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The tables of MANY ordered pairs in one call (pg_anib_rows_batch): what pyani's blastn jobs leave in their .blast_tab files
+        for a whole run.  Returns (results, offsets, rows): results[i] is anib_pairs' record of pair i (ANIB_DTYPE), and pair i owns
+        rows[offsets[i]:offsets[i + 1]] (ANIB_ROW_DTYPE), the rows anib_pair_rows gives for it, in the caller's pair order.  Every
+        launch packs its rows on the device, so only live rows come back.  A pair with status PG_E_CAPACITY owns no rows."""
+        q, s = self._ids(qry_ids), self._ids(sbj_ids)
+        if len(q) != len(s):
+            raise ValueError("qry_ids and sbj_ids must have the same length")
+        out = np.zeros(len(q), dtype=self.ANIB_DTYPE)
+        offsets = np.zeros(len(q) + 1, dtype=np.uint64)
+        self._check(self.lib.pg_anib_rows_batch(self._h, q.ctypes.data, s.ctypes.data, len(q), int(fragsize), out.ctypes.data,
+                                                offsets.ctypes.data))
+        return out, offsets, self.anib_rows_read(int(offsets[-1]))
+
+    def anib_rows_read(self, n_rows: int) -> np.ndarray:
+        """The rows of the latest anib_rows_batch on this engine (pg_anib_rows_read); n_rows = its offsets[-1].  PyaniGpuError
+        (PG_E_ARG) when there has been none."""
+        rows = np.zeros(int(n_rows), dtype=self.ANIB_ROW_DTYPE)
+        self._check(self.lib.pg_anib_rows_read(self._h, rows.ctypes.data if len(rows) else None))
+        return rows
+
     # -- measurement ----------------------------------------------------------------------------------------------
     # -- sketch mode (fastANI-shaped estimate; never mixed into the exact results) ----------------------------------------------
     SKETCH_DTYPE = np.dtype([("ani", "<f8"), ("matches", "<i4"), ("fragments", "<i4"), ("status", "<i4"), ("reserved", "<i4")])

@@ -67,7 +67,7 @@ def _static_parts_by_hub(a: np.ndarray, b: np.ndarray, parts: int) -> List[np.nd
 
 class MultiEngine:
     """Engines on several devices behind the Engine calls the module functions use: genome store (replicated), anim_pairs / anib_pairs /
-    anim_alignments_batch (pairs pulled in chunks by the devices), tetra_counts / tetra_matrix (genomes counted in shards)."""
+    anim_alignments_batch / anib_rows_batch (pairs pulled in chunks by the devices), tetra_counts / tetra_matrix (genomes counted in shards)."""
 
     def __init__(self, devices: Sequence[int], chunk_pairs: int = 0):
         if not devices:
@@ -215,19 +215,51 @@ class MultiEngine:
             raise ValueError("qry_ids and sbj_ids must have the same length")
         out = np.zeros(len(qa), dtype=Engine.ANIB_DTYPE)
         if len(qa):
-            # fragment mode: the fragmented (query) genome is the expensive side to set up — keep its pairs together
-            order = np.argsort(qa, kind="stable")
-            bounds = np.flatnonzero(np.diff(qa[order])) + 1
-            groups, chunks, cur, size = np.split(order, bounds), [], [], 0
-            target = max(64, len(qa) // (24 * len(self.engines)) + 1) if self.chunk_pairs <= 0 else self.chunk_pairs
-            for g in groups:
-                cur.append(g); size += len(g)
-                if size >= target:
-                    chunks.append(np.concatenate(cur)); cur, size = [], 0
-            if cur:
-                chunks.append(np.concatenate(cur))
-            self._pull(chunks, lambda e, idx: e.anib_pairs(qa[idx], sa[idx], fragsize), out)
+            self._pull(self._anib_chunks(qa), lambda e, idx: e.anib_pairs(qa[idx], sa[idx], fragsize), out)
         return out
+
+    def _anib_chunks(self, qa: np.ndarray) -> List[np.ndarray]:
+        """The pair list of a fragment-mode call cut for the devices: the fragmented (query) genome is the expensive side to set
+        up — its pairs stay together (the genome is the hub of its chunk)."""
+        order = np.argsort(qa, kind="stable")
+        bounds = np.flatnonzero(np.diff(qa[order])) + 1
+        groups, chunks, cur, size = np.split(order, bounds), [], [], 0
+        target = max(64, len(qa) // (24 * len(self.engines)) + 1) if self.chunk_pairs <= 0 else self.chunk_pairs
+        for g in groups:
+            cur.append(g); size += len(g)
+            if size >= target:
+                chunks.append(np.concatenate(cur)); cur, size = [], 0
+        if cur:
+            chunks.append(np.concatenate(cur))
+        return chunks
+
+    def anib_rows_batch(self, qry_ids, sbj_ids, fragsize: int = 1020):
+        """Engine.anib_rows_batch over all devices: the pair list is cut exactly as for anib_pairs, the devices pull chunks, and
+        the parts are put back together in the caller's pair order (merge_anib_row_parts).  Returns (results, offsets, rows).
+        Single-process only: pyani_amd.parallel.DistributedEngine has no such call, and there is no collective run_anib."""
+        qa = np.ascontiguousarray(list(qry_ids), dtype=np.int32)
+        sa = np.ascontiguousarray(list(sbj_ids), dtype=np.int32)
+        if len(qa) != len(sa):
+            raise ValueError("qry_ids and sbj_ids must have the same length")
+        n = len(qa)
+        if n == 0 or len(self.engines) == 1:
+            return self.engines[0].anib_rows_batch(qa, sa, fragsize)
+        chunks = self._anib_chunks(qa)
+        parts = [None] * len(chunks)
+        lock = threading.Lock()
+        nxt = [0]
+
+        def worker(e):
+            while True:
+                with lock:
+                    k = nxt[0]
+                    nxt[0] += 1
+                if k >= len(chunks):
+                    return
+                idx = chunks[k]
+                parts[k] = e.anib_rows_batch(qa[idx], sa[idx], fragsize)
+        self._all(worker)
+        return merge_anib_row_parts(n, chunks, parts)
 
     # -- alignment records (run_anim(write_output=True): the .delta / .filter files) -----------------------------------------------
     def anim_alignments_batch(self, ref_ids, qry_ids, maxmatch: bool = False, with_indels: bool = False):
@@ -331,6 +363,28 @@ def merge_alignment_parts(n: int, chunks: List[np.ndarray], parts, with_indels: 
                 lo, hi = int(ioff[a]), int(ioff[b])
                 indels[int(ioffsets[dst]):int(ioffsets[dst]) + hi - lo] = ind[lo:hi]
     return offsets, recs, ioffsets, indels
+
+
+def merge_anib_row_parts(n: int, chunks: List[np.ndarray], parts):
+    """Put the per-chunk results of Engine.anib_rows_batch — (results, offsets, rows) over the chunk's own pairs — back into ONE
+    result over the caller's n pairs, in the caller's order.  chunks[k][j] is the caller's index of pair j of part k."""
+    results = np.zeros(n, dtype=Engine.ANIB_DTYPE)
+    counts = np.zeros(n, dtype=np.int64)
+    for idx, (res, off, _) in zip(chunks, parts):
+        if len(idx):
+            results[idx] = res
+            counts[idx] = np.diff(np.asarray(off, dtype=np.int64))
+    offsets = np.zeros(n + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum(counts)
+    rows = np.zeros(int(offsets[-1]), dtype=Engine.ANIB_ROW_DTYPE)
+    for idx, (_, off, part_rows) in zip(chunks, parts):
+        off = np.asarray(off, dtype=np.int64)
+        for j, p in enumerate(idx):
+            a, b = int(off[j]), int(off[j + 1])
+            if b > a:
+                dst = int(offsets[p])
+                rows[dst:dst + b - a] = part_rows[a:b]
+    return results, offsets, rows
 
 
 def engine_for(devices: Optional[Iterable[int]] = None, workers: Optional[int] = None):
