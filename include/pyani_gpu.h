@@ -170,6 +170,20 @@ int pg_anim_set_workers(pg_ctx* ctx, int workers);
  * Synchronises the context's streams. */
 int pg_anim_counters(pg_ctx* ctx, uint64_t* out, int reset);
 
+/* ---- development ------------------------------------------------------------------------------------------------------------
+ * Caller-chosen rectangles through the forced re-alignment launches of the extender (the four kernels a batch runs after its
+ * walks: narrow / wide windows of one wave, the group of four waves, the column strips), so that tests can place a rectangle on a
+ * window boundary, a stream end or a hand-over between kernels instead of waiting for a genome pair to produce one.
+ * rects[4 n]: (A0, A1, B0, B1) per rectangle as the walk hands them to its forced runs — stream positions of the resident genomes
+ * ref_id / qry_id, both ends inclusive, B in the coordinates of the query strand (0 forward, 1 reverse complement).
+ * Per rectangle: errors[i] = error count of the optimal global path, w_used[i] = the band it was certified with (-1: the whole
+ * rectangle), status[i] = 0 certified, 2 = the corner stayed unreachable or no engine held the run (what flags a unit PG_E_CAPACITY
+ * in a batch; errors and w_used are 0 then).  Every rectangle is a unit of its own, so a failure marks that rectangle alone.
+ * Honoured only under PYANI_DEV_KNOBS=1 (PG_E_ARG without it).  PG_E_ARG also for a side below 1, a rectangle outside its stream
+ * and a side longer than one engine call aligns (10 000 bases: MUMmer's MAX_ALIGNMENT_LENGTH).  Not while enqueued calls are in flight. */
+int pg_anim_forced_rects(pg_ctx* ctx, int32_t ref_id, int32_t qry_id, int strand, uint32_t n, const int32_t* rects, int32_t* errors,
+                         int32_t* w_used, int32_t* status);
+
 /* Work-memory budget of pg_anim_pairs: at most max_pairs ordered pairs and max_matches exact matches in flight (about 384 bytes
  * of device scratch per match, grown on demand; default 131072 pairs / 512 Mi matches, split over the context's two workers =
  * launches of up to 65536 pairs / 256 Mi matches, ~68 GB each).  Larger calls are split transparently; results do not depend on

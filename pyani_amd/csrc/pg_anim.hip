@@ -1010,6 +1010,32 @@ static int cluster_stage(Batch& B) {
   return PG_OK;
 }
 
+// The forced re-alignments of a launch: the request array (short runs from slot 0 up, long ones from slot req_cap - 1 down; their
+// counts at cur[PNC_FORCED_N] / cur[PNC_FORCED_LONG]) through the four kernels in turn.  wide: 3 * req_cap slots (the lists handed
+// from kernel to kernel); gscratch: forced_scratch_waves(ctx) * PN_GLOBAL_WORDS words.  Called by the batch's extension stage and by
+// pg_anim_forced_rects_run (development: caller-chosen rectangles).
+static uint32_t forced_scratch_waves(const pg_ctx* ctx) { return (uint32_t)ctx->num_cu * 12u; }   // forced kernels with the LDS store: 12 KiB of LDS each: 12 per CU
+static uint32_t diag_only_waves(const pg_ctx* ctx) { return (uint32_t)ctx->num_cu * 32u; }   // gap / forward / backward pre-passes and the narrow forced kernel: no LDS, diagonal engine only, <= 64 registers: 8 per SIMD
+static void launch_forced(pg_ctx* ctx, const RefDesc* refs_d, const UnitDesc* units_d, PnForcedReq* reqs, uint32_t req_cap, uint32_t* cur, int32_t* pn_n,
+                          uint32_t* gscratch, uint32_t* wide) {
+  // narrow bands first (five waves per SIMD), then the runs that asked for a wide one (pga_postnuc.inc, pn_forced_wave)
+  const uint32_t pn_waves = forced_scratch_waves(ctx);
+  const uint32_t pn_waves_pre = diag_only_waves(ctx);
+  const uint32_t win_max = (uint32_t)ctx->anim_pn_window_max, group_max = (uint32_t)ctx->anim_pn_group_max;
+  hipLaunchKernelGGL(anim_postnuc_forced_kernel, dim3(pn_waves_pre), dim3(64), 0, cur_stream(ctx), refs_d, units_d, reqs,
+                     cur + PNC_FORCED_N, req_cap, cur + PNC_FORCED_CUR, pn_n, wide, cur + PNC_WIDE_N, win_max);
+  hipLaunchKernelGGL(anim_postnuc_forced_wide_kernel, dim3(pn_waves), dim3(64), 0, cur_stream(ctx), refs_d, units_d, reqs,
+                     cur + PNC_FORCED_N, req_cap, cur + PNC_WIDE_CUR, pn_n, gscratch, wide, cur + PNC_WIDE_N,
+                     wide + req_cap, cur + PNC_HUGE_N, win_max);
+  // runs whose band spans more than one wave's 2048 diagonals: a workgroup of four waves each (2 workgroups per CU: the 8192-diagonal form holds 242 VGPRs); what the group
+  // cannot hold either: the column strips, one wave per run (a list that is empty on every genome workload seen so far)
+  hipLaunchKernelGGL(anim_postnuc_forced_huge_kernel, dim3((uint32_t)ctx->num_cu * 2u), dim3(64 * PN_HUGE_WAVES), 0, cur_stream(ctx), refs_d,
+                     units_d, reqs, cur + PNC_HUGE_CUR, pn_n, wide + req_cap, cur + PNC_HUGE_N, wide + 2 * (size_t)req_cap,
+                     cur + PNC_STRIPS_N, group_max);
+  hipLaunchKernelGGL(anim_postnuc_forced_strips_kernel, dim3(pn_waves), dim3(64), 0, cur_stream(ctx), refs_d, units_d, reqs,
+                     cur + PNC_STRIPS_CUR, pn_n, gscratch, wide + 2 * (size_t)req_cap, cur + PNC_STRIPS_N);
+}
+
 // A4x: MUMmer's own extension algorithm — the (unit, chain) work list, the pre-passes over it (match-to-match gaps, forward
 // extensions, backward searches), the pairs' walks on persistent waves, then the forced re-alignments the walks deferred.
 static int extend_stage(Batch& B) {
@@ -1037,9 +1063,9 @@ static int extend_stage(Batch& B) {
   }
   PG_HIP(ctx, A->pn_cursor.reserve(PNC_WORDS));
   uint32_t* const cur = A->pn_cursor;
-  const uint32_t pn_waves = (uint32_t)ctx->num_cu * 12u;   // forced kernels with the LDS store: 12 KiB of LDS each: 12 per CU
+  const uint32_t pn_waves = forced_scratch_waves(ctx);
   const uint32_t pn_walk_waves = (uint32_t)ctx->num_cu * 8u;   // the walk / rehearsal kernels: 219 / 173 VGPRs, two waves per SIMD — one persistent wave per resident slot
-  const uint32_t pn_waves_pre = (uint32_t)ctx->num_cu * 32u;   // gap / forward / backward pre-passes and the narrow forced kernel: no LDS, diagonal engine only, <= 64 registers: 8 per SIMD
+  const uint32_t pn_waves_pre = diag_only_waves(ctx);
   const uint32_t pn_waves_scr = ctx->anim_gap_lanes ? (pn_waves > pn_walk_waves ? pn_waves : pn_walk_waves) : pn_waves_pre;      // (only the walks, the wide forced kernel and the all-gaps form of the gap kernel use the global scratch)
   PG_HIP(ctx, A->pn_gscratch.reserve((size_t)pn_waves_scr * PN_GLOBAL_WORDS));
   const bool trace = B.trace;      // the walks list their pieces and align everything themselves
@@ -1101,22 +1127,75 @@ static int extend_stage(Batch& B) {
     PG_HIP(ctx, hipMemsetAsync(A->pn_n, 0, (size_t)n_units * 4, cur_stream(ctx)));
   pg_prof_end(ctx);
   pg_prof_begin(ctx, PG_K_ANIM_EXTLANE);     // (the forced re-alignments, deferred: pga_postnuc.inc)
-  if (n_wl) {      // narrow bands first (five waves per SIMD), then the runs that asked for a wide one (pga_postnuc.inc, pn_forced_wave)
-    const uint32_t win_max = (uint32_t)ctx->anim_pn_window_max, group_max = (uint32_t)ctx->anim_pn_group_max;
-    hipLaunchKernelGGL(anim_postnuc_forced_kernel, dim3(pn_waves_pre), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, A->pn_reqs,
-                       cur + PNC_FORCED_N, (uint32_t)req_cap, cur + PNC_FORCED_CUR, A->pn_n, A->pn_wide, cur + PNC_WIDE_N, win_max);
-    hipLaunchKernelGGL(anim_postnuc_forced_wide_kernel, dim3(pn_waves), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, A->pn_reqs,
-                       cur + PNC_FORCED_N, (uint32_t)req_cap, cur + PNC_WIDE_CUR, A->pn_n, A->pn_gscratch, A->pn_wide, cur + PNC_WIDE_N,
-                       A->pn_wide + req_cap, cur + PNC_HUGE_N, win_max);
-    // runs whose band spans more than one wave's 2048 diagonals: a workgroup of four waves each (2 workgroups per CU: the 8192-diagonal form holds 242 VGPRs); what the group
-    // cannot hold either: the column strips, one wave per run (a list that is empty on every workload seen so far)
-    hipLaunchKernelGGL(anim_postnuc_forced_huge_kernel, dim3((uint32_t)ctx->num_cu * 2u), dim3(64 * PN_HUGE_WAVES), 0, cur_stream(ctx), A->refs_d,
-                       A->units_d, A->pn_reqs, cur + PNC_HUGE_CUR, A->pn_n, A->pn_wide + req_cap, cur + PNC_HUGE_N, A->pn_wide + 2 * req_cap,
-                       cur + PNC_STRIPS_N, group_max);
-    hipLaunchKernelGGL(anim_postnuc_forced_strips_kernel, dim3(pn_waves), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, A->pn_reqs,
-                       cur + PNC_STRIPS_CUR, A->pn_n, A->pn_gscratch, A->pn_wide + 2 * req_cap, cur + PNC_STRIPS_N);
-  }
+  if (n_wl) launch_forced(ctx, A->refs_d, A->units_d, A->pn_reqs, (uint32_t)req_cap, cur, A->pn_n, A->pn_gscratch, A->pn_wide);
   pg_prof_end(ctx);
+  return PG_OK;
+}
+
+// Development (pg_anim_forced_rects): caller-chosen rectangles through launch_forced, the product's own forced launches.  The
+// descriptors are a batch's (one RefDesc; UnitDesc per rectangle, all of the same query strand: a unit entry of its own is what
+// tells a failed rectangle from its neighbours, the flag being per unit), the request array is filled with forced_errors' split
+// (sum of sides > 1500: from the back), every rectangle has a zeroed PnAln of its own as dst.  Ids, strand and pointers were checked
+// by the caller; the rectangles are checked here: a side is at most what the walk hands one engine call (MAX_ALIGNMENT_LENGTH).
+int pg_anim_forced_rects_run(pg_ctx* ctx, int32_t ref_id, int32_t qry_id, int strand, uint32_t n, const int32_t* rects, int32_t* errors,
+                             int32_t* w_used, int32_t* status) {
+  const PgGenome& G = ctx->genomes[ref_id];
+  const PgGenome& H = ctx->genomes[qry_id];
+  for (uint32_t i = 0; i < n; ++i) {
+    const int64_t A0 = rects[4 * i], A1 = rects[4 * i + 1], B0 = rects[4 * i + 2], B1 = rects[4 * i + 3];
+    const int64_t N = A1 - A0 + 1, M = B1 - B0 + 1;
+    if (N < 1 || M < 1) return pg_fail(ctx, PG_E_ARG, "pg_anim_forced_rects: a rectangle with a side below 1");
+    if (A0 < 0 || A1 >= (int64_t)G.stream_len || B0 < 0 || B1 >= (int64_t)H.stream_len) return pg_fail(ctx, PG_E_ARG, "pg_anim_forced_rects: a rectangle outside its stream");
+    if (N > pgn::MAX_ALIGNMENT_LENGTH || M > pgn::MAX_ALIGNMENT_LENGTH)
+      return pg_fail(ctx, PG_E_ARG, "pg_anim_forced_rects: a side longer than one engine call aligns (MAX_ALIGNMENT_LENGTH)");
+  }
+  AnimScratch* A = anim_scratch(ctx);
+  (void)hipGetLastError();
+  RefDesc ref{ctx->d_codes + G.arena_start / 16, ctx->d_mask + G.arena_start / 32, (int32_t)G.stream_len, nullptr, 0};
+  std::vector<UnitDesc> units(n, UnitDesc{ctx->d_codes + H.arena_start / 16, ctx->d_mask + H.arena_start / 32, (int32_t)H.stream_len, nullptr, 0, strand, 0, 0});
+  PgDevBuf<RefDesc> refs_d;
+  PgDevBuf<UnitDesc> units_d;
+  PgDevBuf<PnForcedReq> reqs_d;
+  PgDevBuf<pgn::PnAln> dst_d;
+  PgDevBuf<int32_t> pn_n_d;
+  PgDevBuf<uint32_t> wide_d, cur_d;
+  const uint32_t req_cap = n;
+  PG_HIP(ctx, refs_d.reserve(1));
+  PG_HIP(ctx, reserve_all(n, n, units_d, reqs_d, dst_d, pn_n_d));
+  PG_HIP(ctx, wide_d.reserve(3 * (size_t)req_cap));
+  PG_HIP(ctx, cur_d.reserve(PNC_WORDS));
+  PG_HIP(ctx, A->pn_gscratch.reserve((size_t)forced_scratch_waves(ctx) * PN_GLOBAL_WORDS));
+  std::vector<PnForcedReq> reqs(req_cap);
+  std::vector<uint32_t> slot_of(n);
+  uint32_t cur[PNC_WORDS] = {0};
+  for (uint32_t i = 0; i < n; ++i) {
+    const int32_t A0 = rects[4 * i], A1 = rects[4 * i + 1], B0 = rects[4 * i + 2], B1 = rects[4 * i + 3];
+    const bool big = (A1 - A0) + (B1 - B0) > 1500;
+    const uint32_t at = big ? cur[PNC_FORCED_LONG]++ : cur[PNC_FORCED_N]++;
+    slot_of[i] = big ? req_cap - 1 - at : at;
+    reqs[slot_of[i]] = PnForcedReq{A0, A1, B0, B1, i, 0, dst_d.p + i};
+  }
+  hipStream_t st = cur_stream(ctx);
+  PG_HIP(ctx, hipMemcpyAsync(refs_d, &ref, sizeof(ref), hipMemcpyHostToDevice, st));
+  PG_HIP(ctx, hipMemcpyAsync(units_d, units.data(), (size_t)n * sizeof(UnitDesc), hipMemcpyHostToDevice, st));
+  PG_HIP(ctx, hipMemcpyAsync(reqs_d, reqs.data(), (size_t)n * sizeof(PnForcedReq), hipMemcpyHostToDevice, st));
+  PG_HIP(ctx, hipMemcpyAsync(cur_d, cur, sizeof(cur), hipMemcpyHostToDevice, st));
+  PG_HIP(ctx, hipMemsetAsync(dst_d, 0, (size_t)n * sizeof(pgn::PnAln), st));
+  PG_HIP(ctx, hipMemsetAsync(pn_n_d, 0, (size_t)n * 4, st));
+  launch_forced(ctx, refs_d, units_d, reqs_d, req_cap, cur_d, pn_n_d, A->pn_gscratch, wide_d);
+  PG_HIP(ctx, hipGetLastError());
+  std::vector<pgn::PnAln> dst(n);
+  std::vector<int32_t> pn_n(n);
+  PG_HIP(ctx, hipMemcpyAsync(reqs.data(), reqs_d, (size_t)n * sizeof(PnForcedReq), hipMemcpyDeviceToHost, st));
+  PG_HIP(ctx, hipMemcpyAsync(dst.data(), dst_d, (size_t)n * sizeof(pgn::PnAln), hipMemcpyDeviceToHost, st));
+  PG_HIP(ctx, hipMemcpyAsync(pn_n.data(), pn_n_d, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  PG_HIP(ctx, hipStreamSynchronize(st));
+  for (uint32_t i = 0; i < n; ++i) {
+    const bool failed = pn_n[i] < 0;      // the unit flag: the corner stayed unreachable, or no engine held the run
+    status[i] = failed ? 2 : 0;
+    errors[i] = failed ? 0 : dst[i].errors;
+    w_used[i] = failed ? 0 : reqs[slot_of[i]].w;
+  }
   return PG_OK;
 }
 

@@ -202,6 +202,9 @@ struct PgAlnSink {
   std::vector<std::vector<int64_t>> indels;       // parallel to alns (with_indels)
 };
 int pg_anim_counters_read(pg_ctx* ctx, uint64_t* out /*[64]*/, int reset);
+// development (pg_anim_forced_rects): n checked rectangles (A0, A1, B0, B1) of one (reference, query strand) through the forced launches
+int pg_anim_forced_rects_run(pg_ctx* ctx, int32_t ref_id, int32_t qry_id, int strand, uint32_t n, const int32_t* rects, int32_t* errors,
+                             int32_t* w_used, int32_t* status);
 void pg_anim_set_sink(PgAlnSink* sink);           // thread-local; nullptr = none
 void pg_anim_drop_lists(pg_ctx* ctx);   // per-genome seed lists: must go when the genome store is cleared
 void pg_sketch_drop(pg_ctx* ctx);       // ... and the sketches of the sketch mode (pg_sketch.hip)

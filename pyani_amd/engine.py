@@ -200,6 +200,17 @@ class Engine:
         self._check(self.lib.pg_anim_counters(self._h, out.ctypes.data, int(bool(reset))))
         return out
 
+    def anim_forced_rects(self, ref_id: int, qry_id: int, strand: int, rects) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Development (pg_anim_forced_rects, honoured under PYANI_DEV_KNOBS=1): rectangles (A0, A1, B0, B1) — stream positions, ends
+        inclusive, B in strand coordinates — through the extender's forced launches.  Returns (errors, w_used, status) per rectangle:
+        w_used -1 = the whole rectangle; status 0 = certified, 2 = corner unreachable / capacity."""
+        r = np.ascontiguousarray(rects, dtype=np.int32).reshape(-1, 4)
+        n = len(r)
+        errors, w_used, status = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        self._check(self.lib.pg_anim_forced_rects(self._h, int(ref_id), int(qry_id), int(strand), n, r.ctypes.data, errors.ctypes.data,
+                                                  w_used.ctypes.data, status.ctypes.data))
+        return errors, w_used, status
+
     def anim_set_batch_budget(self, max_pairs: int, max_matches: int) -> None:
         self._check(self.lib.pg_anim_set_batch_budget(self._h, int(max_pairs), int(max_matches)))
 

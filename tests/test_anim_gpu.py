@@ -251,6 +251,16 @@ def test_batch_split_does_not_change_results_and_edge_inputs(eng):
     assert mm.tobytes() == ref[:30].tobytes()
 
 
+def _forced_counters(e):
+    """The forced re-alignments of the calls since the last reset, by pg_anim_counters: passes by span class (out[27..30]: up to 256 / 512 /
+    2048 diagonals, beyond), diagonal-engine calls in the narrow kernel, on the wide kernel's windows, in the group of four waves
+    (out[32 + 4 k], k = 4 .. 7); a pass that made no diagonal-engine call ran on the strips."""
+    c = [int(v) for v in e.anim_counters()]
+    d = dict(passes=c[27:31], narrow=c[32 + 16], wide=c[32 + 20] + c[32 + 24], group=c[32 + 28])
+    d["strips"] = sum(d["passes"]) - d["narrow"] - d["wide"] - d["group"]
+    return d
+
+
 def test_gap_forms_and_extenders_of_the_postnuc_stage_agree(monkeypatch):
     """The match-to-match alignments of a cluster run on one LANE each when their rectangle is small enough to rule out trimming
     and the break rule (pga_postnuc.inc, PN_SMALL) and on the wave engine otherwise: switching the lane form off
@@ -259,13 +269,15 @@ def test_gap_forms_and_extenders_of_the_postnuc_stage_agree(monkeypatch):
     from pyani_amd.engine import Engine
     n, L = 10, 250_000
     data = [synth.genome(5, n, g, L) for g in range(n)]
-    out = {}
+    out, counters = {}, {}
     for lanes in ("1", "0"):
         monkeypatch.setenv("PYANI_ANIM_GAP_LANES", lanes)
         with Engine(0) as e:
             ids = [e.add_genome(*d) for d in data]
             pairs = [(a, b) for a in ids for b in ids if a != b]
+            e.anim_counters(reset=True)
             out[lanes] = e.anim_pairs([a for a, _ in pairs], [b for _, b in pairs])
+            counters[lanes] = _forced_counters(e)
     assert (out["1"]["status"] == 0).sum() >= 40
     assert out["1"].tobytes() == out["0"].tobytes()
     # the backward searches run ahead of the units' walks (rehearsal + one wave per predicted search; results are taken only when
@@ -288,8 +300,22 @@ def test_gap_forms_and_extenders_of_the_postnuc_stage_agree(monkeypatch):
         with Engine(0) as e:
             ids = [e.add_genome(*d) for d in data]
             pairs = [(a, b) for a in ids for b in ids if a != b]
+            e.anim_counters(reset=True)
             got = e.anim_pairs([a for a, _ in pairs], [b for _, b in pairs])
+            counters[(window_max, group_max)] = _forced_counters(e)
         assert got.tobytes() == out["1"].tobytes(), (window_max, group_max)
+    # ... and the counters say that the three configurations are three ways: the default run has forced passes beyond 256 diagonals,
+    # on single-wave windows; capped at 256 the same passes are the group's; with the group off they are the strips'
+    default = counters["1"]
+    assert default["passes"][1] + default["passes"][2] + default["passes"][3] > 0 and default["wide"] > 0, default
+    assert counters["0"] == default
+    capped = counters[("256", "8184")]
+    assert capped["group"] > default["group"] and capped["group"] >= default["wide"] and capped["wide"] == 0 and capped["strips"] == default["strips"], capped
+    no_group = counters[("256", "0")]
+    assert no_group["group"] == 0 and no_group["wide"] == 0 and no_group["strips"] >= default["wide"] > 0, no_group
+    assert sum(capped["passes"]) == sum(no_group["passes"]) == sum(default["passes"])      # the same ladder of bands whichever engine runs it
+    narrowest = counters[("128", "3064")]
+    assert narrowest["wide"] == 0 and narrowest["group"] >= capped["group"] - default["group"] > 0, narrowest      # (group_max 3064: the widest runs go on to the strips)
 
 
 def test_cluster_stage_forms_do_not_change_results(eng, monkeypatch):

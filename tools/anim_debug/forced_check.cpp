@@ -5,20 +5,22 @@
 // a row), hence no genome pair reaches this through the C ABI: the check drives the engines directly — pgn::ScalarEngine (the
 // definition the GPU engines follow cell for cell, and what anim_trace_kernel runs) and pgd::DiagWaveEngine (the host emulation
 // of the GPU's diagonal-window wave engines, same header the kernels compile).
-// The referee is a plain-integer statement of sw_align's forced alignment written here (whole rectangle, int64 scores, MUMmer's
-// tie order MATCH > INSERT > DELETE on the state of origin, errors riding along): no packed words, no band, no floor.
+// The referee is the plain-integer statement of sw_align's forced alignment in forced_referee.h (whole rectangle, int64 scores,
+// MUMmer's tie order MATCH > INSERT > DELETE on the state of origin, errors riding along): no packed words, no band, no floor.
 //   case A  20 matching bases, 700 unrelated ones, 1200 matching: the optimal path's prefix falls to about -1 650 before it recovers
 //           (rounds 3-4, floor -1024: its cells saturated and the run came back with another path's error count)
 //   case B  20 matching, 1500 unrelated, 2500 matching: the prefix minimum lies below the floor (-2700) on EVERY path to the corner:
 //           the run must FAIL LOUDLY (engine overflow -> PG_E_CAPACITY on the pair), not return the count of an unreachable word
 //   case C  1500 bases with 30 scattered mismatches: an ordinary rectangle
-// Prints one line per case and engine; exit code 0 iff all are as stated.   g++ -O2 -std=c++17 -Ipyani_amd/csrc forced_check.cpp
+// Prints one line per case and engine; exit code 0 iff all are as stated.   g++ -O2 -std=c++17 -pthread -Ipyani_amd/csrc -Itools/anim_debug forced_check.cpp
 #include <cstdio>
 #include <string>
 #include <thread>
 #include <vector>
 #include "pg_nucmer_diag.h"
+#include "forced_referee.h"
 using namespace pga;
+using forced_referee::reference;
 
 struct Packed {
   std::vector<uint32_t> codes, mask;
@@ -46,51 +48,6 @@ static void build(const std::vector<int>& runs, std::string& a, std::string& b) 
       a.push_back(B[c]);
       b.push_back(r < 0 ? B[(c + 1 + rnd4() % 3) & 3] : B[c]);
     }
-}
-
-// sw_align's forced (global, untrimmed) alignment of a[0 .. N) with b[0 .. M) on plain integers: score and errors of the corner
-struct St { long long s; int e; };
-static const long long NEG = -(1ll << 50);
-static void reference(const std::string& a, const std::string& b, long long& score, int& errors, long long& prefix_min) {
-  const int N = (int)a.size(), M = (int)b.size();
-  // states 0 = DELETE (a B base alone: from the left), 1 = INSERT (an A base alone: from above), 2 = MATCH column
-  std::vector<St> prev(3 * (M + 1)), cur(3 * (M + 1));
-  std::vector<long long> pmin_prev(3 * (M + 1)), pmin_cur(3 * (M + 1));      // the lowest score along the chosen path to each state
-  auto better = [](const St& x, int sx, const St& y, int sy) { return x.s != y.s ? x.s > y.s : sx > sy; };      // ties: MATCH > INSERT > DELETE
-  for (int i = 0; i <= N; ++i) {
-    for (int j = 0; j <= M; ++j) {
-      St D{NEG, 0}, I{NEG, 0}, Mm{NEG, 0};
-      long long pD = 0, pI = 0, pM = 0;
-      if (i == 0 && j == 0) { Mm = St{0, 0}; }
-      else {
-        if (j >= 1) {      // DELETE from the left cell's states
-          const St* L = &cur[3 * (j - 1)]; const long long* pl = &pmin_cur[3 * (j - 1)];
-          int bs = -1; St bv{NEG, 0};
-          for (int st = 0; st < 3; ++st) { if (L[st].s <= NEG / 2) continue; const St c{L[st].s + (st == 0 ? -7 : -10), L[st].e + 1}; if (bs < 0 || better(c, st, bv, bs)) { bv = c; bs = st; } }
-          if (bs >= 0) { D = bv; pD = pl[bs] < bv.s ? pl[bs] : bv.s; }
-        }
-        if (i >= 1) {      // INSERT from the cell above
-          const St* U = &prev[3 * j]; const long long* pu = &pmin_prev[3 * j];
-          int bs = -1; St bv{NEG, 0};
-          for (int st = 0; st < 3; ++st) { if (U[st].s <= NEG / 2) continue; const St c{U[st].s + (st == 1 ? -7 : -10), U[st].e + 1}; if (bs < 0 || better(c, st, bv, bs)) { bv = c; bs = st; } }
-          if (bs >= 0) { I = bv; pI = pu[bs] < bv.s ? pu[bs] : bv.s; }
-        }
-        if (i >= 1 && j >= 1) {      // MATCH column from the best state of the diagonal cell
-          const St* G = &prev[3 * (j - 1)]; const long long* pg = &pmin_prev[3 * (j - 1)];
-          int bs = -1; St bv{NEG, 0};
-          for (int st = 0; st < 3; ++st) { if (G[st].s <= NEG / 2) continue; if (bs < 0 || better(G[st], st, bv, bs)) { bv = G[st]; bs = st; } }
-          if (bs >= 0) { const bool same = a[i - 1] == b[j - 1]; Mm = St{bv.s + (same ? 3 : -7), bv.e + (same ? 0 : 1)}; pM = pg[bs] < Mm.s ? pg[bs] : Mm.s; }
-        }
-      }
-      cur[3 * j] = D; cur[3 * j + 1] = I; cur[3 * j + 2] = Mm;
-      pmin_cur[3 * j] = pD; pmin_cur[3 * j + 1] = pI; pmin_cur[3 * j + 2] = pM;
-    }
-    prev.swap(cur); pmin_prev.swap(pmin_cur);
-  }
-  const St* C = &prev[3 * M];
-  int bs = -1; St bv{NEG, 0};
-  for (int st = 0; st < 3; ++st) { if (C[st].s <= NEG / 2) continue; if (bs < 0 || better(C[st], st, bv, bs)) { bv = C[st]; bs = st; } }
-  score = bv.s; errors = bv.e; prefix_min = pmin_prev[3 * M + bs];
 }
 
 int main() {
