@@ -285,12 +285,20 @@ int pg_anib_rows_read(pg_ctx* ctx, pg_anib_row* out);
 /* ---- sketch mode: an opt-in ESTIMATE in the shape of pyani's fastANI wrapper -------------------------
  * Replaces the `fastANI -q <query> -r <ref> --fragLen 3000 -k 16 --minFraction 0.2` job of pyani/fastani.py:193-229
  * (construct_fastani_cmdline) and the line parse_fastani_file reads back (fastani.py:231-270): ANI estimate, matching fragments,
- * query fragments.  Definition (pyani_amd/csrc/pg_sketch_core.h): canonical 16-mers sampled 1 in `scale` by a hash (FracMinHash);
- * the query's records cut into non-overlapping fragments of `frag_len` bases; per fragment the share C of its sampled k-mers that
- * occur anywhere in the reference, identity = C^(1/16); a fragment matches with >= 2 hits and identity >= 0.80; ani = mean identity
- * of the matching fragments (a FRACTION, as ComparisonResult.ani), status PG_SKETCH_NO_RESULT when fewer than min_fraction of
- * the fragments match (fastANI writes no line then).  Sketches are built on first use and cached per genome.  An estimate with
- * its own columns: nothing of it enters the exact ANIm / ANIb results.  Limits: k = 16 only; <= 24 576 fragments per query. */
+ * query fragments.  Definition (pyani_amd/csrc/pg_sketch_core.h), for a k-mer size 8 <= k <= 16 (fastANI's --kmer; default 16):
+ * a canonical k-mer is a 2k-bit integer (first base in the high bits, min of forward and reverse complement), sampled 1 in `scale`
+ * by a hash (FracMinHash); a window exists iff its k bases are unambiguous and inside one record; the query's records are cut into
+ * non-overlapping fragments of `frag_len` bases, and a sampled k-mer belongs to the fragment that holds all k of its bases; per
+ * fragment the share C = h / n of its sampled k-mers that occur anywhere in the reference, identity = C^(1/k):
+ *   k = 16: four correctly rounded square roots;
+ *   k = 8 ... 15: y = those four square roots (at or above the root), then exactly 12 Newton steps, each p = y; k - 2 times
+ *   p = p * y; y = y - (p * y - C) / (k * p), every operation rounded on its own (the same bits on host and device);
+ * a fragment matches with h >= 2 and identity >= 0.80; ani = mean identity of the matching fragments, summed in ascending fragment
+ * order (a FRACTION, as ComparisonResult.ani), status PG_SKETCH_NO_RESULT when fewer than min_fraction of the fragments match
+ * (fastANI writes no line then).  Sketches are built on first use and cached per genome under (k, frag_len, scale): a call with
+ * other values rebuilds.  An estimate with its own columns: nothing of it enters the exact ANIm / ANIb results.
+ * Limits: <= 24 576 fragments per query (PG_E_CAPACITY); kmer outside 8 ... 16: PG_E_ARG.  pg_sketch_pairs is pg_sketch_pairs_k
+ * with kmer = 16. */
 typedef struct {
   double ani;          /* mean identity estimate of the matching fragments, 0 ... 1 (0 when status != 0) */
   int32_t matches;     /* fragments with an identity estimate >= 0.80 */
@@ -301,6 +309,8 @@ typedef struct {
 #define PG_SKETCH_NO_RESULT 1
 int pg_sketch_pairs(pg_ctx* ctx, const int32_t* qry_ids, const int32_t* ref_ids, uint64_t n_pairs, int32_t frag_len, int32_t scale,
                     double min_fraction, pg_sketch_result* out);
+int pg_sketch_pairs_k(pg_ctx* ctx, const int32_t* qry_ids, const int32_t* ref_ids, uint64_t n_pairs, int32_t kmer, int32_t frag_len,
+                      int32_t scale, double min_fraction, pg_sketch_result* out);
 
 /* ---- classify: clique sweep over identity thresholds ------------------------------------------------------------------
  * The compute of `pyani classify`.  These calls read caller matrices only: they touch no genome, seed list or ANIm worker slot, so

@@ -80,6 +80,7 @@ SIGNATURES = {
     "pg_anib_rows_batch": (_int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp]),
     "pg_anib_rows_read": (_int, [_vp, _vp]),
     "pg_sketch_pairs": (_int, [_vp, _vp, _vp, _u64, _i32, _i32, ctypes.c_double, _vp]),
+    "pg_sketch_pairs_k": (_int, [_vp, _vp, _vp, _u64, _i32, _i32, _i32, ctypes.c_double, _vp]),
     "pg_classify_edges": (_int, [_vp, _vp, _vp, _u32, ctypes.c_double, ctypes.c_double, _P(_u64), _P(_u32)]),
     "pg_classify_edge_identities": (_int, [_vp, _vp, _u64]),
     "pg_classify_sweep": (_int, [_vp, _vp, _u64, _vp, _vp, _vp]),

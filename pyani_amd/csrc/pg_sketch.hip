@@ -2,9 +2,10 @@
 // pyani/fastani.py:193-270, construct_fastani_cmdline / parse_fastani_file).  An opt-in ESTIMATE with its own result struct — nothing
 // here touches the exact ANIm / ANIb results.  Integer / byte work over the 2-bit packed genomes already resident in HBM; no MFMA.
 //
-//   S1 sketch_scan_kernel   once per genome (cached with its frag_len / scale): one coalesced pass over the packed stream; every lane
-//                           rolls the canonical 16-mers of 32 consecutive start positions out of three code words and two mask
-//                           words, keeps the sampled ones (mix32(kmer) & (scale - 1) == 0: 1 in 16), and
+//   S1 sketch_scan_kernel   once per genome (cached with its k / frag_len / scale): one coalesced pass over the packed stream; every lane
+//                           rolls the canonical k-mers of 32 consecutive start positions out of three code words and two mask
+//                           words (32 + k - 1 <= 47 bases for every k of 8 ... 16; k is a compile-time parameter, chosen by a host
+//                           switch), keeps the sampled ones (mix32(kmer) & (scale - 1) == 0: 1 in 16), and
 //                             - inserts them into the genome's k-mer SET (open addressing in HBM, <= 1/2 load: the reference role),
 //                             - appends (k-mer, fragment) for those that lie inside a fragment (the query role), counting per fragment.
 //                           Two launches: count (sizes the arrays exactly), then fill.
@@ -25,7 +26,7 @@ namespace {
 
 struct SketchGenome {
   bool built = false;
-  int32_t frag_len = 0, scale = 0;
+  int32_t kmer = 0, frag_len = 0, scale = 0;
   uint32_t n_frags = 0, n_occ = 0, cap_mask = 0;
   PgDevBuf<uint32_t> occ_kmer, occ_frag, frag_n, tab;
   PgDevBuf<int32_t> rec_tab;       // [2 (n_rec + 1)]: rec_start | frag_base (device)
@@ -61,7 +62,7 @@ __device__ __forceinline__ int rec_of(const int32_t* __restrict__ rec_start, int
 }
 
 // counters: [0] sampled k-mers (all), [1] occurrences inside fragments (fill pass: the append cursor)
-template <bool FILL>
+template <bool FILL, int K>
 __global__ __launch_bounds__(256) void sketch_scan_kernel(const uint32_t* __restrict__ codes, const uint32_t* __restrict__ mask, int64_t stream_len,
                                                            const int32_t* __restrict__ rec_tab, int n_rec, int32_t frag_len, uint32_t scale,
                                                            uint32_t log2_scale, uint32_t* __restrict__ counters, uint32_t* __restrict__ occ_kmer,
@@ -79,13 +80,14 @@ __global__ __launch_bounds__(256) void sketch_scan_kernel(const uint32_t* __rest
     uint32_t f = 0, r = 0;
     int rec = -1;
     int32_t rec_lo = 0, rec_hi = -1, fb = 0, n_full = 0;
-    for (int t = 0; t < 47; ++t) {      // base 32 c + t enters the window; the k-mer that ENDS on it starts at 32 c + t - 15
+    constexpr uint64_t WINDOW = (1ull << K) - 1ull;      // the K mask bits of a window
+    for (int t = 0; t < 32 + K - 1; ++t) {      // base 32 c + t enters the window; the k-mer that ENDS on it starts at 32 c + t - (K - 1)
       const uint32_t code = t < 32 ? (uint32_t)(c01 >> (2 * t)) & 3u : (c2 >> (2 * (t - 32))) & 3u;
-      f = pgs::roll_fwd(f, code); r = pgs::roll_rc(r, code);
-      const int s = t - 15;
+      f = pgs::roll_fwd(f, code, K); r = pgs::roll_rc(r, code, K);
+      const int s = t - (K - 1);
       if (s < 0) continue;
       const int64_t p = 32 * c + s;
-      if (p + 16 > stream_len || ((m >> s) & 0xFFFFull) != 0xFFFFull) continue;      // an ambiguity symbol, a record end, the stream's end
+      if (p + K > stream_len || ((m >> s) & WINDOW) != WINDOW) continue;      // an ambiguity symbol, a record end, the stream's end
       const uint32_t canon = f < r ? f : r;
       if (!pgs::sampled(canon, scale)) continue;
       ++n_all;
@@ -103,7 +105,7 @@ __global__ __launch_bounds__(256) void sketch_scan_kernel(const uint32_t* __rest
         fb = frag_base[rec]; n_full = (rec_hi - rec_lo + 1) / frag_len;
       }
       const int32_t x = (int32_t)p - rec_lo, j = x / frag_len;
-      if (j >= n_full || x - j * frag_len + 16 > frag_len) continue;      // the record's tail, or a k-mer across two fragments
+      if (j >= n_full || x - j * frag_len + K > frag_len) continue;      // the record's tail, or a k-mer across two fragments
       ++n_in;
       if (FILL) {
         const uint32_t at = atomicAdd(&counters[1], 1u);
@@ -121,6 +123,7 @@ __global__ __launch_bounds__(256) void sketch_scan_kernel(const uint32_t* __rest
 struct SketchJob {      // one workgroup: a query against up to SK_REFS references
   const uint32_t *occ_kmer, *occ_frag, *frag_n;
   uint32_t n_occ, n_frags, n_refs, log2_scale;
+  int32_t kmer;      // one k per call: uniform over the workgroup
   const uint32_t* tab[4];
   uint32_t cap_mask[4];
   uint32_t out[4];      // pair indices of the call
@@ -156,14 +159,16 @@ __global__ __launch_bounds__(256) void sketch_pairs_kernel(const SketchJob* __re
     int32_t matches = 0;
     for (uint32_t f = 0; f < nf; ++f) {
       const uint32_t n = J.frag_n[f], h = hits[g * nf + f];
-      if (pgs::frag_matches(h, n)) { sum = sum + pgs::frag_identity(h, n); ++matches; }
+      if (n == 0u || h < 2u) continue;
+      const double ident = J.kmer == 16 ? pgs::frag_identity(h, n, 16) : pgs::frag_identity(h, n, J.kmer);      // (16: the four roots alone)
+      if (ident >= pgs::MIN_IDENTITY) { sum = sum + ident; ++matches; }
     }
     pg_sketch_result o;
     o.matches = matches; o.fragments = (int32_t)nf;
     const bool enough = matches > 0 && (double)matches >= J.min_fraction * (double)nf;
     o.ani = enough ? sum / (double)matches : 0.0;
     o.status = enough ? 0 : PG_SKETCH_NO_RESULT; o.reserved = 0;
-    out[J.out[g]] = o;
+    out[jobs[blockIdx.x].out[g]] = o;      // (indexed by the lane: read from memory, so that J stays in registers)
   }
 }
 
@@ -172,9 +177,29 @@ SketchStore* store_of(pg_ctx* ctx) {
   return static_cast<SketchStore*>(ctx->sketch_store);
 }
 
-int build_sketch(pg_ctx* ctx, SketchStore* ST, int32_t gid, int32_t frag_len, int32_t scale, uint32_t log2_scale) {
+// the scan kernel of a k-mer size: K is a compile-time parameter of the kernel (window, mask constant, fragment rule)
+template <bool FILL>
+auto scan_kernel_of(int32_t kmer) -> decltype(&sketch_scan_kernel<FILL, 16>) {
+  switch (kmer) {
+    case 8: return sketch_scan_kernel<FILL, 8>;
+    case 9: return sketch_scan_kernel<FILL, 9>;
+    case 10: return sketch_scan_kernel<FILL, 10>;
+    case 11: return sketch_scan_kernel<FILL, 11>;
+    case 12: return sketch_scan_kernel<FILL, 12>;
+    case 13: return sketch_scan_kernel<FILL, 13>;
+    case 14: return sketch_scan_kernel<FILL, 14>;
+    case 15: return sketch_scan_kernel<FILL, 15>;
+    case 16: return sketch_scan_kernel<FILL, 16>;
+  }
+  return nullptr;      // (pg_sketch_pairs_k refuses every other k before it gets here)
+}
+
+int build_sketch(pg_ctx* ctx, SketchStore* ST, int32_t gid, int32_t kmer, int32_t frag_len, int32_t scale, uint32_t log2_scale) {
   SketchGenome& S = ST->g[gid];
-  if (S.built && S.frag_len == frag_len && S.scale == scale) return PG_OK;
+  if (S.built && S.kmer == kmer && S.frag_len == frag_len && S.scale == scale) return PG_OK;
+  const auto scan_count = scan_kernel_of<false>(kmer);
+  const auto scan_fill = scan_kernel_of<true>(kmer);
+  if (!scan_count || !scan_fill) return pg_fail(ctx, PG_E_ARG, "sketch: no scan kernel for this k-mer size");
   S = SketchGenome{};
   const PgGenome& G = ctx->genomes[gid];
   std::vector<int32_t> rec_tab(2 * (G.n_rec + 1));
@@ -192,7 +217,7 @@ int build_sketch(pg_ctx* ctx, SketchStore* ST, int32_t gid, int32_t frag_len, in
   const uint32_t* codes = ctx->d_codes + G.arena_start / 16;
   const uint32_t* mask = ctx->d_mask + G.arena_start / 32;
   const dim3 grid((uint32_t)std::min<uint64_t>((G.stream_len / 32 + 255) / 256 + 1, (uint64_t)ctx->num_cu * 8));
-  hipLaunchKernelGGL((sketch_scan_kernel<false>), grid, dim3(256), 0, ctx->stream, codes, mask, (int64_t)G.stream_len, S.rec_tab, (int)G.n_rec, frag_len,
+  hipLaunchKernelGGL(scan_count, grid, dim3(256), 0, ctx->stream, codes, mask, (int64_t)G.stream_len, S.rec_tab, (int)G.n_rec, frag_len,
                      (uint32_t)scale, log2_scale, ST->counters, nullptr, nullptr, nullptr, nullptr, 0u);
   PG_HIP(ctx, hipGetLastError());
   uint32_t cnt[2];
@@ -200,7 +225,7 @@ int build_sketch(pg_ctx* ctx, SketchStore* ST, int32_t gid, int32_t frag_len, in
   PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
   uint32_t cap = 1024;
   while (cap < 2 * cnt[0]) cap <<= 1;
-  S.cap_mask = cap - 1; S.n_occ = cnt[1]; S.n_frags = nf; S.frag_len = frag_len; S.scale = scale;
+  S.cap_mask = cap - 1; S.n_occ = cnt[1]; S.n_frags = nf; S.kmer = kmer; S.frag_len = frag_len; S.scale = scale;
   if ((rc = sk_malloc(ctx, S.tab, (size_t)cap))) return rc;
   if ((rc = sk_malloc(ctx, S.occ_kmer, (size_t)cnt[1] + 1))) return rc;
   if ((rc = sk_malloc(ctx, S.occ_frag, (size_t)cnt[1] + 1))) return rc;
@@ -208,7 +233,7 @@ int build_sketch(pg_ctx* ctx, SketchStore* ST, int32_t gid, int32_t frag_len, in
   PG_HIP(ctx, hipMemsetAsync(S.tab, 0xFF, (size_t)cap * 4, ctx->stream));
   PG_HIP(ctx, hipMemsetAsync(S.frag_n, 0, (size_t)(nf + 1) * 4, ctx->stream));
   PG_HIP(ctx, hipMemsetAsync(ST->counters, 0, 8, ctx->stream));
-  hipLaunchKernelGGL((sketch_scan_kernel<true>), grid, dim3(256), 0, ctx->stream, codes, mask, (int64_t)G.stream_len, S.rec_tab, (int)G.n_rec, frag_len,
+  hipLaunchKernelGGL(scan_fill, grid, dim3(256), 0, ctx->stream, codes, mask, (int64_t)G.stream_len, S.rec_tab, (int)G.n_rec, frag_len,
                      (uint32_t)scale, log2_scale, ST->counters, S.occ_kmer, S.occ_frag, S.frag_n, S.tab, S.cap_mask);
   PG_HIP(ctx, hipGetLastError());
   S.built = true;
@@ -224,7 +249,13 @@ void pg_sketch_drop(pg_ctx* ctx) {
 
 extern "C" int pg_sketch_pairs(pg_ctx* ctx, const int32_t* qry_ids, const int32_t* ref_ids, uint64_t n_pairs, int32_t frag_len, int32_t scale,
                                double min_fraction, pg_sketch_result* out) {
+  return pg_sketch_pairs_k(ctx, qry_ids, ref_ids, n_pairs, 16, frag_len, scale, min_fraction, out);      // fastANI's default -k 16: one code path
+}
+
+extern "C" int pg_sketch_pairs_k(pg_ctx* ctx, const int32_t* qry_ids, const int32_t* ref_ids, uint64_t n_pairs, int32_t kmer, int32_t frag_len,
+                                 int32_t scale, double min_fraction, pg_sketch_result* out) {
   if (!ctx || !out || (n_pairs && (!qry_ids || !ref_ids))) return pg_fail(ctx, PG_E_ARG, "bad argument");
+  if (kmer < pgs::K_MIN || kmer > pgs::K_MAX) return pg_fail(ctx, PG_E_ARG, "sketch: the k-mer size must be 8 ... 16");
   if (frag_len < 64 || scale < 1 || scale > 4096 || (scale & (scale - 1)) || !(min_fraction >= 0.0 && min_fraction <= 1.0))
     return pg_fail(ctx, PG_E_ARG, "sketch: frag_len >= 64, scale a power of two <= 4096, 0 <= min_fraction <= 1");
   for (uint64_t i = 0; i < n_pairs; ++i)
@@ -241,7 +272,7 @@ extern "C" int pg_sketch_pairs(pg_ctx* ctx, const int32_t* qry_ids, const int32_
   std::vector<char> need(ctx->genomes.size(), 0);
   for (uint64_t i = 0; i < n_pairs; ++i) { need[qry_ids[i]] = 1; need[ref_ids[i]] = 1; }
   for (size_t g = 0; g < need.size(); ++g)
-    if (need[g] && (rc = build_sketch(ctx, ST, (int32_t)g, frag_len, scale, log2_scale))) return rc;
+    if (need[g] && (rc = build_sketch(ctx, ST, (int32_t)g, kmer, frag_len, scale, log2_scale))) return rc;
   // jobs: the pairs by query, up to SK_REFS references per workgroup (fewer when the query's fragment counters would not fit LDS)
   std::vector<uint64_t> idx(n_pairs);
   for (uint64_t i = 0; i < n_pairs; ++i) idx[i] = i;
@@ -254,7 +285,7 @@ extern "C" int pg_sketch_pairs(pg_ctx* ctx, const int32_t* qry_ids, const int32_
     if (per_ref > 96 * 1024) return pg_fail(ctx, PG_E_CAPACITY, "sketch: more than 24 576 fragments in one query genome");
     const uint32_t g_max = (uint32_t)std::min<size_t>(SK_REFS, (96 * 1024) / per_ref);
     SketchJob J{};
-    J.occ_kmer = Q.occ_kmer; J.occ_frag = Q.occ_frag; J.frag_n = Q.frag_n; J.n_occ = Q.n_occ; J.n_frags = Q.n_frags; J.log2_scale = log2_scale;
+    J.occ_kmer = Q.occ_kmer; J.occ_frag = Q.occ_frag; J.frag_n = Q.frag_n; J.n_occ = Q.n_occ; J.n_frags = Q.n_frags; J.log2_scale = log2_scale; J.kmer = kmer;
     J.min_fraction = min_fraction;
     uint32_t g = 0;
     while (a < n_pairs && g < g_max && qry_ids[idx[a]] == qry_ids[idx[a - g]]) {

@@ -3,11 +3,12 @@
 pyani's fastANI support shells out to the third-party `fastANI` program once per ordered pair (fastani.py:139-229:
 generate_fastani_commands / construct_fastani_cmdline, `--fragLen 3000 -k 16 --minFraction 0.2`) and parses the one-line result file
 (fastani.py:231-270: parse_fastani_file -> ComparisonResult(reference, query, ani, matches, fragments)).  Here the estimate is computed
-in-process on the GPU from the packed genomes already resident in HBM (pg_sketch_pairs, pyani_amd/csrc/pg_sketch.hip), with the same
-parameters, the same result tuple, the same result-file line and the same failure for pairs without a result — but by an estimator
+in-process on the GPU from the packed genomes already resident in HBM (pg_sketch_pairs_k, pyani_amd/csrc/pg_sketch.hip), with the same
+parameters (fragLen, kmerSize 8 ... 16, minFraction: fastani_parser.py:100-132), the same result tuple, the same result-file line and the same failure for pairs without a result — but by an estimator
 of its own (FracMinHash containment per query fragment: pyani_amd/csrc/pg_sketch_core.h), NOT by fastANI's MashMap pipeline: the
 numbers are fastANI-SHAPED estimates with their own error bar, kept in their own columns and files and never
-written into the exact ANIm / ANIb matrices.  No CPU fallback: the functions that compute need an Engine."""
+written into the exact ANIm / ANIb matrices.  No CPU fallback: the functions that compute need an Engine.  The driver over a
+directory of FASTA files is pyani_amd/subcmd_fastani.py (run_fastani)."""
 from pathlib import Path
 from typing import Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
@@ -31,15 +32,24 @@ class ComparisonResult(NamedTuple):
 def get_version() -> str:
     """What a Comparison row records as program version: this engine's sketch mode, not a fastANI binary."""
     from . import _lib
-    return f"pyani_amd sketch mode (FracMinHash containment, k = 16) / {_lib.load().pg_version().decode()}"
+    return f"pyani_amd sketch mode (FracMinHash containment, k = 8 ... 16) / {_lib.load().pg_version().decode()}"
+
+
+KMER_MIN, KMER_MAX = 8, 16      # pgs::K_MIN / K_MAX (pyani's --kmer: "kmer size <= 16")
+
+
+def check_kmer(kmerSize: int) -> int:
+    """The k-mer size as an int; PyaniFastANIException outside 8 ... 16 (before any engine is touched)."""
+    if isinstance(kmerSize, bool) or int(kmerSize) != kmerSize or not KMER_MIN <= int(kmerSize) <= KMER_MAX:
+        raise PyaniFastANIException(f"the sketch mode works on k-mers of {KMER_MIN} to {KMER_MAX} bases (fastANI's -k, default 16): got {kmerSize!r}")
+    return int(kmerSize)
 
 
 def calculate_fastani_pairs(engine, qry_ids: Sequence[int], ref_ids: Sequence[int], fragLen: int = 3000, kmerSize: int = 16,
                             minFraction: float = 0.2, scale: int = 16) -> np.ndarray:
     """The estimates of many ordered pairs in one call (one record per pair: ani, matches, fragments, status)."""
-    if kmerSize != 16:
-        raise PyaniFastANIException("the sketch mode works on 16-mers (fastANI's default -k 16) only")
-    return engine.sketch_pairs(qry_ids, ref_ids, frag_len=fragLen, scale=scale, min_fraction=minFraction)
+    kmer = check_kmer(kmerSize)
+    return engine.sketch_pairs(qry_ids, ref_ids, frag_len=fragLen, scale=scale, min_fraction=minFraction, kmer=kmer)
 
 
 def comparison_results(engine, files: Sequence[Path], ids: Sequence[int], fragLen: int = 3000, kmerSize: int = 16,
@@ -47,6 +57,7 @@ def comparison_results(engine, files: Sequence[Path], ids: Sequence[int], fragLe
     """What pyani's loop over generate_fastani_commands + parse_fastani_file yields for an input set: every ordered pair INCLUDING a
     genome against itself (fastani.py:166-184 runs query x reference over the whole file list), keyed (query stem, reference stem);
     None where fastANI would have written an empty file."""
+    check_kmer(kmerSize)
     files = [Path(f) for f in files]
     q = [ids[i] for i in range(len(files)) for _ in files]
     r = [ids[j] for _ in files for j in range(len(files))]
@@ -83,16 +94,18 @@ def parse_fastani_file(filename: Path) -> ComparisonResult:
     return ComparisonResult(line[0], line[1], 0.01 * float(line[2]), int(line[3]), int(line[4]))
 
 
-def comparison_row(result: Optional[ComparisonResult], query: Path, reference: Path, fragLen: int, query_length: int) -> dict:
+def comparison_row(result: Optional[ComparisonResult], query: Path, reference: Path, fragLen: int, query_length: int,
+                   kmerSize: int = 16, minFraction: float = 0.2) -> dict:
     """The Comparison row the reference's driver makes of one result (subcmd_fastani.py:437-474): an empty result file becomes
     (query, ref, 0, 0, 0); aln_length = matches * fragLen, sim_errs = (fragments - matches) * fragLen, cov_query = matches * fragLen /
-    query length, identity = the ANI fraction, cov_subject None."""
+    query length, identity = the ANI fraction, cov_subject None; kmersize and minmatch are the run's --kmer and --minFraction
+    (subcmd_fastani.py:461-476)."""
     if result is None:
         result = ComparisonResult(query, reference, 0, 0, 0)
     q, r, ani, matches, num_frags = result
     return {"query": q, "subject": r, "aln_length": int(matches * fragLen), "sim_errs": int(int(num_frags) * fragLen - matches * fragLen),
             "identity": float(ani), "cov_query": float(matches) * fragLen / query_length, "cov_subject": None, "program": "fastANI",
-            "fragsize": fragLen, "maxmatch": False}
+            "fragsize": fragLen, "maxmatch": False, "kmersize": kmerSize, "minmatch": minFraction}
 
 
 def result_matrices(labels: Sequence[str], results: Dict[Tuple[str, str], Optional[ComparisonResult]]):

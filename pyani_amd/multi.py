@@ -65,8 +65,20 @@ def _static_parts_by_hub(a: np.ndarray, b: np.ndarray, parts: int) -> List[np.nd
     return out
 
 
+def _shares_by_query(qa: np.ndarray, parts: int) -> List[np.ndarray]:
+    """Indices of a sketch call's pair list dealt into `parts` shares (some may be empty): all pairs of one query genome in one
+    share, the queries in id order handed to the share with the fewest pairs so far (ties: the first)."""
+    order = np.argsort(qa, kind="stable")
+    groups = np.split(order, np.flatnonzero(np.diff(qa[order])) + 1)
+    shares, size = [[] for _ in range(parts)], [0] * parts
+    for g in groups:
+        p = size.index(min(size))
+        shares[p].append(g); size[p] += len(g)
+    return [np.concatenate(x) if x else np.zeros(0, dtype=np.int64) for x in shares]
+
+
 class MultiEngine:
-    """Engines on several devices behind the Engine calls the module functions use: genome store (replicated), anim_pairs / anib_pairs /
+    """Engines on several devices behind the Engine calls the module functions use: genome store (replicated), anim_pairs / anib_pairs / sketch_pairs /
     anim_alignments_batch / anib_rows_batch (pairs pulled in chunks by the devices), tetra_counts / tetra_matrix (genomes counted in shards)."""
 
     def __init__(self, devices: Sequence[int], chunk_pairs: int = 0):
@@ -232,6 +244,28 @@ class MultiEngine:
         if cur:
             chunks.append(np.concatenate(cur))
         return chunks
+
+    # -- sketch mode ---------------------------------------------------------------------------------------------------------
+    def sketch_pairs(self, qry_ids, ref_ids, frag_len: int = 3000, scale: int = 16, min_fraction: float = 0.2, kmer: int = 16) -> np.ndarray:
+        """Engine.sketch_pairs over all devices.  The pairs are dealt by QUERY genome into one share per device — the pairs kernel
+        streams a query's occurrence list once per up to four references, so a query's references belong together — ONE call per
+        device; the records come back in the caller's order."""
+        qa = np.ascontiguousarray(list(qry_ids), dtype=np.int32)
+        ra = np.ascontiguousarray(list(ref_ids), dtype=np.int32)
+        if len(qa) != len(ra):
+            raise ValueError("qry_ids and ref_ids must have the same length")
+        out = np.zeros(len(qa), dtype=Engine.SKETCH_DTYPE)
+        if len(qa) == 0:
+            return out
+        shares = _shares_by_query(qa, len(self.engines))
+
+        def run(e):
+            idx = shares[self.engines.index(e)]
+            return e.sketch_pairs(qa[idx], ra[idx], frag_len, scale, min_fraction, kmer) if len(idx) else None
+        for idx, res in zip(shares, self._all(run)):
+            if res is not None:
+                out[idx] = res
+        return out
 
     def anib_rows_batch(self, qry_ids, sbj_ids, fragsize: int = 1020):
         """Engine.anib_rows_batch over all devices: the pair list is cut exactly as for anib_pairs, the devices pull chunks, and
