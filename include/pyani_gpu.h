@@ -119,7 +119,13 @@ int pg_tetra_corr_rows_dev(pg_ctx* ctx, const double* d_z, const uint8_t* d_pres
  * anim.py:396); PG_E_CAPACITY = internal buffers overflowed for this pair.
  * MUMmer itself is third-party and absent from the reference tree: behaviour is reconstructed and calibrated against
  * the MUMmer output files the reference's tests hold (every fixture reproduced exactly).
- * reserved = number of alignments BEFORE the 1-to-1 filter (what nucmer's .delta would hold). */
+ * reserved = number of alignments BEFORE the 1-to-1 filter (what nucmer's .delta would hold).
+ * Limits: a genome in the reference role may have any number of copies of a k-mer and any size below 2^30 - 1 bases (a reference
+ * of 2^30 - 1 or more bases is refused: PG_E_CAPACITY for the call, its positions do not fit the seeding table's 30 bits).  The
+ * seeding stage holds one reference k-mer group (1 of 16384 of the 16-mer space) in a table of at most 16384 slots, half full at
+ * most; a group of n entries is seeded in ceil(n / 8192) passes, each of which streams the group's queries once more.  One pass
+ * serves genomes up to ~130 Mb without a k-mer family of more than ~8000 copies; beyond that results are the same and seeding
+ * takes that many times longer for the groups concerned. */
 typedef struct {
   int64_t ref_aln_len, qry_aln_len, sim_errors, n_alignments;
   double identity;
@@ -251,7 +257,12 @@ int pg_anib_reduce(pg_ctx* ctx, uint32_t n_pairs, const uint64_t* offsets, const
  * Limits: fragsize <= 1020 (pyani's default and maximum in practice; larger values are rejected with PG_E_ARG — the fragment's
  * DP lives in LDS).  Query genomes of any bacterial or fungal size: up to 15 872 fragments (16.1 Mb at 1020 nt) the per-fragment
  * counters sit in LDS, beyond that in HBM (round 5: there used to be a hard limit); only a query of more than ~10^6 fragments
- * (1 Gb) comes back with status = PG_E_CAPACITY (n_frags set, everything else 0), the call going on with the others. */
+ * (1 Gb) comes back with status = PG_E_CAPACITY (n_frags set, everything else 0), the call going on with the others.
+ * Subject genomes: no size or repeat cap from seeding either.  The seeding stage holds one coarse k-mer group of the subject (1 of
+ * 2048 of the 16-mer space) in a table of at most 16384 slots, half full at most; a group of n entries is seeded in ceil(n / 8192)
+ * passes, each of which streams the group's query entries once more: one pass up to ~16 Mb, two up to ~33 Mb, and so on (a
+ * k-mer family of thousands of copies adds passes for its group alone).  The 2^30 - 1 base limit of ANIm's reference role belongs
+ * to ANIm's seeding table and does not apply here. */
 typedef struct {
   int64_t aln_length, sim_errors;
   double pid;

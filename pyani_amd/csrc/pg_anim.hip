@@ -23,12 +23,15 @@
 // scratch is freed by deleting it); pg_anim_run_batch is a sequence of stage functions over one Batch struct, in launch order.
 //
 // Every kernel has a scalar statement in pg_anim_core.h that compiles for the host (tools/anim_debug); the two are kept
-// in lock-step and compared on the GPU by tests/test_anim_gpu.py.  Limits: genomes up to ~14 Mb (a reference k-mer
-// group must fit a 16384-slot LDS table; PG_E_CAPACITY otherwise), chain scores < 2^24.
+// in lock-step and compared on the GPU by tests/test_anim_gpu.py.  Limits: a reference k-mer group of n entries is seeded in
+// ceil(n / 8192) passes through a 16384-slot LDS table (pg_seed_plan.h: one pass for fine groups up to ~130 Mb, for the fragment
+// mode's coarse groups up to ~16 Mb; more beyond, same results); a reference of 2^30 - 1 or more bases is refused by the block
+// kernel's table (30 position bits, PG_E_CAPACITY); chain scores < 2^24.
 #include <tuple>
 #include <unordered_map>
 #include "pg_internal.h"
 #include "pg_devbuf.h"
+#include "pg_seed_plan.h"
 #include "pg_anim_core.h"
 #include "pg_nucmer_core.h"
 #include "pg_nucmer_diag.h"
@@ -554,7 +557,8 @@ struct Batch {
   void set_pairs(uint32_t n) { n_pairs = n; n_units = 2 * n; }   // (frag_limit_pairs and seed_stage shorten the launch)
   int qstep = SEED_STEP;               // query-strand sampling of the seed lists
   bool use_mirror = false, use_blocks = false, trace = false;
-  uint32_t blk_slots = SEED_MAX_SLOTS;
+  uint32_t max_slots = SEED_MAX_SLOTS;   // the largest LDS table either seeding kernel may use (PYANI_SEED_MAX_SLOTS lowers it)
+  uint32_t blk_slots = SEED_MAX_SLOTS;   // the table size a block is planned for (<= max_slots)
   // descriptors
   std::vector<int32_t> ref_list;       // distinct references, in the order of ref_ids
   std::vector<uint32_t> ref_of_pair;
@@ -571,6 +575,7 @@ struct Batch {
   std::vector<SeedSlot> bslots;
   std::vector<int32_t> bpair;
   uint32_t slots = 256, n_srefs = 0, n_blks = 0, slot_shift = 0;
+  uint32_t seed_passes = 1;            // most passes a planned group needs (pg_seed_plan.h); > 1 launches the kernels with the pass loop
   uint32_t slice_stride = 0;           // the slice table is laid out for the whole batch even if only a prefix is seeded again
   // what the stages leave for the next ones
   std::vector<uint32_t> cnt, moff, choff;   // per unit: matches, slice offsets (moff.back() = M), cluster offsets
@@ -710,7 +715,9 @@ static void assign_mirrors(Batch& B, uint32_t limit) {
 // The block kernel's plan for the seeded pairs of [0, limit), and its upload.
 // Slots: per run of seeded pairs with one reference, a pair listed k times goes to the run's k-th slot (a slot's queries are
 // distinct).  Blocks: consecutive slots while their largest groups sum to at most half the table and there are at most
-// SEED_BLOCK_SLOTS of them; per block, its distinct queries (sorted) and the [slot][query] -> pair table.
+// SEED_BLOCK_SLOTS of them; per block, its distinct queries (sorted) and the [slot][query] -> pair table.  The first slot of a
+// block is taken whatever its size: a slot whose largest group exceeds half the largest table is therefore alone in its block,
+// and its groups are seeded in passes (pg_seed_plan.h).
 static int plan_seed_blocks(Batch& B, uint32_t limit) {
   pg_ctx* ctx = B.ctx;
   AnimScratch* A = B.A;
@@ -733,7 +740,7 @@ static int plan_seed_blocks(Batch& B, uint32_t limit) {
   std::vector<SeedQry>& bqry = B.bqry;
   std::vector<int32_t>& bpair = B.bpair;
   blks.clear(); bslots.clear(); bqry.clear(); bpair.clear();
-  uint32_t max_sum = 1;
+  uint32_t max_sum = 1, max_lone = 0, max_shared = 0;   // largest block sum; of the blocks of one slot; of the others
   for (uint32_t s0 = 0; s0 < slot_ref.size();) {
     uint32_t s1 = s0, sum = 0;
     while (s1 < slot_ref.size() && s1 - s0 < (uint32_t)SEED_BLOCK_SLOTS) {
@@ -743,6 +750,8 @@ static int plan_seed_blocks(Batch& B, uint32_t limit) {
       ++s1;
     }
     max_sum = sum > max_sum ? sum : max_sum;
+    if (s1 - s0 == 1) max_lone = sum > max_lone ? sum : max_lone;
+    else max_shared = sum > max_shared ? sum : max_shared;
     std::vector<int32_t> qs;
     for (uint32_t t = s0; t < s1; ++t) {
       const PgGenome& G = ctx->genomes[slot_ref[t]];
@@ -767,9 +776,11 @@ static int plan_seed_blocks(Batch& B, uint32_t limit) {
   }
   if (bpair.size() > (size_t)0x7FFFFFFF) return pg_fail(ctx, PG_E_CAPACITY, "anim seeding: block pair tables too large");
   B.slots = 256;
-  while (B.slots < 2 * max_sum) B.slots <<= 1;
-  if (B.slots > SEED_MAX_SLOTS)
-    return pg_fail(ctx, PG_E_CAPACITY, "anim seeding: a reference k-mer group does not fit the LDS table (genome too large or too repetitive)");
+  while (B.slots < 2 * (uint64_t)max_sum && B.slots < B.max_slots) B.slots <<= 1;
+  // Passes: only a block of one slot may need them (the kernel cuts that slot's group; it cannot cut a table shared by several).
+  if (pg_seed_pass_count(max_shared, B.slots) != 1)
+    return pg_fail(ctx, PG_E_INTERNAL, "anim seeding: a block of several slots does not fit half its table");
+  B.seed_passes = pg_seed_pass_count(max_lone, B.slots);
   B.slot_shift = 0;
   while ((B.slots << B.slot_shift) < (1u << (32 - SEED_GROUP_BITS))) ++B.slot_shift;
   const uint32_t n_blks = B.n_blks = (uint32_t)blks.size();
@@ -796,9 +807,8 @@ static int plan_seed_pairs(Batch& B, uint32_t limit, const std::vector<int32_t>&
   uint32_t max_group = 1;
   for (int32_t g : seed_refs) if (LSv[g].ref_max > max_group) max_group = LSv[g].ref_max;
   B.slots = 256;
-  while (B.slots < 2 * max_group) B.slots <<= 1;
-  if (B.slots > SEED_MAX_SLOTS)
-    return pg_fail(ctx, PG_E_CAPACITY, "anim seeding: a reference k-mer group does not fit the LDS table (genome too large or too repetitive)");
+  while (B.slots < 2 * (uint64_t)max_group && B.slots < B.max_slots) B.slots <<= 1;
+  B.seed_passes = pg_seed_pass_count(max_group, B.slots);   // a larger coarse group is seeded in passes
   PG_HIP(ctx, A->slice_d.reserve((size_t)B.slice_stride * SEED_CGROUPS));
   B.srefs.clear();   // one entry per reference with seeded pairs: [pair_begin, pair_end) spans them (pairs in between that
                      // are not seeded have empty slices)
@@ -854,10 +864,9 @@ static int seed_stage(Batch& B) {
   B.sqry.resize(B.n_pairs);
   B.slice_stride = B.n_pairs;
   if (!A->lds_attr_set) {   // per context = per device (the attribute is a property of the function ON a device)
-    PG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(anim_seed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(SEED_MAX_SLOTS * 8 + SEED_STAGE_BYTES)));
-    PG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(anim_seed_pair_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(SEED_MAX_SLOTS * 8 + SEED_STAGE_BYTES)));
+    for (const void* fn : {reinterpret_cast<const void*>(anim_seed_kernel<false>), reinterpret_cast<const void*>(anim_seed_kernel<true>),
+                           reinterpret_cast<const void*>(anim_seed_pair_kernel<false>), reinterpret_cast<const void*>(anim_seed_pair_kernel<true>)})
+      PG_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SEED_MAX_SLOTS * 8 + SEED_STAGE_BYTES)));
     A->lds_attr_set = true;
   }
   // The append buffer of the seed pass and the hit buffers hold the batch budget for a large call (no overflow re-runs), but no more
@@ -882,16 +891,22 @@ static int seed_stage(Batch& B) {
     uint32_t counts[2] = {0, 0};   // matches appended, hits recorded
     int rc;
     if ((rc = plan_seeding(B, n_pairs))) return rc;   // (again after a split: a pair whose partner left the launch is seeded itself)
+    if (pg_dev_env("PYANI_SEED_PLAN_LOG"))   // (development: what the plan came to, one line per seeding launch; tests read it)
+      fprintf(stderr, "[seed-plan] kernel=%s slots=%u passes=%u launches=%u\n", B.use_blocks ? "block" : "per_pair", B.slots, B.seed_passes,
+              B.use_blocks ? B.n_blks : B.n_srefs);
     PG_HIP(ctx, hipMemsetAsync(A->mem_count, 0, n_units * 4, cur_stream(ctx)));
     PG_HIP(ctx, hipMemsetAsync(A->seed_total, 0, 8, cur_stream(ctx)));   // [0] matches, [1] hits
     PG_HIP(ctx, hipMemsetAsync(A->hit_count, 0, n_units * 4, cur_stream(ctx)));
     pg_prof_begin(ctx, PG_K_ANIM_SEED);
+    // (the kernels with the pass loop only when the plan needs a second pass somewhere: the hot path keeps its code)
     if (B.use_blocks && B.n_blks)
-      hipLaunchKernelGGL(anim_seed_kernel, dim3(B.n_blks, SEED_GROUPS), dim3(SEED_BLOCK), (size_t)B.slots * 8 + SEED_STAGE_BYTES, cur_stream(ctx),
+      hipLaunchKernelGGL(B.seed_passes > 1 ? anim_seed_kernel<true> : anim_seed_kernel<false>, dim3(B.n_blks, SEED_GROUPS), dim3(SEED_BLOCK),
+                         (size_t)B.slots * 8 + SEED_STAGE_BYTES, cur_stream(ctx),
                          A->sblk_d, A->sslot_d, A->sbq_d, A->spt_d, B.slots - 1, B.slot_shift, A->hits_d, hit_cap,
                          A->seed_total + 1, A->hit_count, qstep);
     else if (!B.use_blocks && B.n_srefs)
-      hipLaunchKernelGGL(anim_seed_pair_kernel, dim3(B.n_srefs, SEED_CGROUPS), dim3(SEED_BLOCK), (size_t)B.slots * 8 + SEED_STAGE_BYTES, cur_stream(ctx),
+      hipLaunchKernelGGL(B.seed_passes > 1 ? anim_seed_pair_kernel<true> : anim_seed_pair_kernel<false>, dim3(B.n_srefs, SEED_CGROUPS), dim3(SEED_BLOCK),
+                         (size_t)B.slots * 8 + SEED_STAGE_BYTES, cur_stream(ctx),
                          A->srefs_d, A->sqry_d, A->slice_d, B.slice_stride, B.slots - 1, A->hits_d, hit_cap, A->seed_total + 1,
                          A->hit_count, qstep);
     pg_prof_end(ctx);
@@ -1259,12 +1274,20 @@ int pg_anim_run_batch(pg_ctx* ctx, const int32_t* ref_ids, const int32_t* qry_id
   B.use_mirror = !frag && !pg_dev_env("PYANI_ANIM_NO_MIRROR");
   // Seeding kernel: ANIm uses the block kernel (anim_seed_kernel); fragment mode — and ANIm under the development switch
   // PYANI_SEED_PER_PAIR=1, which tests hold against it — the per-pair kernel (anim_seed_pair_kernel).  PYANI_SEED_BLOCK_SLOTS
-  // (development): the table size a block is planned for (default SEED_MAX_SLOTS).
+  // (development): the table size a block is planned for (default SEED_MAX_SLOTS).  PYANI_SEED_MAX_SLOTS (development): the
+  // largest table either kernel may use, a power of two from 256 to SEED_MAX_SLOTS (anything else is ignored); blocks are planned
+  // for the smaller of the two.  It lets tests force passes (pg_seed_plan.h) on genomes of a few hundred kb.  PYANI_SEED_PLAN_LOG
+  // (development): seed_stage prints the planned kernel, table size and pass count of every seeding launch to stderr.
   B.use_blocks = !frag && !(pg_dev_env("PYANI_SEED_PER_PAIR") && atoi(pg_dev_env("PYANI_SEED_PER_PAIR")) == 1);
   if (pg_dev_env("PYANI_SEED_BLOCK_SLOTS")) {
     const int want = atoi(pg_dev_env("PYANI_SEED_BLOCK_SLOTS"));
     B.blk_slots = want >= 512 && want <= (int)SEED_MAX_SLOTS ? (uint32_t)want : SEED_MAX_SLOTS;
   }
+  if (pg_dev_env("PYANI_SEED_MAX_SLOTS")) {
+    const int want = atoi(pg_dev_env("PYANI_SEED_MAX_SLOTS"));
+    if (want >= 256 && want <= (int)SEED_MAX_SLOTS && (want & (want - 1)) == 0) B.max_slots = (uint32_t)want;
+  }
+  if (B.blk_slots > B.max_slots) B.blk_slots = B.max_slots;
   B.trace = tls_sink && tls_sink->with_indels;
   if ((rc = build_descriptors(B))) return rc;
   if ((rc = seed_stage(B))) return rc;

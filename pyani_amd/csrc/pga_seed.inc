@@ -270,6 +270,12 @@ __device__ __forceinline__ void seed_stage_flush(Match* stage, uint32_t* stage_n
 // bandwidth- rather than latency-bound.  Matches are appended to one batch-wide buffer (the `strand` field carries the
 // unit index until the scatter); unit_count[] is exact even when the buffer overflows, which is what the host uses to
 // size the slices (and to re-run a prefix).
+//
+// PASSES (anim_seed_pair_kernel<true>, launched only when a planned coarse group holds more than half a table): the entries
+// [goff[8 c], goff[8 (c + 1)]) are cut into passes (pg_seed_plan.h); per pass the table is cleared, filled with the pass's
+// entries and probed by the whole query stream.  Only the table repeats: staging carries over, with one final flush.  The
+// single-pass kernel is the instantiation without the loop and compiles to what it was before passes existed.
+template <bool PASSES>
 __global__ __launch_bounds__(SEED_BLOCK) void anim_seed_pair_kernel(const SeedRef* __restrict__ srefs, const SeedQry* __restrict__ sqry,
                                                                     const SeedSlice* __restrict__ slice, uint32_t n_pairs,
                                                                     uint32_t slot_mask, Match* __restrict__ buf, uint32_t cap,
@@ -288,105 +294,125 @@ __global__ __launch_bounds__(SEED_BLOCK) void anim_seed_pair_kernel(const SeedRe
   for (uint32_t i = tid; i <= slot_mask; i += SEED_BLOCK) tab[i] = SLOT_EMPTY;
   if (tid < SEED_BLOCK / 64) stage_n[tid] = 0;
   __syncthreads();
-  for (uint32_t e = SR.goff[SEED_SUB * g] + tid; e < SR.goff[SEED_SUB * (g + 1)]; e += SEED_BLOCK) {
-    const unsigned long long v = SR.list[e];
+  uint32_t pass = 0, n_pass = 1, grp_begin = 0, grp_n = 0;   // (PASSES only)
+  if constexpr (PASSES) {
+    grp_begin = SR.goff[SEED_SUB * g];
+    grp_n = SR.goff[SEED_SUB * (g + 1)] - grp_begin;
+    n_pass = pg_seed_pass_count(grp_n, slot_mask + 1);   // uniform per workgroup
+  }
+  auto insert = [&](unsigned long long v) {
     uint32_t slot = (uint32_t)(v >> (SEED_KEY_SHIFT + 5)) & slot_mask;   // hash bits 5.. (slot_mask <= 2^14 - 1)
-    while (atomicCAS(&tab[slot], SLOT_EMPTY, v) != SLOT_EMPTY) slot = (slot + 1) & slot_mask;
-  }
-  __syncthreads();
-  // this wave's share of the reference's pairs: a contiguous range, its descriptors fetched 64 at a time
-  const uint32_t n_mine_all = SR.pair_end - SR.pair_begin;
-  const uint32_t per_wave = (n_mine_all + SEED_BLOCK / 64 - 1) / (SEED_BLOCK / 64);
-  const uint32_t my_begin = SR.pair_begin + wave * per_wave;
-  const uint32_t my_end = my_begin + per_wave < SR.pair_end ? my_begin + per_wave : SR.pair_end;
-  const SeedSlice* __restrict__ row = slice + (size_t)g * n_pairs;
-  for (uint32_t chunk = my_begin; chunk < my_end; chunk += 64) {
-    SeedSlice mine{0, 0, 0};
-    const uint64_t* mylist = nullptr;
-    if (chunk + lane < my_end) { mine = row[chunk + lane]; mylist = sqry[chunk + lane].list; }
-    const uint32_t in_chunk = my_end - chunk < 64 ? my_end - chunk : 64;
-    // The chunk's work as a sequence of row blocks (<= SEED_UNROLL rows of 64 entries of one (pair, strand) slice),
-    // software-pipelined: the loads of block k+1 are in flight while block k is looked up.
-    struct Blk { uint32_t j, strand, e0, e_end; const uint64_t* list; bool valid; };
-    auto slice_of = [&](uint32_t j, uint32_t strand, Blk& o) {
-      const uint32_t begin = (uint32_t)__builtin_amdgcn_readlane((int)mine.begin, j);
-      const uint32_t n0 = (uint32_t)__builtin_amdgcn_readlane((int)mine.n0, j), n1 = (uint32_t)__builtin_amdgcn_readlane((int)mine.n1, j);
-      o.j = j; o.strand = strand;
-      o.e0 = strand ? begin + n0 : begin;
-      o.e_end = o.e0 + (strand ? n1 : n0);
-      o.list = reinterpret_cast<const uint64_t*>(
-          ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)((unsigned long long)mylist >> 32), j) << 32) |
-          (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(unsigned long long)mylist, j));
-    };
-    auto first_from = [&](uint32_t j, uint32_t strand) {   // first non-empty slice at or after (j, strand)
-      Blk o{0, 0, 0, 0, nullptr, false};
-      for (; j < in_chunk; ++j, strand = 0)
-        for (; strand < 2; ++strand) {
-          slice_of(j, strand, o);
-          if (o.e0 < o.e_end) { o.valid = true; return o; }
-        }
-      return o;
-    };
-    auto next_of = [&](const Blk& c) {
-      if (c.e0 + 64 * SEED_UNROLL < c.e_end) { Blk o = c; o.e0 += 64 * SEED_UNROLL; return o; }
-      return c.strand == 0 ? first_from(c.j, 1) : first_from(c.j + 1, 0);
-    };
-    auto load = [&](const Blk& c, unsigned long long (&qv)[SEED_UNROLL]) {
-#pragma unroll
-      for (int t = 0; t < SEED_UNROLL; ++t) {
-        const uint32_t e = c.e0 + 64 * t + lane;
-        qv[t] = e < c.e_end ? __builtin_nontemporal_load(&c.list[e]) : SLOT_EMPTY;
-      }
-    };
-    auto process = [&](const Blk& c, const unsigned long long (&qv)[SEED_UNROLL]) {
-      const uint32_t unit = 2 * (chunk + c.j) + c.strand;
-#pragma unroll
-      for (int t = 0; t < SEED_UNROLL; ++t) {
-        if (qv[t] == SLOT_EMPTY) continue;
-        const uint32_t key = (uint32_t)(qv[t] >> SEED_KEY_SHIFT);
-        const uint32_t qctx = (uint32_t)(qv[t] >> 32) & 0x7FFu;   // bit 0: flag, bits 1..10: left bases
-        const int32_t q = (int32_t)(uint32_t)qv[t];
-        uint32_t slot_b = ((key >> 5) & slot_mask) << 3;   // byte offset of the slot (the probe steps in bytes: add + and per step)
-        const uint32_t byte_mask = (slot_mask << 3) | 7u;
-        const char* const tab_b = reinterpret_cast<const char*>(tab);
-        // one exit condition and no break / continue inside: the compiler turns anything else into a state machine of
-        // exec-mask bookkeeping, and the per-CU scalar unit is a bottleneck of this kernel
-        // 32-bit tests only (64-bit integer compares are slower): an entry's low word is a position, never all ones, so the
-        // low word alone says "empty"; the key sits in the top 21 bits of the high word
-        const uint32_t qhi = (uint32_t)(qv[t] >> 32);
-        unsigned long long v = *reinterpret_cast<const unsigned long long*>(tab_b + slot_b);
-        while ((uint32_t)v != 0xFFFFFFFFu) {   // load factor <= 1/2: every probe sequence ends
-          if ((((uint32_t)(v >> 32) ^ qhi) >> (SEED_KEY_SHIFT - 32)) == 0u) {
-            int32_t left = -1;
-            bool report = true;
-            const uint32_t rctx = (uint32_t)(v >> 32) & 0x7FFu;
-            if (rctx & qctx & 1u) {
-              const uint32_t x = (rctx ^ qctx) >> 1;
-              const uint32_t diff = (x | (x >> 1)) & 0x155u;
-              left = diff ? (__ffs(diff) - 1) >> 1 : SEED_STEP;
-              report = left < step;   // inside a longer match: an earlier sampled position (every step-th) reports it
-            }
-            if (report) seed_stage_hit(stage, stage_n, wave, Match{(int32_t)(uint32_t)v, q, left, (int32_t)unit}, buf, cap, total, hit_count);
-          }
-          slot_b = (slot_b + 8u) & byte_mask;
-          v = *reinterpret_cast<const unsigned long long*>(tab_b + slot_b);
-        }
-      }
-      seed_stage_flush(stage, stage_n, wave, lane, false, buf, cap, total, hit_count);
-    };
-    unsigned long long qa[SEED_UNROLL], qb[SEED_UNROLL];
-    Blk A = first_from(0, 0);
-    if (A.valid) load(A, qa);
-    while (A.valid) {
-      Blk B = next_of(A);
-      if (B.valid) load(B, qb);
-      process(A, qa);
-      if (!B.valid) break;
-      A = next_of(B);
-      if (A.valid) load(A, qa);
-      process(B, qb);
+    while (atomicCAS(&tab[slot], SLOT_EMPTY, v) != SLOT_EMPTY) slot = (slot + 1) & slot_mask;   // <= half full per pass: ends
+  };
+  do {   // (single-pass instantiation: one trip, no loop)
+    if constexpr (PASSES) {
+      const PgSeedPass R = pg_seed_pass_range(grp_n, slot_mask + 1, pass);
+      for (uint32_t e = grp_begin + R.begin + tid; e < grp_begin + R.end; e += SEED_BLOCK) insert(SR.list[e]);
+    } else {
+      for (uint32_t e = SR.goff[SEED_SUB * g] + tid; e < SR.goff[SEED_SUB * (g + 1)]; e += SEED_BLOCK) insert(SR.list[e]);
     }
-  }
+    __syncthreads();
+    // this wave's share of the reference's pairs: a contiguous range, its descriptors fetched 64 at a time
+    const uint32_t n_mine_all = SR.pair_end - SR.pair_begin;
+    const uint32_t per_wave = (n_mine_all + SEED_BLOCK / 64 - 1) / (SEED_BLOCK / 64);
+    const uint32_t my_begin = SR.pair_begin + wave * per_wave;
+    const uint32_t my_end = my_begin + per_wave < SR.pair_end ? my_begin + per_wave : SR.pair_end;
+    const SeedSlice* __restrict__ row = slice + (size_t)g * n_pairs;
+    for (uint32_t chunk = my_begin; chunk < my_end; chunk += 64) {
+      SeedSlice mine{0, 0, 0};
+      const uint64_t* mylist = nullptr;
+      if (chunk + lane < my_end) { mine = row[chunk + lane]; mylist = sqry[chunk + lane].list; }
+      const uint32_t in_chunk = my_end - chunk < 64 ? my_end - chunk : 64;
+      // The chunk's work as a sequence of row blocks (<= SEED_UNROLL rows of 64 entries of one (pair, strand) slice),
+      // software-pipelined: the loads of block k+1 are in flight while block k is looked up.
+      struct Blk { uint32_t j, strand, e0, e_end; const uint64_t* list; bool valid; };
+      auto slice_of = [&](uint32_t j, uint32_t strand, Blk& o) {
+        const uint32_t begin = (uint32_t)__builtin_amdgcn_readlane((int)mine.begin, j);
+        const uint32_t n0 = (uint32_t)__builtin_amdgcn_readlane((int)mine.n0, j), n1 = (uint32_t)__builtin_amdgcn_readlane((int)mine.n1, j);
+        o.j = j; o.strand = strand;
+        o.e0 = strand ? begin + n0 : begin;
+        o.e_end = o.e0 + (strand ? n1 : n0);
+        o.list = reinterpret_cast<const uint64_t*>(
+            ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)((unsigned long long)mylist >> 32), j) << 32) |
+            (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(unsigned long long)mylist, j));
+      };
+      auto first_from = [&](uint32_t j, uint32_t strand) {   // first non-empty slice at or after (j, strand)
+        Blk o{0, 0, 0, 0, nullptr, false};
+        for (; j < in_chunk; ++j, strand = 0)
+          for (; strand < 2; ++strand) {
+            slice_of(j, strand, o);
+            if (o.e0 < o.e_end) { o.valid = true; return o; }
+          }
+        return o;
+      };
+      auto next_of = [&](const Blk& c) {
+        if (c.e0 + 64 * SEED_UNROLL < c.e_end) { Blk o = c; o.e0 += 64 * SEED_UNROLL; return o; }
+        return c.strand == 0 ? first_from(c.j, 1) : first_from(c.j + 1, 0);
+      };
+      auto load = [&](const Blk& c, unsigned long long (&qv)[SEED_UNROLL]) {
+#pragma unroll
+        for (int t = 0; t < SEED_UNROLL; ++t) {
+          const uint32_t e = c.e0 + 64 * t + lane;
+          qv[t] = e < c.e_end ? __builtin_nontemporal_load(&c.list[e]) : SLOT_EMPTY;
+        }
+      };
+      auto process = [&](const Blk& c, const unsigned long long (&qv)[SEED_UNROLL]) {
+        const uint32_t unit = 2 * (chunk + c.j) + c.strand;
+#pragma unroll
+        for (int t = 0; t < SEED_UNROLL; ++t) {
+          if (qv[t] == SLOT_EMPTY) continue;
+          const uint32_t key = (uint32_t)(qv[t] >> SEED_KEY_SHIFT);
+          const uint32_t qctx = (uint32_t)(qv[t] >> 32) & 0x7FFu;   // bit 0: flag, bits 1..10: left bases
+          const int32_t q = (int32_t)(uint32_t)qv[t];
+          uint32_t slot_b = ((key >> 5) & slot_mask) << 3;   // byte offset of the slot (the probe steps in bytes: add + and per step)
+          const uint32_t byte_mask = (slot_mask << 3) | 7u;
+          const char* const tab_b = reinterpret_cast<const char*>(tab);
+          // one exit condition and no break / continue inside: the compiler turns anything else into a state machine of
+          // exec-mask bookkeeping, and the per-CU scalar unit is a bottleneck of this kernel
+          // 32-bit tests only (64-bit integer compares are slower): an entry's low word is a position, never all ones, so the
+          // low word alone says "empty"; the key sits in the top 21 bits of the high word
+          const uint32_t qhi = (uint32_t)(qv[t] >> 32);
+          unsigned long long v = *reinterpret_cast<const unsigned long long*>(tab_b + slot_b);
+          while ((uint32_t)v != 0xFFFFFFFFu) {   // load factor <= 1/2: every probe sequence ends
+            if ((((uint32_t)(v >> 32) ^ qhi) >> (SEED_KEY_SHIFT - 32)) == 0u) {
+              int32_t left = -1;
+              bool report = true;
+              const uint32_t rctx = (uint32_t)(v >> 32) & 0x7FFu;
+              if (rctx & qctx & 1u) {
+                const uint32_t x = (rctx ^ qctx) >> 1;
+                const uint32_t diff = (x | (x >> 1)) & 0x155u;
+                left = diff ? (__ffs(diff) - 1) >> 1 : SEED_STEP;
+                report = left < step;   // inside a longer match: an earlier sampled position (every step-th) reports it
+              }
+              if (report) seed_stage_hit(stage, stage_n, wave, Match{(int32_t)(uint32_t)v, q, left, (int32_t)unit}, buf, cap, total, hit_count);
+            }
+            slot_b = (slot_b + 8u) & byte_mask;
+            v = *reinterpret_cast<const unsigned long long*>(tab_b + slot_b);
+          }
+        }
+        seed_stage_flush(stage, stage_n, wave, lane, false, buf, cap, total, hit_count);
+      };
+      unsigned long long qa[SEED_UNROLL], qb[SEED_UNROLL];
+      Blk A = first_from(0, 0);
+      if (A.valid) load(A, qa);
+      while (A.valid) {
+        Blk B = next_of(A);
+        if (B.valid) load(B, qb);
+        process(A, qa);
+        if (!B.valid) break;
+        A = next_of(B);
+        if (A.valid) load(A, qa);
+        process(B, qb);
+      }
+    }
+    if constexpr (PASSES) {
+      if (++pass < n_pass) {   // the next pass's table: every wave is done with this one first
+        __syncthreads();
+        for (uint32_t i = tid; i <= slot_mask; i += SEED_BLOCK) tab[i] = SLOT_EMPTY;
+        __syncthreads();
+      }
+    }
+  } while (PASSES && pass < n_pass);
   seed_stage_flush(stage, stage_n, wave, lane, true, buf, cap, total, hit_count);   // what is still staged (uniform point)
 }
 
@@ -422,6 +448,13 @@ struct SeedBlk {
 };
 // Slot of a 18-bit key in a table of slot_mask + 1 = 2^(18 - slot_shift) slots: the key's top bits (hash bits slot_shift ..
 // 17, the best mixed of a multiplicative hash below the group bits).
+//
+// PASSES (anim_seed_kernel<true>, launched only when a planned block needs them): a slot whose group holds more than half a
+// table is alone in its block (the planning rule above takes the first slot whatever its size and no second one beside it),
+// so passes apply to blocks of ONE slot: its group's entries are cut into passes (pg_seed_plan.h), filled by the whole
+// workgroup, and every pass is probed by the block's whole query stream.  Blocks of several slots take one pass, as in the
+// single-pass kernel.  Only the table repeats; staging carries over, with one final flush.
+template <bool PASSES>
 __global__ __launch_bounds__(SEED_BLOCK) void anim_seed_kernel(const SeedBlk* __restrict__ blks, const SeedSlot* __restrict__ slots,
                                                                const SeedQry* __restrict__ bqry, const int32_t* __restrict__ pair_of,
                                                                uint32_t slot_mask, uint32_t slot_shift, Match* __restrict__ buf,
@@ -438,139 +471,165 @@ __global__ __launch_bounds__(SEED_BLOCK) void anim_seed_kernel(const SeedBlk* __
   for (uint32_t i = tid; i <= slot_mask; i += SEED_BLOCK) tab[i] = SLOT_EMPTY;
   if (tid < SEED_BLOCK / 64) stage_n[tid] = 0;
   __syncthreads();
-  for (uint32_t k = wave; k < B.slot_end - B.slot_begin; k += SEED_BLOCK / 64) {   // one slot per wave at a time
-    const SeedSlot S = slots[B.slot_begin + k];
-    const uint32_t e_end = S.goff[g + 1];
-    for (uint32_t e = S.goff[g] + lane; e < e_end; e += 64) {
-      const unsigned long long v = S.list[e];
-      const unsigned long long t = (((v >> SEED_KEY_SHIFT) & SEED_KEY_MASK) << SEED_TAB_KEY_SHIFT) | (((v >> 32) & 0x7FFull) << SEED_TAB_CTX_SHIFT) |
-                                   ((unsigned long long)k << SEED_TAB_SLOT_SHIFT) | (uint32_t)v;
-      uint32_t slot = (uint32_t)(t >> (SEED_TAB_KEY_SHIFT + slot_shift)) & slot_mask;
-      while (atomicCAS(&tab[slot], SLOT_EMPTY, t) != SLOT_EMPTY) slot = (slot + 1) & slot_mask;
+  auto insert = [&](unsigned long long v, uint32_t k) {   // list entry v of slot k -> table entry
+    const unsigned long long t = (((v >> SEED_KEY_SHIFT) & SEED_KEY_MASK) << SEED_TAB_KEY_SHIFT) | (((v >> 32) & 0x7FFull) << SEED_TAB_CTX_SHIFT) |
+                                 ((unsigned long long)k << SEED_TAB_SLOT_SHIFT) | (uint32_t)v;
+    uint32_t slot = (uint32_t)(t >> (SEED_TAB_KEY_SHIFT + slot_shift)) & slot_mask;
+    while (atomicCAS(&tab[slot], SLOT_EMPTY, t) != SLOT_EMPTY) slot = (slot + 1) & slot_mask;   // <= half full per pass: ends
+  };
+  const bool lone = PASSES && B.slot_end - B.slot_begin == 1;   // a block of one slot: the only kind that may need passes
+  uint32_t pass = 0, n_pass = 1, grp_begin = 0, grp_n = 0;      // (PASSES only; uniform per workgroup)
+  const uint64_t* grp_list = nullptr;
+  if constexpr (PASSES) {
+    if (lone) {
+      const SeedSlot S = slots[B.slot_begin];
+      grp_list = S.list;
+      grp_begin = S.goff[g];
+      grp_n = S.goff[g + 1] - grp_begin;
+      n_pass = pg_seed_pass_count(grp_n, slot_mask + 1);
     }
   }
-  __syncthreads();
-  // This wave's share of the block's queries: a contiguous range, in chunks of 32 queries = 64 slices (lane i: query i / 2,
-  // strand i & 1), their group-g offsets read straight from the queries' offset tables (strand s: sub-list seed_sub(g, 1, s)).
-  // A chunk's non-empty slices are packed back to back into full rows of 64 entries (a slice holds ~60 entries per strand of a
-  // 5 Mb query: one row per slice would leave a third of the lanes idle and put one memory round trip behind every row).
-  const uint32_t n_qry = B.qry_end - B.qry_begin;
-  const int32_t* __restrict__ ptab = pair_of + B.pair_tab;
-  const uint32_t per_wave = (n_qry + SEED_BLOCK / 64 - 1) / (SEED_BLOCK / 64);
-  const uint32_t my_begin = wave * per_wave;
-  const uint32_t my_end = my_begin + per_wave < n_qry ? my_begin + per_wave : n_qry;
-  const uint32_t sub0 = seed_sub(g, 1, 0), sub1 = seed_sub(g, 1, 1);
-  for (uint32_t chunk = my_begin; chunk < my_end; chunk += 32) {
-    uint32_t n = 0;
-    unsigned long long base = 0;   // address of the slice's entry 0
-    if (chunk + (lane >> 1) < my_end) {
-      const SeedQry Q = bqry[B.qry_begin + chunk + (lane >> 1)];
-      const uint32_t sub = (lane & 1u) ? sub1 : sub0;
-      const uint32_t b = Q.goff[sub];
-      n = Q.goff[sub + 1] - b;
-      base = (unsigned long long)(Q.list + b);
-    }
-    // compaction: lane r takes the r-th non-empty slice (src = its lane above: the slice id)
-    const uint64_t ne = __ballot(n != 0);
-    const uint32_t n_ne = (uint32_t)__popcll(ne);
-    uint32_t src = 0;
-    {
-      uint64_t m = ne;   // select the (lane + 1)-th set bit: binary search on prefix popcounts
-      uint32_t lo = 0;
-#pragma unroll
-      for (uint32_t w = 32; w > 0; w >>= 1) {
-        const uint64_t low = w == 64 ? m : (m & ((1ull << w) - 1ull));
-        const uint32_t c = (uint32_t)__popcll(low);
-        if (lane >= lo + c) { lo += c; m >>= w; src += w; } else { m = low; }
+  do {   // (single-pass instantiation: one trip, no loop)
+    if (lone) {
+      const PgSeedPass R = pg_seed_pass_range(grp_n, slot_mask + 1, pass);
+      for (uint32_t e = grp_begin + R.begin + tid; e < grp_begin + R.end; e += SEED_BLOCK) insert(grp_list[e], 0u);
+    } else {
+      for (uint32_t k = wave; k < B.slot_end - B.slot_begin; k += SEED_BLOCK / 64) {   // one slot per wave at a time
+        const SeedSlot S = slots[B.slot_begin + k];
+        const uint32_t e_end = S.goff[g + 1];
+        for (uint32_t e = S.goff[g] + lane; e < e_end; e += 64) insert(S.list[e], k);
       }
     }
-    const uint32_t pulled = (uint32_t)__shfl(n, (int)src, 64);   // (all lanes: a bpermute reads 0 from an inactive lane)
-    const uint32_t cn = lane < n_ne ? pulled : 0u;
-    const unsigned long long cbase = ((unsigned long long)(uint32_t)__shfl((int)(uint32_t)(base >> 32), (int)src, 64) << 32) |
-                                     (uint32_t)__shfl((int)(uint32_t)base, (int)src, 64);
-    uint32_t c = cn;   // exclusive prefix of the packed slice lengths: where slice `lane` starts in the chunk's stream
+    __syncthreads();
+    // This wave's share of the block's queries: a contiguous range, in chunks of 32 queries = 64 slices (lane i: query i / 2,
+    // strand i & 1), their group-g offsets read straight from the queries' offset tables (strand s: sub-list seed_sub(g, 1, s)).
+    // A chunk's non-empty slices are packed back to back into full rows of 64 entries (a slice holds ~60 entries per strand of a
+    // 5 Mb query: one row per slice would leave a third of the lanes idle and put one memory round trip behind every row).
+    const uint32_t n_qry = B.qry_end - B.qry_begin;
+    const int32_t* __restrict__ ptab = pair_of + B.pair_tab;
+    const uint32_t per_wave = (n_qry + SEED_BLOCK / 64 - 1) / (SEED_BLOCK / 64);
+    const uint32_t my_begin = wave * per_wave;
+    const uint32_t my_end = my_begin + per_wave < n_qry ? my_begin + per_wave : n_qry;
+    const uint32_t sub0 = seed_sub(g, 1, 0), sub1 = seed_sub(g, 1, 1);
+    for (uint32_t chunk = my_begin; chunk < my_end; chunk += 32) {
+      uint32_t n = 0;
+      unsigned long long base = 0;   // address of the slice's entry 0
+      if (chunk + (lane >> 1) < my_end) {
+        const SeedQry Q = bqry[B.qry_begin + chunk + (lane >> 1)];
+        const uint32_t sub = (lane & 1u) ? sub1 : sub0;
+        const uint32_t b = Q.goff[sub];
+        n = Q.goff[sub + 1] - b;
+        base = (unsigned long long)(Q.list + b);
+      }
+      // compaction: lane r takes the r-th non-empty slice (src = its lane above: the slice id)
+      const uint64_t ne = __ballot(n != 0);
+      const uint32_t n_ne = (uint32_t)__popcll(ne);
+      uint32_t src = 0;
+      {
+        uint64_t m = ne;   // select the (lane + 1)-th set bit: binary search on prefix popcounts
+        uint32_t lo = 0;
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(c, o, 64); if ((int)lane >= o) c += t; }
-    const uint32_t T = (uint32_t)__shfl((int)c, 63, 64);
-    c -= cn;
-    const unsigned long long cstart = cbase - (unsigned long long)c * 8ull;   // entry e of the stream (in slice `lane`) at cstart + 8 e
-    // row at E: lane l holds stream entry E + l, of the slice j = (slices starting at or before it) - 1
-    auto load = [&](uint32_t E, unsigned long long (&qv)[SEED_UNROLL], uint32_t (&sid)[SEED_UNROLL]) {
-#pragma unroll
-      for (int t = 0; t < SEED_UNROLL; ++t) {
-        const uint32_t R = E + 64u * (uint32_t)t;
-        qv[t] = SLOT_EMPTY;
-        sid[t] = 0;
-        if (R < T) {
-          const uint32_t before = (uint32_t)__popcll(__ballot(lane < n_ne && c < R));
-          uint64_t in_row = __ballot(lane < n_ne && c >= R && c < R + 64u), S = 0;
-          while (in_row) {   // (one or two slices start inside a row)
-            const int i = __ffsll((unsigned long long)in_row) - 1;
-            S |= 1ull << ((uint32_t)__builtin_amdgcn_readlane((int)c, i) - R);
-            in_row &= in_row - 1ull;
-          }
-          const uint32_t at = before + __builtin_amdgcn_mbcnt_hi((uint32_t)(S >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)S, 0u)) +
-                              (uint32_t)((S >> lane) & 1ull);
-          const int j = (int)at - 1;
-          const unsigned long long st = ((unsigned long long)(uint32_t)__shfl((int)(uint32_t)(cstart >> 32), j, 64) << 32) |
-                                        (uint32_t)__shfl((int)(uint32_t)cstart, j, 64);
-          sid[t] = (uint32_t)__shfl((int)src, j, 64);
-          if (R + lane < T) qv[t] = __builtin_nontemporal_load(reinterpret_cast<const uint64_t*>(st + 8ull * (R + lane)));
+        for (uint32_t w = 32; w > 0; w >>= 1) {
+          const uint64_t low = w == 64 ? m : (m & ((1ull << w) - 1ull));
+          const uint32_t c = (uint32_t)__popcll(low);
+          if (lane >= lo + c) { lo += c; m >>= w; src += w; } else { m = low; }
         }
       }
-    };
-    auto process = [&](const unsigned long long (&qv)[SEED_UNROLL], const uint32_t (&sid)[SEED_UNROLL]) {
+      const uint32_t pulled = (uint32_t)__shfl(n, (int)src, 64);   // (all lanes: a bpermute reads 0 from an inactive lane)
+      const uint32_t cn = lane < n_ne ? pulled : 0u;
+      const unsigned long long cbase = ((unsigned long long)(uint32_t)__shfl((int)(uint32_t)(base >> 32), (int)src, 64) << 32) |
+                                       (uint32_t)__shfl((int)(uint32_t)base, (int)src, 64);
+      uint32_t c = cn;   // exclusive prefix of the packed slice lengths: where slice `lane` starts in the chunk's stream
 #pragma unroll
-      for (int t = 0; t < SEED_UNROLL; ++t) {
-        if (qv[t] == SLOT_EMPTY) continue;
-        const uint32_t qhi = (uint32_t)(qv[t] >> 32);
-        const uint32_t qkey = (qhi >> (SEED_KEY_SHIFT - 32)) & SEED_KEY_MASK;
-        const uint32_t qctx = qhi & 0x7FFu;   // bit 0: flag, bits 1..10: left bases
-        const int32_t q = (int32_t)(uint32_t)qv[t];
-        const uint32_t qcode = ((chunk + (sid[t] >> 1)) << 6) | (sid[t] & 1u);   // query in block, strand (the slot is or'ed in)
-        uint32_t slot_b = ((qkey >> slot_shift) & slot_mask) << 3;   // byte offset of the slot
-        const uint32_t byte_mask = (slot_mask << 3) | 7u;
-        const char* const tab_b = reinterpret_cast<const char*>(tab);
-        // (single exit, 32-bit tests only: see the per-pair kernel)
-        unsigned long long v = *reinterpret_cast<const unsigned long long*>(tab_b + slot_b);
-        while ((uint32_t)v != 0xFFFFFFFFu) {   // load factor <= 1/2: every probe sequence ends
-          const uint32_t vhi = (uint32_t)(v >> 32);
-          if ((vhi >> (SEED_TAB_KEY_SHIFT - 32)) == qkey) {
-            int32_t left = -1;
-            bool report = true;
-            const uint32_t rctx = (vhi >> (SEED_TAB_CTX_SHIFT - 32)) & 0x7FFu;
-            if (rctx & qctx & 1u) {
-              const uint32_t x = (rctx ^ qctx) >> 1;
-              const uint32_t diff = (x | (x >> 1)) & 0x155u;
-              left = diff ? (__ffs(diff) - 1) >> 1 : SEED_STEP;
-              report = left < step;   // inside a longer match: an earlier sampled position (every step-th) reports it
+      for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(c, o, 64); if ((int)lane >= o) c += t; }
+      const uint32_t T = (uint32_t)__shfl((int)c, 63, 64);
+      c -= cn;
+      const unsigned long long cstart = cbase - (unsigned long long)c * 8ull;   // entry e of the stream (in slice `lane`) at cstart + 8 e
+      // row at E: lane l holds stream entry E + l, of the slice j = (slices starting at or before it) - 1
+      auto load = [&](uint32_t E, unsigned long long (&qv)[SEED_UNROLL], uint32_t (&sid)[SEED_UNROLL]) {
+#pragma unroll
+        for (int t = 0; t < SEED_UNROLL; ++t) {
+          const uint32_t R = E + 64u * (uint32_t)t;
+          qv[t] = SLOT_EMPTY;
+          sid[t] = 0;
+          if (R < T) {
+            const uint32_t before = (uint32_t)__popcll(__ballot(lane < n_ne && c < R));
+            uint64_t in_row = __ballot(lane < n_ne && c >= R && c < R + 64u), S = 0;
+            while (in_row) {   // (one or two slices start inside a row)
+              const int i = __ffsll((unsigned long long)in_row) - 1;
+              S |= 1ull << ((uint32_t)__builtin_amdgcn_readlane((int)c, i) - R);
+              in_row &= in_row - 1ull;
             }
-            if (report) {
-              const uint32_t code = qcode | ((vhi & 7u) << 3) | (((uint32_t)v >> (SEED_TAB_SLOT_SHIFT - 1)) & 6u);
-              const int32_t unit = seed_block_unit(ptab, n_qry, code);
-              if (unit >= 0)
-                seed_stage_hit(stage, stage_n, wave, Match{(int32_t)((uint32_t)v & SEED_TAB_POS_MASK), q, left, unit}, buf, cap, total, hit_count);
-            }
+            const uint32_t at = before + __builtin_amdgcn_mbcnt_hi((uint32_t)(S >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)S, 0u)) +
+                                (uint32_t)((S >> lane) & 1ull);
+            const int j = (int)at - 1;
+            const unsigned long long st = ((unsigned long long)(uint32_t)__shfl((int)(uint32_t)(cstart >> 32), j, 64) << 32) |
+                                          (uint32_t)__shfl((int)(uint32_t)cstart, j, 64);
+            sid[t] = (uint32_t)__shfl((int)src, j, 64);
+            if (R + lane < T) qv[t] = __builtin_nontemporal_load(reinterpret_cast<const uint64_t*>(st + 8ull * (R + lane)));
           }
-          slot_b = (slot_b + 8u) & byte_mask;
-          v = *reinterpret_cast<const unsigned long long*>(tab_b + slot_b);
         }
+      };
+      auto process = [&](const unsigned long long (&qv)[SEED_UNROLL], const uint32_t (&sid)[SEED_UNROLL]) {
+#pragma unroll
+        for (int t = 0; t < SEED_UNROLL; ++t) {
+          if (qv[t] == SLOT_EMPTY) continue;
+          const uint32_t qhi = (uint32_t)(qv[t] >> 32);
+          const uint32_t qkey = (qhi >> (SEED_KEY_SHIFT - 32)) & SEED_KEY_MASK;
+          const uint32_t qctx = qhi & 0x7FFu;   // bit 0: flag, bits 1..10: left bases
+          const int32_t q = (int32_t)(uint32_t)qv[t];
+          const uint32_t qcode = ((chunk + (sid[t] >> 1)) << 6) | (sid[t] & 1u);   // query in block, strand (the slot is or'ed in)
+          uint32_t slot_b = ((qkey >> slot_shift) & slot_mask) << 3;   // byte offset of the slot
+          const uint32_t byte_mask = (slot_mask << 3) | 7u;
+          const char* const tab_b = reinterpret_cast<const char*>(tab);
+          // (single exit, 32-bit tests only: see the per-pair kernel)
+          unsigned long long v = *reinterpret_cast<const unsigned long long*>(tab_b + slot_b);
+          while ((uint32_t)v != 0xFFFFFFFFu) {   // load factor <= 1/2: every probe sequence ends
+            const uint32_t vhi = (uint32_t)(v >> 32);
+            if ((vhi >> (SEED_TAB_KEY_SHIFT - 32)) == qkey) {
+              int32_t left = -1;
+              bool report = true;
+              const uint32_t rctx = (vhi >> (SEED_TAB_CTX_SHIFT - 32)) & 0x7FFu;
+              if (rctx & qctx & 1u) {
+                const uint32_t x = (rctx ^ qctx) >> 1;
+                const uint32_t diff = (x | (x >> 1)) & 0x155u;
+                left = diff ? (__ffs(diff) - 1) >> 1 : SEED_STEP;
+                report = left < step;   // inside a longer match: an earlier sampled position (every step-th) reports it
+              }
+              if (report) {
+                const uint32_t code = qcode | ((vhi & 7u) << 3) | (((uint32_t)v >> (SEED_TAB_SLOT_SHIFT - 1)) & 6u);
+                const int32_t unit = seed_block_unit(ptab, n_qry, code);
+                if (unit >= 0)
+                  seed_stage_hit(stage, stage_n, wave, Match{(int32_t)((uint32_t)v & SEED_TAB_POS_MASK), q, left, unit}, buf, cap, total, hit_count);
+              }
+            }
+            slot_b = (slot_b + 8u) & byte_mask;
+            v = *reinterpret_cast<const unsigned long long*>(tab_b + slot_b);
+          }
+        }
+        seed_stage_flush(stage, stage_n, wave, lane, false, buf, cap, total, hit_count);
+      };
+      // software-pipelined: the loads of the next SEED_UNROLL rows are in flight while these are looked up
+      unsigned long long qa[SEED_UNROLL], qb[SEED_UNROLL];
+      uint32_t sa[SEED_UNROLL], sb[SEED_UNROLL];
+      constexpr uint32_t STEP = 64u * SEED_UNROLL;
+      if (T) load(0, qa, sa);
+      for (uint32_t E = 0; E < T; E += 2 * STEP) {
+        if (E + STEP < T) load(E + STEP, qb, sb);
+        process(qa, sa);
+        if (E + STEP >= T) break;
+        if (E + 2 * STEP < T) load(E + 2 * STEP, qa, sa);
+        process(qb, sb);
       }
-      seed_stage_flush(stage, stage_n, wave, lane, false, buf, cap, total, hit_count);
-    };
-    // software-pipelined: the loads of the next SEED_UNROLL rows are in flight while these are looked up
-    unsigned long long qa[SEED_UNROLL], qb[SEED_UNROLL];
-    uint32_t sa[SEED_UNROLL], sb[SEED_UNROLL];
-    constexpr uint32_t STEP = 64u * SEED_UNROLL;
-    if (T) load(0, qa, sa);
-    for (uint32_t E = 0; E < T; E += 2 * STEP) {
-      if (E + STEP < T) load(E + STEP, qb, sb);
-      process(qa, sa);
-      if (E + STEP >= T) break;
-      if (E + 2 * STEP < T) load(E + 2 * STEP, qa, sa);
-      process(qb, sb);
     }
-  }
+    if constexpr (PASSES) {
+      if (++pass < n_pass) {   // the next pass's table: every wave is done with this one first
+        __syncthreads();
+        for (uint32_t i = tid; i <= slot_mask; i += SEED_BLOCK) tab[i] = SLOT_EMPTY;
+        __syncthreads();
+      }
+    }
+  } while (PASSES && pass < n_pass);
   seed_stage_flush(stage, stage_n, wave, lane, true, buf, cap, total, hit_count);   // what is still staged (uniform point)
 }
 
