@@ -293,6 +293,19 @@ int pg_anib_rows_batch(pg_ctx* ctx, const int32_t* qry_ids, const int32_t* sbj_i
                        pg_anib_result* out, uint64_t* row_offsets);
 int pg_anib_rows_read(pg_ctx* ctx, pg_anib_row* out);
 
+/* Which diagonals fragment mode takes a candidate's initial HSPs from — a per-context setting, PG_ANIB_SEARCH_SEEDS by default.
+ *   PG_ANIB_SEARCH_SEEDS      the diagonals of the search's own seeds (16-mers, and the word tier's 11-mers): every table and
+ *                             tuple as it has always been;
+ *   PG_ANIB_SEARCH_ALL_DIAGS  opt-in: the preliminary stage also walks the diagonals within 47 of a candidate's that hold no seed,
+ *                             as blastn takes its initial HSPs from every 11-mer diagonal.  Closes most of the "+-1 mismatch" rows
+ *                             against blastn on 74 - 85 % pairs; costs kernel time (measured gain and cost).
+ * pg_anib_pairs, pg_anib_pair_rows and pg_anib_rows_batch read the setting once, at entry.  Any other value: PG_E_ARG, the setting
+ * stays.  Tables of the two modes differ in a few rows per hundred fragments at most; a run should not mix them. */
+#define PG_ANIB_SEARCH_SEEDS 0u
+#define PG_ANIB_SEARCH_ALL_DIAGS 1u
+int pg_anib_set_search(pg_ctx* ctx, uint32_t mode);
+int pg_anib_get_search(pg_ctx* ctx, uint32_t* mode);
+
 /* ---- sketch mode: an opt-in ESTIMATE in the shape of pyani's fastANI wrapper -------------------------
  * Replaces the `fastANI -q <query> -r <ref> --fragLen 3000 -k 16 --minFraction 0.2` job of pyani/fastani.py:193-229
  * (construct_fastani_cmdline) and the line parse_fastani_file reads back (fastani.py:231-270): ANI estimate, matching fragments,

@@ -36,6 +36,8 @@ K_TOTAL = 20      # PG_K__COUNT of the header: every slot, the two cluster slots
 K_ANIB_ROWS_SCAN, K_ANIB_ROWS_PACK = 21, 22      # (20 is no slot: K_TOTAL is a published value)
 K_END = 23        # PG_K__END of the header: one past the last slot
 PG_SKETCH_NO_RESULT = 1
+PG_ANIB_SEARCH_SEEDS, PG_ANIB_SEARCH_ALL_DIAGS = 0, 1
+ANIB_SEARCH_MODES = {"seeds": PG_ANIB_SEARCH_SEEDS, "all_diagonals": PG_ANIB_SEARCH_ALL_DIAGS}      # the names the Python layer uses
 
 # every symbol declared in include/pyani_gpu.h: (name, restype, argtypes)
 _vp, _i32, _u32, _u64, _int = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
@@ -79,6 +81,8 @@ SIGNATURES = {
     "pg_anib_pair_rows": (_int, [_vp, _i32, _i32, _u32, _vp, _u32, _P(_u32)]),
     "pg_anib_rows_batch": (_int, [_vp, _vp, _vp, _u64, _u32, _vp, _vp]),
     "pg_anib_rows_read": (_int, [_vp, _vp]),
+    "pg_anib_set_search": (_int, [_vp, _u32]),
+    "pg_anib_get_search": (_int, [_vp, _P(_u32)]),
     "pg_sketch_pairs": (_int, [_vp, _vp, _vp, _u64, _i32, _i32, ctypes.c_double, _vp]),
     "pg_sketch_pairs_k": (_int, [_vp, _vp, _vp, _u64, _i32, _i32, _i32, ctypes.c_double, _vp]),
     "pg_classify_edges": (_int, [_vp, _vp, _vp, _u32, ctypes.c_double, ctypes.c_double, _P(_u64), _P(_u32)]),
@@ -114,6 +118,13 @@ class DistStats(ctypes.Structure):
 
 
 _lib = None
+
+
+def anib_search_code(name) -> int:
+    """The PG_ANIB_SEARCH_* value of a search mode's name; ValueError for anything else (no library call is made)."""
+    if not isinstance(name, str) or name not in ANIB_SEARCH_MODES:
+        raise ValueError(f"unknown ANIb search mode {name!r}: one of {sorted(ANIB_SEARCH_MODES)}")
+    return ANIB_SEARCH_MODES[name]
 
 
 class PyaniGpuError(RuntimeError):

@@ -15,6 +15,7 @@ The fragment-vs-genome SEARCH replaces BLAST+ (`blastn -task blastn`, third-part
 engine's fragment mode (pg_anib_pairs: seeds from the LDS-table seeding, X-drop gapped extension with blastn's scores);
 how closely it follows BLAST+'s own tables on the reference's fixtures is stated in DESIGN.md.
 """
+import contextlib
 import gzip
 from pathlib import Path
 from typing import Dict, Iterable, List, Tuple
@@ -22,6 +23,7 @@ from typing import Dict, Iterable, List, Tuple
 import numpy as np
 import pandas as pd
 
+from . import _lib
 from .engine import Engine, default_engine
 
 FRAGSIZE = 1020  # pyani_config.FRAGSIZE
@@ -121,11 +123,31 @@ def parse_blast_tab(filename, engine: Engine = None) -> Tuple[int, int, float]:
     return int(aln[0]), int(err[0]), float(pid[0])
 
 
-def calculate_anib_pairs(infiles: Iterable, engine: Engine = None, fragsize: int = FRAGSIZE
+@contextlib.contextmanager
+def search_mode(engine, search: str):
+    """The engine's ANIb search mode set to `search` ("seeds" | "all_diagonals": Engine.anib_set_search) for the body and put back
+    afterwards, on errors too.  An unknown name is a ValueError before the engine is touched."""
+    _lib.anib_search_code(search)
+    previous = engine.anib_search
+    engine.anib_set_search(search)
+    try:
+        yield engine
+    finally:
+        engine.anib_set_search(previous)
+
+
+def calculate_anib_pairs(infiles: Iterable, engine: Engine = None, fragsize: int = FRAGSIZE, search: str = "seeds"
                          ) -> Tuple[Dict[Tuple[str, str], Tuple[int, int, float]], Dict[str, int]]:
     """All ordered comparisons between the FASTA files: {(query stem, subject stem): (aln_length, sim_errors, mean pident)}
-    — parse_blast_tab's tuple for `<query>_vs_<subject>.blast_tab` — and the genome lengths keyed by stem."""
+    — parse_blast_tab's tuple for `<query>_vs_<subject>.blast_tab` — and the genome lengths keyed by stem.
+    search: the engine's ANIb search mode for this call (Engine.anib_set_search); the engine's own setting comes back afterwards."""
+    _lib.anib_search_code(search)
     eng = engine or default_engine()
+    with search_mode(eng, search):
+        return _calculate_anib_pairs(infiles, eng, fragsize)
+
+
+def _calculate_anib_pairs(infiles, eng, fragsize):
     files = sorted(Path(f) for f in infiles)
     stems = [f.stem for f in files]
     if len(set(stems)) != len(stems):

@@ -1402,8 +1402,10 @@ static int anib_frag_stage(pg_ctx* ctx, AnimScratch* A, const int32_t* qry_ids, 
                      A->fr_ebase, F.fragsize, A->fr_off, A->fr_entries);
   pg_prof_end(ctx);
   pg_prof_begin(ctx, PG_K_ANIB_FRAG);
+  // (both instantiations report to the PG_K_ANIB_FRAG slot)
+  const auto frag_kernel = F.search == PG_ANIB_SEARCH_ALL_DIAGS ? anib_frag_kernel<true> : anib_frag_kernel<false>;
   if (slots)
-    hipLaunchKernelGGL(anib_frag_kernel, dim3((uint32_t)slots), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, A->fr_pairs, A->fr_slot_pair,
+    hipLaunchKernelGGL(frag_kernel, dim3((uint32_t)slots), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, A->fr_pairs, A->fr_slot_pair,
                        A->fr_off, A->fr_entries, A->fr_ebase, A->fr_rows, A->fr_nrows, (const uint32_t*)nullptr, (const WordIdx*)nullptr);
   pg_prof_end(ctx);
   hipLaunchKernelGGL(anib_reduce_pairs_kernel, dim3((n_pairs + 63) / 64), dim3(64), 0, cur_stream(ctx), A->fr_pairs, n_pairs, A->fr_rows, A->fr_nrows,
@@ -1438,7 +1440,7 @@ static int anib_frag_stage(pg_ctx* ctx, AnimScratch* A, const int32_t* qry_ids, 
       PG_HIP(ctx, hipStreamSynchronize(cur_stream(ctx)));
       if (n_list) {
         pg_prof_begin(ctx, PG_K_ANIB_FRAG);
-        hipLaunchKernelGGL(anib_frag_kernel, dim3(n_list), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, A->fr_pairs, A->fr_slot_pair,
+        hipLaunchKernelGGL(frag_kernel, dim3(n_list), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, A->fr_pairs, A->fr_slot_pair,
                            A->fr_off, A->fr_entries, A->fr_ebase, A->fr_rows, A->fr_nrows, (const uint32_t*)A->fr_list, (const WordIdx*)A->fr_widx);
         pg_prof_end(ctx);
         hipLaunchKernelGGL(anib_reduce_pairs_kernel, dim3((n_pairs + 63) / 64), dim3(64), 0, cur_stream(ctx), A->fr_pairs, n_pairs, A->fr_rows,

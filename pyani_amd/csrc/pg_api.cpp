@@ -1099,6 +1099,7 @@ static int anib_pairs_body(pg_ctx* ctx, const int32_t* qry_ids, const int32_t* s
   for (uint64_t i = 0; i < n_pairs; ++i)
     if (qry_ids[i] < 0 || (size_t)qry_ids[i] >= ctx->genomes.size() || sbj_ids[i] < 0 || (size_t)sbj_ids[i] >= ctx->genomes.size())
       return pg_fail(ctx, PG_E_ARG, "genome id out of range");
+  const uint32_t search = ctx->anib_search;      // the setting as the call found it: every launch of the call searches the same way
   int rc;
   if ((rc = pg_upload(ctx))) return rc;
   // A query genome with more fragments than a launch's per-genome counters hold (15 872: 16.1 Mb at 1020 nt) cannot be searched:
@@ -1137,7 +1138,7 @@ static int anib_pairs_body(pg_ctx* ctx, const int32_t* qry_ids, const int32_t* s
       for (uint64_t k = i; k < j; ++k) { s.push_back(sbj_ids[order[k]]); q.push_back(qry_ids[order[k]]); }
       res.assign(j - i, pg_anib_result{});
       PgRowSink sink;
-      PgFragArgs F{(int32_t)fragsize, res.data(), nullptr, 0, nullptr, max_slots, rows ? &sink : nullptr};
+      PgFragArgs F{(int32_t)fragsize, res.data(), nullptr, 0, nullptr, max_slots, rows ? &sink : nullptr, search};
       uint32_t done = 0;
       const int rc2 = pg_anim_run_batch(ctx, s.data(), q.data(), (uint32_t)(j - i), 0, 1, max_matches, nullptr, &done, &F);
       if (rc2) return rc2;
@@ -1182,13 +1183,27 @@ int pg_anib_pair_rows(pg_ctx* ctx, int32_t qry_id, int32_t sbj_id, uint32_t frag
   if (!ctx || !n_out || fragsize == 0 || fragsize > 1020 || (cap && !out)) return pg_fail(ctx, PG_E_ARG, "bad argument");
   if (qry_id < 0 || (size_t)qry_id >= ctx->genomes.size() || sbj_id < 0 || (size_t)sbj_id >= ctx->genomes.size())
     return pg_fail(ctx, PG_E_ARG, "genome id out of range");
+  const uint32_t search = ctx->anib_search;
   PG_HIP(ctx, hipSetDevice(ctx->device));
   int rc;
   if ((rc = pg_upload(ctx))) return rc;
   pg_anib_result res{};
-  PgFragArgs F{(int32_t)fragsize, &res, out, cap, n_out, ANIB_MAX_SLOTS};
+  PgFragArgs F{(int32_t)fragsize, &res, out, cap, n_out, ANIB_MAX_SLOTS, nullptr, search};
   uint32_t done = 0;
   return pg_anim_run_batch(ctx, &sbj_id, &qry_id, 1, 0, 1, anim_match_budget(ctx), nullptr, &done, &F);
+}
+
+int pg_anib_set_search(pg_ctx* ctx, uint32_t mode) {
+  if (!ctx) return PG_E_ARG;
+  if (mode != PG_ANIB_SEARCH_SEEDS && mode != PG_ANIB_SEARCH_ALL_DIAGS) return pg_fail(ctx, PG_E_ARG, "pg_anib_set_search: unknown search mode");
+  ctx->anib_search = mode;
+  return PG_OK;
+}
+int pg_anib_get_search(pg_ctx* ctx, uint32_t* mode) {
+  if (!ctx) return PG_E_ARG;
+  if (!mode) return pg_fail(ctx, PG_E_ARG, "bad argument");
+  *mode = ctx->anib_search;
+  return PG_OK;
 }
 
 // ---- measurement -----------------------------------------------------------------------------------------------

@@ -102,6 +102,7 @@ struct pg_ctx {
   double dist_ms[3] = {0.0, 0.0, 0.0};   // kernel milliseconds of the latest pg_dist_load / _hist / _kde while profiling is on (pg_dist_last_ms)
   std::mutex anim_mu, err_mu, prof_mu;
   int anib_word_tier = 1;      // fragment mode: search failed fragments again with blastn-sized (11-mer) seeds
+  uint32_t anib_search = 0;    // fragment mode: PG_ANIB_SEARCH_SEEDS, or PG_ANIB_SEARCH_ALL_DIAGS (pg_anib_set_search)
   int anim_pn_window_max = 2048;   // forced runs: the widest single-wave window (development: smaller values push runs on to the group kernel)
   int anim_pn_group_max = 8184;    // ... and the widest band the group of four waves takes (development: 0 = everything beyond one wave on the strips)
   int anim_gap_lanes = 1;      // postnuc: small match-to-match gaps on one lane each (0: all gaps on the wave engine; tests compare the two)
@@ -171,6 +172,7 @@ struct PgFragArgs {
   uint32_t* n_rows_out;
   uint64_t max_slots;         // (pair, fragment) slots per launch
   struct PgRowSink* sink = nullptr;   // optional: the rows of EVERY pair of the launch, packed on the device (pg_anib_rows_batch)
+  uint32_t search = 0;        // PG_ANIB_SEARCH_*: the context's setting as the call found it at entry
 };
 // Where a fragment-mode launch leaves its tables when PgFragArgs::sink is set: the rows of its pairs back to back in launch order
 // (fragments in order, a fragment's rows best score first), and how many each pair owns.  One sink per launch chain: the caller's.

@@ -111,6 +111,10 @@ __global__ __launch_bounds__(256) void anib_bucket_kernel(const UnitDesc* __rest
 struct FragBandLds { int32_t h[FRAG_BAND], x[FRAG_BAND], y[FRAG_BAND], hs[FRAG_BAND], xs[FRAG_BAND], ys[FRAG_BAND]; };
 static_assert(FRAG_BAND == 256, "four diagonals per lane");
 
+// (a template on the kernel's mode only so that each instantiation of anib_frag_kernel owns a copy: it stays a called function, and the
+// LDS addresses every call site of one kernel passes are constants the compiler folds into that copy — a copy shared by two kernels
+// takes them as arguments and the default kernel's register allocation changes)
+template <bool ALL_DIAGS>
 __device__ FragExt frag_extend_wave(FragBandLds& B, const uint8_t* __restrict__ qb, int32_t qmax, const uint8_t* __restrict__ sb, int32_t smax,
                                     int32_t abs_floor = FRAG_NEG, int32_t xdrop = FRAG_XDROP) {
   const int lane = threadIdx.x & 63;
@@ -330,7 +334,15 @@ struct DiagMatch {
 #define PGA_FRAG_WAVES 3
 #endif
 #define PGA_FRAG_ATTR __attribute__((amdgpu_waves_per_eu(PGA_FRAG_WAVES, PGA_FRAG_WAVES)))
-__global__ __launch_bounds__(64) PGA_FRAG_ATTR void anib_frag_kernel(const RefDesc* __restrict__ refs, const UnitDesc* __restrict__ units,
+// ALL_DIAGS (PG_ANIB_SEARCH_ALL_DIAGS, pg_anib_set_search): the preliminary stage also walks the diagonals of a candidate's band that hold
+// no seed (the CPU checker's ANIB_ALL_DIAGS) — blastn takes its initial HSPs from every 11-mer diagonal.  FRAG_XDIAGS diagonals per
+// candidate, one lane each in two rounds; their initial HSPs (best [0, FRAG_XDIAGS), second [FRAG_XDIAGS, 2 FRAG_XDIAGS), the diagonal
+// implied by the index) live in 3 KiB of LDS that only this instantiation has.  <false> is the kernel as it was.
+constexpr int FRAG_XDIAGS = 2 * FRAG_VOTE_FAR - 1;
+// (with them the block's LDS allows two waves per SIMD, so that is what ALL_DIAGS asks for; the default asks for what it always has)
+#define PGA_FRAG_ATTR_MODE __attribute__((amdgpu_waves_per_eu(ALL_DIAGS ? 2 : PGA_FRAG_WAVES, PGA_FRAG_WAVES)))
+template <bool ALL_DIAGS>
+__global__ __launch_bounds__(64) PGA_FRAG_ATTR_MODE void anib_frag_kernel(const RefDesc* __restrict__ refs, const UnitDesc* __restrict__ units,
                                                        const FragPair* __restrict__ pairs, const uint32_t* __restrict__ slot_pair,
                                                        const uint32_t* __restrict__ frag_off, const FragSeed* __restrict__ entries,
                                                        const uint64_t* __restrict__ ebase, FragRow* __restrict__ rows,
@@ -356,6 +368,13 @@ __global__ __launch_bounds__(64) PGA_FRAG_ATTR void anib_frag_kernel(const RefDe
   __shared__ int s_nc[2];
   __shared__ FragRow s_rows[FRAG_ROWS];
   __shared__ int s_nrows;
+  [[maybe_unused]] FragInit* s_x = nullptr;     // ALL_DIAGS: the initial HSPs of the current candidate's seedless diagonals
+  if constexpr (ALL_DIAGS) {
+    __shared__ FragInit s_xinit[3 * 64];        // (2 FRAG_XDIAGS used; the tail stays 0: three ballots of 64 cover it)
+    static_assert(2 * FRAG_XDIAGS <= 3 * 64, "three entries per lane");
+    s_x = s_xinit;
+    for (int t = threadIdx.x; t < 3 * 64; t += 64) s_xinit[t] = FragInit{0, 0, 0, 0};
+  }
   const bool word = slot_list != nullptr;       // second pass: the failed fragments, with blastn-sized word seeds added
   const uint32_t slot = word ? slot_list[blockIdx.x] : blockIdx.x;
   const int lane = threadIdx.x;
@@ -606,29 +625,96 @@ __global__ __launch_bounds__(64) PGA_FRAG_ATTR void anib_frag_kernel(const RefDe
           }
           return record_of(R.rec_start, R.n_rec, (int32_t)(inits[t].q_off + diags[t])) == srec;
         };
-        // every lane ranks its two entries (lane, 64 + lane) among the eligible ones in blastn's order
-        const unsigned long long el[2] = {__ballot(eligible(lane)), __ballot(eligible(64 + lane))};      // (uniform masks)
-        int rank[2] = {-1, -1};
-        for (int w = 0; w < 2; ++w) {
-          if (!((el[w] >> lane) & 1ull)) continue;
-          const FragInit me = inits[64 * w + lane];
-          const int64_t md = diags[lane];
-          int r = 0;
-          for (int v = 0; v < 2; ++v)
-            for (unsigned long long m = el[v]; m; m &= m - 1) {
-              const int t = (int)__builtin_ctzll(m);
-              if ((v != w || t != lane) && frag_init_before(inits[64 * v + t], diags[t], me, md)) ++r;
+        if constexpr (ALL_DIAGS) {
+          // the band's diagonals that hold no seed and lie outside every earlier candidate's neighbourhood: one lane walks one whole
+          // diagonal.  DiagMatch answers false for every subject position outside [s_lo, s_hi) and packed_window reads nothing outside
+          // the subject's arrays, so a diagonal that runs off either end of the subject, or into another record, is walked like any other.
+          for (int j = lane; j < FRAG_XDIAGS; j += 64) {
+            const int64_t d2 = diag_c - (FRAG_VOTE_FAR - 1) + j;
+            bool skip = false;
+            for (int t = 0; t < n; ++t) skip = skip || diags[t] == d2;
+            for (int p = 0; p < c; ++p) {
+              const int64_t d1 = d2 - ((int64_t)s_anchor[strand][p].s - s_anchor[strand][p].q);
+              skip = skip || (d1 < FRAG_VOTE_FAR && -d1 < FRAG_VOTE_FAR);
             }
-          rank[w] = r;
+            FragInit in{0, 0, 0, 0}, in2{0, 0, 0, 0};
+            if (!skip) {
+              DiagMatch match{s_qpk2[strand], s_qok2[strand], qlen, R.codes, R.mask, (int32_t)R.len, d2, (int64_t)s_lo, (int64_t)s_hi, -64, 0u};
+              in = frag_diag_walk(match, qlen, d2, &in2);
+              if (in.score <= 0 || record_of(R.rec_start, R.n_rec, (int32_t)(in.q_off + d2)) != srec) in = in2 = FragInit{0, 0, 0, 0};
+            }
+            s_x[j] = in;
+            s_x[FRAG_XDIAGS + j] = in2;
+          }
+          __syncthreads();
         }
-        const int n_elig = __popcll(el[0]) + __popcll(el[1]);
+        // every lane ranks its two entries (lane, 64 + lane) among the eligible ones in blastn's order; ALL_DIAGS: word w >= 2 of the masks is
+        // entries [64 (w - 2), 64 (w - 1)) of s_x, three more per lane
+        constexpr int NW = ALL_DIAGS ? 5 : 2;
+        unsigned long long el[NW];      // (uniform masks)
+        int rank[NW];
+        int n_elig;
+        [[maybe_unused]] auto ent = [&](int v, int t) -> FragInit { return v >= 2 ? s_x[64 * (v - 2) + t] : inits[64 * v + t]; };
+        [[maybe_unused]] auto ent_diag = [&](int v, int t) -> int64_t {
+          if (v < 2) return diags[t];
+          const int j = 64 * (v - 2) + t;
+          return diag_c - (FRAG_VOTE_FAR - 1) + (j >= FRAG_XDIAGS ? j - FRAG_XDIAGS : j);
+        };
+        if constexpr (!ALL_DIAGS) {
+          el[0] = __ballot(eligible(lane)); el[1] = __ballot(eligible(64 + lane));
+          rank[0] = rank[1] = -1;
+          for (int w = 0; w < 2; ++w) {
+            if (!((el[w] >> lane) & 1ull)) continue;
+            const FragInit me = inits[64 * w + lane];
+            const int64_t md = diags[lane];
+            int r = 0;
+            for (int v = 0; v < 2; ++v)
+              for (unsigned long long m = el[v]; m; m &= m - 1) {
+                const int t = (int)__builtin_ctzll(m);
+                if ((v != w || t != lane) && frag_init_before(inits[64 * v + t], diags[t], me, md)) ++r;
+              }
+            rank[w] = r;
+          }
+          n_elig = __popcll(el[0]) + __popcll(el[1]);
+        } else {
+          el[0] = __ballot(eligible(lane)); el[1] = __ballot(eligible(64 + lane));
+          for (int k = 0; k < 3; ++k) el[2 + k] = __ballot(s_x[64 * k + lane].score > 0);
+          n_elig = 0;
+          for (int w = 0; w < NW; ++w) {
+            n_elig += __popcll(el[w]);
+            rank[w] = -1;
+            if (!((el[w] >> lane) & 1ull)) continue;
+            const FragInit me = ent(w, lane);
+            const int64_t md = ent_diag(w, lane);
+            int r = 0;
+            for (int v = 0; v < NW; ++v)
+              for (unsigned long long m = el[v]; m; m &= m - 1) {
+                const int t = (int)__builtin_ctzll(m);
+                if ((v != w || t != lane) && frag_init_before(ent(v, t), ent_diag(v, t), me, md)) ++r;
+              }
+            rank[w] = r;
+          }
+        }
         FragPrelim pre[BL_MAX_PRELIMS], first{0, 0, 0, 0, 0, 0, 0};
         int np = 0, tried = 0;
         for (int r = 0; r < n_elig && tried < BL_MAX_PRELIMS; ++r) {      // (uniform)
-          const unsigned long long m0 = __ballot(rank[0] == r), m1 = __ballot(rank[1] == r);
-          const int x = m0 ? (int)__builtin_ctzll(m0) : 64 + (int)__builtin_ctzll(m1);
-          const FragInit J = inits[x];
-          const int64_t dj = diags[x & (FRAG_MAX_SEEDS - 1)];
+          FragInit J;
+          int64_t dj;
+          if constexpr (!ALL_DIAGS) {
+            const unsigned long long m0 = __ballot(rank[0] == r), m1 = __ballot(rank[1] == r);
+            const int x = m0 ? (int)__builtin_ctzll(m0) : 64 + (int)__builtin_ctzll(m1);
+            J = inits[x];
+            dj = diags[x & (FRAG_MAX_SEEDS - 1)];
+          } else {
+            int xv = -1, xt = 0;
+            for (int w = NW - 1; w >= 0; --w) {
+              const unsigned long long mw = __ballot(rank[w] == r);
+              if (mw) { xv = w; xt = (int)__builtin_ctzll(mw); }
+            }
+            if (xv < 0) continue;      // (uniform; no entry of this rank means two of equal rank: frag_init_before is total on distinct (diagonal, q_start))
+            J = ent(xv, xt);
+            dj = ent_diag(xv, xt);
+          }
           bool inside = false;
           for (int u = 0; u < np; ++u) inside = inside || frag_init_contained(J, dj, pre[u]);
           if (inside) continue;
@@ -641,12 +727,12 @@ __global__ __launch_bounds__(64) PGA_FRAG_ATTR void anib_frag_kernel(const RefDe
           for (int32_t t = lane; t < pq_r; t += 64) s_q[t] = q_at(g0 + 1 + t);
           for (int32_t t = lane; t < ps_r; t += 64) s_s[t] = s_at(as + 1 + t);
           __syncthreads();
-          const FragExt Rp = frag_extend_wave(B, s_q, pq_r, s_s, ps_r, FRAG_NEG, FRAG_XDROP_PRELIM);
+          const FragExt Rp = frag_extend_wave<ALL_DIAGS>(B, s_q, pq_r, s_s, ps_r, FRAG_NEG, FRAG_XDROP_PRELIM);
           __syncthreads();
           for (int32_t t = lane; t < pq_l; t += 64) s_q[t] = q_at(g0 - 1 - t);
           for (int32_t t = lane; t < ps_l; t += 64) s_s[t] = s_at(as - 1 - t);
           __syncthreads();
-          const FragExt Lp = frag_extend_wave(B, s_q, pq_l, s_s, ps_l, FRAG_NEG, FRAG_XDROP_PRELIM);
+          const FragExt Lp = frag_extend_wave<ALL_DIAGS>(B, s_q, pq_l, s_s, ps_l, FRAG_NEG, FRAG_XDROP_PRELIM);
           const FragPrelim Pp{Rp.score + Lp.score + FRAG_MATCH, g0 - Lp.di, g0 + 1 + Rp.di, g0, (int64_t)as - Lp.dj, (int64_t)as + 1 + Rp.dj, dj};
           if (tried++ == 0) first = Pp;
           if (frag_evalue_ok_db(Pp.score, qlen, db_len, R.n_rec)) pre[np++] = Pp;
@@ -677,8 +763,8 @@ __global__ __launch_bounds__(64) PGA_FRAG_ATTR void anib_frag_kernel(const RefDe
       __syncthreads();
       // a chance hit gets blastn's PRELIMINARY look first (frag_hsp, pg_anib_core.h): X-drop 30 bits; what misses the e-value there is dropped
       FragExt Rp{0, 0, 0, 0, 0};
-      if (weak) Rp = frag_extend_wave(B, s_q, qmax_r, s_s, smax_r, FRAG_NEG, FRAG_XDROP_PRELIM);
-      FragExt Rr = weak ? Rp : frag_extend_wave(B, s_q, qmax_r, s_s, smax_r);
+      if (weak) Rp = frag_extend_wave<ALL_DIAGS>(B, s_q, qmax_r, s_s, smax_r, FRAG_NEG, FRAG_XDROP_PRELIM);
+      FragExt Rr = weak ? Rp : frag_extend_wave<ALL_DIAGS>(B, s_q, qmax_r, s_s, smax_r);
       // leftward
       const int32_t qmax_l = A.q;
       int32_t smax_l = A.s - s_lo; if (smax_l > cap) smax_l = cap; if (smax_l < 0) smax_l = 0;
@@ -689,35 +775,35 @@ __global__ __launch_bounds__(64) PGA_FRAG_ATTR void anib_frag_kernel(const RefDe
       FragExt Ll;
       bool dropped = false;
       if (weak) {
-        const FragExt Lp = frag_extend_wave(B, s_q, qmax_l, s_s, smax_l, FRAG_NEG, FRAG_XDROP_PRELIM);
+        const FragExt Lp = frag_extend_wave<ALL_DIAGS>(B, s_q, qmax_l, s_s, smax_l, FRAG_NEG, FRAG_XDROP_PRELIM);
         dropped = !frag_prelim_goes_on(Rp.score + Lp.score + FRAG_MATCH * A.len, [&](int32_t sc) { return frag_evalue_ok_db(sc, qlen, db_len, R.n_rec); });      // (uniform)
         Ll = Lp;
         if (!dropped) {      // it passed: the final alignment of both sides
-          Ll = frag_extend_wave(B, s_q, qmax_l, s_s, smax_l);
+          Ll = frag_extend_wave<ALL_DIAGS>(B, s_q, qmax_l, s_s, smax_l);
           __syncthreads();
           for (int32_t t = lane; t < qmax_r; t += 64) s_q[t] = q_at(A.q + A.len + t);
           for (int32_t t = lane; t < smax_r; t += 64) s_s[t] = s_at(A.s + A.len + t);
           __syncthreads();
-          Rr = frag_extend_wave(B, s_q, qmax_r, s_s, smax_r);
+          Rr = frag_extend_wave<ALL_DIAGS>(B, s_q, qmax_r, s_s, smax_r);
           __syncthreads();
           for (int32_t t = lane; t < qmax_l; t += 64) s_q[t] = q_at(A.q - 1 - t);
           for (int32_t t = lane; t < smax_l; t += 64) s_s[t] = s_at(A.s - 1 - t);
           __syncthreads();
         }
       } else {
-        Ll = frag_extend_wave(B, s_q, qmax_l, s_s, smax_l);
+        Ll = frag_extend_wave<ALL_DIAGS>(B, s_q, qmax_l, s_s, smax_l);
       }
       if (dropped) { __syncthreads(); continue; }      // (uniform)
       // the second look (pg_anib_core.h, frag_second_look): a side grown again under the floor the other side's total sets (uniform)
       const int32_t r_total = Rr.score + FRAG_MATCH * A.len, l_total = Ll.score;
       const bool again = frag_evalue_ok_db(r_total + l_total, qlen, db_len, R.n_rec);      // (a row that fails the e-value already is not looked at again)
-      if (again && frag_second_look(r_total, Ll.score)) Ll = frag_extend_wave(B, s_q, qmax_l, s_s, smax_l, -r_total);
+      if (again && frag_second_look(r_total, Ll.score)) Ll = frag_extend_wave<ALL_DIAGS>(B, s_q, qmax_l, s_s, smax_l, -r_total);
       if (again && frag_second_look(l_total, Rr.score)) {
         __syncthreads();
         for (int32_t t = lane; t < qmax_r; t += 64) s_q[t] = q_at(A.q + A.len + t);
         for (int32_t t = lane; t < smax_r; t += 64) s_s[t] = s_at(A.s + A.len + t);
         __syncthreads();
-        Rr = frag_extend_wave(B, s_q, qmax_r, s_s, smax_r, -l_total);
+        Rr = frag_extend_wave<ALL_DIAGS>(B, s_q, qmax_r, s_s, smax_r, -l_total);
       }
       if (lane == 0) {
         const FragHit h = frag_join(Ll, Rr, A.q, A.s, A.len);

@@ -328,6 +328,20 @@ class Engine:
         self._check(self.lib.pg_anib_rows_read(self._h, rows.ctypes.data if len(rows) else None))
         return rows
 
+    def anib_set_search(self, mode: str) -> None:
+        """Which diagonals fragment mode takes a candidate's initial HSPs from (pg_anib_set_search): "seeds" (the default: the search's
+        own seed diagonals) or "all_diagonals" (opt-in: every diagonal of the candidate's band, as blastn does; slower).  Holds for the
+        anib_* calls that start after it.  ValueError for any other name."""
+        code = _lib.anib_search_code(mode)
+        self._check(self.lib.pg_anib_set_search(self._h, code))
+
+    @property
+    def anib_search(self) -> str:
+        """The search mode the next anib_* call will use (pg_anib_get_search)."""
+        m = ctypes.c_uint32(0)
+        self._check(self.lib.pg_anib_get_search(self._h, ctypes.byref(m)))
+        return {v: k for k, v in _lib.ANIB_SEARCH_MODES.items()}[m.value]
+
     # -- measurement ----------------------------------------------------------------------------------------------
     # -- sketch mode (fastANI-shaped estimate; never mixed into the exact results) ----------------------------------------------
     SKETCH_DTYPE = np.dtype([("ani", "<f8"), ("matches", "<i4"), ("fragments", "<i4"), ("status", "<i4"), ("reserved", "<i4")])

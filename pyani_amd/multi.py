@@ -20,6 +20,7 @@ from typing import Iterable, List, Optional, Sequence
 
 import numpy as np
 
+from . import _lib
 from .engine import Engine
 
 
@@ -174,6 +175,16 @@ class MultiEngine:
         """Engine.anim_set_workers on every device (host worker threads / streams per device)."""
         for e in self.engines:
             e.anim_set_workers(workers)
+
+    def anib_set_search(self, mode: str):
+        """Engine.anib_set_search on every device (the name is checked before any engine is touched)."""
+        _lib.anib_search_code(mode)
+        for e in self.engines:
+            e.anib_set_search(mode)
+
+    @property
+    def anib_search(self) -> str:
+        return self.engines[0].anib_search
 
     def anim_counters(self, reset: bool = False) -> np.ndarray:
         """Engine.anim_counters summed over the devices."""

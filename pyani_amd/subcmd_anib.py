@@ -13,15 +13,21 @@ What is kept of the reference's behaviour:
   * results: parse_blast_tab's tuple per ordered pair and process_blast's five matrices (anib.process_blast_results);
   * errors: a pair the engine could not process raises RuntimeError, as calculate_anib_pairs does.
 
+  * `search` picks the engine's search mode for the run (Engine.anib_set_search; the engine's own setting comes back afterwards).  A
+    run that writes its tables also writes `<outdir>/anib_run.json` naming the mode, and recovery refuses a directory whose record
+    names the other one: tables of two modes are not mixed silently.  A directory without a record (BLAST+'s own tables, or an
+    earlier version's) counts as "seeds".
+
 Single-process: one engine, or several GPUs of this node through pyani_amd.multi.MultiEngine (devices / workers).  There is no
 collective (one process per GPU) run_anib: pyani_amd.parallel.DistributedEngine has no rows call.
 """
+import json
 from pathlib import Path
 from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import pandas as pd
 
-from . import anib, anim, files
+from . import _lib, anib, anim, files
 from .engine import Engine, default_engine
 
 ALIGNDIR = "blastn_output"     # pyani_config.ALIGNDIR["ANIb"]
@@ -50,21 +56,46 @@ def table_path(outdir: Path, qstem: str, sstem: str) -> Path:
     return Path(outdir) / ALIGNDIR / (f"{qstem}_vs_{sstem}" + ".blast_tab")
 
 
+RUN_RECORD = "anib_run.json"   # <outdir>/anib_run.json: {"search": ...} of the run that wrote the tables
+
+
+def recorded_search(outdir) -> str:
+    """The search mode the tables under `outdir` were written with; "seeds" when the directory holds no run record."""
+    f = Path(outdir) / RUN_RECORD
+    if not f.is_file():
+        return "seeds"
+    with open(f) as fh:
+        return str(json.load(fh).get("search", "seeds"))
+
+
 def run_anib(indir, outdir=None, fragsize: int = anib.FRAGSIZE, recovery: bool = False, write_output: bool = False,
-             engine: Optional[Engine] = None, devices: Optional[List[int]] = None, workers: Optional[int] = None) -> AnibRun:
+             engine: Optional[Engine] = None, devices: Optional[List[int]] = None, workers: Optional[int] = None,
+             search: str = "seeds") -> AnibRun:
     """ANIb over every FASTA file of `indir`.  outdir is needed for recovery / write_output only.
-    devices / workers: run on several GPUs of this node (pyani_amd/multi.py); ignored when `engine` is given."""
+    devices / workers: run on several GPUs of this node (pyani_amd/multi.py); ignored when `engine` is given.
+    search: "seeds" (default) or "all_diagonals" (Engine.anib_set_search) for this run."""
+    _lib.anib_search_code(search)     # before any work is done
     if write_output and outdir is None:
-        raise ValueError("write_output needs an output directory")     # before any work is done
+        raise ValueError("write_output needs an output directory")
     if recovery and outdir is None:
         raise ValueError("recovery mode needs the output directory of the earlier run")
+    if recovery and recorded_search(outdir) != search:
+        raise ValueError(f"recovery: the tables under {outdir} were written with search={recorded_search(outdir)!r}, this run asks for "
+                         f"{search!r}; the two modes' tables are not mixed")
     own = None
     if engine is None and (devices is not None or workers):
         from . import multi
         engine = multi.engine_for(devices, workers)
         own = engine if isinstance(engine, multi.MultiEngine) else None
     try:
-        return _run_anib(indir, outdir, fragsize, recovery, write_output, engine or default_engine())
+        eng = engine or default_engine()
+        with anib.search_mode(eng, search):
+            run = _run_anib(indir, outdir, fragsize, recovery, write_output, eng)
+        if write_output:
+            with open(Path(outdir) / RUN_RECORD, "w") as fh:
+                json.dump({"search": search, "fragsize": int(fragsize)}, fh)
+                fh.write("\n")
+        return run
     finally:
         if own is not None:
             own.close()
