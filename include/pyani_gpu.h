@@ -336,6 +336,40 @@ int pg_sketch_pairs(pg_ctx* ctx, const int32_t* qry_ids, const int32_t* ref_ids,
 int pg_sketch_pairs_k(pg_ctx* ctx, const int32_t* qry_ids, const int32_t* ref_ids, uint64_t n_pairs, int32_t kmer, int32_t frag_len,
                       int32_t scale, double min_fraction, pg_sketch_result* out);
 
+/* The MAPPED sketch mode (mapping = "window"; opt-in, pg_sketch_pairs / pg_sketch_pairs_k stay as they are).  A fragment's hits must
+ * fall inside ONE window of the reference, and a reference bin keeps one fragment — fastANI's mapping step and its one-to-one rule,
+ * which the mode above lacks (a k-mer found anywhere in the reference counts there).  Definition (pg_sketch_core.h), L = frag_len:
+ * a sampled k-mer occurrence of the reference has the coordinate g = its start in the records back to back WITHOUT separator, bin
+ * g / L of nb = ceil(genome length / L); window w = bins w and w + 1.  Per query fragment: c_b / h_w = its sampled occurrences whose
+ * k-mer occurs in bin b / in window w (once per bin and window); hits = max h_w, window = the lowest w reaching it, bin = window if
+ * c_window >= c_(window + 1), else window + 1 (both -1 when hits = 0); identity = (hits / n)^(1/k) as above; candidate iff hits >= 2 and
+ * identity >= 0.80; among the candidates of one bin the larger identity wins, ties go to the lower fragment index.  matches = the
+ * survivors, ani = their identities summed in fragment order / matches, fragments and the min_fraction rule as above.
+ * pg_sketch_pairs_mapped: the arguments, checks and result struct of pg_sketch_pairs_k.  Each genome used as a reference gets a
+ * position index (built on first use, cached under (kmer, scale): another frag_len does not rebuild it; released with the sketches by
+ * pg_clear_genomes), each query the grouped form of its sketch.  Limits: a reference of more than 8 192 bins (frag_len <= 65 535;
+ * 4 096 bins above that) is refused with PG_E_CAPACITY — the message names the limit in bases at the given frag_len (24.5 Mb at
+ * 3 000); the query's fragment count is not limited.
+ * pg_sketch_pair_fragments: one record per query fragment of ONE pair, in fragment order — where every fragment mapped.  At most
+ * `cap` records are written, *n_out = how many the pair has (PG_OK either way: call again with cap >= *n_out).  identity is 0 when
+ * hits < 2 or n = 0; kept = 1 for a survivor.
+ * pg_sketch_map_last_ms: out2[0] = milliseconds the latest pg_sketch_pairs_mapped / pg_sketch_pair_fragments call spent building
+ * position indexes and grouped sketches (0 when all were cached), out2[1] = in its mapping kernel (HIP events on the context's stream). */
+typedef struct {
+  int32_t window;      /* w*: the lowest window with the most hits, -1 when hits = 0 */
+  int32_t bin;         /* the reference bin the fragment competes for, -1 when hits = 0 */
+  uint32_t hits;       /* h = max over windows */
+  uint32_t n;          /* sampled k-mer occurrences of the fragment */
+  double identity;     /* (hits / n)^(1/k); 0 when hits < 2 or n = 0 */
+  int32_t kept;        /* 1: candidate and the winner of its bin */
+  int32_t reserved;
+} pg_sketch_fragment;
+int pg_sketch_pairs_mapped(pg_ctx* ctx, const int32_t* qry_ids, const int32_t* ref_ids, uint64_t n_pairs, int32_t kmer, int32_t frag_len,
+                           int32_t scale, double min_fraction, pg_sketch_result* out);
+int pg_sketch_pair_fragments(pg_ctx* ctx, int32_t qry_id, int32_t ref_id, int32_t kmer, int32_t frag_len, int32_t scale,
+                             pg_sketch_fragment* out, uint64_t cap, uint64_t* n_out);
+int pg_sketch_map_last_ms(pg_ctx* ctx, double* out2);
+
 /* ---- classify: clique sweep over identity thresholds ------------------------------------------------------------------
  * The compute of `pyani classify`.  These calls read caller matrices only: they touch no genome, seed list or ANIm worker slot, so
  * they need no interlock with the pg_anim_pairs_enqueue / _fetch lanes and may run while enqueued ANIm calls are in flight (own
@@ -453,7 +487,7 @@ int pg_profile_reset(pg_ctx* ctx);
 #define PG_K_ANIB_FRAG 12    /* anib_frag_kernel: anchors + X-drop extensions, one wave per (pair, fragment) */
 #define PG_K_ANIM_FWD 13     /* anim_postnuc_fwd_kernel: the forward extension off every cluster, ahead of the units' walks */
 #define PG_K_ANIM_BWD 14     /* anim_postnuc_rehearse_kernel + anim_postnuc_bwd_kernel: the walks rehearsed, their backward searches run ahead */
-#define PG_K_SKETCH_PAIRS 15 /* sketch_pairs_kernel: the sketch mode's containment pass (pg_sketch_pairs) */
+#define PG_K_SKETCH_PAIRS 15 /* sketch_pairs_kernel: the sketch mode's containment pass (pg_sketch_pairs); sketch_map_kernel of the mapped mode too */
 #define PG_K_CLASSIFY_EDGE 16  /* classify_edge_kernel: ordered minima, floors, edge list (pg_classify_edges) */
 #define PG_K_CLASSIFY_SWEEP 17 /* classify_death_kernel + classify_sweep_kernel: one workgroup per threshold step (pg_classify_sweep) */
 #define PG_K_CLUSTER_PDIST 18   /* cluster_pdist_kernel: Euclidean distances, upper-triangle tiles (pg_cluster_pdist, pg_cluster_linkage*) */

@@ -37,6 +37,7 @@ K_ANIB_ROWS_SCAN, K_ANIB_ROWS_PACK = 21, 22      # (20 is no slot: K_TOTAL is a 
 K_END = 23        # PG_K__END of the header: one past the last slot
 PG_SKETCH_NO_RESULT = 1
 PG_ANIB_SEARCH_SEEDS, PG_ANIB_SEARCH_ALL_DIAGS = 0, 1
+SKETCH_MAPPINGS = ("anywhere", "window")      # sketch mode: a fragment's k-mers found anywhere in the reference / inside one window of it
 ANIB_SEARCH_MODES = {"seeds": PG_ANIB_SEARCH_SEEDS, "all_diagonals": PG_ANIB_SEARCH_ALL_DIAGS}      # the names the Python layer uses
 
 # every symbol declared in include/pyani_gpu.h: (name, restype, argtypes)
@@ -85,6 +86,9 @@ SIGNATURES = {
     "pg_anib_get_search": (_int, [_vp, _P(_u32)]),
     "pg_sketch_pairs": (_int, [_vp, _vp, _vp, _u64, _i32, _i32, ctypes.c_double, _vp]),
     "pg_sketch_pairs_k": (_int, [_vp, _vp, _vp, _u64, _i32, _i32, _i32, ctypes.c_double, _vp]),
+    "pg_sketch_pairs_mapped": (_int, [_vp, _vp, _vp, _u64, _i32, _i32, _i32, ctypes.c_double, _vp]),
+    "pg_sketch_pair_fragments": (_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _u64, _P(_u64)]),
+    "pg_sketch_map_last_ms": (_int, [_vp, _vp]),
     "pg_classify_edges": (_int, [_vp, _vp, _vp, _u32, ctypes.c_double, ctypes.c_double, _P(_u64), _P(_u32)]),
     "pg_classify_edge_identities": (_int, [_vp, _vp, _u64]),
     "pg_classify_sweep": (_int, [_vp, _vp, _u64, _vp, _vp, _vp]),
@@ -125,6 +129,13 @@ def anib_search_code(name) -> int:
     if not isinstance(name, str) or name not in ANIB_SEARCH_MODES:
         raise ValueError(f"unknown ANIb search mode {name!r}: one of {sorted(ANIB_SEARCH_MODES)}")
     return ANIB_SEARCH_MODES[name]
+
+
+def sketch_mapping(name) -> str:
+    """A sketch mapping's name as given; ValueError for anything but "anywhere" / "window" (no library call is made)."""
+    if not isinstance(name, str) or name not in SKETCH_MAPPINGS:
+        raise ValueError(f"unknown sketch mapping {name!r}: one of {list(SKETCH_MAPPINGS)}")
+    return name
 
 
 class PyaniGpuError(RuntimeError):

@@ -27,6 +27,22 @@
 //   * ANI = mean identity of the matching fragments (summed in fragment order), matches = how many, fragments = all of them;
 //     fewer matches than min_fraction * fragments: no result (fastANI writes an empty file; parse_fastani_file raises).
 //
+// MAPPED variant (mapping = "window", opt-in: pg_sketch_pairs_mapped).  Everything above stays — k, canonical k-mers, sampling, the
+// query's fragments, which occurrence belongs to which fragment, n, frag_identity, frag_matches, the min_fraction rule — but a
+// fragment's hits must fall inside ONE window of the reference, as a fastANI mapping does, and a reference bin keeps one fragment:
+//   * a sampled occurrence of the reference has the coordinate g = its start in the genome's sequence with the records back to back
+//     and NO separator base; with L = frag_len, bin b = g / L of nb = ceil(genome length / L) bins (map_bins); window w (0 <= w < nb)
+//     is bins w and w + 1 (the last window: bin nb - 1 alone).  A window may span a record boundary;
+//   * per query fragment, for every sampled occurrence x (with multiplicity, as n counts them) B(x) = the bins in which its canonical
+//     k-mer occurs in the reference; c_b = occurrences with b in B(x); h_w = occurrences with B(x) meeting {w, w + 1}: an occurrence
+//     counts once per bin and once per window, however many copies the reference holds;
+//   * h = max h_w, w* = the LOWEST window that reaches it (map_window_key orders (h, w) that way); bin = w* if c_w* >= c_(w* + 1), else
+//     w* + 1 (map_pick_bin; a c beyond nb - 1 is 0) — without this a fragment that lies exactly on bin f ties between windows f - 1 and f
+//     and collides with its neighbour; h = 0: w* = bin = -1; identity = frag_identity(h, n, k), candidate iff frag_matches(h, n, k);
+//   * one fragment per bin: among the candidates of one bin the larger identity (compared as doubles) wins, ties go to the lowest
+//     fragment index (positive doubles order like their bit patterns: a max over the bits, then a min over the index among equals);
+//   * matches = the survivors, ANI = their identities summed in fragment order / matches, fragments = all of them; min_fraction as above.
+//
 // It is an ESTIMATE with its own columns, never written into the exact ANIm / ANIb matrices; tests/test_sketch_gpu.py holds the GPU
 // against the numpy restatement of this definition (bit-exact) and prices the estimate against the exact engine on C3 pairs.
 #pragma once
@@ -75,6 +91,13 @@ PGS_HD double frag_identity(uint32_t h, uint32_t n, int k) {
   }
   return y;
 }
+// ---- the mapped variant's coordinates and tie rules (see above) ----
+PGS_HD uint32_t map_bins(uint64_t genome_len, uint32_t frag_len) { return (uint32_t)((genome_len + frag_len - 1u) / frag_len); }
+// (hits, window) as one integer whose maximum is the most hits in the lowest window
+PGS_HD uint64_t map_window_key(uint32_t h, uint32_t w) { return ((uint64_t)h << 32) | (uint64_t)(0xFFFFFFFFu - w); }
+PGS_HD uint32_t map_key_hits(uint64_t key) { return (uint32_t)(key >> 32); }
+PGS_HD uint32_t map_key_window(uint64_t key) { return 0xFFFFFFFFu - (uint32_t)key; }
+PGS_HD int32_t map_pick_bin(int32_t w, uint32_t c_w, uint32_t c_next) { return c_w >= c_next ? w : w + 1; }
 PGS_HD bool frag_matches(uint32_t h, uint32_t n, int k) { return n > 0u && h >= 2u && frag_identity(h, n, k) >= MIN_IDENTITY; }
 
 }  // namespace pgs

@@ -346,16 +346,42 @@ class Engine:
     # -- sketch mode (fastANI-shaped estimate; never mixed into the exact results) ----------------------------------------------
     SKETCH_DTYPE = np.dtype([("ani", "<f8"), ("matches", "<i4"), ("fragments", "<i4"), ("status", "<i4"), ("reserved", "<i4")])
 
-    def sketch_pairs(self, qry_ids, ref_ids, frag_len: int = 3000, scale: int = 16, min_fraction: float = 0.2, kmer: int = 16) -> np.ndarray:
+    SKETCH_FRAGMENT_DTYPE = np.dtype([("window", "<i4"), ("bin", "<i4"), ("hits", "<u4"), ("n", "<u4"), ("identity", "<f8"), ("kept", "<i4"),
+                                      ("reserved", "<i4")])
+
+    def sketch_pairs(self, qry_ids, ref_ids, frag_len: int = 3000, scale: int = 16, min_fraction: float = 0.2, kmer: int = 16,
+                     mapping: str = "anywhere") -> np.ndarray:
         """pg_sketch_pairs_k: one record per ORDERED pair (query fragmented, reference as a k-mer set): ani (a fraction), matches,
-        fragments, status (0 / 1 = fewer than min_fraction of the fragments matched: fastANI writes no line then).  kmer: 8 ... 16."""
+        fragments, status (0 / 1 = fewer than min_fraction of the fragments matched: fastANI writes no line then).  kmer: 8 ... 16.
+        mapping="window" (pg_sketch_pairs_mapped, opt-in): a fragment's hits must lie inside one window of two frag_len bins of the
+        reference and a reference bin keeps one fragment, as fastANI's mapping does; any other name: ValueError."""
+        mapping = _lib.sketch_mapping(mapping)
         q, r = self._ids(qry_ids), self._ids(ref_ids)
         if len(q) != len(r):
             raise ValueError("qry_ids and ref_ids must have the same length")
         out = np.zeros(len(q), dtype=self.SKETCH_DTYPE)
-        self._check(self.lib.pg_sketch_pairs_k(self._h, q.ctypes.data, r.ctypes.data, len(q), int(kmer), int(frag_len), int(scale),
-                                               float(min_fraction), out.ctypes.data))
+        entry = self.lib.pg_sketch_pairs_mapped if mapping == "window" else self.lib.pg_sketch_pairs_k
+        self._check(entry(self._h, q.ctypes.data, r.ctypes.data, len(q), int(kmer), int(frag_len), int(scale), float(min_fraction), out.ctypes.data))
         return out
+
+    def sketch_pair_fragments(self, qry_id: int, ref_id: int, frag_len: int = 3000, scale: int = 16, kmer: int = 16) -> np.ndarray:
+        """pg_sketch_pair_fragments: where every fragment of the query mapped under mapping="window" — one SKETCH_FRAGMENT_DTYPE record
+        per fragment in fragment order: window, bin (-1: no hit), hits, n, identity (0 when hits < 2), kept (1: counted in the ANI)."""
+        n = ctypes.c_uint64(0)
+        out = np.zeros(0, dtype=self.SKETCH_FRAGMENT_DTYPE)
+        for _ in range(2):      # the count first, then the records
+            self._check(self.lib.pg_sketch_pair_fragments(self._h, int(qry_id), int(ref_id), int(kmer), int(frag_len), int(scale),
+                                                          out.ctypes.data if len(out) else None, len(out), ctypes.byref(n)))
+            if n.value <= len(out):
+                break
+            out = np.zeros(n.value, dtype=self.SKETCH_FRAGMENT_DTYPE)
+        return out[:n.value]
+
+    def sketch_map_last_ms(self) -> Tuple[float, float]:
+        """pg_sketch_map_last_ms: (index and grouping build, mapping kernel) milliseconds of the latest mapping="window" call."""
+        out = (ctypes.c_double * 2)()
+        self._check(self.lib.pg_sketch_map_last_ms(self._h, ctypes.addressof(out)))
+        return float(out[0]), float(out[1])
 
     # -- classify: clique sweep over identity thresholds (pyani_amd.classify drives these) -------------------------------------
     def classify_edges(self, identity: np.ndarray, coverage: np.ndarray, id_min: float = 0.8, cov_min: float = 0.5) -> Tuple[int, int]:

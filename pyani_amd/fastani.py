@@ -46,14 +46,17 @@ def check_kmer(kmerSize: int) -> int:
 
 
 def calculate_fastani_pairs(engine, qry_ids: Sequence[int], ref_ids: Sequence[int], fragLen: int = 3000, kmerSize: int = 16,
-                            minFraction: float = 0.2, scale: int = 16) -> np.ndarray:
-    """The estimates of many ordered pairs in one call (one record per pair: ani, matches, fragments, status)."""
+                            minFraction: float = 0.2, scale: int = 16, mapping: str = "anywhere") -> np.ndarray:
+    """The estimates of many ordered pairs in one call (one record per pair: ani, matches, fragments, status).  mapping: "anywhere"
+    (a fragment's k-mers found anywhere in the reference) or "window" (inside one window of the reference, one fragment per reference
+    bin: pg_sketch_pairs_mapped); the argument is passed on only when it is not the default."""
     kmer = check_kmer(kmerSize)
-    return engine.sketch_pairs(qry_ids, ref_ids, frag_len=fragLen, scale=scale, min_fraction=minFraction, kmer=kmer)
+    extra = {} if mapping == "anywhere" else {"mapping": mapping}
+    return engine.sketch_pairs(qry_ids, ref_ids, frag_len=fragLen, scale=scale, min_fraction=minFraction, kmer=kmer, **extra)
 
 
 def comparison_results(engine, files: Sequence[Path], ids: Sequence[int], fragLen: int = 3000, kmerSize: int = 16,
-                       minFraction: float = 0.2) -> Dict[Tuple[str, str], Optional[ComparisonResult]]:
+                       minFraction: float = 0.2, mapping: str = "anywhere") -> Dict[Tuple[str, str], Optional[ComparisonResult]]:
     """What pyani's loop over generate_fastani_commands + parse_fastani_file yields for an input set: every ordered pair INCLUDING a
     genome against itself (fastani.py:166-184 runs query x reference over the whole file list), keyed (query stem, reference stem);
     None where fastANI would have written an empty file."""
@@ -61,7 +64,7 @@ def comparison_results(engine, files: Sequence[Path], ids: Sequence[int], fragLe
     files = [Path(f) for f in files]
     q = [ids[i] for i in range(len(files)) for _ in files]
     r = [ids[j] for _ in files for j in range(len(files))]
-    res = calculate_fastani_pairs(engine, q, r, fragLen, kmerSize, minFraction)
+    res = calculate_fastani_pairs(engine, q, r, fragLen, kmerSize, minFraction, mapping=mapping)
     out, k = {}, 0
     for fq in files:
         for fr in files:

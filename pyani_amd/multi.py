@@ -257,10 +257,13 @@ class MultiEngine:
         return chunks
 
     # -- sketch mode ---------------------------------------------------------------------------------------------------------
-    def sketch_pairs(self, qry_ids, ref_ids, frag_len: int = 3000, scale: int = 16, min_fraction: float = 0.2, kmer: int = 16) -> np.ndarray:
-        """Engine.sketch_pairs over all devices.  The pairs are dealt by QUERY genome into one share per device — the pairs kernel
+    def sketch_pairs(self, qry_ids, ref_ids, frag_len: int = 3000, scale: int = 16, min_fraction: float = 0.2, kmer: int = 16,
+                     mapping: str = "anywhere") -> np.ndarray:
+        """Engine.sketch_pairs over all devices (mapping="window" included: the same deal).  The pairs are dealt by QUERY genome into one share per device — the pairs kernel
         streams a query's occurrence list once per up to four references, so a query's references belong together — ONE call per
         device; the records come back in the caller's order."""
+        from . import _lib
+        mapping = _lib.sketch_mapping(mapping)
         qa = np.ascontiguousarray(list(qry_ids), dtype=np.int32)
         ra = np.ascontiguousarray(list(ref_ids), dtype=np.int32)
         if len(qa) != len(ra):
@@ -270,9 +273,11 @@ class MultiEngine:
             return out
         shares = _shares_by_query(qa, len(self.engines))
 
+        extra = () if mapping == "anywhere" else (mapping,)      # (the default call stays the call it was)
+
         def run(e):
             idx = shares[self.engines.index(e)]
-            return e.sketch_pairs(qa[idx], ra[idx], frag_len, scale, min_fraction, kmer) if len(idx) else None
+            return e.sketch_pairs(qa[idx], ra[idx], frag_len, scale, min_fraction, kmer, *extra) if len(idx) else None
         for idx, res in zip(shares, self._all(run)):
             if res is not None:
                 out[idx] = res

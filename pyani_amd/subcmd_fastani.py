@@ -47,21 +47,25 @@ def result_path(outdir: Path, qstem: str, rstem: str) -> Path:
 
 def run_fastani(indir, outdir=None, fragLen: int = 3000, kmerSize: int = 16, minFraction: float = 0.2, recovery: bool = False,
                 write_output: bool = False, engine: Optional[Engine] = None, devices: Optional[List[int]] = None,
-                workers: Optional[int] = None) -> FastaniRun:
+                workers: Optional[int] = None, mapping: str = "anywhere") -> FastaniRun:
     """The sketch mode over every FASTA file of `indir`.  outdir is needed for recovery / write_output only.
-    devices / workers: run on several GPUs of this node (pyani_amd/multi.py); ignored when `engine` is given."""
+    devices / workers: run on several GPUs of this node (pyani_amd/multi.py); ignored when `engine` is given.
+    mapping: "anywhere" (default) or "window" (fastani.calculate_fastani_pairs).  Files, rows and matrices keep their shape.  A
+    recovery run trusts the files it finds: as with kmerSize, the caller keeps ONE outdir per mapping."""
     if write_output and outdir is None:
         raise ValueError("write_output needs an output directory")     # before any work is done
     if recovery and outdir is None:
         raise ValueError("recovery mode needs the output directory of the earlier run")
     kmerSize = fastani.check_kmer(kmerSize)
+    from . import _lib
+    mapping = _lib.sketch_mapping(mapping)
     own = None
     if engine is None and (devices is not None or workers):
         from . import multi
         engine = multi.engine_for(devices, workers)
         own = engine if isinstance(engine, multi.MultiEngine) else None
     try:
-        return _run_fastani(indir, outdir, fragLen, kmerSize, minFraction, recovery, write_output, engine or default_engine())
+        return _run_fastani(indir, outdir, fragLen, kmerSize, minFraction, recovery, write_output, engine or default_engine(), mapping)
     finally:
         if own is not None:
             own.close()
@@ -74,7 +78,7 @@ def _parsed(path: Path) -> Optional[fastani.ComparisonResult]:
         return None
 
 
-def _run_fastani(indir, outdir, fragLen, kmerSize, minFraction, recovery, write_output, eng) -> FastaniRun:
+def _run_fastani(indir, outdir, fragLen, kmerSize, minFraction, recovery, write_output, eng, mapping="anywhere") -> FastaniRun:
     paths = files.get_fasta_paths(Path(indir))
     stems = [p.stem for p in paths]
     if len(set(stems)) != len(stems):
@@ -99,7 +103,7 @@ def _run_fastani(indir, outdir, fragLen, kmerSize, minFraction, recovery, write_
         for p, (gid, total, _) in zip(paths, eng.add_fasta_batch(paths)):
             ids[p.stem], lengths[p.stem] = gid, total
         if todo:
-            recs = fastani.calculate_fastani_pairs(eng, [ids[q] for q, _ in todo], [ids[r] for _, r in todo], fragLen, kmerSize, minFraction)
+            recs = fastani.calculate_fastani_pairs(eng, [ids[q] for q, _ in todo], [ids[r] for _, r in todo], fragLen, kmerSize, minFraction, mapping=mapping)
             if write_output:
                 (Path(outdir) / ALIGNDIR).mkdir(parents=True, exist_ok=True)
             for (q, r), x in zip(todo, recs):
