@@ -370,6 +370,27 @@ int pg_sketch_pair_fragments(pg_ctx* ctx, int32_t qry_id, int32_t ref_id, int32_
                              pg_sketch_fragment* out, uint64_t cap, uint64_t* n_out);
 int pg_sketch_map_last_ms(pg_ctx* ctx, double* out2);
 
+/* ---- screen: all-vs-all matrix of shared sampled k-mers (the pre-filter that says which pairs are worth an exact
+ * comparison).  Definition (pyani_amd/csrc/pg_screen_core.h): S(g) = the DISTINCT canonical k-mers of genome g (8 <= kmer <= 16, all
+ * records, either strand, windows of k unambiguous bases inside one record) with mix32(k-mer) & (scale - 1) == 0; scale a power of two,
+ * 1 ... 65 536.  sizes_out[a] = |S(a)|; shared_out[a * n + b] = |S(a) & S(b)| (symmetric, the diagonal = sizes), rows and columns in the
+ * order of genome_ids.  Integers only: containment, Jaccard index and the identity estimate are the caller's arithmetic
+ * (pyani_amd/screen.py).  No pair loop: the (k-mer, genome) keys of all n genomes are sorted once, and a k-mer held by m genomes adds one to
+ * m (m - 1) / 2 cells.  An ESTIMATE for triage, never written into the exact ANIm / ANIb results.
+ * part / n_parts (1 <= n_parts <= 4096): the call counts only the k-mers of the slice bins [4096 part / n_parts, 4096 (part + 1) / n_parts),
+ * bin = (mix32(k-mer) >> log2(scale)) & 4095; the sizes and matrices of all parts add up to those of n_parts = 1, exactly.
+ * Limits: n <= 8192 and no id twice (PG_E_ARG; the count is checked before the ids are read); kmer or scale outside the above: PG_E_ARG.
+ * The keys are worked off in slices of whole bins of at most max_keys keys (pg_screen_set_budget; 0 = the default 2^28, at most 2^30:
+ * PG_E_ARG beyond); one bin holding more than that: PG_E_NOMEM, the message says so.  The result does not depend on the budget.  Every
+ * device buffer of the call is released before it returns; the sketch mode's caches and the ANIm seed lists are not touched (device
+ * memory running short releases the ANIm launch scratch of an idle context, as in the sketch mode).
+ * pg_screen_last: of the latest pg_screen_matrix on the context, out5 = keys, distinct (k-mer, genome) entries, k-mers held by >= 2
+ * genomes, pair increments, slices; ms3 = milliseconds of the scan passes, of sorting and grouping, of the count kernel (HIP events). */
+int pg_screen_matrix(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kmer, int32_t scale, uint32_t part, uint32_t n_parts,
+                     uint32_t* sizes_out, uint32_t* shared_out);
+int pg_screen_set_budget(pg_ctx* ctx, uint64_t max_keys);
+int pg_screen_last(pg_ctx* ctx, uint64_t* out5, double* ms3);
+
 /* ---- classify: clique sweep over identity thresholds ------------------------------------------------------------------
  * The compute of `pyani classify`.  These calls read caller matrices only: they touch no genome, seed list or ANIm worker slot, so
  * they need no interlock with the pg_anim_pairs_enqueue / _fetch lanes and may run while enqueued ANIm calls are in flight (own

@@ -89,6 +89,9 @@ SIGNATURES = {
     "pg_sketch_pairs_mapped": (_int, [_vp, _vp, _vp, _u64, _i32, _i32, _i32, ctypes.c_double, _vp]),
     "pg_sketch_pair_fragments": (_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _u64, _P(_u64)]),
     "pg_sketch_map_last_ms": (_int, [_vp, _vp]),
+    "pg_screen_matrix": (_int, [_vp, _vp, _u32, _i32, _i32, _u32, _u32, _vp, _vp]),
+    "pg_screen_set_budget": (_int, [_vp, _u64]),
+    "pg_screen_last": (_int, [_vp, _vp, _vp]),
     "pg_classify_edges": (_int, [_vp, _vp, _vp, _u32, ctypes.c_double, ctypes.c_double, _P(_u64), _P(_u32)]),
     "pg_classify_edge_identities": (_int, [_vp, _vp, _u64]),
     "pg_classify_sweep": (_int, [_vp, _vp, _u64, _vp, _vp, _vp]),

@@ -99,6 +99,9 @@ struct pg_ctx {
   void* sketch_store = nullptr;    // per-genome k-mer sketches of the sketch mode (pg_sketch.hip), built on first use
   void* classify_state = nullptr;  // resident edge state of the classify sweep (pg_classify.hip), replaced by every pg_classify_edges
   void* dist_state = nullptr;      // resident values of the distribution calls (pg_dist.hip), replaced by every pg_dist_load
+  uint64_t screen_max_keys = 0;          // pg_screen_set_budget: keys of one slice of a screen call (0: the default, pg_screen_core.h)
+  uint64_t screen_last[5] = {0, 0, 0, 0, 0};   // pg_screen_last: keys, distinct entries, groups of >= 2, pair increments, slices of the latest pg_screen_matrix
+  double screen_ms[3] = {0.0, 0.0, 0.0};      // ... and its scan, sort + group and count milliseconds (HIP events on the context's stream)
   double dist_ms[3] = {0.0, 0.0, 0.0};   // kernel milliseconds of the latest pg_dist_load / _hist / _kde while profiling is on (pg_dist_last_ms)
   std::mutex anim_mu, err_mu, prof_mu;
   int anib_word_tier = 1;      // fragment mode: search failed fragments again with blastn-sized (11-mer) seeds
@@ -215,3 +218,24 @@ void pg_dist_drop(pg_ctx* ctx);         // ... the distribution calls' resident 
 int pg_anib_reduce_run(pg_ctx* ctx, uint32_t n_pairs, const uint64_t* offsets, const uint32_t* n_frags, const int32_t* frag,
                        const int32_t* length, const int32_t* mismatch, const int32_t* gaps, const int32_t* qlen,
                        const double* pident, int64_t* aln_out, int64_t* err_out, double* pid_out);
+
+// Device memory for a sketch (pg_sketch.hip) or a screen call (pg_screen.hip).  The ANIm engine keeps its per-launch scratch and per-genome seed lists for reuse (after a 1000-genome
+// grid: ~200 GB of the 288); a sketch that does not fit beside them takes their place — they are rebuilt on the next ANIm call.
+template <typename T>
+int sk_malloc(pg_ctx* ctx, PgDevBuf<T>& b, size_t n) {      // an empty buffer gets n elements
+  // (PYANI_SKETCH_ALLOC_FAIL under PYANI_DEV_KNOBS=1: every first attempt counts as failed, so that a test can walk the fallback)
+  static const bool fail_first = pg_dev_env("PYANI_SKETCH_ALLOC_FAIL") != nullptr;
+  if (!fail_first && b.reserve(n) == hipSuccess) return PG_OK;
+  (void)hipGetLastError();
+  // The ANIm launch scratch takes the sketches' place — only on an IDLE context: never under an enqueued ANIm call (its thread is using
+  // that scratch), and only after everything the worker streams were given has finished.
+  {
+    std::lock_guard<std::mutex> lk(ctx->anim_async_mu);
+    if (ctx->anim_async[0].busy || ctx->anim_async[1].busy)
+      return pg_fail(ctx, PG_E_NOMEM, "sketch: device memory is short and enqueued ANIm calls are in flight (fetch them first: their launch scratch cannot be released under them)");
+  }
+  PG_HIP(ctx, hipDeviceSynchronize());
+  pg_anim_free_scratch(ctx);
+  PG_HIP_MSG(ctx, "sketch: no device memory, the ANIm scratch released: ", b.reserve(n));
+  return PG_OK;
+}

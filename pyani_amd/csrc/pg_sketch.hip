@@ -69,27 +69,6 @@ struct SketchStore {
   double map_ms[2] = {0.0, 0.0};                    // pg_sketch_map_last_ms
 };
 
-// Device memory for a sketch.  The ANIm engine keeps its per-launch scratch and per-genome seed lists for reuse (after a 1000-genome
-// grid: ~200 GB of the 288); a sketch that does not fit beside them takes their place — they are rebuilt on the next ANIm call.
-template <typename T>
-int sk_malloc(pg_ctx* ctx, PgDevBuf<T>& b, size_t n) {      // an empty buffer gets n elements
-  // (PYANI_SKETCH_ALLOC_FAIL under PYANI_DEV_KNOBS=1: every first attempt counts as failed, so that a test can walk the fallback)
-  static const bool fail_first = pg_dev_env("PYANI_SKETCH_ALLOC_FAIL") != nullptr;
-  if (!fail_first && b.reserve(n) == hipSuccess) return PG_OK;
-  (void)hipGetLastError();
-  // The ANIm launch scratch takes the sketches' place — only on an IDLE context: never under an enqueued ANIm call (its thread is using
-  // that scratch), and only after everything the worker streams were given has finished.
-  {
-    std::lock_guard<std::mutex> lk(ctx->anim_async_mu);
-    if (ctx->anim_async[0].busy || ctx->anim_async[1].busy)
-      return pg_fail(ctx, PG_E_NOMEM, "sketch: device memory is short and enqueued ANIm calls are in flight (fetch them first: their launch scratch cannot be released under them)");
-  }
-  PG_HIP(ctx, hipDeviceSynchronize());
-  pg_anim_free_scratch(ctx);
-  PG_HIP_MSG(ctx, "sketch: no device memory, the ANIm scratch released: ", b.reserve(n));
-  return PG_OK;
-}
-
 // record of stream position p (rec_start[r] <= p < rec_start[r + 1])
 __device__ __forceinline__ int rec_of(const int32_t* __restrict__ rec_start, int n_rec, int32_t p) {
   int lo = 0, hi = n_rec - 1;

@@ -383,6 +383,31 @@ class Engine:
         self._check(self.lib.pg_sketch_map_last_ms(self._h, ctypes.addressof(out)))
         return float(out[0]), float(out[1])
 
+    # -- screen: all-vs-all matrix of shared sampled k-mers (pyani_amd.screen drives these; an estimate for triage) -----------------
+    def screen_matrix(self, ids, kmer: int = 16, scale: int = 256, part: int = 0, n_parts: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+        """pg_screen_matrix: (sizes uint32[n], shared uint32[n, n]) of the genomes in the order given — sizes[a] = the distinct sampled
+        canonical k-mers of genome a, shared[a, b] = how many of them genome b holds too (symmetric, the diagonal = sizes).  part /
+        n_parts: only the k-mers of that share of the 4096 slice bins; the parts' results add up to the whole, exactly."""
+        a = self._ids(ids)
+        n = len(a)
+        sizes = np.zeros(n, dtype=np.uint32)
+        shared = np.zeros((n, n), dtype=np.uint32) if n <= 8192 else np.zeros((0, 0), dtype=np.uint32)      # (beyond: refused before anything is read)
+        self._check(self.lib.pg_screen_matrix(self._h, a.ctypes.data if n else None, n, int(kmer), int(scale), int(part), int(n_parts),
+                                              sizes.ctypes.data if n else None, shared.ctypes.data if shared.size else None))
+        return sizes, shared
+
+    def screen_set_budget(self, max_keys: int = 0) -> None:
+        """pg_screen_set_budget: the (k-mer, genome) keys one slice of a screen_matrix call may hold; 0 = the default (2^28)."""
+        self._check(self.lib.pg_screen_set_budget(self._h, int(max_keys)))
+
+    def screen_last(self) -> dict:
+        """pg_screen_last: counts and stage milliseconds of the latest screen_matrix on this engine."""
+        c = (ctypes.c_uint64 * 5)()
+        ms = (ctypes.c_double * 3)()
+        self._check(self.lib.pg_screen_last(self._h, ctypes.addressof(c), ctypes.addressof(ms)))
+        return {"keys": int(c[0]), "distinct": int(c[1]), "groups": int(c[2]), "pair_increments": int(c[3]), "slices": int(c[4]),
+                "scan_ms": float(ms[0]), "sort_group_ms": float(ms[1]), "count_ms": float(ms[2])}
+
     # -- classify: clique sweep over identity thresholds (pyani_amd.classify drives these) -------------------------------------
     def classify_edges(self, identity: np.ndarray, coverage: np.ndarray, id_min: float = 0.8, cov_min: float = 0.5) -> Tuple[int, int]:
         """pg_classify_edges: the edges of build_graph_from_results (pyani_classify.py:90-111) from two n x n float64 matrices in one

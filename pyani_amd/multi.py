@@ -283,6 +283,29 @@ class MultiEngine:
                 out[idx] = res
         return out
 
+    # -- screen ----------------------------------------------------------------------------------------------------------------
+    def screen_matrix(self, ids, kmer: int = 16, scale: int = 256, part: int = 0, n_parts: int = 1):
+        """Engine.screen_matrix over all devices: the genome store is replicated, so the work is cut by slice bin, not by genome:
+        device d of D takes part D * part + d of D * n_parts — together exactly the bins of the caller's part — and the host adds the
+        integer results: equal to one engine's, whatever the number of devices."""
+        ids = np.ascontiguousarray(list(ids), dtype=np.int32)
+        d = len(self.engines)
+        if d * int(n_parts) > 4096:      # more parts than slice bins: the devices beyond have nothing to take
+            return self.engines[0].screen_matrix(ids, kmer, scale, part, n_parts)
+        res = self._all(lambda e: e.screen_matrix(ids, kmer, scale, int(part) * d + self.engines.index(e), int(n_parts) * d))
+        sizes = np.sum([r[0] for r in res], axis=0, dtype=np.uint64).astype(np.uint32)
+        shared = np.sum([r[1] for r in res], axis=0, dtype=np.uint64).astype(np.uint32)
+        return sizes, shared
+
+    def screen_set_budget(self, max_keys: int = 0):
+        for e in self.engines:
+            e.screen_set_budget(max_keys)
+
+    def screen_last(self) -> dict:
+        """Engine.screen_last of every device: the counts summed, the milliseconds of the slowest device per stage."""
+        per = [e.screen_last() for e in self.engines]
+        return {k: (max if k.endswith("_ms") else sum)(p[k] for p in per) for k in per[0]}
+
     def anib_rows_batch(self, qry_ids, sbj_ids, fragsize: int = 1020):
         """Engine.anib_rows_batch over all devices: the pair list is cut exactly as for anib_pairs, the devices pull chunks, and
         the parts are put back together in the caller's pair order (merge_anib_row_parts).  Returns (results, offsets, rows).

@@ -1,0 +1,75 @@
+"""The screen over a directory of FASTA files: the driver of pyani_amd.screen, in the shape of the other run_* drivers.  pyani has no
+such subcommand — this is the front end a caller puts before run_anim / run_anib on a large collection: every file of `indir` in sorted
+order, ONE engine call for all of them, and the result as labelled frames.  No CLI and no database.
+
+With write_output the frames go to `<outdir>/screen_output/screen_{shared,containment,identity}.tab` in the shape of the legacy
+matrix files (tab-separated, labels on both axes).  These are the screen's OWN files: an estimate, never merged into an ANIm or ANIb result.
+Single-process: one engine, or several GPUs of this node through pyani_amd.multi.MultiEngine (devices / workers).
+"""
+from pathlib import Path
+from typing import Dict, List, NamedTuple, Optional
+
+from . import files, screen
+from .engine import Engine, default_engine
+
+OUTDIR = "screen_output"
+TAB_NAMES = ("shared", "containment", "identity")
+
+
+class ScreenRun(NamedTuple):
+    lengths: Dict[str, int]          # stem -> genome length, file order
+    result: screen.ScreenResult      # labels = the stems, file order
+
+
+def tab_path(outdir, name: str) -> Path:
+    return Path(outdir) / OUTDIR / f"screen_{name}.tab"
+
+
+def write_tabs(outdir, result: screen.ScreenResult) -> List[Path]:
+    (Path(outdir) / OUTDIR).mkdir(parents=True, exist_ok=True)
+    frames = {"shared": result.shared_frame(), "containment": result.containment(), "identity": result.identity()}
+    out = []
+    for name in TAB_NAMES:
+        frames[name].to_csv(tab_path(outdir, name), index=True, sep="\t")
+        out.append(tab_path(outdir, name))
+    return out
+
+
+def run_screen(indir, outdir=None, kmerSize: int = screen.DEFAULT_KMER, scale: int = screen.DEFAULT_SCALE, write_output: bool = False,
+               engine: Optional[Engine] = None, devices: Optional[List[int]] = None, workers: Optional[int] = None) -> ScreenRun:
+    """The screen over every FASTA file of `indir`.  outdir is needed for write_output only.
+    devices / workers: run on several GPUs of this node (pyani_amd/multi.py); ignored when `engine` is given."""
+    if write_output and outdir is None:
+        raise ValueError("write_output needs an output directory")     # before any work is done
+    kmerSize, scale = screen.check_params(kmerSize, scale)
+    own = None
+    if engine is None and (devices is not None or workers):
+        from . import multi
+        engine = multi.engine_for(devices, workers)
+        own = engine if isinstance(engine, multi.MultiEngine) else None
+    try:
+        return _run_screen(indir, outdir, kmerSize, scale, write_output, engine or default_engine())
+    finally:
+        if own is not None:
+            own.close()
+
+
+def _run_screen(indir, outdir, kmerSize, scale, write_output, eng) -> ScreenRun:
+    paths = files.get_fasta_paths(Path(indir))
+    stems = [p.stem for p in paths]
+    if len(set(stems)) != len(stems):
+        raise ValueError("two input files share a stem (pyani keys every result by Path.stem)")
+    scratch_store = eng.genome_count() == 0
+    lengths: Dict[str, int] = {}
+    try:
+        ids = []
+        for p, (gid, total, _) in zip(paths, eng.add_fasta_batch(paths)):
+            ids.append(gid)
+            lengths[p.stem] = total
+        result = screen.screen_genomes(eng, ids, stems, kmerSize, scale)
+    finally:
+        if scratch_store:
+            eng.clear_genomes()
+    if write_output:
+        write_tabs(outdir, result)
+    return ScreenRun(lengths, result)
