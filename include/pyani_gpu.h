@@ -391,6 +391,33 @@ int pg_screen_matrix(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t
 int pg_screen_set_budget(pg_ctx* ctx, uint64_t max_keys);
 int pg_screen_last(pg_ctx* ctx, uint64_t* out5, double* ms3);
 
+/* ---- screen, the selection: which cells of the matrix name a pair worth an exact comparison, decided on the device so that only the kept
+ * pairs come back.  One n x n uint32 matrix is RESIDENT on the context between the calls:
+ * pg_screen_hold is pg_screen_matrix without the n^2 read-back: same arguments, refusals and pg_screen_last; the finished matrix stays on
+ * the device and only sizes_out comes back.  n == 0 is PG_OK and leaves nothing resident.
+ * pg_screen_load makes the caller's matrix (row-major, 1 <= n <= 8192: PG_E_ARG outside, the count checked before the matrix is read) the
+ * resident one; it need not be symmetric nor agree with any sizes.
+ * Either call, once its arguments have passed, releases the matrix and selection of an earlier one BEFORE it makes its own (never two at a
+ * time): a call refused for its arguments changes nothing, one that fails later leaves no matrix resident.
+ * pg_screen_select keeps the cell (a, b) iff a != b and shared[a][b] >= min(need[a], need[b]) — every cell by its OWN value, a diagonal cell
+ * never — and packs the kept cells as (a, b, shared[a][b]) in row-major order (the order of numpy's nonzero; no atomics: a count pass, an
+ * exclusive scan, a fill pass).  need: n uint32 (pyani_amd.screen.identity_thresholds turns an identity threshold into them);
+ * *n_pairs_out = the number of kept cells.  The selection stays on the device until the next pg_screen_select on the context or the
+ * release of the matrix; any number of selections may follow one hold / load.  PG_E_ARG without a resident matrix or when n is not its
+ * size; PG_E_NOMEM when the kept cells (12 bytes each) do not fit.
+ * pg_screen_select_read copies the latest selection to the host: a_out, b_out int32, shared_out uint32, n_pairs entries each (may be NULL
+ * when nothing was kept).  PG_E_ARG before any selection over the resident matrix.
+ * pg_screen_fetch copies the resident matrix to the host (n x n uint32).  PG_E_ARG without one.
+ * pg_screen_release frees the matrix and the selection (PG_OK when there is none); pg_clear_genomes and pg_destroy do the same, and so does
+ * a sketch or screen call that finds device memory short while the matrix sits idle. */
+int pg_screen_hold(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kmer, int32_t scale, uint32_t part, uint32_t n_parts,
+                   uint32_t* sizes_out);
+int pg_screen_load(pg_ctx* ctx, const uint32_t* shared, uint32_t n);
+int pg_screen_select(pg_ctx* ctx, const uint32_t* need, uint32_t n, uint64_t* n_pairs_out);
+int pg_screen_select_read(pg_ctx* ctx, int32_t* a_out, int32_t* b_out, uint32_t* shared_out);
+int pg_screen_fetch(pg_ctx* ctx, uint32_t* shared_out);
+int pg_screen_release(pg_ctx* ctx);
+
 /* ---- classify: clique sweep over identity thresholds ------------------------------------------------------------------
  * The compute of `pyani classify`.  These calls read caller matrices only: they touch no genome, seed list or ANIm worker slot, so
  * they need no interlock with the pg_anim_pairs_enqueue / _fetch lanes and may run while enqueued ANIm calls are in flight (own

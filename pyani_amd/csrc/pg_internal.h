@@ -99,6 +99,7 @@ struct pg_ctx {
   void* sketch_store = nullptr;    // per-genome k-mer sketches of the sketch mode (pg_sketch.hip), built on first use
   void* classify_state = nullptr;  // resident edge state of the classify sweep (pg_classify.hip), replaced by every pg_classify_edges
   void* dist_state = nullptr;      // resident values of the distribution calls (pg_dist.hip), replaced by every pg_dist_load
+  void* screen_state = nullptr;    // resident matrix of the screen's selection (pg_screen.hip), replaced by every pg_screen_hold / pg_screen_load
   uint64_t screen_max_keys = 0;          // pg_screen_set_budget: keys of one slice of a screen call (0: the default, pg_screen_core.h)
   uint64_t screen_last[5] = {0, 0, 0, 0, 0};   // pg_screen_last: keys, distinct entries, groups of >= 2, pair increments, slices of the latest pg_screen_matrix
   double screen_ms[3] = {0.0, 0.0, 0.0};      // ... and its scan, sort + group and count milliseconds (HIP events on the context's stream)
@@ -215,6 +216,7 @@ void pg_anim_drop_lists(pg_ctx* ctx);   // per-genome seed lists: must go when t
 void pg_sketch_drop(pg_ctx* ctx);       // ... and the sketches of the sketch mode (pg_sketch.hip)
 void pg_classify_drop(pg_ctx* ctx);     // ... the classify sweep's edge state (pg_classify.hip): goes with the context or on request
 void pg_dist_drop(pg_ctx* ctx);         // ... the distribution calls' resident values (pg_dist.hip): the same
+void pg_screen_drop(pg_ctx* ctx);       // ... the screen's resident matrix and selection (pg_screen.hip): the same, and with the genome store
 int pg_anib_reduce_run(pg_ctx* ctx, uint32_t n_pairs, const uint64_t* offsets, const uint32_t* n_frags, const int32_t* frag,
                        const int32_t* length, const int32_t* mismatch, const int32_t* gaps, const int32_t* qlen,
                        const double* pident, int64_t* aln_out, int64_t* err_out, double* pid_out);
@@ -236,6 +238,7 @@ int sk_malloc(pg_ctx* ctx, PgDevBuf<T>& b, size_t n) {      // an empty buffer g
   }
   PG_HIP(ctx, hipDeviceSynchronize());
   pg_anim_free_scratch(ctx);
+  pg_screen_drop(ctx);      // an idle resident matrix of the screen's selection goes too (no call of its own allocates through here while it reads one)
   PG_HIP_MSG(ctx, "sketch: no device memory, the ANIm scratch released: ", b.reserve(n));
   return PG_OK;
 }

@@ -21,6 +21,13 @@
 //                           j upward in one matrix row; shared[g_i * n + g_j] += 1 by a uint32 atomic in HBM — integer adds: the result
 //                           does not depend on the order of arrival.
 //   C4 screen_finish_kernel after the last slice: the upper triangle mirrored, the diagonal = size.
+//
+// The SELECTION: pg_screen_hold / pg_screen_load leave an n x n matrix resident on the context (ScreenState), and
+// pg_screen_select packs the cells a != b with shared[a][b] >= min(need[a], need[b]) as (a, b, shared[a][b]) in row-major order:
+//   C5 screen_select_kernel a wave task is SEL_CELLS consecutive cells of one row, 64 at a time (coalesced).  Count pass: the popcounts of the
+//                           task's ballots, one uint64 per task; hipcub exclusive scan; fill pass: the same ballots again, every kept cell
+//                           written at its task's offset + the kept cells before it in the task.  No cursor, no atomic: the order is the
+//                           order of the cells.  Two streaming passes over 4 n^2 bytes.
 #include <algorithm>
 #include <hipcub/hipcub.hpp>
 #include <string>
@@ -199,6 +206,64 @@ __global__ __launch_bounds__(256) void screen_finish_kernel(uint32_t* __restrict
   }
 }
 
+constexpr uint32_t SEL_STEPS = 8;                  // 64-cell steps of one wave task
+constexpr uint32_t SEL_CELLS = 64u * SEL_STEPS;    // cells of one wave task: a piece of ONE matrix row
+
+// Tasks row-major: task = row * tpr + piece (tpr = pieces per row).  !FILL: counts[task] = kept cells of the task, counts[n_tasks] = 0 (the
+// scan's total lands there).  FILL: counts = the scanned offsets; total = their last entry, the room of the three output arrays.
+template <bool FILL>
+__global__ __launch_bounds__(256) void screen_select_kernel(const uint32_t* __restrict__ shared, const uint32_t* __restrict__ need, uint32_t n, uint32_t tpr,
+                                                             uint32_t n_tasks, unsigned long long* __restrict__ counts, unsigned long long total,
+                                                             int32_t* __restrict__ a_out, int32_t* __restrict__ b_out, uint32_t* __restrict__ s_out) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), n_waves = gridDim.x * (blockDim.x >> 6);
+  const unsigned long long below = (1ull << lane) - 1ull;
+  for (uint32_t task = wave; task < n_tasks; task += n_waves) {      // (uniform over the wave: every lane reaches every ballot)
+    const uint32_t row = task / tpr, col0 = (task % tpr) * SEL_CELLS;
+    const uint32_t need_row = need[row];
+    const uint32_t* __restrict__ cells = shared + (size_t)row * n;
+    uint32_t v[SEL_STEPS];
+    bool keep[SEL_STEPS];
+#pragma unroll
+    for (uint32_t u = 0; u < SEL_STEPS; ++u) {
+      const uint32_t col = col0 + 64u * u + lane;
+      const bool in = col < n;
+      v[u] = in ? cells[col] : 0u;
+      const uint32_t need_col = in ? need[col] : 0u;
+      keep[u] = in && col != row && v[u] >= (need_row < need_col ? need_row : need_col);
+    }
+    if (!FILL) {
+      uint32_t c = 0;
+#pragma unroll
+      for (uint32_t u = 0; u < SEL_STEPS; ++u) c += (uint32_t)__popcll(__ballot(keep[u]));
+      if (lane == 0) counts[task] = c;
+    } else {
+      unsigned long long at = counts[task];
+#pragma unroll
+      for (uint32_t u = 0; u < SEL_STEPS; ++u) {
+        const unsigned long long bal = __ballot(keep[u]);
+        const unsigned long long mine = at + (unsigned long long)__popcll(bal & below);
+        if (keep[u] && mine < total) {
+          a_out[mine] = (int32_t)row; b_out[mine] = (int32_t)(col0 + 64u * u + lane); s_out[mine] = v[u];
+        }
+        at += (unsigned long long)__popcll(bal);
+      }
+    }
+  }
+  if (!FILL && blockIdx.x == 0 && threadIdx.x == 0) counts[n_tasks] = 0ull;
+}
+
+struct ScreenState {      // the resident matrix of pg_screen_hold / pg_screen_load and the latest selection over it
+  uint32_t n = 0;
+  PgDevBuf<uint32_t> d_shared;      // n x n
+  bool selected = false;
+  uint64_t n_sel = 0;
+  PgDevBuf<int32_t> d_a, d_b;       // n_sel each
+  PgDevBuf<uint32_t> d_s;
+};
+
+ScreenState* state_of(pg_ctx* ctx) { return static_cast<ScreenState*>(ctx->screen_state); }
+
 struct ScreenEvents {      // pg_screen_last: event pairs on the context's stream, summed per stage after the call's last synchronisation
   std::vector<hipEvent_t> ev;
   std::vector<int> stage;      // of the pair ev[2 i], ev[2 i + 1]
@@ -242,22 +307,29 @@ extern "C" int pg_screen_last(pg_ctx* ctx, uint64_t* out5, double* ms3) {
   return PG_OK;
 }
 
-extern "C" int pg_screen_matrix(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kmer, int32_t scale, uint32_t part, uint32_t n_parts,
-                                uint32_t* sizes_out, uint32_t* shared_out) {
-  if (!ctx) return PG_E_ARG;
+namespace {
+
+// the argument checks of pg_screen_matrix and pg_screen_hold (want_shared: the call has a matrix to copy out, shared_out)
+int screen_check(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kmer, int32_t scale, uint32_t part, uint32_t n_parts, const uint32_t* sizes_out,
+                 bool want_shared, const uint32_t* shared_out) {
   if (n > pgscr::MAX_GENOMES) return pg_fail(ctx, PG_E_ARG, "screen: more than 8192 genomes in one call");      // (before the ids are read)
-  if (n && (!genome_ids || !sizes_out || !shared_out)) return pg_fail(ctx, PG_E_ARG, "bad argument");
+  if (n && (!genome_ids || !sizes_out || (want_shared && !shared_out))) return pg_fail(ctx, PG_E_ARG, "bad argument");
   if (kmer < pgs::K_MIN || kmer > pgs::K_MAX) return pg_fail(ctx, PG_E_ARG, "screen: the k-mer size must be 8 ... 16");
   if (!pgscr::valid_scale(scale)) return pg_fail(ctx, PG_E_ARG, "screen: scale must be a power of two, 1 ... 65536");
   if (n_parts < 1 || n_parts > pgscr::N_BINS || part >= n_parts) return pg_fail(ctx, PG_E_ARG, "screen: 1 <= n_parts <= 4096 and part < n_parts");
-  {
-    std::vector<char> seen(ctx->genomes.size(), 0);
-    for (uint32_t i = 0; i < n; ++i) {
-      if (genome_ids[i] < 0 || (size_t)genome_ids[i] >= ctx->genomes.size()) return pg_fail(ctx, PG_E_ARG, "genome id out of range");
-      if (seen[genome_ids[i]]) return pg_fail(ctx, PG_E_ARG, "screen: genome id " + std::to_string(genome_ids[i]) + " is given twice");
-      seen[genome_ids[i]] = 1;
-    }
+  std::vector<char> seen(ctx->genomes.size(), 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (genome_ids[i] < 0 || (size_t)genome_ids[i] >= ctx->genomes.size()) return pg_fail(ctx, PG_E_ARG, "genome id out of range");
+    if (seen[genome_ids[i]]) return pg_fail(ctx, PG_E_ARG, "screen: genome id " + std::to_string(genome_ids[i]) + " is given twice");
+    seen[genome_ids[i]] = 1;
   }
+  return PG_OK;
+}
+
+// The screen of checked arguments.  The finished matrix is left in d_shared (the caller's: pg_screen_matrix lets it go, pg_screen_hold keeps
+// it); sizes_out, and shared_out where it is given, are on the host when this returns.
+int screen_run(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kmer, int32_t scale, uint32_t part, uint32_t n_parts, uint32_t* sizes_out,
+               uint32_t* shared_out, PgDevBuf<uint32_t>& d_shared) {
   for (int i = 0; i < 5; ++i) ctx->screen_last[i] = 0;
   for (int i = 0; i < 3; ++i) ctx->screen_ms[i] = 0.0;
   if (n == 0) return PG_OK;
@@ -285,7 +357,7 @@ extern "C" int pg_screen_matrix(pg_ctx* ctx, const int32_t* genome_ids, uint32_t
   }
   PgDevBuf<ScreenGenome> d_tab;
   PgDevBuf<unsigned long long> d_hist, d_counters;      // [N_BINS] | [0] append cursor, [1] distinct keys, [2] groups
-  PgDevBuf<uint32_t> d_sizes, d_shared;
+  PgDevBuf<uint32_t> d_sizes;
   if ((rc = sk_malloc(ctx, d_tab, n)) || (rc = sk_malloc(ctx, d_hist, pgscr::N_BINS)) || (rc = sk_malloc(ctx, d_counters, 4)) ||
       (rc = sk_malloc(ctx, d_sizes, n)) || (rc = sk_malloc(ctx, d_shared, (size_t)n * n)))
     return rc;
@@ -408,11 +480,142 @@ extern "C" int pg_screen_matrix(pg_ctx* ctx, const int32_t* genome_ids, uint32_t
   hipLaunchKernelGGL(screen_finish_kernel, dim3(grid_for((uint64_t)n * n, 256 * 4, cu_blocks)), dim3(256), 0, st, d_shared.p, (const uint32_t*)d_sizes.p, n);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(sizes_out, d_sizes, (size_t)n * 4, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(shared_out, d_shared, (size_t)n * n * 4, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && shared_out) e = hipMemcpyAsync(shared_out, d_shared, (size_t)n * n * 4, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return pg_fail(ctx, PG_E_HIP, std::string("screen: ") + hipGetErrorString(e));
   ctx->screen_last[0] = total_keys; ctx->screen_last[1] = n_distinct; ctx->screen_last[2] = n_groups; ctx->screen_last[3] = n_incr;
   ctx->screen_last[4] = slices.size();
   T.sum(ctx->screen_ms);
+  return PG_OK;
+}
+
+}  // namespace
+
+extern "C" int pg_screen_matrix(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kmer, int32_t scale, uint32_t part, uint32_t n_parts,
+                                uint32_t* sizes_out, uint32_t* shared_out) {
+  if (!ctx) return PG_E_ARG;
+  int rc;
+  if ((rc = screen_check(ctx, genome_ids, n, kmer, scale, part, n_parts, sizes_out, true, shared_out))) return rc;
+  PgDevBuf<uint32_t> d_shared;
+  return screen_run(ctx, genome_ids, n, kmer, scale, part, n_parts, sizes_out, shared_out, d_shared);
+}
+
+// ---- the resident matrix and the selection over it ---------------------------------------------------------------------------------------
+void pg_screen_drop(pg_ctx* ctx) {
+  if (!ctx->screen_state) return;
+  delete state_of(ctx);
+  ctx->screen_state = nullptr;
+}
+
+extern "C" int pg_screen_release(pg_ctx* ctx) {
+  if (!ctx) return PG_E_ARG;
+  PG_HIP(ctx, hipSetDevice(ctx->device));
+  PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  pg_screen_drop(ctx);
+  return PG_OK;
+}
+
+extern "C" int pg_screen_hold(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kmer, int32_t scale, uint32_t part, uint32_t n_parts,
+                              uint32_t* sizes_out) {
+  if (!ctx) return PG_E_ARG;
+  int rc;
+  if ((rc = screen_check(ctx, genome_ids, n, kmer, scale, part, n_parts, sizes_out, false, nullptr))) return rc;
+  if ((rc = pg_screen_release(ctx))) return rc;      // the matrix of an earlier call goes before the new one is made: never two at a time
+  PgDevBuf<uint32_t> d_shared;
+  if ((rc = screen_run(ctx, genome_ids, n, kmer, scale, part, n_parts, sizes_out, nullptr, d_shared))) return rc;
+  if (n == 0) return PG_OK;      // (nothing to hold: a selection needs a matrix of one genome or more)
+  ScreenState* S = new ScreenState();
+  S->n = n;
+  S->d_shared = std::move(d_shared);
+  ctx->screen_state = S;
+  return PG_OK;
+}
+
+extern "C" int pg_screen_load(pg_ctx* ctx, const uint32_t* shared, uint32_t n) {
+  if (!ctx) return PG_E_ARG;
+  if (n > pgscr::MAX_GENOMES) return pg_fail(ctx, PG_E_ARG, "screen: more than 8192 genomes in one call");      // (before the matrix is read)
+  if (n == 0 || !shared) return pg_fail(ctx, PG_E_ARG, "screen: bad argument");
+  int rc;
+  if ((rc = pg_screen_release(ctx))) return rc;
+  PgDevBuf<uint32_t> d_shared;
+  if ((rc = sk_malloc(ctx, d_shared, (size_t)n * n))) return rc;
+  PG_HIP(ctx, hipMemcpyAsync(d_shared, shared, (size_t)n * n * 4, hipMemcpyHostToDevice, ctx->stream));
+  PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ScreenState* S = new ScreenState();
+  S->n = n;
+  S->d_shared = std::move(d_shared);
+  ctx->screen_state = S;
+  return PG_OK;
+}
+
+extern "C" int pg_screen_fetch(pg_ctx* ctx, uint32_t* shared_out) {
+  if (!ctx) return PG_E_ARG;
+  ScreenState* S = state_of(ctx);
+  if (!S) return pg_fail(ctx, PG_E_ARG, "screen: no resident matrix (call pg_screen_hold or pg_screen_load first)");
+  if (!shared_out) return pg_fail(ctx, PG_E_ARG, "screen: bad argument");
+  PG_HIP(ctx, hipSetDevice(ctx->device));
+  PG_HIP(ctx, hipMemcpyAsync(shared_out, S->d_shared, (size_t)S->n * S->n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return PG_OK;
+}
+
+extern "C" int pg_screen_select(pg_ctx* ctx, const uint32_t* need, uint32_t n, uint64_t* n_pairs_out) {
+  if (!ctx) return PG_E_ARG;
+  ScreenState* S = state_of(ctx);
+  if (!S) return pg_fail(ctx, PG_E_ARG, "screen: no resident matrix (call pg_screen_hold or pg_screen_load first)");
+  if (n != S->n) return pg_fail(ctx, PG_E_ARG, "screen: the resident matrix is of " + std::to_string(S->n) + " genomes, not " + std::to_string(n));
+  if (!need || !n_pairs_out) return pg_fail(ctx, PG_E_ARG, "screen: bad argument");
+  PG_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  S->selected = false;
+  S->n_sel = 0;
+  // (pg_dev_alloc, not sk_malloc: what sk_malloc gives up when memory is short includes the matrix this call reads)
+  const uint32_t tpr = (n + SEL_CELLS - 1) / SEL_CELLS, n_tasks = n * tpr;      // at most 8192 x 16
+  const dim3 grid(grid_for(n_tasks, 4, (uint32_t)ctx->num_cu * 8u));
+  PgDevBuf<uint32_t> d_need;
+  PgDevBuf<unsigned long long> d_cnt, d_off;
+  PgDevBuf<uint8_t> tmp;
+  int rc;
+  if ((rc = pg_dev_alloc(ctx, "screen", d_need, n, "the thresholds")) || (rc = pg_dev_alloc(ctx, "screen", d_cnt, (size_t)n_tasks + 1, "the task counts")) ||
+      (rc = pg_dev_alloc(ctx, "screen", d_off, (size_t)n_tasks + 1, "the task offsets")))
+    return rc;
+  size_t tmp_bytes = 0;
+  PG_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_cnt.p, d_off.p, (int64_t)n_tasks + 1, st));
+  if ((rc = pg_dev_alloc(ctx, "screen", tmp, tmp_bytes + 16, "the scan's temporary storage"))) return rc;
+  PG_HIP(ctx, hipMemcpyAsync(d_need, need, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(screen_select_kernel<false>, grid, dim3(256), 0, st, (const uint32_t*)S->d_shared.p, (const uint32_t*)d_need.p, n, tpr, n_tasks, d_cnt.p, 0ull,
+                     (int32_t*)nullptr, (int32_t*)nullptr, (uint32_t*)nullptr);
+  PG_HIP(ctx, hipGetLastError());
+  PG_HIP(ctx, hipcub::DeviceScan::ExclusiveSum((void*)tmp.p, tmp_bytes, d_cnt.p, d_off.p, (int64_t)n_tasks + 1, st));
+  unsigned long long total = 0;
+  PG_HIP(ctx, hipMemcpyAsync(&total, d_off.p + n_tasks, 8, hipMemcpyDeviceToHost, st));
+  PG_HIP(ctx, hipStreamSynchronize(st));
+  if (total > (unsigned long long)n * (n - 1u)) return pg_fail(ctx, PG_E_INTERNAL, "screen: the selection counted more cells than the matrix has off its diagonal");
+  if (total) {
+    if ((rc = pg_dev_alloc(ctx, "screen", S->d_a, (size_t)total, "the selected pairs")) || (rc = pg_dev_alloc(ctx, "screen", S->d_b, (size_t)total, "the selected pairs")) ||
+        (rc = pg_dev_alloc(ctx, "screen", S->d_s, (size_t)total, "the selected pairs")))
+      return rc;
+    hipLaunchKernelGGL(screen_select_kernel<true>, grid, dim3(256), 0, st, (const uint32_t*)S->d_shared.p, (const uint32_t*)d_need.p, n, tpr, n_tasks, d_off.p, total,
+                       S->d_a.p, S->d_b.p, S->d_s.p);
+    PG_HIP(ctx, hipGetLastError());
+    PG_HIP(ctx, hipStreamSynchronize(st));      // (d_need and d_off go with this scope)
+  }
+  S->selected = true;
+  S->n_sel = total;
+  *n_pairs_out = total;
+  return PG_OK;
+}
+
+extern "C" int pg_screen_select_read(pg_ctx* ctx, int32_t* a_out, int32_t* b_out, uint32_t* shared_out) {
+  if (!ctx) return PG_E_ARG;
+  ScreenState* S = state_of(ctx);
+  if (!S || !S->selected) return pg_fail(ctx, PG_E_ARG, "screen: no selection (call pg_screen_select first)");
+  if (S->n_sel == 0) return PG_OK;
+  if (!a_out || !b_out || !shared_out) return pg_fail(ctx, PG_E_ARG, "screen: bad argument");
+  PG_HIP(ctx, hipSetDevice(ctx->device));
+  PG_HIP(ctx, hipMemcpyAsync(a_out, S->d_a, S->n_sel * 4, hipMemcpyDeviceToHost, ctx->stream));
+  PG_HIP(ctx, hipMemcpyAsync(b_out, S->d_b, S->n_sel * 4, hipMemcpyDeviceToHost, ctx->stream));
+  PG_HIP(ctx, hipMemcpyAsync(shared_out, S->d_s, S->n_sel * 4, hipMemcpyDeviceToHost, ctx->stream));
+  PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return PG_OK;
 }

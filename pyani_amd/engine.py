@@ -408,6 +408,54 @@ class Engine:
         return {"keys": int(c[0]), "distinct": int(c[1]), "groups": int(c[2]), "pair_increments": int(c[3]), "slices": int(c[4]),
                 "scan_ms": float(ms[0]), "sort_group_ms": float(ms[1]), "count_ms": float(ms[2])}
 
+    # the selection: one matrix resident on the context, the kept pairs packed on the device
+    def screen_hold(self, ids, kmer: int = 16, scale: int = 256, part: int = 0, n_parts: int = 1) -> np.ndarray:
+        """pg_screen_hold: screen_matrix without the n^2 read-back — the matrix stays on the device for screen_select; returns sizes."""
+        a = self._ids(ids)
+        n = len(a)
+        sizes = np.zeros(n, dtype=np.uint32)
+        self._check(self.lib.pg_screen_hold(self._h, a.ctypes.data if n else None, n, int(kmer), int(scale), int(part), int(n_parts),
+                                            sizes.ctypes.data if n else None))
+        self._screen_n = n      # (only a call that succeeded leaves a matrix: its size is the one screen_fetch may rely on)
+        return sizes
+
+    def screen_load(self, shared) -> None:
+        """pg_screen_load: the caller's n x n matrix (uint32; any content) becomes the resident one."""
+        m = np.ascontiguousarray(shared, dtype=np.uint32)
+        if m.ndim != 2 or m.shape[0] != m.shape[1]:
+            raise ValueError(f"a square matrix is needed, not shape {m.shape}")
+        self._check(self.lib.pg_screen_load(self._h, m.ctypes.data if m.size else None, m.shape[0]))
+        self._screen_n = m.shape[0]
+
+    def screen_select(self, need) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """pg_screen_select + pg_screen_select_read: (a int32[m], b int32[m], shared uint32[m]) of the cells a != b of the resident matrix
+        with shared[a][b] >= min(need[a], need[b]), row-major (the order of np.nonzero).  need: uint32[n], n = the resident matrix's."""
+        t = np.ascontiguousarray(need, dtype=np.uint32).reshape(-1)
+        m = ctypes.c_uint64(0)
+        self._check(self.lib.pg_screen_select(self._h, t.ctypes.data if len(t) else None, len(t), ctypes.byref(m)))
+        a, b, s = np.zeros(m.value, dtype=np.int32), np.zeros(m.value, dtype=np.int32), np.zeros(m.value, dtype=np.uint32)
+        self._check(self.lib.pg_screen_select_read(self._h, *(x.ctypes.data if m.value else None for x in (a, b, s))))
+        return a, b, s
+
+    def screen_fetch(self) -> np.ndarray:
+        """pg_screen_fetch: the resident matrix, uint32[n, n]."""
+        n = getattr(self, "_screen_n", 0)      # (the library refuses before it writes when nothing is resident: then n is not looked at)
+        out = np.zeros((n, n), dtype=np.uint32)
+        self._check(self.lib.pg_screen_fetch(self._h, out.ctypes.data if out.size else None))
+        return out
+
+    def screen_release(self) -> None:
+        self._check(self.lib.pg_screen_release(self._h))
+
+    def screen_candidates(self, ids, options, labels=None):
+        """The pairs of the resident genomes `ids` worth an exact comparison (pyani_amd.screen.ScreenedPairs; options: a ScreenOptions or
+        a bare identity threshold): hold -> identity_thresholds -> select -> release.  Equal, in content and order, to
+        screen_genomes(...).candidate_pairs(min_identity, min_shared) without the matrix ever leaving the device."""
+        from . import screen
+        options = screen.check_options(options)
+        ids = [int(i) for i in ids]
+        return screen.candidates_on(self, lambda: self.screen_hold(ids, options.kmer, options.scale), ids, options, labels)
+
     # -- classify: clique sweep over identity thresholds (pyani_amd.classify drives these) -------------------------------------
     def classify_edges(self, identity: np.ndarray, coverage: np.ndarray, id_min: float = 0.8, cov_min: float = 0.5) -> Tuple[int, int]:
         """pg_classify_edges: the edges of build_graph_from_results (pyani_classify.py:90-111) from two n x n float64 matrices in one

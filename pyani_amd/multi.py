@@ -297,6 +297,20 @@ class MultiEngine:
         shared = np.sum([r[1] for r in res], axis=0, dtype=np.uint64).astype(np.uint32)
         return sizes, shared
 
+    def screen_candidates(self, ids, options, labels=None):
+        """Engine.screen_candidates over all devices: the summed screen_matrix above, loaded onto the first engine, selected there.
+        Equal to one engine's."""
+        from . import screen
+        options = screen.check_options(options)
+        ids = [int(i) for i in ids]
+        first = self.engines[0]
+
+        def make_resident():
+            sizes, shared = self.screen_matrix(ids, options.kmer, options.scale)
+            first.screen_load(shared)
+            return sizes
+        return screen.candidates_on(first, make_resident, ids, options, labels)
+
     def screen_set_budget(self, max_keys: int = 0):
         for e in self.engines:
             e.screen_set_budget(max_keys)

@@ -10,9 +10,14 @@ shared[a][b] = |S(a) & S(b)| — and everything floating-point is computed here,
 (a k-mer survives iff none of its k bases changed).  The floor min_shared (default 2) matters: ONE chance k-mer between two unrelated
 genomes of a few thousand sampled k-mers would read as an identity above 0.5.
 
+Screened runs (run_anim / run_anib with screen=...) do not bring the matrix back at all: the selection rule of candidate_pairs reduces
+to ONE INTEGER COMPARISON per cell (identity_thresholds), which the engine applies on the device next to the matrix
+(Engine.screen_candidates) so that only the kept pairs are read back (ScreenedPairs).
+
 An ESTIMATE for triage with its own frames: it is never written into an exact ANIm / ANIb matrix.  What this is modelled on: the
 sketch-then-align front ends of skani, sourmash and dRep; pyani itself has no such step.
 """
+import math
 from typing import List, NamedTuple, Sequence, Tuple
 
 import numpy as np
@@ -29,6 +34,130 @@ def check_params(kmer, scale) -> Tuple[int, int]:
     if isinstance(scale, bool) or int(scale) != scale or not 1 <= int(scale) <= 65536 or int(scale) & (int(scale) - 1):
         raise ValueError(f"scale must be a power of two, 1 ... 65536, not {scale!r}")
     return int(kmer), int(scale)
+
+
+class ScreenOptions(NamedTuple):
+    """What a screened run asks of the screen: keep a pair iff its identity estimate, from either side, is >= min_identity.  There is
+    no default threshold (on C4 0.80 kept every covered pair, 0.85 already lost relatives)."""
+    min_identity: float
+    kmer: int = DEFAULT_KMER
+    scale: int = DEFAULT_SCALE
+    min_shared: int = DEFAULT_MIN_SHARED
+
+
+def check_options(options) -> ScreenOptions:
+    """A ScreenOptions, or a bare number meaning min_identity, validated (no library call): kmer and scale as check_params, min_shared an
+    integer >= 1 (the NaN rows of min_shared = 0 are not carried into the integer rule), min_identity a real number that is not NaN."""
+    if not isinstance(options, ScreenOptions):
+        if isinstance(options, bool) or not isinstance(options, (int, float, np.integer, np.floating)):
+            raise ValueError(f"screen options are a ScreenOptions or a number (the identity threshold), not {options!r}")
+        options = ScreenOptions(options)
+    t = options.min_identity
+    if isinstance(t, bool) or not isinstance(t, (int, float, np.integer, np.floating)) or math.isnan(float(t)):
+        raise ValueError(f"min_identity must be a number, not {t!r}")
+    kmer, scale = check_params(options.kmer, options.scale)
+    ms = options.min_shared
+    if isinstance(ms, bool) or not isinstance(ms, (int, np.integer)) or int(ms) < 1:
+        raise ValueError(f"min_shared must be an integer >= 1, not {ms!r}")
+    return ScreenOptions(float(t), kmer, scale, int(ms))
+
+
+def _identity_of_counts(s: np.ndarray, size: np.ndarray, kmer: int) -> np.ndarray:
+    """The expression of ScreenResult._identity for integer counts s of rows of `size` sampled k-mers (size > 0): numpy's own division
+    and power on float64 arrays, so that the bits are those candidate_pairs compares."""
+    return np.power(s.astype(np.float64) / size.astype(np.float64), 1.0 / kmer)
+
+
+def identity_thresholds(sizes, kmer: int, min_identity: float, min_shared: int = DEFAULT_MIN_SHARED) -> np.ndarray:
+    """need uint32[n]: need[a] = the smallest integer s with min_shared <= s <= sizes[a] and (s / sizes[a]) ** (1 / kmer) >= min_identity,
+    in the float64 arithmetic of ScreenResult.identity; sizes[a] + 1 where there is none (an empty genome included); all 0 where
+    min_identity <= 0.  For a fixed row the identity is monotone in the shared count, so identity[a][b] >= min_identity iff
+    shared[a][b] >= need[a], and candidate_pairs' rule becomes: keep (a, b) iff a != b and shared[a][b] >= min(need[a], need[b])
+    (what the monotonicity rests on).  Found by bisection over s with the very numpy expression of the identity."""
+    kmer, _ = check_params(kmer, 1)
+    if isinstance(min_shared, bool) or int(min_shared) != min_shared or int(min_shared) < 1:
+        raise ValueError(f"min_shared must be an integer >= 1, not {min_shared!r}")
+    t = float(min_identity)
+    if math.isnan(t):
+        raise ValueError("min_identity must be a number")
+    size = np.ascontiguousarray(sizes, dtype=np.int64).reshape(-1)
+    if (size < 0).any() or (size >= 2 ** 32 - 1).any():
+        raise ValueError("sizes must fit uint32")
+    if t <= 0.0:
+        return np.zeros(len(size), dtype=np.uint32)
+    need = size + 1
+    lo = np.full(len(size), int(min_shared), dtype=np.int64)
+    live = np.flatnonzero(lo <= size)
+    if len(live):      # rows whose largest count passes: the answer lies in [lo, hi], and hi always passes
+        live = live[_identity_of_counts(size[live], size[live], kmer) >= t]
+    lo, hi, sz = lo[live], size[live], size[live]
+    while True:
+        open_ = lo < hi
+        if not open_.any():
+            break
+        mid = (lo + hi) // 2
+        ok = _identity_of_counts(mid, sz, kmer) >= t
+        hi = np.where(open_ & ok, mid, hi)
+        lo = np.where(open_ & ~ok, mid + 1, lo)
+    need[live] = hi
+    return need.astype(np.uint32)
+
+
+class ScreenedPairs(NamedTuple):
+    """The pairs a screen kept (Engine.screen_candidates), row-major — the order of ScreenResult.candidate_pairs — and nothing of the
+    others: positions a, b in `labels`, shared = shared[a][b]."""
+    labels: List[str]
+    options: ScreenOptions
+    sizes: np.ndarray       # uint32[n]
+    a: np.ndarray           # int32[m]
+    b: np.ndarray           # int32[m]
+    shared: np.ndarray      # uint32[m]
+
+    def pairs(self) -> List[Tuple[int, int]]:
+        return list(zip(self.a.tolist(), self.b.tolist()))
+
+    def containment(self) -> np.ndarray:
+        """shared[a][b] / sizes[a] of the kept pairs (NaN where sizes[a] == 0)."""
+        size = self.sizes.astype(np.float64)[self.a]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(size > 0, self.shared.astype(np.float64) / size, np.nan)
+
+    def identity(self) -> np.ndarray:
+        """ScreenResult.identity's value of the kept pairs: containment ** (1 / k) where shared >= min_shared, else 0.0."""
+        ok = self.shared >= self.options.min_shared
+        return np.where(ok, np.power(np.where(ok, self.containment(), 1.0), 1.0 / self.options.kmer), 0.0)
+
+    def frame(self) -> pd.DataFrame:
+        """One row per kept pair: query, subject (labels), shared, containment, identity."""
+        lab = np.array(list(self.labels), dtype=object)
+        return pd.DataFrame({"query": lab[self.a] if len(self.a) else [], "subject": lab[self.b] if len(self.b) else [], "shared": self.shared,
+                             "containment": self.containment(), "identity": self.identity()})
+
+
+def _labels_for(ids, labels) -> List[str]:
+    labels = [str(x) for x in (ids if labels is None else labels)]
+    if len(labels) != len(ids):
+        raise ValueError("ids and labels must have the same length")
+    if len(ids) > MAX_GENOMES:
+        raise ValueError(f"a screen call takes at most {MAX_GENOMES} genomes, not {len(ids)}")
+    return labels
+
+
+def candidates_on(engine, make_resident, ids, options, labels=None) -> ScreenedPairs:
+    """The selection on one Engine: make_resident() leaves the matrix of `ids` on it and returns the sizes; then thresholds, select,
+    release (on errors too).  Engine.screen_candidates and MultiEngine.screen_candidates are this with their own make_resident."""
+    options = check_options(options)
+    ids = list(ids)
+    labels = _labels_for(ids, labels)
+    if not ids:
+        return ScreenedPairs(labels, options, np.zeros(0, np.uint32), np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint32))
+    try:
+        sizes = make_resident()
+        need = identity_thresholds(sizes, options.kmer, options.min_identity, options.min_shared)
+        a, b, shared = engine.screen_select(need)
+    finally:
+        engine.screen_release()
+    return ScreenedPairs(labels, options, sizes, a, b, shared)
 
 
 class ScreenResult(NamedTuple):

@@ -18,6 +18,11 @@ What is kept of the reference's behaviour:
     names the other one: tables of two modes are not mixed silently.  A directory without a record (BLAST+'s own tables, or an
     earlier version's) counts as "seeds".
 
+  * `screen` (pyani_amd.screen.ScreenOptions, or a bare identity threshold) searches only the pairs the k-mer screen keeps
+    (Engine.screen_candidates).  A dropped pair has no tuple and no table, and its cells are NaN in all five matrices —
+    not the 1.0 / 0 process_blast starts from, which would read as a perfect match.  The options are part of the run record, and
+    recovery refuses a directory recorded with other options (or with none), as it does for another search mode.
+
 Single-process: one engine, or several GPUs of this node through pyani_amd.multi.MultiEngine (devices / workers).  There is no
 collective (one process per GPU) run_anib: pyani_amd.parallel.DistributedEngine has no rows call.
 """
@@ -27,7 +32,9 @@ from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import pandas as pd
 
-from . import _lib, anib, anim, files
+import numpy as np
+
+from . import _lib, anib, anim, files, screen as screen_mod
 from .engine import Engine, default_engine
 
 ALIGNDIR = "blastn_output"     # pyani_config.ALIGNDIR["ANIb"]
@@ -40,6 +47,7 @@ class AnibRun(NamedTuple):
     matrices: Dict[str, pd.DataFrame]                           # process_blast_results
     recovered: List[Path]                                       # tables reused in recovery mode
     written: List[Path]                                         # tables written by this run
+    screened: Optional[screen_mod.ScreenedPairs] = None         # the pairs the screen kept (screen=...), None for an unscreened run
 
 
 WRITE_CHUNK = 256      # ordered pairs per anib_rows_batch call of write_output (its rows are held on the host)
@@ -56,7 +64,7 @@ def table_path(outdir: Path, qstem: str, sstem: str) -> Path:
     return Path(outdir) / ALIGNDIR / (f"{qstem}_vs_{sstem}" + ".blast_tab")
 
 
-RUN_RECORD = "anib_run.json"   # <outdir>/anib_run.json: {"search": ...} of the run that wrote the tables
+RUN_RECORD = "anib_run.json"   # <outdir>/anib_run.json: {"search": ..., "screen": ...} of the run that wrote the tables
 
 
 def recorded_search(outdir) -> str:
@@ -68,13 +76,29 @@ def recorded_search(outdir) -> str:
         return str(json.load(fh).get("search", "seeds"))
 
 
+def recorded_screen(outdir) -> Optional[dict]:
+    """The screen options the tables under `outdir` were written with, as the record holds them; None for an unscreened run or a
+    directory without a record."""
+    f = Path(outdir) / RUN_RECORD
+    if not f.is_file():
+        return None
+    with open(f) as fh:
+        return json.load(fh).get("screen")
+
+
 def run_anib(indir, outdir=None, fragsize: int = anib.FRAGSIZE, recovery: bool = False, write_output: bool = False,
              engine: Optional[Engine] = None, devices: Optional[List[int]] = None, workers: Optional[int] = None,
-             search: str = "seeds") -> AnibRun:
+             search: str = "seeds", screen=None) -> AnibRun:
     """ANIb over every FASTA file of `indir`.  outdir is needed for recovery / write_output only.
     devices / workers: run on several GPUs of this node (pyani_amd/multi.py); ignored when `engine` is given.
-    search: "seeds" (default) or "all_diagonals" (Engine.anib_set_search) for this run."""
+    search: "seeds" (default) or "all_diagonals" (Engine.anib_set_search) for this run.
+    screen: None (default: all N(N-1) pairs), or a ScreenOptions / a bare identity threshold: after the genomes are loaded and recovery
+    has taken the pairs whose tables exist, the screen runs over ALL genomes of the run and the pairs still to do are cut down to the
+    ones it keeps, in their order.  There is no default threshold — DESIGN.md §16: on C4 0.80 kept every covered pair and dropped
+    97.8 % of all pairs, 0.85 already lost relatives.  min_identity <= 0 keeps every pair (the run equals the unscreened one)."""
     _lib.anib_search_code(search)     # before any work is done
+    if screen is not None:
+        screen = screen_mod.check_options(screen)
     if write_output and outdir is None:
         raise ValueError("write_output needs an output directory")
     if recovery and outdir is None:
@@ -82,6 +106,10 @@ def run_anib(indir, outdir=None, fragsize: int = anib.FRAGSIZE, recovery: bool =
     if recovery and recorded_search(outdir) != search:
         raise ValueError(f"recovery: the tables under {outdir} were written with search={recorded_search(outdir)!r}, this run asks for "
                          f"{search!r}; the two modes' tables are not mixed")
+    screen_record = None if screen is None else dict(screen._asdict())
+    if recovery and recorded_screen(outdir) != screen_record:
+        raise ValueError(f"recovery: the tables under {outdir} were written with screen={recorded_screen(outdir)!r}, this run asks for "
+                         f"{screen_record!r}; a directory holds the tables of one selection")
     own = None
     if engine is None and (devices is not None or workers):
         from . import multi
@@ -90,10 +118,10 @@ def run_anib(indir, outdir=None, fragsize: int = anib.FRAGSIZE, recovery: bool =
     try:
         eng = engine or default_engine()
         with anib.search_mode(eng, search):
-            run = _run_anib(indir, outdir, fragsize, recovery, write_output, eng)
+            run = _run_anib(indir, outdir, fragsize, recovery, write_output, eng, screen)
         if write_output:
             with open(Path(outdir) / RUN_RECORD, "w") as fh:
-                json.dump({"search": search, "fragsize": int(fragsize)}, fh)
+                json.dump({"search": search, "fragsize": int(fragsize), **({} if screen is None else {"screen": screen_record})}, fh)
                 fh.write("\n")
         return run
     finally:
@@ -107,7 +135,7 @@ def _tuple(q: str, s: str, rec) -> Tuple[int, int, float]:
     return int(rec["aln_length"]), int(rec["sim_errors"]), float(rec["pid"])
 
 
-def _run_anib(indir, outdir, fragsize, recovery, write_output, eng) -> AnibRun:
+def _run_anib(indir, outdir, fragsize, recovery, write_output, eng, screen=None) -> AnibRun:
     paths = files.get_fasta_paths(Path(indir))
     stems = [p.stem for p in paths]
     if len(set(stems)) != len(stems):
@@ -134,6 +162,14 @@ def _run_anib(indir, outdir, fragsize, recovery, write_output, eng) -> AnibRun:
         ids = {}
         for p, (gid, total, _) in zip(paths, eng.add_fasta_batch(paths)):
             ids[p.stem], lengths[p.stem] = gid, total
+        screened = None
+        if screen is not None:
+            screened = eng.screen_candidates([ids[s] for s in stems], screen, labels=stems)
+            kept = {(stems[a], stems[b]) for a, b in screened.pairs()}
+            todo = [k for k in todo if k in kept]
+            if write_output:
+                from .subcmd_screen import write_pairs_tab
+                write_pairs_tab(outdir, screened)
         if write_output:
             (Path(outdir) / ALIGNDIR).mkdir(parents=True, exist_ok=True)
             _, fraglengths = anib.fragment_fasta_files(paths, Path(outdir) / ALIGNDIR, fragsize)
@@ -158,5 +194,14 @@ def _run_anib(indir, outdir, fragsize, recovery, write_output, eng) -> AnibRun:
     finally:
         if scratch_store:
             eng.clear_genomes()
-    results = {k: results[k] for k in ((q, s) for q in stems for s in stems if q != s)}      # the run's pair order, whatever was recovered
-    return AnibRun(lengths, fraglengths, results, anib.process_blast_results(results, lengths), recovered, written)
+    results = {k: results[k] for k in ((q, s) for q in stems for s in stems if q != s) if k in results}      # the run's pair order, whatever was recovered (a screened run: without the dropped pairs)
+    mats = anib.process_blast_results(results, lengths)
+    if screened is not None:      # process_blast starts every cell as a perfect match (identity and coverage 1.0, no errors): a pair nobody searched is NaN
+        dropped = [(q, s) for q in stems for s in stems if q != s and (q, s) not in results]
+        if dropped:
+            qi, si = (np.array([stems.index(x[k]) for x in dropped]) for k in (0, 1))
+            for name, frame in mats.items():
+                v = frame.to_numpy(dtype=np.float64, copy=True)
+                v[qi, si] = np.nan
+                mats[name] = type(frame)(v, index=frame.index, columns=frame.columns)
+    return AnibRun(lengths, fraglengths, results, mats, recovered, written, screened)

@@ -13,6 +13,10 @@ What is kept of the reference's behaviour:
   * errors: a pair the engine could not process raises PyaniANImException (the reference: a failed job ->
     PyaniException "Multiprocessing run failed in ANIm"); a pair without any alignment raises ZeroDivisionError exactly as
     parse_delta does on its empty .filter file, unless skip_zero=True (then the pair has no row and its cells stay NaN).
+
+What is added to it: `screen` (pyani_amd.screen.ScreenOptions, or a bare identity threshold) compares only the pairs the k-mer screen keeps
+(Engine.screen_candidates).  A dropped pair is treated as a pair that was never run: no entry in `results`, no Comparison
+row, no output file, NaN cells.  The kept pairs go to `<outdir>/screen_output/screen_pairs.tab` with write_output.
 """
 from itertools import permutations
 from pathlib import Path
@@ -20,7 +24,7 @@ from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import pandas as pd
 
-from . import anim, files
+from . import anim, files, screen as screen_mod
 from .engine import Engine, default_engine
 
 ALIGNDIR = "nucmer_output"     # pyani_config.ALIGNDIR["ANIm"]
@@ -35,6 +39,7 @@ class AnimRun(NamedTuple):
     json: Dict[str, str]                                        # Run.df_* strings
     recovered: List[Path]                                       # output files reused in recovery mode
     written: List[Path]                                         # output files written by this run
+    screened: Optional[screen_mod.ScreenedPairs] = None         # the pairs the screen kept (screen=...), None for an unscreened run
 
 
 WRITE_CHUNK = 256      # ordered pairs per pg_anim_alignments_batch call of write_output (its result is held on the host)
@@ -47,7 +52,8 @@ def outfile_path(outdir: Path, qstem: str, sstem: str, nofilter: bool = False) -
 
 def run_anim(indir, outdir=None, recovery: bool = False, nofilter: bool = False, maxmatch: bool = False,
              write_output: bool = False, skip_zero: bool = False, engine: Optional[Engine] = None,
-             devices: Optional[List[int]] = None, workers: Optional[int] = None, distributed: bool = False, group=None) -> AnimRun:
+             devices: Optional[List[int]] = None, workers: Optional[int] = None, distributed: bool = False, group=None,
+             screen=None) -> AnimRun:
     """ANIm over every FASTA file of `indir`.  outdir is needed for recovery / write_output only.
     devices / workers: run on several GPUs of this node (pyani's `--workers`, subcmd_anim.py:392-396, counts GPUs here): the
     comparisons are pulled from a work queue by one engine per device (pyani_amd/multi.py); ignored when `engine` is given.
@@ -56,9 +62,18 @@ def run_anim(indir, outdir=None, recovery: bool = False, nofilter: bool = False,
     assembles them with one RCCL all-gather; every rank returns the whole run).  In that mode rank 0 alone reads recovery files and
     writes output files, and the list of comparisons still to run is broadcast from rank 0, so every rank provably deals the same
     list.  Never implied: an initialised process group alone changes nothing (a library user calling run_anim on rank 0 only must
-    not deadlock in a collective; passing a DistributedEngine as `engine` is the other explicit way in)."""
+    not deadlock in a collective; passing a DistributedEngine as `engine` is the other explicit way in).
+    screen: None (default: all N(N-1) pairs), or a ScreenOptions / a bare identity threshold: after the genomes are loaded and recovery
+    has taken the pairs whose files exist, the screen runs over ALL genomes of the run and the pairs still to do are cut down to the ones
+    it keeps, in their order.  There is no default threshold — DESIGN.md §16: on C4 0.80 kept every covered pair and dropped 97.8 % of
+    all pairs, 0.85 already lost relatives.  min_identity <= 0 keeps every pair (the run equals the unscreened one).  Not available in
+    a collective run (ValueError before any work)."""
     if write_output and outdir is None:
         raise ValueError("write_output needs an output directory")     # before any work is done
+    if screen is not None:
+        screen = screen_mod.check_options(screen)
+        if distributed or group is not None or type(engine).__name__ == "DistributedEngine":
+            raise ValueError("screen is not available in a collective run (distributed=True, group=, or a DistributedEngine)")
     own = None
     if engine is None and (devices is not None or workers):
         from . import multi
@@ -72,7 +87,7 @@ def run_anim(indir, outdir=None, recovery: bool = False, nofilter: bool = False,
             eng = parallel.engine_for_process_group(eng, group)
         if type(eng).__name__ == "DistributedEngine" and eng.world > 1:
             coll = eng
-        return _run_anim(indir, outdir, recovery, nofilter, maxmatch, write_output, skip_zero, eng, coll)
+        return _run_anim(indir, outdir, recovery, nofilter, maxmatch, write_output, skip_zero, eng, coll, screen)
     finally:
         if own is not None:
             own.close()
@@ -86,7 +101,7 @@ def _bcast(coll, obj):
     return box[0]
 
 
-def _run_anim(indir, outdir, recovery, nofilter, maxmatch, write_output, skip_zero, eng, coll=None) -> AnimRun:
+def _run_anim(indir, outdir, recovery, nofilter, maxmatch, write_output, skip_zero, eng, coll=None, screen=None) -> AnimRun:
     lead = coll is None or coll.rank == 0          # collective run: rank 0 alone touches the output directory
     paths = files.get_fasta_paths(Path(indir))
     stems = [p.stem for p in paths]
@@ -135,6 +150,14 @@ def _run_anim(indir, outdir, recovery, nofilter, maxmatch, write_output, skip_ze
         ids = {}
         for p, (gid, total, _) in zip(paths, eng.add_fasta_batch(paths)):
             ids[p.stem], lengths[p.stem] = gid, total
+        screened = None
+        if screen is not None:
+            screened = eng.screen_candidates([ids[s] for s in stems], screen, labels=stems)
+            kept = {(stems[a], stems[b]) for a, b in screened.pairs()}      # (symmetric: a pair and its reverse are kept together)
+            todo = [k for k in todo if k in kept]
+            if write_output and lead:
+                from .subcmd_screen import write_pairs_tab
+                write_pairs_tab(outdir, screened)
         if todo:
             recs = eng.anim_pairs([ids[q] for q, _ in todo], [ids[s] for _, s in todo], filter_1to1=not nofilter, maxmatch=maxmatch)
             for (q, s), rec in zip(todo, recs):
@@ -163,4 +186,4 @@ def _run_anim(indir, outdir, recovery, nofilter, maxmatch, write_output, skip_ze
         written = _bcast(coll, written)      # (also the point where the other ranks wait for rank 0's files)
     mats = anim.assemble_run_matrices(results, lengths, genome_ids=genome_ids)
     return AnimRun(genome_ids, lengths, results, anim.comparison_rows(results, lengths, genome_ids, maxmatch=maxmatch), mats,
-                   anim.run_matrices_to_json(mats), recovered, written)
+                   anim.run_matrices_to_json(mats), recovered, written, screened)

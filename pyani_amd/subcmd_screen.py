@@ -35,6 +35,14 @@ def write_tabs(outdir, result: screen.ScreenResult) -> List[Path]:
     return out
 
 
+def write_pairs_tab(outdir, screened: screen.ScreenedPairs) -> Path:
+    """`<outdir>/screen_output/screen_pairs.tab` of a screened run: one line per kept pair — query, subject, shared, containment,
+    identity — in the order of the selection."""
+    (Path(outdir) / OUTDIR).mkdir(parents=True, exist_ok=True)
+    screened.frame().to_csv(tab_path(outdir, "pairs"), index=False, sep="\t")
+    return tab_path(outdir, "pairs")
+
+
 def run_screen(indir, outdir=None, kmerSize: int = screen.DEFAULT_KMER, scale: int = screen.DEFAULT_SCALE, write_output: bool = False,
                engine: Optional[Engine] = None, devices: Optional[List[int]] = None, workers: Optional[int] = None) -> ScreenRun:
     """The screen over every FASTA file of `indir`.  outdir is needed for write_output only.
