@@ -418,6 +418,42 @@ int pg_screen_select_read(pg_ctx* ctx, int32_t* a_out, int32_t* b_out, uint32_t*
 int pg_screen_fetch(pg_ctx* ctx, uint32_t* shared_out);
 int pg_screen_release(pg_ctx* ctx);
 
+/* ---- screen, the index: collections beyond 8192 genomes.  The n x n matrix is never formed: the k-mers held by two or
+ * more genomes stay RESIDENT on the context in compressed-row form — group_start uint64[G + 1], member uint32[E], the call indices of a
+ * group's genomes in ascending order — and the matrix is made and selected a BAND of consecutive rows at a time.  The same definitions as
+ * pg_screen_matrix (S(g), sampling, window validity, canonical form); the index is independent of the resident matrix of pg_screen_hold /
+ * _load: either may exist without the other and neither call family touches the other's state (one exception, as for every sketch or
+ * screen call: a pg_screen_index that finds device memory short releases the ANIm launch scratch and an idle resident matrix; the band
+ * calls give up nothing).
+ * pg_screen_index scans, sorts and groups as pg_screen_matrix does (slices under pg_screen_set_budget; PG_E_NOMEM for a bin beyond it) and
+ * appends every slice's grouped entries to the index; a k-mer of one genome only counts into sizes_out[a] = |S(a)|.  Limits: n <= 2^20
+ * (PG_E_ARG beyond, checked before the ids are read), no id twice, kmer and scale as for pg_screen_matrix.  PG_E_NOMEM when the index does
+ * not fit; the message names the entry count.  Once the arguments have passed, the index of an earlier call is released BEFORE the new one
+ * is made (never two at a time): a call refused for its arguments changes nothing, one that fails later leaves none.  n == 0 is PG_OK and
+ * leaves none.  The index lives until the next such call, pg_screen_index_release (PG_OK when there is none), pg_clear_genomes or pg_destroy.
+ * pg_screen_set_band: rows of one band, at most 8192 (PG_E_ARG beyond); 0 = the default, the largest rows <= min(8192, n) with
+ * rows * n <= 2^29 cells.  Band b covers the rows [b rows, min(n, (b + 1) rows)).  No result depends on the setting.
+ * pg_screen_index_select works the bands band_first, band_first + band_step, ... (band_step >= 1: PG_E_ARG otherwise) in ascending order.
+ * Per band: the groups' members inside the band's rows by two binary searches; the cells counted with uint32 atomics, balanced by item
+ * over the groups with a member in the band; the cell of a genome with itself = sizes — the band then equals those rows of
+ * pg_screen_matrix's result — and the rule of pg_screen_select on the rectangle: (a, b) kept iff a != b and
+ * band[a][b] >= min(need[a], need[b]), packed as (a, b, shared) with global indices in row-major order, and copied to the host as the
+ * band finishes.  The device holds one band at a time; the bands' lists concatenated are in the order of pg_screen_select.  need: n
+ * uint32; PG_E_ARG without an index or when n is not its size; *n_pairs_out = the kept cells of the bands worked.
+ * pg_screen_index_read copies the latest selection out (n_pairs entries each; may be NULL when nothing was kept); PG_E_ARG before any.
+ * pg_screen_index_band makes one band and copies it to the host: (rows of the band) x n uint32, row-major.  PG_E_ARG without an index or
+ * for a band that does not exist.
+ * pg_screen_index_last: counts_out[7] = keys, distinct (k-mer, genome) entries, grouped entries E, groups G, slices of the latest
+ * pg_screen_index; bands worked and pair increments (the atomic adds: sum over the groups of members in the band x (members - 1)) of
+ * the latest pg_screen_index_select.  ms_out[4] = scan, sort + group | count, select milliseconds of the same (HIP events). */
+int pg_screen_index(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kmer, int32_t scale, uint32_t* sizes_out);
+int pg_screen_index_release(pg_ctx* ctx);
+int pg_screen_set_band(pg_ctx* ctx, uint32_t rows);
+int pg_screen_index_select(pg_ctx* ctx, const uint32_t* need, uint32_t n, uint32_t band_first, uint32_t band_step, uint64_t* n_pairs_out);
+int pg_screen_index_read(pg_ctx* ctx, int32_t* a_out, int32_t* b_out, uint32_t* shared_out);
+int pg_screen_index_band(pg_ctx* ctx, uint32_t band, uint32_t* out);
+int pg_screen_index_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
+
 /* ---- classify: clique sweep over identity thresholds ------------------------------------------------------------------
  * The compute of `pyani classify`.  These calls read caller matrices only: they touch no genome, seed list or ANIm worker slot, so
  * they need no interlock with the pg_anim_pairs_enqueue / _fetch lanes and may run while enqueued ANIm calls are in flight (own

@@ -28,8 +28,20 @@
 //                           task's ballots, one uint64 per task; hipcub exclusive scan; fill pass: the same ballots again, every kept cell
 //                           written at its task's offset + the kept cells before it in the task.  No cursor, no atomic: the order is the
 //                           order of the cells.  Two streaming passes over 4 n^2 bytes.
+//
+// The INDEX, for collections beyond MAX_GENOMES: C1 and C2 are one front half (screen_front) with two back halves.  The
+// dense calls count every grouped slice into the matrix (DenseBack: C3, C4).  pg_screen_index appends the grouped entries to a resident
+// compressed-row structure instead (IndexBack: group_start, member; sizes by screen_head_wide_kernel), and pg_screen_index_select /
+// _band form the matrix a BAND of rows at a time:
+//   B1 band_prep_kernel     per group the members inside the band's rows (two binary searches); the groups with none are compacted away
+//   B2 band_weight_kernel   + an exclusive scan: item ranges of the remaining groups, mb m items each
+//   B3 band_count_kernel    C3's balance by item; item t -> (t / m, t % m), uint32 atomics into the band
+//   B4 band_diag_kernel     the cell of a genome with itself = size
+//   B5 band_select_kernel   C5's rule and passes on the rectangle; the kept triples go to the host as the band finishes
 #include <algorithm>
 #include <hipcub/hipcub.hpp>
+#include <memory>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -150,6 +162,22 @@ __global__ __launch_bounds__(256) void screen_head_kernel(const unsigned long lo
     if (lsize[i]) atomicAdd(&sizes[i], lsize[i]);
 }
 
+// The head kernel of the index (n up to 2^20: no LDS histogram of the genomes fits).  sizes[g] += 1 by a uint32 atomic in HBM, one per
+// entry, no return value.  The keys stand in (k-mer, genome) order, so the genomes of neighbouring lanes differ inside a group and are
+// unrelated across groups: a wave finds next to nothing to aggregate.  flags as above, and bit 2 = the entry belongs to
+// a k-mer held by two or more genomes (what the index keeps).
+__global__ __launch_bounds__(256) void screen_head_wide_kernel(const unsigned long long* __restrict__ u, uint64_t nu, uint32_t n, uint32_t* __restrict__ sizes,
+                                                                uint8_t* __restrict__ flags) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nu; i += (uint64_t)gridDim.x * blockDim.x) {
+    const unsigned long long key = u[i];
+    const uint32_t canon = (uint32_t)(key >> 32), g = (uint32_t)key;
+    const bool same_prev = i > 0 && (uint32_t)(u[i - 1] >> 32) == canon;
+    const bool same_next = i + 1 < nu && (uint32_t)(u[i + 1] >> 32) == canon;
+    flags[i] = (uint8_t)((!same_prev && same_next ? 1u : 0u) | (same_prev && !same_next ? 2u : 0u) | (same_prev || same_next ? 4u : 0u));
+    if (g < n) atomicAdd(&sizes[g], 1u);
+  }
+}
+
 struct FlagBit {      // the flag array read as one of its bits
   uint32_t bit;
   __host__ __device__ __forceinline__ uint8_t operator()(uint8_t f) const { return (uint8_t)((f >> bit) & 1u); }
@@ -253,6 +281,156 @@ __global__ __launch_bounds__(256) void screen_select_kernel(const uint32_t* __re
   if (!FILL && blockIdx.x == 0 && threadIdx.x == 0) counts[n_tasks] = 0ull;
 }
 
+// ---- the index path: the groups stay resident in compressed-row form, the matrix is formed a band of rows at a time ------
+struct LowHalf {      // the genome of a key
+  __host__ __device__ __forceinline__ uint32_t operator()(unsigned long long key) const { return (uint32_t)key; }
+};
+struct NonZero {
+  __host__ __device__ __forceinline__ uint8_t operator()(uint32_t x) const { return x ? 1 : 0; }
+};
+
+// w[g] = members of slice group g, w[ng] = 0: the input of the scan that continues group_start
+__global__ __launch_bounds__(256) void index_size_kernel(const uint32_t* __restrict__ first, const uint32_t* __restrict__ last, uint32_t ng,
+                                                          unsigned long long* __restrict__ w) {
+  for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g <= ng; g += gridDim.x * blockDim.x)
+    w[g] = g < ng ? (unsigned long long)(last[g] - first[g] + 1u) : 0ull;
+}
+
+// B1 prep: the members of every group that fall into the rows [r0, r1) — they ascend: two binary searches.  lo[g] = the first of them,
+// counted from the group's start; mb[g] = how many.  in_band[0] += the sum of mb (one 64-bit atomic per wave).
+__global__ __launch_bounds__(256) void band_prep_kernel(const unsigned long long* __restrict__ start, const uint32_t* __restrict__ member, uint64_t G,
+                                                         uint32_t r0, uint32_t r1, uint32_t* __restrict__ lo, uint32_t* __restrict__ mb,
+                                                         unsigned long long* __restrict__ in_band) {
+  for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < G; base += (uint64_t)gridDim.x * blockDim.x) {      // (uniform: every lane reaches the shuffles)
+    const uint64_t g = base + threadIdx.x;
+    uint32_t mine = 0;
+    if (g < G) {
+      const uint64_t s = start[g], e = start[g + 1];
+      const uint64_t a = pgscr::lower_bound_u32(member, s, e, r0);
+      const uint64_t b = pgscr::lower_bound_u32(member, a, e, r1);
+      lo[g] = (uint32_t)(a - s);
+      mb[g] = mine = (uint32_t)(b - a);
+    }
+    for (int d = 32; d > 0; d >>= 1) mine += __shfl_down(mine, d, 64);      // (at most 64 x 8192)
+    if ((threadIdx.x & 63u) == 0u && mine) atomicAdd(in_band, (unsigned long long)mine);
+  }
+}
+
+// B2 the weights of the groups with a member in the band (active: their indices, ascending): w[i] = mb m, w[na] = 0
+__global__ __launch_bounds__(256) void band_weight_kernel(const unsigned long long* __restrict__ active, uint64_t na, const unsigned long long* __restrict__ start,
+                                                           const uint32_t* __restrict__ mb, unsigned long long* __restrict__ w) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= na; i += (uint64_t)gridDim.x * blockDim.x) {
+    unsigned long long x = 0ull;
+    if (i < na) { const uint64_t g = active[i]; x = pgscr::band_items(mb[g], (uint32_t)(start[g + 1] - start[g])); }
+    w[i] = x;
+  }
+}
+
+// B3 count: screen_count_kernel's balance by item over the ACTIVE groups (each owns an item or more: the 257-offset window holds).  Item t
+// of a group -> (i, j) = (t / m, t % m): band[(member[lo + i] - r0) n + member[s + j]] += 1; the cell of a genome with itself is left to
+// band_diag_kernel.
+__global__ __launch_bounds__(256) void band_count_kernel(const unsigned long long* __restrict__ start, const uint32_t* __restrict__ member,
+                                                          const unsigned long long* __restrict__ active, const uint32_t* __restrict__ lo,
+                                                          const unsigned long long* __restrict__ off, uint64_t na, unsigned long long P, unsigned long long per,
+                                                          uint32_t n, uint32_t r0, uint32_t r1, uint32_t* __restrict__ band) {
+  __shared__ unsigned long long loff[257];
+  __shared__ uint64_t next_group;
+  const unsigned long long a = (unsigned long long)blockIdx.x * per;
+  const unsigned long long b = a + per < P ? a + per : P;
+  if (a >= b) return;
+  uint64_t glo = 0, ghi = na - 1u;      // the active group of item a: the last one whose offset is <= a (uniform over the workgroup)
+  while (glo < ghi) { const uint64_t mid = (glo + ghi + 1u) >> 1; if (off[mid] <= a) glo = mid; else ghi = mid - 1u; }
+  uint64_t gc = glo;
+  for (unsigned long long ta = a; ta < b; ta += 256ull) {
+    for (uint32_t w = threadIdx.x; w < 257u; w += blockDim.x) loff[w] = gc + w <= na ? off[gc + w] : P;
+    __syncthreads();
+    const unsigned long long t = ta + threadIdx.x;
+    if (t < b) {
+      uint32_t wl = 0, wh = 255;      // the last window entry whose offset is <= t (entries past the last group hold P > t)
+      while (wl < wh) { const uint32_t mid = (wl + wh + 1u) >> 1; if (loff[mid] <= t) wl = mid; else wh = mid - 1u; }
+      const uint64_t ga = gc + wl;
+      if (ga < na) {
+        const uint64_t g = active[ga];
+        const uint64_t s = start[g];
+        const uint32_t m = (uint32_t)(start[g + 1] - s);
+        uint32_t i, j;
+        pgscr::band_item_decode(t - loff[wl], m, &i, &j);
+        const uint64_t pi = s + lo[g] + i;
+        if (pi < s + m) {
+          const uint32_t gi = member[pi], gj = member[s + j];
+          if (gi >= r0 && gi < r1 && gj < n && gi != gj) atomicAdd(&band[(size_t)(gi - r0) * n + gj], 1u);
+        }
+      }
+      if (threadIdx.x == 255u) next_group = loff[wl + 1u] <= t + 1ull ? ga + 1u : ga;      // the group of item ta + 256
+    }
+    __syncthreads();
+    gc = next_group;      // (read only when another round follows: then lane 255 had an item)
+  }
+}
+
+// B4 the diagonal: the cell of row genome a with column genome a = sizes[a]
+__global__ __launch_bounds__(256) void band_diag_kernel(uint32_t* __restrict__ band, const uint32_t* __restrict__ sizes, uint32_t r0, uint32_t r1, uint32_t n) {
+  for (uint32_t r = r0 + blockIdx.x * blockDim.x + threadIdx.x; r < r1; r += gridDim.x * blockDim.x) band[(size_t)(r - r0) * n + r] = sizes[r];
+}
+
+// B5 select: the rule of screen_select_kernel on the rectangle of the rows [r0, r0 + rows) x n columns.  Tasks row-major: task = band row
+// * tpr + piece, SEL_CELLS cells of ONE row; counts / total as there.  The output carries the GLOBAL row r0 + band row.
+template <bool FILL>
+__global__ __launch_bounds__(256) void band_select_kernel(const uint32_t* __restrict__ band, const uint32_t* __restrict__ need, uint32_t n, uint32_t r0, uint32_t tpr,
+                                                           uint32_t n_tasks, unsigned long long* __restrict__ counts, unsigned long long total,
+                                                           int32_t* __restrict__ a_out, int32_t* __restrict__ b_out, uint32_t* __restrict__ s_out) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), n_waves = gridDim.x * (blockDim.x >> 6);
+  const unsigned long long below = (1ull << lane) - 1ull;
+  for (uint32_t task = wave; task < n_tasks; task += n_waves) {      // (uniform over the wave: every lane reaches every ballot)
+    const uint32_t brow = task / tpr, col0 = (task % tpr) * SEL_CELLS;
+    const uint32_t row = r0 + brow;
+    const uint32_t need_row = need[row];
+    const uint32_t* __restrict__ cells = band + (size_t)brow * n;
+    uint32_t v[SEL_STEPS];
+    bool keep[SEL_STEPS];
+#pragma unroll
+    for (uint32_t u = 0; u < SEL_STEPS; ++u) {
+      const uint32_t col = col0 + 64u * u + lane;
+      const bool in = col < n;
+      v[u] = in ? cells[col] : 0u;
+      const uint32_t need_col = in ? need[col] : 0u;
+      keep[u] = in && col != row && v[u] >= (need_row < need_col ? need_row : need_col);
+    }
+    if (!FILL) {
+      uint32_t c = 0;
+#pragma unroll
+      for (uint32_t u = 0; u < SEL_STEPS; ++u) c += (uint32_t)__popcll(__ballot(keep[u]));
+      if (lane == 0) counts[task] = c;
+    } else {
+      unsigned long long at = counts[task];
+#pragma unroll
+      for (uint32_t u = 0; u < SEL_STEPS; ++u) {
+        const unsigned long long bal = __ballot(keep[u]);
+        const unsigned long long mine = at + (unsigned long long)__popcll(bal & below);
+        if (keep[u] && mine < total) {
+          a_out[mine] = (int32_t)row; b_out[mine] = (int32_t)(col0 + 64u * u + lane); s_out[mine] = v[u];
+        }
+        at += (unsigned long long)__popcll(bal);
+      }
+    }
+  }
+  if (!FILL && blockIdx.x == 0 && threadIdx.x == 0) counts[n_tasks] = 0ull;
+}
+
+struct IndexState {      // the resident k-mer index of pg_screen_index and the latest selection over it
+  uint32_t n = 0;
+  uint64_t G = 0, E = 0;                        // groups (k-mers held by >= 2 genomes), grouped entries
+  PgDevBuf<unsigned long long> d_start;         // group_start: G + 1
+  PgDevBuf<uint32_t> d_member;                  // E: the call indices of a group's genomes, ascending inside a group
+  PgDevBuf<uint32_t> d_sizes;                   // n
+  bool selected = false;
+  std::vector<int32_t> a, b;                    // the kept triples of the latest pg_screen_index_select, on the host: bands go as they finish
+  std::vector<uint32_t> s;
+};
+
+IndexState* index_of(pg_ctx* ctx) { return static_cast<IndexState*>(ctx->screen_index_state); }
+
 struct ScreenState {      // the resident matrix of pg_screen_hold / pg_screen_load and the latest selection over it
   uint32_t n = 0;
   PgDevBuf<uint32_t> d_shared;      // n x n
@@ -277,12 +455,12 @@ struct ScreenEvents {      // pg_screen_last: event pairs on the context's strea
   }
   void begin(int st, hipStream_t s) { if (ok) { stage.push_back(st); mark(s); } }
   void end(hipStream_t s) { if (ok) mark(s); }
-  void sum(double* ms3) {
-    ms3[0] = ms3[1] = ms3[2] = 0.0;
+  void sum(double* ms, int n_stages = 3) {
+    for (int i = 0; i < n_stages; ++i) ms[i] = 0.0;
     if (!ok) return;
     for (size_t i = 0; i < stage.size() && 2 * i + 1 < ev.size(); ++i) {
       float x = 0.f;
-      if (hipEventElapsedTime(&x, ev[2 * i], ev[2 * i + 1]) == hipSuccess) ms3[stage[i]] += (double)x; else (void)hipGetLastError();
+      if (hipEventElapsedTime(&x, ev[2 * i], ev[2 * i + 1]) == hipSuccess) ms[stage[i]] += (double)x; else (void)hipGetLastError();
     }
   }
 };
@@ -311,8 +489,9 @@ namespace {
 
 // the argument checks of pg_screen_matrix and pg_screen_hold (want_shared: the call has a matrix to copy out, shared_out)
 int screen_check(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kmer, int32_t scale, uint32_t part, uint32_t n_parts, const uint32_t* sizes_out,
-                 bool want_shared, const uint32_t* shared_out) {
-  if (n > pgscr::MAX_GENOMES) return pg_fail(ctx, PG_E_ARG, "screen: more than 8192 genomes in one call");      // (before the ids are read)
+                 bool want_shared, const uint32_t* shared_out, uint32_t max_n = pgscr::MAX_GENOMES,
+                 const char* too_many = "screen: more than 8192 genomes in one call") {
+  if (n > max_n) return pg_fail(ctx, PG_E_ARG, too_many);      // (before the ids are read)
   if (n && (!genome_ids || !sizes_out || (want_shared && !shared_out))) return pg_fail(ctx, PG_E_ARG, "bad argument");
   if (kmer < pgs::K_MIN || kmer > pgs::K_MAX) return pg_fail(ctx, PG_E_ARG, "screen: the k-mer size must be 8 ... 16");
   if (!pgscr::valid_scale(scale)) return pg_fail(ctx, PG_E_ARG, "screen: scale must be a power of two, 1 ... 65536");
@@ -326,16 +505,28 @@ int screen_check(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kme
   return PG_OK;
 }
 
-// The screen of checked arguments.  The finished matrix is left in d_shared (the caller's: pg_screen_matrix lets it go, pg_screen_hold keeps
-// it); sizes_out, and shared_out where it is given, are on the host when this returns.
-int screen_run(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kmer, int32_t scale, uint32_t part, uint32_t n_parts, uint32_t* sizes_out,
-               uint32_t* shared_out, PgDevBuf<uint32_t>& d_shared) {
-  for (int i = 0; i < 5; ++i) ctx->screen_last[i] = 0;
-  for (int i = 0; i < 3; ++i) ctx->screen_ms[i] = 0.0;
-  if (n == 0) return PG_OK;
-  PG_HIP(ctx, hipSetDevice(ctx->device));
+struct SliceGroups {      // one slice, sorted and grouped, on the device: what the front half hands to a back half
+  const unsigned long long* u;      // the nu distinct keys, sorted
+  uint64_t nu;
+  const uint8_t* flags;             // of the head kernel, one per key
+  const uint32_t* first;            // the first and the last entry of each of the ng k-mers held by >= 2 genomes
+  const uint32_t* last;
+  uint64_t ng;
+  void* tmp;                        // temporary storage of the library calls: what the front half needs, and what prepare() asked for
+  size_t tmp_bytes;
+};
+
+struct FrontTotals { uint64_t keys = 0, distinct = 0, groups = 0, slices = 0; };
+
+// The FRONT HALF of a screen of checked arguments (n >= 1), shared by the dense calls and the index: the count pass, slices of whole bins
+// under the budget, and per slice the fill pass, the radix sort, Unique and the head kernel's sizes and first / last marks (C1, C2 above).
+// What becomes of a grouped slice is the back half's: back.prepare(all keys, keys of the largest slice, its bound of groups, tmp bytes to
+// raise) once before the first slice, back.slice(S, T) per slice.  d_sizes (the caller's, empty) holds the finished sizes on return.
+// wide_head: screen_head_wide_kernel (any n, bit 2 of the flags) instead of the LDS histogram of at most MAX_GENOMES genomes.
+template <typename Back>
+int screen_front(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kmer, int32_t scale, uint32_t part, uint32_t n_parts, bool wide_head,
+                 PgDevBuf<uint32_t>& d_sizes, ScreenEvents& T, FrontTotals& tot, Back& back) {
   int rc;
-  if ((rc = pg_upload(ctx))) return rc;
   const auto scan_count = screen_scan_of<false>(kmer);
   const auto scan_fill = screen_scan_of<true>(kmer);
   if (!scan_count || !scan_fill) return pg_fail(ctx, PG_E_ARG, "screen: no scan kernel for this k-mer size");
@@ -357,15 +548,12 @@ int screen_run(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kmer,
   }
   PgDevBuf<ScreenGenome> d_tab;
   PgDevBuf<unsigned long long> d_hist, d_counters;      // [N_BINS] | [0] append cursor, [1] distinct keys, [2] groups
-  PgDevBuf<uint32_t> d_sizes;
   if ((rc = sk_malloc(ctx, d_tab, n)) || (rc = sk_malloc(ctx, d_hist, pgscr::N_BINS)) || (rc = sk_malloc(ctx, d_counters, 4)) ||
-      (rc = sk_malloc(ctx, d_sizes, n)) || (rc = sk_malloc(ctx, d_shared, (size_t)n * n)))
+      (rc = sk_malloc(ctx, d_sizes, n)))
     return rc;
   PG_HIP(ctx, hipMemcpyAsync(d_tab, tab.data(), (size_t)n * sizeof(ScreenGenome), hipMemcpyHostToDevice, st));
   PG_HIP(ctx, hipMemsetAsync(d_hist, 0, pgscr::N_BINS * 8, st));
   PG_HIP(ctx, hipMemsetAsync(d_sizes, 0, (size_t)n * 4, st));
-  PG_HIP(ctx, hipMemsetAsync(d_shared, 0, (size_t)n * n * 4, st));
-  ScreenEvents T;
   const dim3 scan_grid(grid_for(n_items, 1, cu_blocks));
   std::vector<unsigned long long> hist(pgscr::N_BINS, 0ull);
   if (n_items) {
@@ -394,15 +582,14 @@ int screen_run(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kmer,
     if (cur.keys) slices.push_back(cur);
     for (const Slice& s : slices) { total_keys += s.keys; slice_max = std::max(slice_max, s.keys); }
   }
-  uint64_t n_distinct = 0, n_groups = 0, n_incr = 0;
+  tot.keys = total_keys; tot.slices = slices.size();
   if (!slices.empty()) {
-    PgDevBuf<unsigned long long> keys_a, keys_b, wts, off;
+    PgDevBuf<unsigned long long> keys_a, keys_b;
     PgDevBuf<uint32_t> first, last;
     PgDevBuf<uint8_t> flags, tmp;
     const size_t max_groups = (size_t)(slice_max / 2 + 2);
     if ((rc = sk_malloc(ctx, keys_a, (size_t)slice_max + 1)) || (rc = sk_malloc(ctx, keys_b, (size_t)slice_max + 1)) ||
-        (rc = sk_malloc(ctx, flags, (size_t)slice_max + 1)) || (rc = sk_malloc(ctx, first, max_groups)) || (rc = sk_malloc(ctx, last, max_groups)) ||
-        (rc = sk_malloc(ctx, wts, max_groups)) || (rc = sk_malloc(ctx, off, max_groups)))
+        (rc = sk_malloc(ctx, flags, (size_t)slice_max + 1)) || (rc = sk_malloc(ctx, first, max_groups)) || (rc = sk_malloc(ctx, last, max_groups)))
       return rc;
     // temporary storage of the library calls: the largest any of them asks for at the largest slice
     const int end_bit = 32 + 2 * kmer;
@@ -417,8 +604,7 @@ int screen_run(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kmer,
     tmp_bytes = std::max(tmp_bytes, need);
     PG_HIP(ctx, hipcub::DeviceSelect::Flagged(nullptr, need, counting, is_first, first.p, d_ng, (int64_t)slice_max, st));
     tmp_bytes = std::max(tmp_bytes, need);
-    PG_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, need, wts.p, off.p, (int64_t)max_groups, st));
-    tmp_bytes = std::max(tmp_bytes, need);
+    if ((rc = back.prepare(total_keys, slice_max, max_groups, tmp_bytes))) return rc;
     if ((rc = sk_malloc(ctx, tmp, tmp_bytes + 16))) return rc;
 
     for (const Slice& S : slices) {
@@ -441,50 +627,96 @@ int screen_run(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kmer,
       if (cnt[0] != S.keys)
         return pg_fail(ctx, PG_E_INTERNAL, "screen: the fill pass appended " + std::to_string(cnt[0]) + " keys where the count pass saw " + std::to_string(S.keys));
       const uint64_t nu = cnt[1];
-      n_distinct += nu;
-      hipLaunchKernelGGL(screen_head_kernel, dim3(grid_for(nu, 256 * 16, cu_blocks)), dim3(256), 0, st, (const unsigned long long*)keys_a.p, nu, n, d_sizes.p,
-                         flags.p);
+      tot.distinct += nu;
+      hipLaunchKernelGGL(wide_head ? screen_head_wide_kernel : screen_head_kernel, dim3(grid_for(nu, 256 * 16, cu_blocks)), dim3(256), 0, st,
+                         (const unsigned long long*)keys_a.p, nu, n, d_sizes.p, flags.p);
       PG_HIP(ctx, hipGetLastError());
       tb = tmp_bytes;
       PG_HIP(ctx, hipcub::DeviceSelect::Flagged((void*)tmp.p, tb, counting, is_first, first.p, d_ng, (int64_t)nu, st));
       tb = tmp_bytes;
       PG_HIP(ctx, hipcub::DeviceSelect::Flagged((void*)tmp.p, tb, counting, is_last, last.p, d_ng, (int64_t)nu, st));
       PG_HIP(ctx, hipMemcpyAsync(&cnt[2], d_ng, 8, hipMemcpyDeviceToHost, st));
+      T.end(st);
       PG_HIP(ctx, hipStreamSynchronize(st));
       const uint64_t ng = cnt[2];
       if (ng + 1 > max_groups) return pg_fail(ctx, PG_E_INTERNAL, "screen: more groups than half the keys");
-      unsigned long long P = 0;
-      if (ng) {
-        hipLaunchKernelGGL(screen_weight_kernel, dim3(grid_for(ng + 1, 256, cu_blocks)), dim3(256), 0, st, (const uint32_t*)first.p, (const uint32_t*)last.p,
-                           (uint32_t)ng, wts.p);
-        PG_HIP(ctx, hipGetLastError());
-        tb = tmp_bytes;
-        PG_HIP(ctx, hipcub::DeviceScan::ExclusiveSum((void*)tmp.p, tb, wts.p, off.p, (int64_t)(ng + 1), st));
-        PG_HIP(ctx, hipMemcpyAsync(&P, off.p + ng, 8, hipMemcpyDeviceToHost, st));
-      }
-      T.end(st);
-      PG_HIP(ctx, hipStreamSynchronize(st));
-      n_groups += ng; n_incr += P;
-      // count
-      if (P) {
-        const uint64_t n_wg = std::max<uint64_t>(1, std::min<uint64_t>((P + 2047) / 2048, (uint64_t)ctx->num_cu * 32));
-        const unsigned long long per = (P + n_wg - 1) / n_wg;
-        T.begin(2, st);
-        hipLaunchKernelGGL(screen_count_kernel, dim3((uint32_t)((P + per - 1) / per)), dim3(256), 0, st, (const unsigned long long*)keys_a.p,
-                           (const uint32_t*)first.p, (const uint32_t*)last.p, (const unsigned long long*)off.p, (uint32_t)ng, P, per, n, d_shared.p);
-        T.end(st);
-        PG_HIP(ctx, hipGetLastError());
-      }
+      tot.groups += ng;
+      const SliceGroups G{keys_a.p, nu, flags.p, first.p, last.p, ng, (void*)tmp.p, tmp_bytes};
+      if ((rc = back.slice(G, T))) return rc;
     }
   }
-  hipLaunchKernelGGL(screen_finish_kernel, dim3(grid_for((uint64_t)n * n, 256 * 4, cu_blocks)), dim3(256), 0, st, d_shared.p, (const uint32_t*)d_sizes.p, n);
+  return PG_OK;
+}
+
+// The back half of the dense calls (C2's item ranges, C3): every grouped slice is counted into the n x n matrix.
+struct DenseBack {
+  pg_ctx* ctx;
+  uint32_t n;
+  uint32_t* d_shared;
+  PgDevBuf<unsigned long long> wts, off;
+  uint64_t n_incr = 0;
+  int prepare(uint64_t, uint64_t, size_t max_groups, size_t& tmp_bytes) {
+    int rc;
+    if ((rc = sk_malloc(ctx, wts, max_groups)) || (rc = sk_malloc(ctx, off, max_groups))) return rc;
+    size_t need = 0;
+    PG_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, need, wts.p, off.p, (int64_t)max_groups, ctx->stream));
+    tmp_bytes = std::max(tmp_bytes, need);
+    return PG_OK;
+  }
+  int slice(const SliceGroups& S, ScreenEvents& T) {
+    hipStream_t st = ctx->stream;
+    unsigned long long P = 0;
+    if (S.ng) {
+      T.begin(1, st);
+      hipLaunchKernelGGL(screen_weight_kernel, dim3(grid_for(S.ng + 1, 256, (uint32_t)ctx->num_cu * 8u)), dim3(256), 0, st, S.first, S.last, (uint32_t)S.ng, wts.p);
+      PG_HIP(ctx, hipGetLastError());
+      size_t tb = S.tmp_bytes;
+      PG_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(S.tmp, tb, wts.p, off.p, (int64_t)(S.ng + 1), st));
+      PG_HIP(ctx, hipMemcpyAsync(&P, off.p + S.ng, 8, hipMemcpyDeviceToHost, st));
+      T.end(st);
+      PG_HIP(ctx, hipStreamSynchronize(st));
+    }
+    n_incr += P;
+    if (P) {
+      const uint64_t n_wg = std::max<uint64_t>(1, std::min<uint64_t>((P + 2047) / 2048, (uint64_t)ctx->num_cu * 32));
+      const unsigned long long per = (P + n_wg - 1) / n_wg;
+      T.begin(2, st);
+      hipLaunchKernelGGL(screen_count_kernel, dim3((uint32_t)((P + per - 1) / per)), dim3(256), 0, st, S.u, S.first, S.last, (const unsigned long long*)off.p,
+                         (uint32_t)S.ng, P, per, n, d_shared);
+      T.end(st);
+      PG_HIP(ctx, hipGetLastError());
+    }
+    return PG_OK;
+  }
+};
+
+// The screen of checked arguments.  The finished matrix is left in d_shared (the caller's: pg_screen_matrix lets it go, pg_screen_hold keeps
+// it); sizes_out, and shared_out where it is given, are on the host when this returns.
+int screen_run(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kmer, int32_t scale, uint32_t part, uint32_t n_parts, uint32_t* sizes_out,
+               uint32_t* shared_out, PgDevBuf<uint32_t>& d_shared) {
+  for (int i = 0; i < 5; ++i) ctx->screen_last[i] = 0;
+  for (int i = 0; i < 3; ++i) ctx->screen_ms[i] = 0.0;
+  if (n == 0) return PG_OK;
+  PG_HIP(ctx, hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = pg_upload(ctx))) return rc;
+  hipStream_t st = ctx->stream;
+  if ((rc = sk_malloc(ctx, d_shared, (size_t)n * n))) return rc;
+  PG_HIP(ctx, hipMemsetAsync(d_shared, 0, (size_t)n * n * 4, st));
+  PgDevBuf<uint32_t> d_sizes;
+  ScreenEvents T;
+  FrontTotals tot;
+  DenseBack back{ctx, n, d_shared.p};
+  if ((rc = screen_front(ctx, genome_ids, n, kmer, scale, part, n_parts, false, d_sizes, T, tot, back))) return rc;
+  hipLaunchKernelGGL(screen_finish_kernel, dim3(grid_for((uint64_t)n * n, 256 * 4, (uint32_t)ctx->num_cu * 8u)), dim3(256), 0, st, d_shared.p,
+                     (const uint32_t*)d_sizes.p, n);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(sizes_out, d_sizes, (size_t)n * 4, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && shared_out) e = hipMemcpyAsync(shared_out, d_shared, (size_t)n * n * 4, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return pg_fail(ctx, PG_E_HIP, std::string("screen: ") + hipGetErrorString(e));
-  ctx->screen_last[0] = total_keys; ctx->screen_last[1] = n_distinct; ctx->screen_last[2] = n_groups; ctx->screen_last[3] = n_incr;
-  ctx->screen_last[4] = slices.size();
+  ctx->screen_last[0] = tot.keys; ctx->screen_last[1] = tot.distinct; ctx->screen_last[2] = tot.groups; ctx->screen_last[3] = back.n_incr;
+  ctx->screen_last[4] = tot.slices;
   T.sum(ctx->screen_ms);
   return PG_OK;
 }
@@ -617,5 +849,330 @@ extern "C" int pg_screen_select_read(pg_ctx* ctx, int32_t* a_out, int32_t* b_out
   PG_HIP(ctx, hipMemcpyAsync(b_out, S->d_b, S->n_sel * 4, hipMemcpyDeviceToHost, ctx->stream));
   PG_HIP(ctx, hipMemcpyAsync(shared_out, S->d_s, S->n_sel * 4, hipMemcpyDeviceToHost, ctx->stream));
   PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return PG_OK;
+}
+
+// ---- the screen index and its bands ----------------------------------------------------------------------------------------
+namespace {
+
+// The back half of pg_screen_index: the grouped entries of every slice are appended to group_start / member; nothing is counted.
+struct IndexBack {
+  pg_ctx* ctx;
+  IndexState* I;
+  PgDevBuf<unsigned long long> wts, d_sel;      // the groups' sizes of a slice | [0] the entries Flagged kept
+  size_t cap_groups = 0, cap_entries = 0;
+  int prepare(uint64_t total_keys, uint64_t slice_max, size_t max_groups, size_t& tmp_bytes) {
+    // every grouped entry is a distinct key and every group holds two of them or more: E <= keys, G <= keys / 2
+    cap_entries = (size_t)total_keys;
+    cap_groups = (size_t)(total_keys / 2);
+    hipStream_t st = ctx->stream;
+    int rc;
+    if ((rc = sk_malloc(ctx, wts, max_groups)) || (rc = sk_malloc(ctx, d_sel, 1))) return rc;
+    if (sk_malloc(ctx, I->d_member, cap_entries + 1) || sk_malloc(ctx, I->d_start, cap_groups + 2))
+      return pg_fail(ctx, PG_E_NOMEM, "screen: no device memory for an index of up to " + std::to_string(cap_entries) + " entries (4 bytes each) in " +
+                                          std::to_string(cap_groups) + " groups (8 bytes each)");
+    PG_HIP(ctx, hipMemsetAsync(I->d_start, 0, 8, st));
+    hipcub::TransformInputIterator<uint32_t, LowHalf, const unsigned long long*> genome((const unsigned long long*)nullptr, LowHalf{});
+    hipcub::TransformInputIterator<uint8_t, FlagBit, const uint8_t*> grouped((const uint8_t*)nullptr, FlagBit{2u});
+    size_t need = 0;
+    PG_HIP(ctx, hipcub::DeviceSelect::Flagged(nullptr, need, genome, grouped, I->d_member.p, d_sel.p, (int64_t)slice_max, st));
+    tmp_bytes = std::max(tmp_bytes, need);
+    PG_HIP(ctx, hipcub::DeviceScan::ExclusiveScan(nullptr, need, wts.p, I->d_start.p, hipcub::Sum(), 0ull, (int64_t)max_groups, st));
+    tmp_bytes = std::max(tmp_bytes, need);
+    return PG_OK;
+  }
+  int slice(const SliceGroups& S, ScreenEvents& T) {
+    if (!S.ng) return PG_OK;
+    hipStream_t st = ctx->stream;
+    if (I->G + S.ng > cap_groups) return pg_fail(ctx, PG_E_INTERNAL, "screen: more groups than half the keys");
+    T.begin(1, st);
+    // group_start continues at E: the slice's group sizes scanned from there; the entry after the last group is the next slice's first
+    hipLaunchKernelGGL(index_size_kernel, dim3(grid_for(S.ng + 1, 256, (uint32_t)ctx->num_cu * 8u)), dim3(256), 0, st, S.first, S.last, (uint32_t)S.ng, wts.p);
+    PG_HIP(ctx, hipGetLastError());
+    size_t tb = S.tmp_bytes;
+    PG_HIP(ctx, hipcub::DeviceScan::ExclusiveScan(S.tmp, tb, wts.p, I->d_start.p + I->G, hipcub::Sum(), (unsigned long long)I->E, (int64_t)(S.ng + 1), st));
+    // member: the genomes of the grouped entries, in key order (inside a group the call index ascends: it is the low half of the key)
+    hipcub::TransformInputIterator<uint32_t, LowHalf, const unsigned long long*> genome(S.u, LowHalf{});
+    hipcub::TransformInputIterator<uint8_t, FlagBit, const uint8_t*> grouped(S.flags, FlagBit{2u});
+    tb = S.tmp_bytes;
+    PG_HIP(ctx, hipcub::DeviceSelect::Flagged(S.tmp, tb, genome, grouped, I->d_member.p + I->E, d_sel.p, (int64_t)S.nu, st));   // (at most nu <= the slice's keys: room by cap_entries)
+    unsigned long long kept = 0, end = 0;
+    PG_HIP(ctx, hipMemcpyAsync(&kept, d_sel.p, 8, hipMemcpyDeviceToHost, st));
+    PG_HIP(ctx, hipMemcpyAsync(&end, I->d_start.p + I->G + S.ng, 8, hipMemcpyDeviceToHost, st));
+    T.end(st);
+    PG_HIP(ctx, hipStreamSynchronize(st));
+    if (end != I->E + kept || I->E + kept > cap_entries)
+      return pg_fail(ctx, PG_E_INTERNAL, "screen: the index took " + std::to_string(kept) + " entries of a slice whose groups hold " + std::to_string(end - I->E));
+    I->G += S.ng; I->E += kept;
+    return PG_OK;
+  }
+};
+
+// the band setting of the context against an index of n genomes
+uint32_t rows_for(const pg_ctx* ctx, uint32_t n) { return pgscr::band_rows(ctx->screen_band_rows, n); }
+
+struct BandWork {      // the device buffers of the band calls: one band and what prep, count and select need beside it
+  PgDevBuf<uint32_t> band, lo, mb, need, s;
+  PgDevBuf<unsigned long long> active, wts, off, counters, cnt, coff;      // counters: [0] active groups, [1] members in the band
+  PgDevBuf<int32_t> a, b;
+  PgDevBuf<uint8_t> tmp;
+  size_t tmp_bytes = 0;
+};
+
+// (pg_dev_alloc, not sk_malloc: the band calls leave the resident matrix of pg_screen_hold / _load alone, however short memory is)
+int band_alloc(pg_ctx* ctx, const IndexState* I, uint32_t rows, bool select, BandWork& W) {
+  hipStream_t st = ctx->stream;
+  const size_t G = (size_t)I->G;
+  int rc;
+  if ((rc = pg_dev_alloc(ctx, "screen", W.band, (size_t)rows * I->n, "a band of the index")) || (rc = pg_dev_alloc(ctx, "screen", W.lo, G, "the band's group ranges")) ||
+      (rc = pg_dev_alloc(ctx, "screen", W.mb, G, "the band's group ranges")) || (rc = pg_dev_alloc(ctx, "screen", W.active, G, "the band's groups")) ||
+      (rc = pg_dev_alloc(ctx, "screen", W.wts, G + 1, "the band's group weights")) || (rc = pg_dev_alloc(ctx, "screen", W.off, G + 1, "the band's item offsets")) ||
+      (rc = pg_dev_alloc(ctx, "screen", W.counters, 2, "the band's counters")))
+    return rc;
+  hipcub::CountingInputIterator<unsigned long long> counting(0ull);
+  hipcub::TransformInputIterator<uint8_t, NonZero, const uint32_t*> has((const uint32_t*)W.mb.p, NonZero{});
+  size_t need = 0;
+  PG_HIP(ctx, hipcub::DeviceSelect::Flagged(nullptr, need, counting, has, W.active.p, W.counters.p, (int64_t)G, st));
+  W.tmp_bytes = std::max(W.tmp_bytes, need);
+  PG_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, need, W.wts.p, W.off.p, (int64_t)G + 1, st));
+  W.tmp_bytes = std::max(W.tmp_bytes, need);
+  if (select) {
+    const uint32_t tpr = (I->n + SEL_CELLS - 1) / SEL_CELLS;
+    const size_t n_tasks = (size_t)rows * tpr;
+    if ((rc = pg_dev_alloc(ctx, "screen", W.need, I->n, "the thresholds")) || (rc = pg_dev_alloc(ctx, "screen", W.cnt, n_tasks + 1, "the task counts")) ||
+        (rc = pg_dev_alloc(ctx, "screen", W.coff, n_tasks + 1, "the task offsets")))
+      return rc;
+    PG_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, need, W.cnt.p, W.coff.p, (int64_t)n_tasks + 1, st));
+    W.tmp_bytes = std::max(W.tmp_bytes, need);
+  }
+  return pg_dev_alloc(ctx, "screen", W.tmp, W.tmp_bytes + 16, "the library calls' temporary storage");
+}
+
+// B1 ... B4: the rows [r0, r1) of the matrix in W.band, the diagonal included.  *incr += the increments of the count kernel.
+int band_fill(pg_ctx* ctx, const IndexState* I, uint32_t r0, uint32_t r1, BandWork& W, uint64_t* incr) {
+  hipStream_t st = ctx->stream;
+  const uint32_t n = I->n, cu_blocks = (uint32_t)ctx->num_cu * 8u;
+  PG_HIP(ctx, hipMemsetAsync(W.band, 0, (size_t)(r1 - r0) * n * 4, st));
+  if (I->G) {
+    PG_HIP(ctx, hipMemsetAsync(W.counters, 0, 2 * 8, st));
+    hipLaunchKernelGGL(band_prep_kernel, dim3(grid_for(I->G, 256, cu_blocks)), dim3(256), 0, st, (const unsigned long long*)I->d_start.p, (const uint32_t*)I->d_member.p,
+                       I->G, r0, r1, W.lo.p, W.mb.p, W.counters.p + 1);
+    PG_HIP(ctx, hipGetLastError());
+    hipcub::CountingInputIterator<unsigned long long> counting(0ull);
+    hipcub::TransformInputIterator<uint8_t, NonZero, const uint32_t*> has((const uint32_t*)W.mb.p, NonZero{});
+    size_t tb = W.tmp_bytes;
+    PG_HIP(ctx, hipcub::DeviceSelect::Flagged((void*)W.tmp.p, tb, counting, has, W.active.p, W.counters.p, (int64_t)I->G, st));
+    unsigned long long c[2] = {0, 0};
+    PG_HIP(ctx, hipMemcpyAsync(c, W.counters, 2 * 8, hipMemcpyDeviceToHost, st));
+    PG_HIP(ctx, hipStreamSynchronize(st));
+    const uint64_t na = c[0];
+    if (na > I->G) return pg_fail(ctx, PG_E_INTERNAL, "screen: more groups in a band than in the index");
+    if (na) {
+      unsigned long long P = 0;
+      hipLaunchKernelGGL(band_weight_kernel, dim3(grid_for(na + 1, 256, cu_blocks)), dim3(256), 0, st, (const unsigned long long*)W.active.p, na,
+                         (const unsigned long long*)I->d_start.p, (const uint32_t*)W.mb.p, W.wts.p);
+      PG_HIP(ctx, hipGetLastError());
+      tb = W.tmp_bytes;
+      PG_HIP(ctx, hipcub::DeviceScan::ExclusiveSum((void*)W.tmp.p, tb, W.wts.p, W.off.p, (int64_t)(na + 1), st));
+      PG_HIP(ctx, hipMemcpyAsync(&P, W.off.p + na, 8, hipMemcpyDeviceToHost, st));
+      PG_HIP(ctx, hipStreamSynchronize(st));
+      if (P < c[1]) return pg_fail(ctx, PG_E_INTERNAL, "screen: fewer items in a band than members");
+      *incr += P - c[1];      // every member of the band meets itself once among its group's items: no increment (band_count_kernel)
+      const uint64_t n_wg = std::max<uint64_t>(1, std::min<uint64_t>((P + 2047) / 2048, (uint64_t)ctx->num_cu * 32));
+      const unsigned long long per = (P + n_wg - 1) / n_wg;
+      hipLaunchKernelGGL(band_count_kernel, dim3((uint32_t)((P + per - 1) / per)), dim3(256), 0, st, (const unsigned long long*)I->d_start.p,
+                         (const uint32_t*)I->d_member.p, (const unsigned long long*)W.active.p, (const uint32_t*)W.lo.p, (const unsigned long long*)W.off.p, na, P, per,
+                         n, r0, r1, W.band.p);
+      PG_HIP(ctx, hipGetLastError());
+    }
+  }
+  hipLaunchKernelGGL(band_diag_kernel, dim3(grid_for(r1 - r0, 256, cu_blocks)), dim3(256), 0, st, W.band.p, (const uint32_t*)I->d_sizes.p, r0, r1, n);
+  PG_HIP(ctx, hipGetLastError());
+  return PG_OK;
+}
+
+}  // namespace
+
+void pg_screen_index_drop(pg_ctx* ctx) {
+  if (!ctx->screen_index_state) return;
+  delete index_of(ctx);
+  ctx->screen_index_state = nullptr;
+}
+
+extern "C" int pg_screen_index_release(pg_ctx* ctx) {
+  if (!ctx) return PG_E_ARG;
+  PG_HIP(ctx, hipSetDevice(ctx->device));
+  PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  pg_screen_index_drop(ctx);
+  return PG_OK;
+}
+
+extern "C" int pg_screen_set_band(pg_ctx* ctx, uint32_t rows) {
+  if (!ctx) return PG_E_ARG;
+  if (rows > pgscr::MAX_BAND_ROWS) return pg_fail(ctx, PG_E_ARG, "screen: a band is of at most 8192 rows");
+  ctx->screen_band_rows = rows;
+  return PG_OK;
+}
+
+extern "C" int pg_screen_index_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out) {
+  if (!ctx || !counts_out || !ms_out) return pg_fail(ctx, PG_E_ARG, "bad argument");
+  for (int i = 0; i < 7; ++i) counts_out[i] = ctx->screen_index_last[i];
+  for (int i = 0; i < 4; ++i) ms_out[i] = ctx->screen_index_ms[i];
+  return PG_OK;
+}
+
+extern "C" int pg_screen_index(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kmer, int32_t scale, uint32_t* sizes_out) {
+  if (!ctx) return PG_E_ARG;
+  int rc;
+  if ((rc = screen_check(ctx, genome_ids, n, kmer, scale, 0, 1, sizes_out, false, nullptr, pgscr::INDEX_MAX_GENOMES,
+                         "screen: more than 1048576 (2^20) genomes in one index")))
+    return rc;
+  if ((rc = pg_screen_index_release(ctx))) return rc;      // the index of an earlier call goes before the new one is made: never two at a time
+  for (int i = 0; i < 7; ++i) ctx->screen_index_last[i] = 0;
+  for (int i = 0; i < 4; ++i) ctx->screen_index_ms[i] = 0.0;
+  if (n == 0) return PG_OK;      // (nothing to index)
+  PG_HIP(ctx, hipSetDevice(ctx->device));
+  if ((rc = pg_upload(ctx))) return rc;
+  hipStream_t st = ctx->stream;
+  std::unique_ptr<IndexState> I(new IndexState());
+  I->n = n;
+  ScreenEvents T;
+  FrontTotals tot;
+  {
+    IndexBack back{ctx, I.get()};
+    if ((rc = screen_front(ctx, genome_ids, n, kmer, scale, 0, 1, true, I->d_sizes, T, tot, back))) return rc;
+  }      // (the slices' buffers are gone here)
+  if (!I->d_start.p) {      // no slice at all: an index without groups
+    if ((rc = sk_malloc(ctx, I->d_start, 1)) || (rc = sk_malloc(ctx, I->d_member, 1))) return rc;
+    PG_HIP(ctx, hipMemsetAsync(I->d_start, 0, 8, st));
+  }
+  PG_HIP(ctx, hipMemcpyAsync(sizes_out, I->d_sizes, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  PG_HIP(ctx, hipStreamSynchronize(st));
+  // the arrays were sized by the keys before anything was grouped: an index that is much smaller moves into blocks of its own size
+  if (I->d_member.cap > 2 * (size_t)I->E + 1024) {
+    PgDevBuf<uint32_t> m;
+    PgDevBuf<unsigned long long> s;
+    if (m.reserve((size_t)I->E + 1) == hipSuccess && s.reserve((size_t)I->G + 1) == hipSuccess) {
+      PG_HIP(ctx, hipMemcpyAsync(m, I->d_member, (size_t)I->E * 4, hipMemcpyDeviceToDevice, st));
+      PG_HIP(ctx, hipMemcpyAsync(s, I->d_start, ((size_t)I->G + 1) * 8, hipMemcpyDeviceToDevice, st));
+      PG_HIP(ctx, hipStreamSynchronize(st));
+      I->d_member = std::move(m); I->d_start = std::move(s);
+    } else {
+      (void)hipGetLastError();      // (no room for the copy: the index stays where it is)
+    }
+  }
+  ctx->screen_index_last[0] = tot.keys; ctx->screen_index_last[1] = tot.distinct; ctx->screen_index_last[2] = I->E; ctx->screen_index_last[3] = I->G;
+  ctx->screen_index_last[4] = tot.slices;
+  double ms[3];
+  T.sum(ms);
+  ctx->screen_index_ms[0] = ms[0]; ctx->screen_index_ms[1] = ms[1];
+  ctx->screen_index_state = I.release();
+  return PG_OK;
+}
+
+extern "C" int pg_screen_index_band(pg_ctx* ctx, uint32_t band, uint32_t* out) {
+  if (!ctx) return PG_E_ARG;
+  IndexState* I = index_of(ctx);
+  if (!I) return pg_fail(ctx, PG_E_ARG, "screen: no resident index (call pg_screen_index first)");
+  const uint32_t rows = rows_for(ctx, I->n), n_bands = pgscr::band_count(I->n, rows);
+  if (band >= n_bands) return pg_fail(ctx, PG_E_ARG, "screen: band " + std::to_string(band) + " does not exist (the index has " + std::to_string(n_bands) + " bands of " +
+                                                         std::to_string(rows) + " rows)");
+  if (!out) return pg_fail(ctx, PG_E_ARG, "screen: bad argument");
+  PG_HIP(ctx, hipSetDevice(ctx->device));
+  uint32_t r0, r1;
+  pgscr::band_range(band, rows, I->n, &r0, &r1);
+  BandWork W;
+  uint64_t incr = 0;
+  int rc;
+  if ((rc = band_alloc(ctx, I, r1 - r0, false, W)) || (rc = band_fill(ctx, I, r0, r1, W, &incr))) return rc;
+  PG_HIP(ctx, hipMemcpyAsync(out, W.band, (size_t)(r1 - r0) * I->n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  PG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return PG_OK;
+}
+
+extern "C" int pg_screen_index_select(pg_ctx* ctx, const uint32_t* need, uint32_t n, uint32_t band_first, uint32_t band_step, uint64_t* n_pairs_out) {
+  if (!ctx) return PG_E_ARG;
+  IndexState* I = index_of(ctx);
+  if (!I) return pg_fail(ctx, PG_E_ARG, "screen: no resident index (call pg_screen_index first)");
+  if (n != I->n) return pg_fail(ctx, PG_E_ARG, "screen: the resident index is of " + std::to_string(I->n) + " genomes, not " + std::to_string(n));
+  if (band_step < 1) return pg_fail(ctx, PG_E_ARG, "screen: band_step must be 1 or more");
+  if (!need || !n_pairs_out) return pg_fail(ctx, PG_E_ARG, "screen: bad argument");
+  PG_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  I->selected = false;
+  I->a.clear(); I->b.clear(); I->s.clear();
+  ctx->screen_index_last[5] = ctx->screen_index_last[6] = 0;
+  ctx->screen_index_ms[2] = ctx->screen_index_ms[3] = 0.0;
+  const uint32_t rows = rows_for(ctx, n), n_bands = pgscr::band_count(n, rows);
+  const uint32_t tpr = (n + SEL_CELLS - 1) / SEL_CELLS;
+  uint64_t incr = 0, worked = 0;
+  ScreenEvents T;
+  if (band_first < n_bands) {
+    BandWork W;
+    int rc;
+    if ((rc = band_alloc(ctx, I, std::min(rows, n), true, W))) return rc;
+    PG_HIP(ctx, hipMemcpyAsync(W.need, need, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    for (uint64_t band = band_first; band < n_bands; band += band_step) {
+      uint32_t r0, r1;
+      pgscr::band_range((uint32_t)band, rows, n, &r0, &r1);
+      T.begin(2, st);
+      rc = band_fill(ctx, I, r0, r1, W, &incr);
+      T.end(st);
+      if (rc) return rc;
+      const uint32_t n_tasks = (r1 - r0) * tpr;      // rows * n <= 2^33 cells in pieces of 512: below 2^32
+      const dim3 grid(grid_for(n_tasks, 4, (uint32_t)ctx->num_cu * 8u));
+      T.begin(3, st);
+      hipLaunchKernelGGL(band_select_kernel<false>, grid, dim3(256), 0, st, (const uint32_t*)W.band.p, (const uint32_t*)W.need.p, n, r0, tpr, n_tasks, W.cnt.p, 0ull,
+                         (int32_t*)nullptr, (int32_t*)nullptr, (uint32_t*)nullptr);
+      PG_HIP(ctx, hipGetLastError());
+      size_t tb = W.tmp_bytes;
+      PG_HIP(ctx, hipcub::DeviceScan::ExclusiveSum((void*)W.tmp.p, tb, W.cnt.p, W.coff.p, (int64_t)n_tasks + 1, st));
+      unsigned long long total = 0;
+      PG_HIP(ctx, hipMemcpyAsync(&total, W.coff.p + n_tasks, 8, hipMemcpyDeviceToHost, st));
+      PG_HIP(ctx, hipStreamSynchronize(st));
+      if (total > (unsigned long long)(r1 - r0) * n) return pg_fail(ctx, PG_E_INTERNAL, "screen: the selection counted more cells than the band has");
+      if (total) {
+        if (W.a.reserve((size_t)total) != hipSuccess || W.b.reserve((size_t)total) != hipSuccess || W.s.reserve((size_t)total) != hipSuccess) {
+          (void)hipGetLastError();
+          return pg_fail(ctx, PG_E_NOMEM, "screen: no device memory for the " + std::to_string(total) + " selected pairs of a band");
+        }
+        hipLaunchKernelGGL(band_select_kernel<true>, grid, dim3(256), 0, st, (const uint32_t*)W.band.p, (const uint32_t*)W.need.p, n, r0, tpr, n_tasks, W.coff.p, total,
+                           W.a.p, W.b.p, W.s.p);
+        PG_HIP(ctx, hipGetLastError());
+        // the band's triples go to the host as it finishes: the device never holds more than one band
+        const size_t at = I->a.size();
+        try {
+          I->a.resize(at + total); I->b.resize(at + total); I->s.resize(at + total);
+        } catch (const std::bad_alloc&) {
+          I->a.clear(); I->b.clear(); I->s.clear();
+          return pg_fail(ctx, PG_E_NOMEM, "screen: no host memory for " + std::to_string(at + total) + " selected pairs");
+        }
+        PG_HIP(ctx, hipMemcpyAsync(I->a.data() + at, W.a, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+        PG_HIP(ctx, hipMemcpyAsync(I->b.data() + at, W.b, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+        PG_HIP(ctx, hipMemcpyAsync(I->s.data() + at, W.s, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+      }
+      T.end(st);
+      PG_HIP(ctx, hipStreamSynchronize(st));
+      ++worked;
+    }
+  }
+  double ms[4];
+  T.sum(ms, 4);
+  ctx->screen_index_ms[2] = ms[2]; ctx->screen_index_ms[3] = ms[3];
+  ctx->screen_index_last[5] = worked; ctx->screen_index_last[6] = incr;
+  I->selected = true;
+  *n_pairs_out = I->a.size();
+  return PG_OK;
+}
+
+extern "C" int pg_screen_index_read(pg_ctx* ctx, int32_t* a_out, int32_t* b_out, uint32_t* shared_out) {
+  if (!ctx) return PG_E_ARG;
+  IndexState* I = index_of(ctx);
+  if (!I || !I->selected) return pg_fail(ctx, PG_E_ARG, "screen: no selection over an index (call pg_screen_index_select first)");
+  if (I->a.empty()) return PG_OK;
+  if (!a_out || !b_out || !shared_out) return pg_fail(ctx, PG_E_ARG, "screen: bad argument");
+  std::copy(I->a.begin(), I->a.end(), a_out);
+  std::copy(I->b.begin(), I->b.end(), b_out);
+  std::copy(I->s.begin(), I->s.end(), shared_out);
   return PG_OK;
 }

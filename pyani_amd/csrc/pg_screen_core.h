@@ -53,4 +53,41 @@ PGS_HD void screen_tri_decode(uint64_t t, uint32_t m, uint32_t* i_out, uint32_t*
   *j_out = (uint32_t)i + 1u + (uint32_t)(t - tri_row_start((uint32_t)i, m));
 }
 
+// ---- the screen index: collections beyond MAX_GENOMES, worked a BAND of matrix rows at a time ---------------------------
+constexpr uint32_t INDEX_MAX_GENOMES = 1u << 20;  // per pg_screen_index call
+constexpr uint32_t MAX_BAND_ROWS = 8192;          // the largest pg_screen_set_band takes, and the default's cap
+constexpr uint64_t MAX_BAND_CELLS = 1ull << 29;   // the default band: rows * n <= 2^29 cells (2 GiB of uint32)
+
+// the default band of n >= 1 genomes: the largest rows <= min(MAX_BAND_ROWS, n) with rows * n <= MAX_BAND_CELLS (>= 1 for n <= 2^29)
+PGS_HD uint32_t band_default_rows(uint32_t n) {
+  uint64_t rows = MAX_BAND_CELLS / n;
+  if (rows > MAX_BAND_ROWS) rows = MAX_BAND_ROWS;
+  if (rows > n) rows = n;
+  return (uint32_t)rows;
+}
+// setting: what pg_screen_set_band holds (0 = the default)
+PGS_HD uint32_t band_rows(uint32_t setting, uint32_t n) { return setting ? setting : band_default_rows(n); }
+PGS_HD uint32_t band_count(uint32_t n, uint32_t rows) { return (uint32_t)(((uint64_t)n + rows - 1u) / rows); }
+// band b (< band_count) covers the rows [r0, r1) = [b rows, min(n, (b + 1) rows))
+PGS_HD void band_range(uint32_t b, uint32_t rows, uint32_t n, uint32_t* r0, uint32_t* r1) {
+  const uint64_t lo = (uint64_t)b * rows, hi = lo + rows;
+  *r0 = (uint32_t)(lo < n ? lo : n);
+  *r1 = (uint32_t)(hi < n ? hi : n);
+}
+// A group of m members, mb of them in the band, owns mb m items: item t (< mb m <= 2^13 2^20) -> (i, j) = (member of the band, member of
+// the group), row-major, so that consecutive items run j upward along one band row.
+PGS_HD uint64_t band_items(uint32_t mb, uint32_t m) { return (uint64_t)mb * m; }
+PGS_HD void band_item_decode(uint64_t t, uint32_t m, uint32_t* i_out, uint32_t* j_out) {
+  *i_out = (uint32_t)(t / m);
+  *j_out = (uint32_t)(t % m);
+}
+// the first position p in [lo, hi) of an ascending array with a[p] >= x (hi where there is none)
+PGS_HD uint64_t lower_bound_u32(const uint32_t* a, uint64_t lo, uint64_t hi, uint32_t x) {
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo) / 2u;
+    if (a[mid] < x) lo = mid + 1u; else hi = mid;
+  }
+  return lo;
+}
+
 }  // namespace pgscr

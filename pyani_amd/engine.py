@@ -447,14 +447,64 @@ class Engine:
     def screen_release(self) -> None:
         self._check(self.lib.pg_screen_release(self._h))
 
-    def screen_candidates(self, ids, options, labels=None):
+    def screen_candidates(self, ids, options, labels=None, path: str = "auto"):
         """The pairs of the resident genomes `ids` worth an exact comparison (pyani_amd.screen.ScreenedPairs; options: a ScreenOptions or
-        a bare identity threshold): hold -> identity_thresholds -> select -> release.  Equal, in content and order, to
-        screen_genomes(...).candidate_pairs(min_identity, min_shared) without the matrix ever leaving the device."""
+        a bare identity threshold).  path "dense": hold -> identity_thresholds -> select -> release, at most 8192 genomes; "index":
+        screen_index -> identity_thresholds -> screen_index_select -> release, up to 2^20 genomes, the matrix formed a band at a time
+        (DESIGN.md §16.2); "auto": dense up to screen.DENSE_MAX_GENOMES, the index beyond.  Both paths give the same ScreenedPairs: equal,
+        in content and order, to screen_genomes(...).candidate_pairs(min_identity, min_shared) without the matrix ever leaving the device."""
         from . import screen
         options = screen.check_options(options)
         ids = [int(i) for i in ids]
+        if screen.resolve_path(path, len(ids)) == "index":
+            return screen.index_candidates_on([self], lambda fn: [fn(self, 0)], ids, options, labels)
         return screen.candidates_on(self, lambda: self.screen_hold(ids, options.kmer, options.scale), ids, options, labels)
+
+    # the index (DESIGN.md §16.2): the grouped k-mers resident on the context, the matrix counted and selected a band of rows at a time
+    def screen_index(self, ids, kmer: int = 16, scale: int = 256) -> np.ndarray:
+        """pg_screen_index: builds the resident k-mer index of the genomes in the order given (up to 2^20) and returns sizes uint32[n]."""
+        a = self._ids(ids)
+        n = len(a)
+        sizes = np.zeros(n if n <= (1 << 20) else 0, dtype=np.uint32)      # (beyond: refused before anything is read)
+        self._check(self.lib.pg_screen_index(self._h, a.ctypes.data if n else None, n, int(kmer), int(scale), sizes.ctypes.data if sizes.size else None))
+        self._index_n = n      # (only a call that succeeded leaves an index: its size is the one screen_index_band may rely on)
+        return sizes
+
+    def screen_set_band(self, rows: int = 0) -> None:
+        """pg_screen_set_band: the matrix rows of one band of the index calls, at most 8192; 0 = the default (screen.default_band_rows)."""
+        self._check(self.lib.pg_screen_set_band(self._h, int(rows)))
+        self._band_rows = int(rows)
+
+    def screen_index_select(self, need, band_first: int = 0, band_step: int = 1) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """pg_screen_index_select + pg_screen_index_read: screen_select's triples of the bands band_first, band_first + band_step, ...
+        of the resident index, row-major."""
+        t = np.ascontiguousarray(need, dtype=np.uint32).reshape(-1)
+        m = ctypes.c_uint64(0)
+        self._check(self.lib.pg_screen_index_select(self._h, t.ctypes.data if len(t) else None, len(t), int(band_first), int(band_step), ctypes.byref(m)))
+        a, b, s = np.zeros(m.value, dtype=np.int32), np.zeros(m.value, dtype=np.int32), np.zeros(m.value, dtype=np.uint32)
+        self._check(self.lib.pg_screen_index_read(self._h, *(x.ctypes.data if m.value else None for x in (a, b, s))))
+        return a, b, s
+
+    def screen_index_band(self, band: int) -> np.ndarray:
+        """pg_screen_index_band: the finished band `band` of the resident index, uint32[rows of the band, n]: those rows of screen_matrix."""
+        from . import screen
+        n = getattr(self, "_index_n", 0)      # (the library refuses before it writes when there is no index or no such band)
+        ranges = screen.band_ranges(n, getattr(self, "_band_rows", 0))
+        r0, r1 = ranges[band] if 0 <= int(band) < len(ranges) else (0, 0)
+        out = np.zeros((r1 - r0, n), dtype=np.uint32)
+        self._check(self.lib.pg_screen_index_band(self._h, int(band), out.ctypes.data if out.size else None))
+        return out
+
+    def screen_index_last(self) -> dict:
+        """pg_screen_index_last: counts and stage milliseconds of the latest screen_index and of the latest screen_index_select."""
+        c = (ctypes.c_uint64 * 7)()
+        ms = (ctypes.c_double * 4)()
+        self._check(self.lib.pg_screen_index_last(self._h, ctypes.addressof(c), ctypes.addressof(ms)))
+        return {"keys": int(c[0]), "distinct": int(c[1]), "entries": int(c[2]), "groups": int(c[3]), "slices": int(c[4]), "bands": int(c[5]),
+                "pair_increments": int(c[6]), "scan_ms": float(ms[0]), "sort_group_ms": float(ms[1]), "count_ms": float(ms[2]), "select_ms": float(ms[3])}
+
+    def screen_index_release(self) -> None:
+        self._check(self.lib.pg_screen_index_release(self._h))
 
     # -- classify: clique sweep over identity thresholds (pyani_amd.classify drives these) -------------------------------------
     def classify_edges(self, identity: np.ndarray, coverage: np.ndarray, id_min: float = 0.8, cov_min: float = 0.5) -> Tuple[int, int]:

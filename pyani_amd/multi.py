@@ -297,12 +297,17 @@ class MultiEngine:
         shared = np.sum([r[1] for r in res], axis=0, dtype=np.uint64).astype(np.uint32)
         return sizes, shared
 
-    def screen_candidates(self, ids, options, labels=None):
-        """Engine.screen_candidates over all devices: the summed screen_matrix above, loaded onto the first engine, selected there.
-        Equal to one engine's."""
+    def screen_candidates(self, ids, options, labels=None, path: str = "auto"):
+        """Engine.screen_candidates over all devices.  Dense path: the summed screen_matrix above, loaded onto the first engine, selected
+        there.  Index path: EVERY engine builds the whole index — the store is replicated, and so is the scan, the sort
+        and the grouping — and only the count and the selection are divided: engine d of D takes the bands d, d + D, ..., and the parts
+        are merged by a stable sort on the row (a row lies in one band, so in one part).  What dividing only the back half is worth has
+        not been measured.  Equal to one engine's on either path."""
         from . import screen
         options = screen.check_options(options)
         ids = [int(i) for i in ids]
+        if screen.resolve_path(path, len(ids)) == "index":
+            return screen.index_candidates_on(self.engines, lambda fn: self._all(lambda e: fn(e, self.engines.index(e))), ids, options, labels)
         first = self.engines[0]
 
         def make_resident():
@@ -314,6 +319,10 @@ class MultiEngine:
     def screen_set_budget(self, max_keys: int = 0):
         for e in self.engines:
             e.screen_set_budget(max_keys)
+
+    def screen_set_band(self, rows: int = 0):
+        for e in self.engines:
+            e.screen_set_band(rows)
 
     def screen_last(self) -> dict:
         """Engine.screen_last of every device: the counts summed, the milliseconds of the slowest device per stage."""

@@ -24,7 +24,47 @@ import numpy as np
 import pandas as pd
 
 DEFAULT_KMER, DEFAULT_SCALE, DEFAULT_MIN_SHARED = 16, 256, 2
-MAX_GENOMES = 8192
+MAX_GENOMES = 8192                 # screen_genomes: a dense ScreenResult
+DENSE_MAX_GENOMES = 8192           # screen_candidates(path="auto"): the dense path up to here, the index path beyond (read at call time)
+INDEX_MAX_GENOMES = 1 << 20        # the index path (Engine.screen_index)
+MAX_BAND_ROWS, MAX_BAND_CELLS = 8192, 1 << 29
+PATHS = ("auto", "dense", "index")
+
+
+def default_band_rows(n: int) -> int:
+    """The default band of the index path for n >= 1 genomes: the largest rows <= min(8192, n) with rows * n <= 2^29 cells."""
+    if n < 1:
+        raise ValueError("a band needs a genome")
+    return min(MAX_BAND_ROWS, n, MAX_BAND_CELLS // n)
+
+
+def band_ranges(n: int, rows: int = 0) -> List[Tuple[int, int]]:
+    """[(r0, r1)] of the bands of n genomes at the band setting `rows` (0 = the default): band b covers [b rows, min(n, (b + 1) rows))."""
+    if n == 0:
+        return []
+    rows = int(rows) or default_band_rows(n)
+    if not 1 <= rows <= MAX_BAND_ROWS:
+        raise ValueError(f"a band is of 1 ... {MAX_BAND_ROWS} rows, not {rows}")
+    return [(r0, min(n, r0 + rows)) for r0 in range(0, n, rows)]
+
+
+def merge_dealt(parts) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(a, b, shared) of the selections of dealt bands — part d holds the bands d, d + D, ..., each row-major — put back into global
+    row-major order: concatenated, then a STABLE sort on the row.  A row lies in one band and so in one part, in column order."""
+    a = np.concatenate([np.asarray(p[0], dtype=np.int32) for p in parts]) if parts else np.zeros(0, np.int32)
+    b = np.concatenate([np.asarray(p[1], dtype=np.int32) for p in parts]) if parts else np.zeros(0, np.int32)
+    s = np.concatenate([np.asarray(p[2], dtype=np.uint32) for p in parts]) if parts else np.zeros(0, np.uint32)
+    order = np.argsort(a, kind="stable")
+    return a[order], b[order], s[order]
+
+
+def resolve_path(path: str, n: int) -> str:
+    """"dense" or "index" for a screen_candidates call over n genomes: "auto" is dense up to DENSE_MAX_GENOMES."""
+    if path not in PATHS:
+        raise ValueError(f"path must be one of {PATHS}, not {path!r}")
+    if path == "auto":
+        return "dense" if n <= DENSE_MAX_GENOMES else "index"
+    return path
 
 
 def check_params(kmer, scale) -> Tuple[int, int]:
@@ -134,13 +174,37 @@ class ScreenedPairs(NamedTuple):
                              "containment": self.containment(), "identity": self.identity()})
 
 
-def _labels_for(ids, labels) -> List[str]:
+def _labels_for(ids, labels, limit: int = MAX_GENOMES) -> List[str]:
     labels = [str(x) for x in (ids if labels is None else labels)]
     if len(labels) != len(ids):
         raise ValueError("ids and labels must have the same length")
-    if len(ids) > MAX_GENOMES:
-        raise ValueError(f"a screen call takes at most {MAX_GENOMES} genomes, not {len(ids)}")
+    if len(ids) > limit:
+        raise ValueError(f"a screen call takes at most {limit} genomes, not {len(ids)}")
     return labels
+
+
+def index_candidates_on(engines, run_all, ids, options, labels=None) -> ScreenedPairs:
+    """The selection through the index on the D engines given: every one builds the index of `ids` (the genome store is
+    replicated, and so is this scan), engine d selects the bands d, d + D, ..., and the parts are merged by merge_dealt; the indexes are
+    released, on errors too.  run_all(fn) -> [fn(engine, d) for each engine] (in threads for several).  Equal to the dense path."""
+    options = check_options(options)
+    ids = list(ids)
+    labels = _labels_for(ids, labels, INDEX_MAX_GENOMES)
+    if not ids:
+        return ScreenedPairs(labels, options, np.zeros(0, np.uint32), np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint32))
+    d = len(engines)
+
+    def part(engine, k):
+        sizes = engine.screen_index(ids, options.kmer, options.scale)
+        need = identity_thresholds(sizes, options.kmer, options.min_identity, options.min_shared)
+        return sizes, engine.screen_index_select(need, band_first=k, band_step=d)
+    try:
+        parts = run_all(part)
+    finally:
+        for e in engines:
+            e.screen_index_release()
+    a, b, shared = parts[0][1] if d == 1 else merge_dealt([p[1] for p in parts])
+    return ScreenedPairs(labels, options, parts[0][0], a, b, shared)
 
 
 def candidates_on(engine, make_resident, ids, options, labels=None) -> ScreenedPairs:

@@ -18,7 +18,8 @@ TAB_NAMES = ("shared", "containment", "identity")
 
 class ScreenRun(NamedTuple):
     lengths: Dict[str, int]          # stem -> genome length, file order
-    result: screen.ScreenResult      # labels = the stems, file order
+    result: Optional[screen.ScreenResult]      # labels = the stems, file order; None above screen.DENSE_MAX_GENOMES (no dense frames exist)
+    screened: Optional[screen.ScreenedPairs] = None      # the kept pairs (min_identity=...), None without
 
 
 def tab_path(outdir, name: str) -> Path:
@@ -44,29 +45,39 @@ def write_pairs_tab(outdir, screened: screen.ScreenedPairs) -> Path:
 
 
 def run_screen(indir, outdir=None, kmerSize: int = screen.DEFAULT_KMER, scale: int = screen.DEFAULT_SCALE, write_output: bool = False,
-               engine: Optional[Engine] = None, devices: Optional[List[int]] = None, workers: Optional[int] = None) -> ScreenRun:
+               engine: Optional[Engine] = None, devices: Optional[List[int]] = None, workers: Optional[int] = None,
+               min_identity: Optional[float] = None) -> ScreenRun:
     """The screen over every FASTA file of `indir`.  outdir is needed for write_output only.
-    devices / workers: run on several GPUs of this node (pyani_amd/multi.py); ignored when `engine` is given."""
+    devices / workers: run on several GPUs of this node (pyani_amd/multi.py); ignored when `engine` is given.
+    min_identity: when given, the pairs whose identity estimate reaches it are selected on the device (Engine.screen_candidates,
+    ScreenRun.screened) and written to screen_pairs.tab with write_output.  More than screen.DENSE_MAX_GENOMES files have no dense frames:
+    `result` is None, only the kept pairs exist, and a call without min_identity raises ValueError."""
     if write_output and outdir is None:
         raise ValueError("write_output needs an output directory")     # before any work is done
     kmerSize, scale = screen.check_params(kmerSize, scale)
+    if min_identity is not None:
+        min_identity = screen.check_options(screen.ScreenOptions(min_identity, kmerSize, scale)).min_identity
     own = None
     if engine is None and (devices is not None or workers):
         from . import multi
         engine = multi.engine_for(devices, workers)
         own = engine if isinstance(engine, multi.MultiEngine) else None
     try:
-        return _run_screen(indir, outdir, kmerSize, scale, write_output, engine or default_engine())
+        return _run_screen(indir, outdir, kmerSize, scale, write_output, engine or default_engine(), min_identity)
     finally:
         if own is not None:
             own.close()
 
 
-def _run_screen(indir, outdir, kmerSize, scale, write_output, eng) -> ScreenRun:
+def _run_screen(indir, outdir, kmerSize, scale, write_output, eng, min_identity=None) -> ScreenRun:
     paths = files.get_fasta_paths(Path(indir))
     stems = [p.stem for p in paths]
     if len(set(stems)) != len(stems):
         raise ValueError("two input files share a stem (pyani keys every result by Path.stem)")
+    dense = len(paths) <= screen.DENSE_MAX_GENOMES
+    if not dense and min_identity is None:      # before any work is done
+        raise ValueError(f"{len(paths)} genomes are more than the {screen.DENSE_MAX_GENOMES} a dense screen matrix takes: "
+                         "pass min_identity to get the kept pairs instead (ScreenRun.screened)")
     scratch_store = eng.genome_count() == 0
     lengths: Dict[str, int] = {}
     try:
@@ -74,10 +85,16 @@ def _run_screen(indir, outdir, kmerSize, scale, write_output, eng) -> ScreenRun:
         for p, (gid, total, _) in zip(paths, eng.add_fasta_batch(paths)):
             ids.append(gid)
             lengths[p.stem] = total
-        result = screen.screen_genomes(eng, ids, stems, kmerSize, scale)
+        result = screen.screen_genomes(eng, ids, stems, kmerSize, scale) if dense else None
+        screened = None
+        if min_identity is not None:
+            screened = eng.screen_candidates(ids, screen.ScreenOptions(min_identity, kmerSize, scale), labels=stems)
     finally:
         if scratch_store:
             eng.clear_genomes()
     if write_output:
-        write_tabs(outdir, result)
-    return ScreenRun(lengths, result)
+        if result is not None:
+            write_tabs(outdir, result)
+        if screened is not None:
+            write_pairs_tab(outdir, screened)
+    return ScreenRun(lengths, result, screened)
