@@ -454,6 +454,38 @@ int pg_screen_index_read(pg_ctx* ctx, int32_t* a_out, int32_t* b_out, uint32_t* 
 int pg_screen_index_band(pg_ctx* ctx, uint32_t band, uint32_t* out);
 int pg_screen_index_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
 
+/* ---- screen, the components: which genomes belong together.  The connected components of the graph whose edges are the
+ * entries (a[e], b[e]) of a list over n nodes, direction ignored, and two sums per node, all integers that depend on neither the order of
+ * the list nor any schedule:
+ *   root[v]    int32   the smallest node of v's component
+ *   entries[v] uint64  the list entries with a[e] == v and a[e] != b[e]
+ *   weight[v]  uint64  the sum of shared[e] over those entries (shared == NULL: every entry counts 1)
+ * The list may be unsorted, hold a pair in one direction only and hold an entry twice; an entry with a[e] == b[e] is ignored altogether.
+ * A union-find forest in one array that only atomics write (a compare-and-swap hooks the larger root under the smaller, an atomic minimum
+ * halves paths), entries and weight by 64-bit integer atomics after a run of equal a has been summed inside its wave, then one flattening
+ * pass.  No thread waits for another.
+ * pg_screen_components takes the list from the host: m entries (64-bit; uploaded in chunks of 2^24, so the device never holds the whole
+ * list), 1 <= n <= 2^20.  PG_E_ARG, checked before anything is copied or replaced: n outside that range, an index outside [0, n), m > 0
+ * with a NULL a or b.  *n_components_out = the number of components (the nodes with root[v] == v).
+ * pg_screen_index_components takes it from the resident index instead: the bands band_first, band_first + band_step, ... are counted and
+ * selected exactly as pg_screen_index_select does (same need, rule and band setting), and every band's kept triples are hooked and
+ * accumulated where they stand on the device — no pair is copied to the host.  *n_pairs_out = the kept cells, what pg_screen_index_select
+ * reports; the result is that of pg_screen_components over the list pg_screen_index_select + _read return for the same bands (dealt
+ * bands: one forest per part, joined by pyani_amd.screen.merge_components).  The index, its latest selection and pg_screen_index_last
+ * are left as they were.  PG_E_ARG as pg_screen_index_select.
+ * The result stays RESIDENT in a state of its own, independent of the resident matrix and of the index, until the next ACCEPTED
+ * components call (a refused one leaves it readable), pg_screen_components_release (PG_OK when there is none), pg_clear_genomes or
+ * pg_destroy.  pg_screen_components_read copies it out: n entries each; PG_E_ARG when there is none.
+ * pg_screen_components_last: counts_out[4] = n, entries worked (a != b), entries ignored (a == b), components; ms_out[3] = band count +
+ * select (the index path only), hook + accumulate, flatten milliseconds (HIP events on the context's stream); all 0 when nothing is
+ * resident. */
+int pg_screen_components(pg_ctx* ctx, const int32_t* a, const int32_t* b, const uint32_t* shared, uint64_t m, uint32_t n, uint32_t* n_components_out);
+int pg_screen_index_components(pg_ctx* ctx, const uint32_t* need, uint32_t n, uint32_t band_first, uint32_t band_step, uint32_t* n_components_out,
+                               uint64_t* n_pairs_out);
+int pg_screen_components_read(pg_ctx* ctx, int32_t* root_out, uint64_t* entries_out, uint64_t* weight_out);
+int pg_screen_components_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
+int pg_screen_components_release(pg_ctx* ctx);
+
 /* ---- classify: clique sweep over identity thresholds ------------------------------------------------------------------
  * The compute of `pyani classify`.  These calls read caller matrices only: they touch no genome, seed list or ANIm worker slot, so
  * they need no interlock with the pg_anim_pairs_enqueue / _fetch lanes and may run while enqueued ANIm calls are in flight (own

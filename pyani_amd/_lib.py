@@ -105,6 +105,11 @@ SIGNATURES = {
     "pg_screen_index_read": (_int, [_vp, _vp, _vp, _vp]),
     "pg_screen_index_band": (_int, [_vp, _u32, _vp]),
     "pg_screen_index_last": (_int, [_vp, _vp, _vp]),
+    "pg_screen_components": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _P(_u32)]),
+    "pg_screen_index_components": (_int, [_vp, _vp, _u32, _u32, _u32, _P(_u32), _P(_u64)]),
+    "pg_screen_components_read": (_int, [_vp, _vp, _vp, _vp]),
+    "pg_screen_components_last": (_int, [_vp, _vp, _vp]),
+    "pg_screen_components_release": (_int, [_vp]),
     "pg_classify_edges": (_int, [_vp, _vp, _vp, _u32, ctypes.c_double, ctypes.c_double, _P(_u64), _P(_u32)]),
     "pg_classify_edge_identities": (_int, [_vp, _vp, _u64]),
     "pg_classify_sweep": (_int, [_vp, _vp, _u64, _vp, _vp, _vp]),

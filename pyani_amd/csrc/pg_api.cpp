@@ -355,6 +355,7 @@ void pg_destroy(pg_ctx* ctx) {
   pg_dist_drop(ctx);
   pg_screen_drop(ctx);
   pg_screen_index_drop(ctx);
+  pg_screen_components_drop(ctx);
   prof_drain(ctx);
   delete ctx;                // the buffers and the streams go here, on the context's device
   (void)hipGetLastError();   // teardown errors must not surface in a later context's launch checks
@@ -462,6 +463,7 @@ int pg_clear_genomes(pg_ctx* ctx) {
   pg_sketch_drop(ctx);
   pg_screen_drop(ctx);
   pg_screen_index_drop(ctx);
+  pg_screen_components_drop(ctx);
   ctx->genomes.clear();
   ctx->arena_used = 0;
   ctx->n_resident = 0;

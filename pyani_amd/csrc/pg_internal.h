@@ -107,6 +107,9 @@ struct pg_ctx {
   uint32_t screen_band_rows = 0;         // pg_screen_set_band: matrix rows of one band of the index calls (0: the default, pg_screen_core.h)
   uint64_t screen_index_last[7] = {0, 0, 0, 0, 0, 0, 0};   // pg_screen_index_last: keys, distinct, grouped entries, groups, slices | bands worked, pair increments
   double screen_index_ms[4] = {0.0, 0.0, 0.0, 0.0};        // ... scan, sort + group (the build) | count, select (the latest selection)
+  void* screen_components_state = nullptr;      // resident components of the latest pg_screen_components / pg_screen_index_components (pg_screen.hip); independent of both above
+  uint64_t screen_components_last[4] = {0, 0, 0, 0};      // pg_screen_components_last: nodes, entries worked, entries ignored (a == b), components
+  double screen_components_ms[3] = {0.0, 0.0, 0.0};      // ... band count + select (index path), hook + accumulate, flatten milliseconds
   double dist_ms[3] = {0.0, 0.0, 0.0};   // kernel milliseconds of the latest pg_dist_load / _hist / _kde while profiling is on (pg_dist_last_ms)
   std::mutex anim_mu, err_mu, prof_mu;
   int anib_word_tier = 1;      // fragment mode: search failed fragments again with blastn-sized (11-mer) seeds
@@ -221,6 +224,7 @@ void pg_sketch_drop(pg_ctx* ctx);       // ... and the sketches of the sketch mo
 void pg_classify_drop(pg_ctx* ctx);     // ... the classify sweep's edge state (pg_classify.hip): goes with the context or on request
 void pg_dist_drop(pg_ctx* ctx);         // ... the distribution calls' resident values (pg_dist.hip): the same
 void pg_screen_drop(pg_ctx* ctx);       // ... the screen's resident matrix and selection (pg_screen.hip): the same, and with the genome store
+void pg_screen_components_drop(pg_ctx* ctx); // ... the screen's resident components (pg_screen.hip): with the context, the genome store or on request
 void pg_screen_index_drop(pg_ctx* ctx); // ... the screen's resident k-mer index and its selection (pg_screen.hip): with the context, the genome store or on request
 int pg_anib_reduce_run(pg_ctx* ctx, uint32_t n_pairs, const uint64_t* offsets, const uint32_t* n_frags, const int32_t* frag,
                        const int32_t* length, const int32_t* mismatch, const int32_t* gaps, const int32_t* qlen,

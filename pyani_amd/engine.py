@@ -506,6 +506,62 @@ class Engine:
     def screen_index_release(self) -> None:
         self._check(self.lib.pg_screen_index_release(self._h))
 
+    # the components: which genomes belong together, a forest resident on the context
+    def _screen_components_read(self, n: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        root, entries, weight = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+        self._check(self.lib.pg_screen_components_read(self._h, root.ctypes.data, entries.ctypes.data, weight.ctypes.data))
+        return root, entries, weight
+
+    def screen_components(self, a, b, shared=None, n: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """pg_screen_components + pg_screen_components_read: (root int32[n], entries uint64[n], weight uint64[n]) of the list of entries
+        (a[e], b[e], shared[e]) over n nodes, as pyani_amd.screen.components_of_pairs states them; shared=None counts 1 everywhere.  The
+        number of components is screen_components_last()["components"]."""
+        x = np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+        y = np.ascontiguousarray(b, dtype=np.int32).reshape(-1)
+        s = None if shared is None else np.ascontiguousarray(shared, dtype=np.uint32).reshape(-1)
+        if len(x) != len(y) or (s is not None and len(s) != len(x)):
+            raise ValueError("a, b and shared must have the same length")
+        m = len(x)
+        c = ctypes.c_uint32(0)
+        self._check(self.lib.pg_screen_components(self._h, x.ctypes.data if m else None, y.ctypes.data if m else None,
+                                                  s.ctypes.data if s is not None and m else None, m, int(n), ctypes.byref(c)))
+        return self._screen_components_read(int(n))
+
+    def screen_index_components(self, need, band_first: int = 0, band_step: int = 1) -> Tuple[np.ndarray, np.ndarray, np.ndarray, int]:
+        """pg_screen_index_components + pg_screen_components_read: (root, entries, weight, n_pairs) of the kept cells of the bands
+        band_first, band_first + band_step, ... of the resident index — screen_components of the list screen_index_select would return,
+        n_pairs its length — without a pair leaving the device."""
+        t = np.ascontiguousarray(need, dtype=np.uint32).reshape(-1)
+        c, m = ctypes.c_uint32(0), ctypes.c_uint64(0)
+        self._check(self.lib.pg_screen_index_components(self._h, t.ctypes.data if len(t) else None, len(t), int(band_first), int(band_step),
+                                                        ctypes.byref(c), ctypes.byref(m)))
+        return (*self._screen_components_read(len(t)), int(m.value))
+
+    def screen_components_last(self) -> dict:
+        """pg_screen_components_last: counts and stage milliseconds of the resident components (all 0 when there are none)."""
+        c = (ctypes.c_uint64 * 4)()
+        ms = (ctypes.c_double * 3)()
+        self._check(self.lib.pg_screen_components_last(self._h, ctypes.addressof(c), ctypes.addressof(ms)))
+        return {"n": int(c[0]), "entries": int(c[1]), "ignored": int(c[2]), "components": int(c[3]),
+                "select_ms": float(ms[0]), "hook_ms": float(ms[1]), "flatten_ms": float(ms[2])}
+
+    def screen_components_release(self) -> None:
+        self._check(self.lib.pg_screen_components_release(self._h))
+
+    def screen_components_of(self, ids, options, labels=None, path: str = "auto"):
+        """The connected components of the pairs the screen keeps among the resident genomes `ids` (pyani_amd.screen.ScreenComponents).
+        path "dense": screen_candidates, then the list entry (the kept pairs are read back once); "index": screen_index ->
+        identity_thresholds -> screen_index_components -> release, on errors too — no pair is read back; "auto" as screen_candidates."""
+        from . import screen
+        options = screen.check_options(options)
+        ids = [int(i) for i in ids]
+        if screen.resolve_path(path, len(ids)) == "index":
+            return screen.index_components_on([self], lambda fn: [fn(self, 0)], ids, options, labels)
+        try:
+            return self.screen_candidates(ids, options, labels, path="dense").components(engine=self)
+        finally:
+            self.screen_components_release()
+
     # -- classify: clique sweep over identity thresholds (pyani_amd.classify drives these) -------------------------------------
     def classify_edges(self, identity: np.ndarray, coverage: np.ndarray, id_min: float = 0.8, cov_min: float = 0.5) -> Tuple[int, int]:
         """pg_classify_edges: the edges of build_graph_from_results (pyani_classify.py:90-111) from two n x n float64 matrices in one

@@ -316,6 +316,25 @@ class MultiEngine:
             return sizes
         return screen.candidates_on(first, make_resident, ids, options, labels)
 
+    def screen_components_of(self, ids, options, labels=None, path: str = "auto"):
+        """Engine.screen_components_of over all devices.  Dense path: the first engine does the work.  Index path: every
+        engine builds the whole index as for screen_candidates, engine d of D hooks and accumulates the kept cells of the bands d, d + D,
+        ... into a forest of its own, and screen.merge_components joins the D forests on the first engine.  Equal to one engine's."""
+        from . import screen
+        options = screen.check_options(options)
+        ids = [int(i) for i in ids]
+        if screen.resolve_path(path, len(ids)) == "index":
+            return screen.index_components_on(self.engines, lambda fn: self._all(lambda e: fn(e, self.engines.index(e))), ids, options, labels)
+        return self.engines[0].screen_components_of(ids, options, labels, path="dense")
+
+    def screen_components(self, a, b, shared=None, n: int = 0):
+        """Engine.screen_components on the first engine (a list call has nothing to divide)."""
+        return self.engines[0].screen_components(a, b, shared, n=n)
+
+    def screen_components_release(self):
+        for e in self.engines:
+            e.screen_components_release()
+
     def screen_set_budget(self, max_keys: int = 0):
         for e in self.engines:
             e.screen_set_budget(max_keys)

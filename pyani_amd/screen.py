@@ -14,11 +14,15 @@ Screened runs (run_anim / run_anib with screen=...) do not bring the matrix back
 to ONE INTEGER COMPARISON per cell (identity_thresholds), which the engine applies on the device next to the matrix
 (Engine.screen_candidates) so that only the kept pairs are read back (ScreenedPairs).
 
+Which genomes BELONG TOGETHER is the last step: the connected components of the kept pairs (components_of_pairs is
+the statement, Engine.screen_components / screen_index_components the kernels, ScreenComponents the table: one representative per
+component is the dereplicated set), had through the index without a single pair leaving the device (Engine.screen_components_of).
+
 An ESTIMATE for triage with its own frames: it is never written into an exact ANIm / ANIb matrix.  What this is modelled on: the
 sketch-then-align front ends of skani, sourmash and dRep; pyani itself has no such step.
 """
 import math
-from typing import List, NamedTuple, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import pandas as pd
@@ -172,6 +176,190 @@ class ScreenedPairs(NamedTuple):
         lab = np.array(list(self.labels), dtype=object)
         return pd.DataFrame({"query": lab[self.a] if len(self.a) else [], "subject": lab[self.b] if len(self.b) else [], "shared": self.shared,
                              "containment": self.containment(), "identity": self.identity()})
+
+    def components(self, engine=None) -> "ScreenComponents":
+        """The connected components of the kept pairs: on `engine` (Engine.screen_components), or by the numpy statement
+        components_of_pairs when none is given.  Both give the same ScreenComponents."""
+        n = len(self.labels)
+        if n == 0:
+            return components_from_nodes(self.labels, np.zeros(0, np.int32), np.zeros(0, np.uint64), np.zeros(0, np.uint64))
+        nodes = components_of_pairs(self.a, self.b, self.shared, n) if engine is None else engine.screen_components(self.a, self.b, self.shared, n=n)
+        return components_from_nodes(self.labels, *nodes)
+
+
+# ---- the connected components of the kept pairs (DESIGN.md §16.3) ---------------------------------------------------------------------------
+def _check_entries(a, b, shared, n):
+    n = int(n)
+    if not 1 <= n <= INDEX_MAX_GENOMES:
+        raise ValueError(f"components are of 1 ... {INDEX_MAX_GENOMES} nodes, not {n}")
+    a = np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+    b = np.ascontiguousarray(b, dtype=np.int64).reshape(-1)
+    s = None if shared is None else np.ascontiguousarray(shared, dtype=np.uint32).reshape(-1)
+    if len(a) != len(b) or (s is not None and len(s) != len(a)):
+        raise ValueError("a, b and shared must have the same length")
+    if len(a) and (min(a.min(), b.min()) < 0 or max(a.max(), b.max()) >= n):
+        raise ValueError(f"an entry names a node outside [0, {n})")
+    return a, b, s, n
+
+
+def components_of_pairs(a, b, shared, n) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """THE STATEMENT of the components (the host's; Engine.screen_components is held to it): for the list of entries (a[e], b[e], shared[e])
+    over n nodes — unsorted, a pair in one direction or both, an entry once or several times; shared=None counts 1 everywhere — the three
+    node arrays
+
+        root[v]    int32   the smallest node of v's connected component (direction ignored)
+        entries[v] uint64  the entries with a[e] == v and a[e] != b[e]
+        weight[v]  uint64  the sum of shared[e] over those entries
+
+    An entry with a[e] == b[e] is ignored altogether.  Integers, independent of the list's order.  Rounds of hooking every entry's larger
+    root under its smaller one (np.minimum.at) and pointer jumping to the fixed point, until no entry joins two trees: a pointer only
+    ever goes to a smaller node, so a tree's root is its smallest node, and the trees are the components."""
+    a, b, s, n = _check_entries(a, b, shared, n)
+    live = a != b
+    a, b = a[live], b[live]
+    entries = np.bincount(a, minlength=n).astype(np.uint64)
+    if s is None:
+        weight = entries.copy()
+    else:      # float64 sums of 16-bit halves: exact below 2^37 entries
+        s = s[live]
+        lo = np.bincount(a, weights=(s & np.uint32(0xFFFF)).astype(np.float64), minlength=n).astype(np.uint64)
+        hi = np.bincount(a, weights=(s >> np.uint32(16)).astype(np.float64), minlength=n).astype(np.uint64)
+        weight = lo + (hi << np.uint64(16))
+    root = np.arange(n, dtype=np.int64)
+    while True:
+        ra, rb = root[a], root[b]
+        join = ra != rb
+        if not join.any():
+            break
+        a, b, ra, rb = a[join], b[join], ra[join], rb[join]      # (an entry inside one tree stays inside it: it is not looked at again)
+        np.minimum.at(root, np.maximum(ra, rb), np.minimum(ra, rb))      # (what is hooked is a root: root[r] == r before)
+        while True:
+            up = root[root]
+            if (up == root).all():
+                break
+            root = up
+    return root.astype(np.int32), entries, weight
+
+
+class ScreenComponents(NamedTuple):
+    """The connected components of a list of kept pairs over the genomes `labels` (None: the nodes go by their index).  root, entries and
+    weight are the node arrays of components_of_pairs; everything else is derived from them by components_from_nodes: components numbered
+    by ascending root, members ascending inside a component."""
+    labels: Optional[List[str]]
+    root: np.ndarray             # int32[n]
+    entries: np.ndarray          # uint64[n]
+    weight: np.ndarray           # uint64[n]
+    component: np.ndarray        # int32[n]: the component of every node
+    start: np.ndarray            # int64[C + 1]: component c owns member[start[c]:start[c + 1]]
+    member: np.ndarray           # int32[n]
+    size: np.ndarray             # int64[C]
+    edges: np.ndarray            # uint64[C]: the sum of `entries` over the members (ordered pairs, for a list that holds both directions)
+    complete: np.ndarray         # bool[C]: edges == size (size - 1) — every ordered pair of members was kept; meaningful for a duplicate-free list
+    representative: np.ndarray   # int32[C]: the member of the greatest weight, ties to the smallest index; a singleton represents itself
+
+    def _names(self, nodes) -> list:
+        nodes = np.asarray(nodes)
+        return nodes.tolist() if self.labels is None else [self.labels[i] for i in nodes.tolist()]
+
+    def members(self, c: int) -> np.ndarray:
+        """The nodes of component c, ascending."""
+        if not 0 <= int(c) < len(self.size):
+            raise IndexError(f"component {c} does not exist ({len(self.size)} components)")
+        return self.member[int(self.start[c]):int(self.start[c + 1])]
+
+    def frame(self) -> pd.DataFrame:
+        """One row per component: component, size, representative (label), edges, complete."""
+        return pd.DataFrame({"component": np.arange(len(self.size), dtype=np.int64), "size": self.size, "representative": self._names(self.representative),
+                             "edges": self.edges, "complete": self.complete})
+
+    def membership_frame(self) -> pd.DataFrame:
+        """One row per genome, in the order of `labels`: genome, component, representative (of its component)."""
+        return pd.DataFrame({"genome": self._names(np.arange(len(self.root))), "component": self.component.astype(np.int64),
+                             "representative": self._names(self.representative[self.component])})
+
+    def representatives(self) -> list:
+        """The dereplicated set: one label per component, in component order."""
+        return self._names(self.representative)
+
+
+def components_from_nodes(labels, root, entries, weight) -> ScreenComponents:
+    """The ScreenComponents of the three node arrays (numpy on the host: n <= 2^20)."""
+    root = np.ascontiguousarray(root, dtype=np.int32)
+    entries = np.ascontiguousarray(entries, dtype=np.uint64)
+    weight = np.ascontiguousarray(weight, dtype=np.uint64)
+    n = len(root)
+    if labels is not None:
+        labels = [str(x) for x in labels]
+        if len(labels) != n:
+            raise ValueError("labels and nodes must have the same length")
+    if len(entries) != n or len(weight) != n:
+        raise ValueError("root, entries and weight must have the same length")
+    if n == 0:
+        z = np.zeros(0, np.int32)
+        return ScreenComponents(labels, root, entries, weight, z, np.zeros(1, np.int64), z, np.zeros(0, np.int64), np.zeros(0, np.uint64), np.zeros(0, bool), z)
+    node = np.arange(n, dtype=np.int64)
+    if (root < 0).any() or (root > node).any() or (root[root] != root).any():
+        raise ValueError("root is no flattened forest (root[v] <= v and root[root[v]] == root[v])")
+    _, component = np.unique(root, return_inverse=True)      # (ascending roots: the numbering)
+    component = component.reshape(-1)
+    size = np.bincount(component).astype(np.int64)
+    start = np.concatenate([[0], np.cumsum(size)]).astype(np.int64)
+    member = np.argsort(component, kind="stable")
+    edges = np.add.reduceat(entries[member], start[:-1])      # (every component has a member: no empty slice)
+    sz = size.astype(np.uint64)
+    complete = edges == sz * (sz - np.uint64(1))
+    best = np.lexsort((node, ~weight, component))      # by component, then weight descending (~ reverses uint64), then index ascending
+    return ScreenComponents(labels, root, entries, weight, component.astype(np.int32), start, member.astype(np.int32), size, edges, complete,
+                            best[start[:-1]].astype(np.int32))
+
+
+def merge_components(parts, n, engine=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(root, entries, weight) of the whole list from the node arrays of its PARTS — parts[d] = (root_d, entries_d, weight_d) of some of
+    the entries, e.g. of the bands dealt to device d.  entries and weight add.  Each part is a forest of its own entries; the forests are
+    joined by ONE list call over the entries (v, root_d[v]) with root_d[v] != v of every part (engine.screen_components, or the statement
+    when no engine is given): v is connected to root_d[v] in part d, and every connection of part d runs through such entries."""
+    n = int(n)
+    entries, weight = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+    va, vb = [], []
+    for root, e, w in parts:
+        root = np.ascontiguousarray(root, dtype=np.int32)
+        if len(root) != n or len(e) != n or len(w) != n:
+            raise ValueError(f"a part is not of {n} nodes")
+        entries += np.asarray(e, dtype=np.uint64)
+        weight += np.asarray(w, dtype=np.uint64)
+        v = np.flatnonzero(root != np.arange(n, dtype=np.int32)).astype(np.int32)
+        va.append(v)
+        vb.append(root[v])
+    a = np.concatenate(va) if va else np.zeros(0, np.int32)
+    b = np.concatenate(vb) if vb else np.zeros(0, np.int32)
+    root = (components_of_pairs(a, b, None, n) if engine is None else engine.screen_components(a, b, None, n=n))[0]
+    return root, entries, weight
+
+
+def index_components_on(engines, run_all, ids, options, labels=None) -> ScreenComponents:
+    """The components through the index on the D engines given, without a pair leaving a device: every engine builds the index, engine d
+    hooks and accumulates the kept cells of the bands d, d + D, ... (Engine.screen_index_components), and the parts are joined by
+    merge_components on the first engine; the indexes and the parts' resident results are released, on errors too.  run_all as for
+    index_candidates_on.  Equal to index_candidates_on(...).components()."""
+    options = check_options(options)
+    ids = list(ids)
+    labels = _labels_for(ids, labels, INDEX_MAX_GENOMES)
+    if not ids:
+        return components_from_nodes(labels, np.zeros(0, np.int32), np.zeros(0, np.uint64), np.zeros(0, np.uint64))
+    d = len(engines)
+
+    def part(engine, k):
+        sizes = engine.screen_index(ids, options.kmer, options.scale)
+        need = identity_thresholds(sizes, options.kmer, options.min_identity, options.min_shared)
+        return engine.screen_index_components(need, band_first=k, band_step=d)[:3]
+    try:
+        parts = run_all(part)
+        nodes = parts[0] if d == 1 else merge_components(parts, len(ids), engine=engines[0])
+    finally:
+        for e in engines:
+            e.screen_index_release()
+            e.screen_components_release()
+    return components_from_nodes(labels, *nodes)
 
 
 def _labels_for(ids, labels, limit: int = MAX_GENOMES) -> List[str]:

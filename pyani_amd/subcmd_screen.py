@@ -4,6 +4,8 @@ order, ONE engine call for all of them, and the result as labelled frames.  No C
 
 With write_output the frames go to `<outdir>/screen_output/screen_{shared,containment,identity}.tab` in the shape of the legacy
 matrix files (tab-separated, labels on both axes).  These are the screen's OWN files: an estimate, never merged into an ANIm or ANIb result.
+With min_identity the kept pairs go to `screen_pairs.tab`, and with components=True their connected components to
+`screen_components.tab` and `screen_membership.tab`.
 Single-process: one engine, or several GPUs of this node through pyani_amd.multi.MultiEngine (devices / workers).
 """
 from pathlib import Path
@@ -20,6 +22,7 @@ class ScreenRun(NamedTuple):
     lengths: Dict[str, int]          # stem -> genome length, file order
     result: Optional[screen.ScreenResult]      # labels = the stems, file order; None above screen.DENSE_MAX_GENOMES (no dense frames exist)
     screened: Optional[screen.ScreenedPairs] = None      # the kept pairs (min_identity=...), None without
+    components: Optional[screen.ScreenComponents] = None      # their connected components (components=True), None without
 
 
 def tab_path(outdir, name: str) -> Path:
@@ -44,16 +47,30 @@ def write_pairs_tab(outdir, screened: screen.ScreenedPairs) -> Path:
     return tab_path(outdir, "pairs")
 
 
+def write_components_tabs(outdir, components: screen.ScreenComponents) -> List[Path]:
+    """`<outdir>/screen_output/screen_components.tab` — one line per component: component, size, representative, edges, complete — and
+    `screen_membership.tab` — one line per genome: genome, component, representative."""
+    (Path(outdir) / OUTDIR).mkdir(parents=True, exist_ok=True)
+    components.frame().to_csv(tab_path(outdir, "components"), index=False, sep="\t")
+    components.membership_frame().to_csv(tab_path(outdir, "membership"), index=False, sep="\t")
+    return [tab_path(outdir, "components"), tab_path(outdir, "membership")]
+
+
 def run_screen(indir, outdir=None, kmerSize: int = screen.DEFAULT_KMER, scale: int = screen.DEFAULT_SCALE, write_output: bool = False,
                engine: Optional[Engine] = None, devices: Optional[List[int]] = None, workers: Optional[int] = None,
-               min_identity: Optional[float] = None) -> ScreenRun:
+               min_identity: Optional[float] = None, components: bool = False) -> ScreenRun:
     """The screen over every FASTA file of `indir`.  outdir is needed for write_output only.
     devices / workers: run on several GPUs of this node (pyani_amd/multi.py); ignored when `engine` is given.
     min_identity: when given, the pairs whose identity estimate reaches it are selected on the device (Engine.screen_candidates,
     ScreenRun.screened) and written to screen_pairs.tab with write_output.  More than screen.DENSE_MAX_GENOMES files have no dense frames:
-    `result` is None, only the kept pairs exist, and a call without min_identity raises ValueError."""
+    `result` is None, only the kept pairs exist, and a call without min_identity raises ValueError.
+    components: with True (it needs min_identity) the connected components of the kept pairs are worked out on the device too
+    (ScreenedPairs.components; ScreenRun.components) and written to screen_components.tab and screen_membership.tab with
+    write_output.  The default leaves the run as it was."""
     if write_output and outdir is None:
         raise ValueError("write_output needs an output directory")     # before any work is done
+    if components and min_identity is None:
+        raise ValueError("components=True needs min_identity: the components are those of the kept pairs")
     kmerSize, scale = screen.check_params(kmerSize, scale)
     if min_identity is not None:
         min_identity = screen.check_options(screen.ScreenOptions(min_identity, kmerSize, scale)).min_identity
@@ -63,13 +80,13 @@ def run_screen(indir, outdir=None, kmerSize: int = screen.DEFAULT_KMER, scale: i
         engine = multi.engine_for(devices, workers)
         own = engine if isinstance(engine, multi.MultiEngine) else None
     try:
-        return _run_screen(indir, outdir, kmerSize, scale, write_output, engine or default_engine(), min_identity)
+        return _run_screen(indir, outdir, kmerSize, scale, write_output, engine or default_engine(), min_identity, components)
     finally:
         if own is not None:
             own.close()
 
 
-def _run_screen(indir, outdir, kmerSize, scale, write_output, eng, min_identity=None) -> ScreenRun:
+def _run_screen(indir, outdir, kmerSize, scale, write_output, eng, min_identity=None, components=False) -> ScreenRun:
     paths = files.get_fasta_paths(Path(indir))
     stems = [p.stem for p in paths]
     if len(set(stems)) != len(stems):
@@ -89,6 +106,12 @@ def _run_screen(indir, outdir, kmerSize, scale, write_output, eng, min_identity=
         screened = None
         if min_identity is not None:
             screened = eng.screen_candidates(ids, screen.ScreenOptions(min_identity, kmerSize, scale), labels=stems)
+        comps = None
+        if components:
+            try:
+                comps = screened.components(engine=eng)
+            finally:
+                eng.screen_components_release()
     finally:
         if scratch_store:
             eng.clear_genomes()
@@ -97,4 +120,6 @@ def _run_screen(indir, outdir, kmerSize, scale, write_output, eng, min_identity=
             write_tabs(outdir, result)
         if screened is not None:
             write_pairs_tab(outdir, screened)
-    return ScreenRun(lengths, result, screened)
+        if comps is not None:
+            write_components_tabs(outdir, comps)
+    return ScreenRun(lengths, result, screened, comps)
