@@ -40,6 +40,23 @@ struct PgEventPair {
   int which;
 };
 
+// What the latest screen calls did (pg_screen.hip): counts, and milliseconds between HIP events on the context's stream.  Only the three
+// entry points pg_screen_last, pg_screen_index_last and pg_screen_components_last know the order of these in the C ABI's arrays.
+struct PgScreenStats {
+  uint64_t keys = 0, distinct = 0, groups = 0, pair_increments = 0, slices = 0;      // sampled keys, distinct entries, groups of >= 2 genomes
+  double scan_ms = 0.0, group_ms = 0.0, count_ms = 0.0;                              // scan, sort + group, count
+};
+struct PgScreenIndexStats {
+  uint64_t keys = 0, distinct = 0, entries = 0, groups = 0, slices = 0;      // the build: entries = the grouped ones the index keeps
+  uint64_t bands = 0, pair_increments = 0;                                   // the latest selection: bands worked, increments of its count kernel
+  double scan_ms = 0.0, group_ms = 0.0;                                      // the build
+  double count_ms = 0.0, select_ms = 0.0;                                    // the latest selection
+};
+struct PgScreenComponentsStats {
+  uint64_t nodes = 0, worked = 0, ignored = 0, components = 0;      // entries worked, entries ignored (a == b)
+  double select_ms = 0.0, hook_ms = 0.0, flatten_ms = 0.0;          // band count + select (index path), hook + accumulate, flatten
+};
+
 struct pg_ctx {
   ~pg_ctx();   // destroys the streams (pg_api.cpp); the buffers below free themselves
   int device = 0;
@@ -101,15 +118,12 @@ struct pg_ctx {
   void* dist_state = nullptr;      // resident values of the distribution calls (pg_dist.hip), replaced by every pg_dist_load
   void* screen_state = nullptr;    // resident matrix of the screen's selection (pg_screen.hip), replaced by every pg_screen_hold / pg_screen_load
   uint64_t screen_max_keys = 0;          // pg_screen_set_budget: keys of one slice of a screen call (0: the default, pg_screen_core.h)
-  uint64_t screen_last[5] = {0, 0, 0, 0, 0};   // pg_screen_last: keys, distinct entries, groups of >= 2, pair increments, slices of the latest pg_screen_matrix
-  double screen_ms[3] = {0.0, 0.0, 0.0};      // ... and its scan, sort + group and count milliseconds (HIP events on the context's stream)
+  PgScreenStats screen_stats;            // pg_screen_last: the latest pg_screen_matrix / pg_screen_hold
   void* screen_index_state = nullptr;    // resident k-mer index of pg_screen_index and its latest selection (pg_screen.hip); independent of screen_state
   uint32_t screen_band_rows = 0;         // pg_screen_set_band: matrix rows of one band of the index calls (0: the default, pg_screen_core.h)
-  uint64_t screen_index_last[7] = {0, 0, 0, 0, 0, 0, 0};   // pg_screen_index_last: keys, distinct, grouped entries, groups, slices | bands worked, pair increments
-  double screen_index_ms[4] = {0.0, 0.0, 0.0, 0.0};        // ... scan, sort + group (the build) | count, select (the latest selection)
+  PgScreenIndexStats screen_index_stats; // pg_screen_index_last: the latest pg_screen_index and the latest selection over it
   void* screen_components_state = nullptr;      // resident components of the latest pg_screen_components / pg_screen_index_components (pg_screen.hip); independent of both above
-  uint64_t screen_components_last[4] = {0, 0, 0, 0};      // pg_screen_components_last: nodes, entries worked, entries ignored (a == b), components
-  double screen_components_ms[3] = {0.0, 0.0, 0.0};      // ... band count + select (index path), hook + accumulate, flatten milliseconds
+  PgScreenComponentsStats screen_components_stats;      // pg_screen_components_last: the resident components' call
   double dist_ms[3] = {0.0, 0.0, 0.0};   // kernel milliseconds of the latest pg_dist_load / _hist / _kde while profiling is on (pg_dist_last_ms)
   std::mutex anim_mu, err_mu, prof_mu;
   int anib_word_tier = 1;      // fragment mode: search failed fragments again with blastn-sized (11-mer) seeds
