@@ -486,6 +486,45 @@ int pg_screen_components_read(pg_ctx* ctx, int32_t* root_out, uint64_t* entries_
 int pg_screen_components_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
 int pg_screen_components_release(pg_ctx* ctx);
 
+/* ---- screen, the search: new genomes against a resident collection.  S(g), size, kmer and scale as for
+ * pg_screen_matrix.  A collection ("db") of n <= 2^20 genomes is indexed once; then, per call, q query genomes are placed against it:
+ *   hits[i][b] = |S(query i) & S(db b)|, a q x n rectangle of uint32, row-major
+ * There is NO diagonal: a query that is also a db genome meets itself with hits = size, a cell like any other.  The rule of
+ * pg_screen_select on the rectangle: (i, b) kept iff hits[i][b] >= min(need_q[i], need_db[b]) — exactly the cells (a in queries, b in db)
+ * that pg_screen_select over db + queries keeps.  Integers only; no result depends on a schedule, a slice or a chunk.
+ * pg_screen_search_index scans, sorts and groups as pg_screen_index does (slices under pg_screen_set_budget) and keeps EVERY distinct
+ * k-mer — its value, and the call indices of its holders, singletons included — with a directory from slice bin to slice.  Arguments
+ * and refusals as pg_screen_index; sizes_out: n uint32.  The index is a state of its own, independent of the resident matrix, of the
+ * index of pg_screen_index and of the components; it names the db genomes by call index only and reads nothing of the genome store
+ * after the build, so it SURVIVES pg_clear_genomes: index a collection, clear the store, load query batches into the freed memory.  It
+ * lives until the next pg_screen_search_index whose arguments pass (the old index goes first), pg_screen_search_index_release (PG_OK
+ * when there is none) or pg_destroy.  n = 0 is accepted and leaves no index.
+ * pg_screen_search_count places q resident genomes (ids of the genome store as it is NOW; none twice) against the index, with the
+ * index's kmer and scale: q <= the band's rows (pg_screen_set_band; the default here min(8192, 2^29 / n): a rectangle of at most 2 GiB).
+ * The queries' keys are sliced under pg_screen_set_budget on their own; per slice every distinct query k-mer is looked up (bin -> slice,
+ * binary search) and every (query holder, db holder) pair of a matched k-mer adds one to its cell.  sizes_out: q uint32, the queries'
+ * sizes.  The rectangle stays resident until the next accepted count, the release or pg_destroy.
+ * pg_screen_search_select applies the rule to the resident rectangle (q and n must be the resident ones); *n_pairs_out = the kept
+ * cells; pg_screen_search_read copies them out row-major: a_out (0 ... q - 1, the query's position in the count call), b_out (the db
+ * genome's position in the index call) int32, shared_out uint32; the arrays may be NULL when nothing was kept.
+ * pg_screen_search_fetch copies the rectangle out (q x n uint32).
+ * PG_E_ARG, before anything is replaced: no resident search index; n or q not the resident ones; q above the band's rows; a query id
+ * out of range or given twice; a NULL array with a non-zero count; select or fetch without a counted rectangle, read without a selection.
+ * pg_screen_search_last: counts_out[10] = sampled keys, distinct k-mers D, (k-mer, genome) entries E, slices of the resident index | of
+ * the latest count: the queries' keys, their distinct k-mers (= lookups), the matched ones, increments of the count kernel (= the sum
+ * of the rectangle), slices | the device bytes the index's buffers HOLD (their allocated sizes: about 12 D + 4 E once the arrays have
+ * moved into blocks of their own size — an array within a sixteenth of its bound, or one there is no room to copy, stays in the
+ * block sized by the keys).  ms_out[7] = scan, sort + group of the build | scan, sort + group, lookup (the mark of the runs, their
+ * compaction, the lookup kernel, the matched runs' compaction), count (weights, scan, count kernel) of the latest count | its latest
+ * selection (HIP events; no pair spans a host synchronisation).  All 0 without an index. */
+int pg_screen_search_index(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kmer, int32_t scale, uint32_t* sizes_out);
+int pg_screen_search_index_release(pg_ctx* ctx);
+int pg_screen_search_count(pg_ctx* ctx, const int32_t* query_ids, uint32_t q, uint32_t* sizes_out);
+int pg_screen_search_select(pg_ctx* ctx, const uint32_t* need_q, uint32_t q, const uint32_t* need_db, uint32_t n, uint64_t* n_pairs_out);
+int pg_screen_search_read(pg_ctx* ctx, int32_t* a_out, int32_t* b_out, uint32_t* shared_out);
+int pg_screen_search_fetch(pg_ctx* ctx, uint32_t* out);
+int pg_screen_search_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
+
 /* ---- classify: clique sweep over identity thresholds ------------------------------------------------------------------
  * The compute of `pyani classify`.  These calls read caller matrices only: they touch no genome, seed list or ANIm worker slot, so
  * they need no interlock with the pg_anim_pairs_enqueue / _fetch lanes and may run while enqueued ANIm calls are in flight (own

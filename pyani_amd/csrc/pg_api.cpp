@@ -356,6 +356,7 @@ void pg_destroy(pg_ctx* ctx) {
   pg_screen_drop(ctx);
   pg_screen_index_drop(ctx);
   pg_screen_components_drop(ctx);
+  pg_screen_search_drop(ctx);
   prof_drain(ctx);
   delete ctx;                // the buffers and the streams go here, on the context's device
   (void)hipGetLastError();   // teardown errors must not surface in a later context's launch checks

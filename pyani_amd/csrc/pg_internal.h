@@ -40,8 +40,8 @@ struct PgEventPair {
   int which;
 };
 
-// What the latest screen calls did (pg_screen.hip): counts, and milliseconds between HIP events on the context's stream.  Only the three
-// entry points pg_screen_last, pg_screen_index_last and pg_screen_components_last know the order of these in the C ABI's arrays.
+// What the latest screen calls did (pg_screen.hip): counts, and milliseconds between HIP events on the context's stream.  Only the four
+// entry points pg_screen_last, pg_screen_index_last, pg_screen_components_last and pg_screen_search_last know the order of these in the C ABI's arrays.
 struct PgScreenStats {
   uint64_t keys = 0, distinct = 0, groups = 0, pair_increments = 0, slices = 0;      // sampled keys, distinct entries, groups of >= 2 genomes
   double scan_ms = 0.0, group_ms = 0.0, count_ms = 0.0;                              // scan, sort + group, count
@@ -55,6 +55,14 @@ struct PgScreenIndexStats {
 struct PgScreenComponentsStats {
   uint64_t nodes = 0, worked = 0, ignored = 0, components = 0;      // entries worked, entries ignored (a == b)
   double select_ms = 0.0, hook_ms = 0.0, flatten_ms = 0.0;          // band count + select (index path), hook + accumulate, flatten
+};
+
+struct PgScreenSearchStats {
+  uint64_t keys = 0, kmers = 0, entries = 0, slices = 0, index_bytes = 0;                // the search index: sampled keys, distinct k-mers, (k-mer, genome) entries, device bytes its buffers hold
+  uint64_t query_keys = 0, lookups = 0, matched = 0, increments = 0, query_slices = 0;   // the latest count: lookups = the distinct k-mers of the queries
+  double index_scan_ms = 0.0, index_group_ms = 0.0;                                      // the build
+  double scan_ms = 0.0, group_ms = 0.0, lookup_ms = 0.0, count_ms = 0.0;                 // the latest count
+  double select_ms = 0.0;                                                                // the latest selection
 };
 
 struct pg_ctx {
@@ -124,6 +132,8 @@ struct pg_ctx {
   PgScreenIndexStats screen_index_stats; // pg_screen_index_last: the latest pg_screen_index and the latest selection over it
   void* screen_components_state = nullptr;      // resident components of the latest pg_screen_components / pg_screen_index_components (pg_screen.hip); independent of both above
   PgScreenComponentsStats screen_components_stats;      // pg_screen_components_last: the resident components' call
+  void* screen_search_state = nullptr;          // resident search index of pg_screen_search_index and the latest rectangle counted against it (pg_screen.hip); independent of the three above and of the genome store
+  PgScreenSearchStats screen_search_stats;      // pg_screen_search_last: the resident search index, the latest count and selection over it
   double dist_ms[3] = {0.0, 0.0, 0.0};   // kernel milliseconds of the latest pg_dist_load / _hist / _kde while profiling is on (pg_dist_last_ms)
   std::mutex anim_mu, err_mu, prof_mu;
   int anib_word_tier = 1;      // fragment mode: search failed fragments again with blastn-sized (11-mer) seeds
@@ -240,6 +250,7 @@ void pg_dist_drop(pg_ctx* ctx);         // ... the distribution calls' resident 
 void pg_screen_drop(pg_ctx* ctx);       // ... the screen's resident matrix and selection (pg_screen.hip): the same, and with the genome store
 void pg_screen_components_drop(pg_ctx* ctx); // ... the screen's resident components (pg_screen.hip): with the context, the genome store or on request
 void pg_screen_index_drop(pg_ctx* ctx); // ... the screen's resident k-mer index and its selection (pg_screen.hip): with the context, the genome store or on request
+void pg_screen_search_drop(pg_ctx* ctx); // ... the screen's resident search index and rectangle (pg_screen.hip): with the context or on request — NOT with the genome store: it names genomes by call index only
 int pg_anib_reduce_run(pg_ctx* ctx, uint32_t n_pairs, const uint64_t* offsets, const uint32_t* n_frags, const int32_t* frag,
                        const int32_t* length, const int32_t* mismatch, const int32_t* gaps, const int32_t* qlen,
                        const double* pident, int64_t* aln_out, int64_t* err_out, double* pid_out);

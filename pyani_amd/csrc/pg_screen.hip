@@ -33,7 +33,9 @@
 //                           (coalesced).  Count pass: the popcounts of the task's ballots, one uint64 per task; hipcub exclusive scan; fill
 //                           pass: the same ballots again, every kept cell written at its task's offset + the kept cells before it in the
 //                           task.  No cursor, no atomic: the order is the order of the cells.  Two streaming passes over the rectangle.
-//                           select_rows is its one host side: the dense selection is the rectangle [0, n) of the resident matrix.
+//                           select_rows is its one host side: the dense selection is the rectangle [0, n) of the resident matrix.  The
+//                           rows' thresholds are an array of their own and the diagonal test a switch: the square calls pass one array
+//                           twice and keep the test, the search (queries x collection) passes two and has no diagonal.
 //
 // pgscr_index.inc — the INDEX, for collections beyond MAX_GENOMES: C1 and C2 are one front half (screen_front) with two
 // back halves.  The dense calls count every grouped slice into the matrix (DenseBack: C3, C4).  pg_screen_index appends the grouped
@@ -44,6 +46,13 @@
 //   B3 band_count_kernel    C3's balance by item (item_walk); item t -> (t / m, t % m), uint32 atomics into the band
 //   B4 band_diag_kernel     the cell of a genome with itself = size
 //   B5 screen_select_kernel C5 on the band's rectangle (select_rows); the kept triples go to the host as the band finishes
+//
+// pgscr_search.inc — the SEARCH: new genomes against a resident collection.  pg_screen_search_index is screen_front with
+// a third back half (SearchBack: every distinct k-mer with its value, singletons included, in compressed-row form, and a bin -> slice
+// directory); pg_screen_search_count runs screen_front over the queries (QueryBack) and counts a q x n rectangle; C5 selects on it:
+//   S1 search_lookup_kernel one thread per distinct query k-mer: bin -> slice, binary search over the slice's k-mer values
+//   S2 screen_weight_kernel<SearchWeight> + an exclusive scan over the matched k-mers: m_q m_d items each
+//   S3 search_count_kernel  C3's balance by item (item_walk); item t -> (t / m_d, t % m_d), uint32 atomics into the rectangle
 //
 // pgscr_components.inc — the COMPONENTS: which genomes belong together.  pg_screen_components (a list from the host) and
 // pg_screen_index_components (the bands' kept triples, where B5 left them on the device) hook a union-find forest that only atomics write
@@ -60,8 +69,8 @@
 
 namespace {
 
-// the stages whose milliseconds pg_screen_last, pg_screen_index_last and pg_screen_components_last report
-enum ScreenStage { ST_SCAN, ST_GROUP, ST_COUNT, ST_SELECT, ST_HOOK, ST_FLATTEN };
+// the stages whose milliseconds pg_screen_last, pg_screen_index_last, pg_screen_components_last and pg_screen_search_last report
+enum ScreenStage { ST_SCAN, ST_GROUP, ST_COUNT, ST_SELECT, ST_HOOK, ST_FLATTEN, ST_LOOKUP };
 
 struct ScreenEvents {      // event pairs on the context's stream, summed per stage after the call's last synchronisation
   std::vector<hipEvent_t> ev;
@@ -113,3 +122,4 @@ hipError_t tmp_room(size_t& tmp_bytes, Query query) {
 #include "pgscr_select.inc"
 #include "pgscr_index.inc"
 #include "pgscr_components.inc"
+#include "pgscr_search.inc"

@@ -74,6 +74,13 @@ PGS_HD void band_range(uint32_t b, uint32_t rows, uint32_t n, uint32_t* r0, uint
   *r0 = (uint32_t)(lo < n ? lo : n);
   *r1 = (uint32_t)(hi < n ? hi : n);
 }
+// the search: a chunk of query rows against the n >= 1 columns of a collection.  The same setting; the default is not capped
+// by n — the rows are other genomes than the columns — only by MAX_BAND_ROWS and MAX_BAND_CELLS (>= 512 rows for n <= INDEX_MAX_GENOMES)
+PGS_HD uint32_t search_default_rows(uint32_t n) {
+  const uint64_t rows = MAX_BAND_CELLS / n;
+  return (uint32_t)(rows > MAX_BAND_ROWS ? MAX_BAND_ROWS : (rows < 1 ? 1 : rows));
+}
+PGS_HD uint32_t search_rows(uint32_t setting, uint32_t n) { return setting ? setting : search_default_rows(n); }
 // A group of m members, mb of them in the band, owns mb m items: item t (< mb m <= 2^13 2^20) -> (i, j) = (member of the band, member of
 // the group), row-major, so that consecutive items run j upward along one band row.
 PGS_HD uint64_t band_items(uint32_t mb, uint32_t m) { return (uint64_t)mb * m; }

@@ -234,6 +234,7 @@ struct SliceGroups {      // one slice, sorted and grouped, on the device: what 
   uint64_t ng;
   void* tmp;                        // temporary storage of the library calls: what the front half needs, and what prepare() asked for
   size_t tmp_bytes;
+  uint32_t bin_lo, bin_hi;          // the slice's bins [bin_lo, bin_hi)
 };
 
 struct FrontTotals { uint64_t keys = 0, distinct = 0, groups = 0, slices = 0; };
@@ -362,7 +363,7 @@ int screen_front(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kme
       const uint64_t ng = cnt[2];
       if (ng + 1 > max_groups) return pg_fail(ctx, PG_E_INTERNAL, "screen: more groups than half the keys");
       tot.groups += ng;
-      const SliceGroups G{keys_a.p, nu, flags.p, first.p, last.p, ng, (void*)tmp.p, tmp_bytes};
+      const SliceGroups G{keys_a.p, nu, flags.p, first.p, last.p, ng, (void*)tmp.p, tmp_bytes, S.lo, S.hi};
       if ((rc = back.slice(G, T))) return rc;
     }
   }

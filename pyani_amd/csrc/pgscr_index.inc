@@ -246,7 +246,7 @@ int band_loop(pg_ctx* ctx, const IndexState* I, const uint32_t* need, uint32_t b
       unsigned long long total = 0;
       { ScreenEvents::Stage fill(T, stages.fill, st); rc = band_fill(ctx, I, r0, r1, W, &tot.incr); }
       if (rc) return rc;
-      { ScreenEvents::Stage select(T, stages.select, st); rc = select_rows(ctx, W.band.p, n, r0, r1 - r0, W.sel, (void*)W.tmp.p, W.tmp_bytes, W.a, W.b, W.s, &total); }
+      { ScreenEvents::Stage select(T, stages.select, st); rc = select_rows(ctx, W.band.p, (const uint32_t*)W.sel.need.p, true, n, r0, r1 - r0, W.sel, (void*)W.tmp.p, W.tmp_bytes, W.a, W.b, W.s, &total); }
       if (rc) return rc;
       { ScreenEvents::Stage working(T, stages.work, st); rc = work(r0, r1, total, W); }
       if (rc) return rc;

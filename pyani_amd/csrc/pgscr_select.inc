@@ -8,9 +8,12 @@ constexpr uint32_t SEL_CELLS = 64u * SEL_STEPS;    // cells of one wave task: a 
 // C5: the rule on a rectangle, cells = its rows [r0, r0 + rows) x n columns (the dense selection: r0 = 0, rows = n).  Tasks row-major:
 // task = row of the rectangle * tpr + piece (tpr = pieces per row).  !FILL: counts[task] = kept cells of the task, counts[n_tasks] = 0
 // (the scan's total lands there).  FILL: counts = the scanned offsets; total = their last entry, the room of the three output arrays.
-// The output carries the GLOBAL row r0 + row of the rectangle.
+// The output carries the GLOBAL row r0 + row of the rectangle.  need_row (read at the global row) and need_col are one array for the
+// square calls, whose rows and columns are the same genomes: diagonal = the cell col == row is the genome with itself and is never kept.
+// The search (pgscr_search.inc) has queries on the rows and the collection on the columns: two arrays, and no diagonal to skip.
 template <bool FILL>
-__global__ __launch_bounds__(256) void screen_select_kernel(const uint32_t* __restrict__ rect, const uint32_t* __restrict__ need, uint32_t n, uint32_t r0, uint32_t tpr,
+__global__ __launch_bounds__(256) void screen_select_kernel(const uint32_t* __restrict__ rect, const uint32_t* __restrict__ need_row_of,
+                                                             const uint32_t* __restrict__ need_col_of, bool diagonal, uint32_t n, uint32_t r0, uint32_t tpr,
                                                              uint32_t n_tasks, unsigned long long* __restrict__ counts, unsigned long long total,
                                                              int32_t* __restrict__ a_out, int32_t* __restrict__ b_out, uint32_t* __restrict__ s_out) {
   const uint32_t lane = threadIdx.x & 63u;
@@ -19,7 +22,7 @@ __global__ __launch_bounds__(256) void screen_select_kernel(const uint32_t* __re
   for (uint32_t task = wave; task < n_tasks; task += n_waves) {      // (uniform over the wave: every lane reaches every ballot)
     const uint32_t brow = task / tpr, col0 = (task % tpr) * SEL_CELLS;
     const uint32_t row = r0 + brow;
-    const uint32_t need_row = need[row];
+    const uint32_t need_row = need_row_of[row];
     const uint32_t* __restrict__ cells = rect + (size_t)brow * n;
     uint32_t v[SEL_STEPS];
     bool keep[SEL_STEPS];
@@ -28,8 +31,8 @@ __global__ __launch_bounds__(256) void screen_select_kernel(const uint32_t* __re
       const uint32_t col = col0 + 64u * u + lane;
       const bool in = col < n;
       v[u] = in ? cells[col] : 0u;
-      const uint32_t need_col = in ? need[col] : 0u;
-      keep[u] = in && col != row && v[u] >= (need_row < need_col ? need_row : need_col);
+      const uint32_t need_col = in ? need_col_of[col] : 0u;
+      keep[u] = in && !(diagonal && col == row) && v[u] >= (need_row < need_col ? need_row : need_col);
     }
     if (!FILL) {
       uint32_t c = 0;
@@ -72,28 +75,30 @@ int select_alloc(pg_ctx* ctx, uint32_t n, uint32_t rows, SelectWork& W, size_t& 
   return PG_OK;
 }
 
-// The one selection: the rows [r0, r0 + rows) of the matrix stand in rect, the thresholds in W.need.  Count pass, scan, the total read
+// The one selection: the rows [r0, r0 + rows) of the matrix stand in rect, the columns' thresholds in W.need and the rows' in need_row
+// (on the device, read at r0 + row; the square calls pass W.need there too, and diagonal = true).  Count pass, scan, the total read
 // back (the stream is synchronised there), room for the total in a, b, s (the caller's: a buffer that has the room is left alone), fill
 // pass — queued, not waited for.  *total_out = the kept triples, in row-major order.
-int select_rows(pg_ctx* ctx, const uint32_t* rect, uint32_t n, uint32_t r0, uint32_t rows, SelectWork& W, void* tmp, size_t tmp_bytes, PgDevBuf<int32_t>& a,
+int select_rows(pg_ctx* ctx, const uint32_t* rect, const uint32_t* need_row, bool diagonal, uint32_t n, uint32_t r0, uint32_t rows, SelectWork& W, void* tmp, size_t tmp_bytes, PgDevBuf<int32_t>& a,
                 PgDevBuf<int32_t>& b, PgDevBuf<uint32_t>& s, unsigned long long* total_out) {
   hipStream_t st = ctx->stream;
   const uint32_t tpr = (n + SEL_CELLS - 1) / SEL_CELLS, n_tasks = select_tasks(n, rows);
   const dim3 grid(grid_for(n_tasks, 4, (uint32_t)ctx->num_cu * 8u));
-  hipLaunchKernelGGL(screen_select_kernel<false>, grid, dim3(256), 0, st, rect, (const uint32_t*)W.need.p, n, r0, tpr, n_tasks, W.cnt.p, 0ull, (int32_t*)nullptr,
+  hipLaunchKernelGGL(screen_select_kernel<false>, grid, dim3(256), 0, st, rect, need_row, (const uint32_t*)W.need.p, diagonal, n, r0, tpr, n_tasks, W.cnt.p, 0ull, (int32_t*)nullptr,
                      (int32_t*)nullptr, (uint32_t*)nullptr);
   PG_HIP(ctx, hipGetLastError());
   PG_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, W.cnt.p, W.off.p, (int64_t)n_tasks + 1, st));
   unsigned long long total = 0;
   PG_HIP(ctx, hipMemcpyAsync(&total, W.off.p + n_tasks, 8, hipMemcpyDeviceToHost, st));
   PG_HIP(ctx, hipStreamSynchronize(st));
-  if (total > (unsigned long long)rows * (n - 1u)) return pg_fail(ctx, PG_E_INTERNAL, "screen: the selection counted more cells than its rows have off the diagonal");
+  if (total > (unsigned long long)rows * (diagonal ? n - 1u : n))
+    return pg_fail(ctx, PG_E_INTERNAL, diagonal ? "screen: the selection counted more cells than its rows have off the diagonal" : "screen: the selection counted more cells than its rows have");
   if (total) {
     int rc;
     if ((rc = pg_dev_alloc(ctx, "screen", a, (size_t)total, "the selected pairs")) || (rc = pg_dev_alloc(ctx, "screen", b, (size_t)total, "the selected pairs")) ||
         (rc = pg_dev_alloc(ctx, "screen", s, (size_t)total, "the selected pairs")))
       return rc;
-    hipLaunchKernelGGL(screen_select_kernel<true>, grid, dim3(256), 0, st, rect, (const uint32_t*)W.need.p, n, r0, tpr, n_tasks, W.off.p, total, a.p, b.p, s.p);
+    hipLaunchKernelGGL(screen_select_kernel<true>, grid, dim3(256), 0, st, rect, need_row, (const uint32_t*)W.need.p, diagonal, n, r0, tpr, n_tasks, W.off.p, total, a.p, b.p, s.p);
     PG_HIP(ctx, hipGetLastError());
   }
   *total_out = total;
@@ -188,7 +193,7 @@ extern "C" int pg_screen_select(pg_ctx* ctx, const uint32_t* need, uint32_t n, u
   if ((rc = select_alloc(ctx, n, n, W, tmp_bytes)) || (rc = pg_dev_alloc(ctx, "screen", tmp, tmp_bytes + 16, "the scan's temporary storage"))) return rc;
   PG_HIP(ctx, hipMemcpyAsync(W.need, need, (size_t)n * 4, hipMemcpyHostToDevice, st));
   unsigned long long total = 0;
-  if ((rc = select_rows(ctx, S->d_shared.p, n, 0, n, W, (void*)tmp.p, tmp_bytes, S->d_a, S->d_b, S->d_s, &total))) return rc;      // the band [0, n)
+  if ((rc = select_rows(ctx, S->d_shared.p, (const uint32_t*)W.need.p, true, n, 0, n, W, (void*)tmp.p, tmp_bytes, S->d_a, S->d_b, S->d_s, &total))) return rc;      // the band [0, n)
   if (total) PG_HIP(ctx, hipStreamSynchronize(st));      // (W goes with this scope)
   S->selected = true;
   S->n_sel = total;

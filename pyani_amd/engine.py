@@ -562,6 +562,80 @@ class Engine:
         finally:
             self.screen_components_release()
 
+    # the search: a collection resident as a k-mer index with its keys, new genomes placed against it
+    def screen_search_index(self, ids, kmer: int = 16, scale: int = 256, labels=None) -> np.ndarray:
+        """pg_screen_search_index: builds the resident SEARCH index of the genomes in the order given (up to 2^20; every distinct k-mer
+        with its value, singletons included) and returns sizes uint32[n].  It survives clear_genomes: index the collection, clear the
+        store, load the queries.  labels: the db genomes' names for screen_search (default: the ids)."""
+        from . import screen
+        a = self._ids(ids)
+        n = len(a)
+        labels = screen.search_labels(a.tolist(), labels, "db")
+        sizes = np.zeros(n if n <= (1 << 20) else 0, dtype=np.uint32)      # (beyond: refused before anything is read)
+        try:
+            self._check(self.lib.pg_screen_search_index(self._h, a.ctypes.data if n else None, n, int(kmer), int(scale), sizes.ctypes.data if sizes.size else None))
+        except _lib.PyaniGpuError as err:
+            if err.code != _lib.PG_E_ARG:      # refused arguments leave the earlier index; any other failure comes after it was released
+                self._search, self._search_q = None, 0
+            raise
+        self._search = {"n": n, "kmer": int(kmer), "scale": int(scale), "sizes": sizes, "labels": labels}      # (only a call that succeeded leaves an index)
+        self._search_q = 0
+        return sizes
+
+    def screen_search_count(self, query_ids) -> np.ndarray:
+        """pg_screen_search_count: the rectangle of the resident genomes `query_ids` (at most the band's rows: screen_set_band) against the
+        search index stays on the device; returns the queries' sizes uint32[q]."""
+        a = self._ids(query_ids)
+        q = len(a)
+        sizes = np.zeros(q, dtype=np.uint32)
+        self._check(self.lib.pg_screen_search_count(self._h, a.ctypes.data if q else None, q, sizes.ctypes.data if q else None))
+        self._search_q = q
+        return sizes
+
+    def screen_search_select(self, need_q, need_db) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """pg_screen_search_select + pg_screen_search_read: (a int32[m], b int32[m], shared uint32[m]) of the cells of the resident
+        rectangle with hits[a][b] >= min(need_q[a], need_db[b]), row-major (pyani_amd.screen.select_rectangle states it)."""
+        tq = np.ascontiguousarray(need_q, dtype=np.uint32).reshape(-1)
+        td = np.ascontiguousarray(need_db, dtype=np.uint32).reshape(-1)
+        m = ctypes.c_uint64(0)
+        self._check(self.lib.pg_screen_search_select(self._h, tq.ctypes.data if len(tq) else None, len(tq), td.ctypes.data if len(td) else None, len(td),
+                                                     ctypes.byref(m)))
+        a, b, s = np.zeros(m.value, dtype=np.int32), np.zeros(m.value, dtype=np.int32), np.zeros(m.value, dtype=np.uint32)
+        self._check(self.lib.pg_screen_search_read(self._h, *(x.ctypes.data if m.value else None for x in (a, b, s))))
+        return a, b, s
+
+    def screen_search_fetch(self) -> np.ndarray:
+        """pg_screen_search_fetch: the resident rectangle, uint32[q, n]."""
+        info = getattr(self, "_search", None)      # (the library refuses before it writes when nothing is resident: then the shape is not looked at)
+        out = np.zeros((getattr(self, "_search_q", 0), info["n"] if info else 0), dtype=np.uint32)
+        self._check(self.lib.pg_screen_search_fetch(self._h, out.ctypes.data if out.size else None))
+        return out
+
+    def screen_search_last(self) -> dict:
+        """pg_screen_search_last: counts and stage milliseconds of the resident search index, the latest count and the latest selection."""
+        c = (ctypes.c_uint64 * 10)()
+        ms = (ctypes.c_double * 7)()
+        self._check(self.lib.pg_screen_search_last(self._h, ctypes.addressof(c), ctypes.addressof(ms)))
+        return {"keys": int(c[0]), "kmers": int(c[1]), "entries": int(c[2]), "slices": int(c[3]), "query_keys": int(c[4]), "lookups": int(c[5]),
+                "matched": int(c[6]), "increments": int(c[7]), "query_slices": int(c[8]), "index_bytes": int(c[9]), "index_scan_ms": float(ms[0]), "index_sort_group_ms": float(ms[1]),
+                "scan_ms": float(ms[2]), "sort_group_ms": float(ms[3]), "lookup_ms": float(ms[4]), "count_ms": float(ms[5]), "select_ms": float(ms[6])}
+
+    def screen_search_index_release(self) -> None:
+        self._check(self.lib.pg_screen_search_index_release(self._h))
+        self._search, self._search_q = None, 0
+
+    def screen_search(self, query_ids, options, query_labels=None):
+        """The db genomes each of the resident genomes `query_ids` is related to (pyani_amd.screen.SearchHits; options: a ScreenOptions
+        with the index's kmer and scale, or a bare identity threshold for an index of the defaults): chunks of band_rows queries are
+        counted against the resident search index, given their thresholds and selected on the device.  Exactly the cells (query, db
+        genome) that screen_candidates over db + queries would keep.  The index stays resident: many searches per index."""
+        from . import screen
+        options = screen.check_options(options)
+        query_ids = [int(i) for i in query_ids]
+        query_labels = screen.search_labels(query_ids, query_labels, "query")
+        query_sizes, a, b, shared = screen.search_chunks(self, query_ids, options)
+        return screen.SearchHits(query_labels, list(self._search["labels"]), options, query_sizes, self._search["sizes"], a, b, shared)
+
     # -- classify: clique sweep over identity thresholds (pyani_amd.classify drives these) -------------------------------------
     def classify_edges(self, identity: np.ndarray, coverage: np.ndarray, id_min: float = 0.8, cov_min: float = 0.5) -> Tuple[int, int]:
         """pg_classify_edges: the edges of build_graph_from_results (pyani_classify.py:90-111) from two n x n float64 matrices in one

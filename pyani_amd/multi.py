@@ -327,6 +327,51 @@ class MultiEngine:
             return screen.index_components_on(self.engines, lambda fn: self._all(lambda e: fn(e, self.engines.index(e))), ids, options, labels)
         return self.engines[0].screen_components_of(ids, options, labels, path="dense")
 
+    def screen_search_index(self, ids, kmer: int = 16, scale: int = 256, labels=None):
+        """Engine.screen_search_index over all devices: the collection is dealt into D contiguous ranges of call
+        indices and engine d indexes its range ONLY, so the index's memory and its build time divide (fewer ranges than devices when the
+        collection is that small: the engines beyond hold no index).  Returns the sizes in the order given.  A call that fails on any
+        engine, for whatever reason, leaves NO index on any of them."""
+        from . import screen
+        ids = [int(i) for i in ids]
+        labels = screen.search_labels(ids, labels, "db")
+        d = len(self.engines)
+        bounds = [len(ids) * k // d for k in range(d + 1)]
+        self._search_ranges = [(bounds[k], bounds[k + 1]) for k in range(d)]
+
+        def part(e):
+            lo, hi = self._search_ranges[self.engines.index(e)]
+            return e.screen_search_index(ids[lo:hi], kmer, scale, labels[lo:hi])
+        try:
+            sizes = np.concatenate(self._all(part)) if ids else np.zeros(0, np.uint32)
+        except Exception:      # one engine's refusal or failure leaves the engines with indexes of different calls: none is kept
+            self.screen_search_index_release()
+            raise
+        self._search = {"n": len(ids), "kmer": int(kmer), "scale": int(scale), "sizes": sizes, "labels": labels}
+        return sizes
+
+    def screen_search(self, query_ids, options, query_labels=None):
+        """Engine.screen_search over all devices: every engine counts ALL queries against its range of the collection and selects
+        locally — need_db depends on a db genome's own size only — and screen.merge_search_parts puts the parts together per query row
+        with the ranges' column offsets added.  Equal to one engine's."""
+        from . import screen
+        options = screen.check_options(options)
+        query_ids = [int(i) for i in query_ids]
+        query_labels = screen.search_labels(query_ids, query_labels, "query")
+        info = getattr(self, "_search", None)
+        if not info or not info["n"]:
+            raise ValueError("no search index on these engines (call screen_search_index first)")
+        holders = [(e, lo) for e, (lo, hi) in zip(self.engines, self._search_ranges) if hi > lo]
+        parts = self._all(lambda e: screen.search_chunks(e, query_ids, options) if any(e is h for h, _ in holders) else None)
+        parts = [p for p in parts if p is not None]
+        a, b, shared = screen.merge_search_parts([(lo, *p[1:]) for (_, lo), p in zip(holders, parts)])
+        return screen.SearchHits(query_labels, list(info["labels"]), options, parts[0][0], info["sizes"], a, b, shared)
+
+    def screen_search_index_release(self):
+        for e in self.engines:
+            e.screen_search_index_release()
+        self._search, self._search_ranges = None, []
+
     def screen_components(self, a, b, shared=None, n: int = 0):
         """Engine.screen_components on the first engine (a list call has nothing to divide)."""
         return self.engines[0].screen_components(a, b, shared, n=n)

@@ -42,6 +42,14 @@ def default_band_rows(n: int) -> int:
     return min(MAX_BAND_ROWS, n, MAX_BAND_CELLS // n)
 
 
+def default_search_rows(n: int) -> int:
+    """The default chunk of queries of a search against n >= 1 db genomes: the largest rows <= 8192 with rows * n <= 2^29 cells (not capped
+    by n: the rows are other genomes than the columns)."""
+    if n < 1:
+        raise ValueError("a search needs a db genome")
+    return max(1, min(MAX_BAND_ROWS, MAX_BAND_CELLS // n))
+
+
 def band_ranges(n: int, rows: int = 0) -> List[Tuple[int, int]]:
     """[(r0, r1)] of the bands of n genomes at the band setting `rows` (0 = the default): band b covers [b rows, min(n, (b + 1) rows))."""
     if n == 0:
@@ -473,3 +481,115 @@ def screen_genomes(engine, ids: Sequence[int], labels: Sequence[str], kmer: int 
         raise ValueError(f"a screen call takes at most {MAX_GENOMES} genomes, not {len(ids)}")
     sizes, shared = engine.screen_matrix(ids, kmer=kmer, scale=scale)
     return ScreenResult(labels, kmer, scale, sizes, shared)
+
+
+# ---- the search: new genomes against a resident collection ------------------------------------------------------------------
+def select_rectangle(hits, need_q, need_db) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """THE STATEMENT of the search's selection (the host's; Engine.screen_search_select is held to it): for hits uint32[q, n] — hits[i][b] =
+    the sampled k-mers query i shares with db genome b — the triples (i, b, hits[i][b]) with hits[i][b] >= min(need_q[i], need_db[b]),
+    row-major: int32, int32, uint32.  The rule of candidate_pairs (identity_thresholds) on a rectangle; there is no diagonal: a query
+    that is also a db genome meets itself like any other."""
+    hits = np.ascontiguousarray(hits, dtype=np.uint32)
+    need_q = np.ascontiguousarray(need_q, dtype=np.uint32).reshape(-1)
+    need_db = np.ascontiguousarray(need_db, dtype=np.uint32).reshape(-1)
+    if hits.ndim != 2 or hits.shape != (len(need_q), len(need_db)):
+        raise ValueError(f"hits of shape {hits.shape} do not go with {len(need_q)} query and {len(need_db)} db thresholds")
+    a, b = np.nonzero(hits >= np.minimum.outer(need_q, need_db))
+    return a.astype(np.int32), b.astype(np.int32), hits[a, b]
+
+
+def merge_search_parts(parts) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(a, b, shared) of a search whose collection was dealt into contiguous ranges of columns: parts[d] = (col0, a, b, shared), the
+    row-major triples of ALL queries against the db genomes [col0, col0 + n_d), b counted from col0; the ranges ascend with d.  The column
+    offsets are added and the parts merged per query row in ascending d (a stable sort on the row): ascending b inside a row follows."""
+    a = np.concatenate([np.asarray(p[1], dtype=np.int32) for p in parts]) if parts else np.zeros(0, np.int32)
+    b = np.concatenate([np.asarray(p[2], dtype=np.int32) + np.int32(p[0]) for p in parts]) if parts else np.zeros(0, np.int32)
+    s = np.concatenate([np.asarray(p[3], dtype=np.uint32) for p in parts]) if parts else np.zeros(0, np.uint32)
+    order = np.argsort(a, kind="stable")
+    return a[order], b[order], s[order]
+
+
+class SearchHits(NamedTuple):
+    """The cells a search kept (Engine.screen_search), row-major: a = the position in `query_labels`, b = the position in `db_labels`,
+    shared = |S(query a) & S(db b)|.  An ESTIMATE, as every frame of the screen."""
+    query_labels: List[str]
+    db_labels: List[str]
+    options: ScreenOptions
+    query_sizes: np.ndarray     # uint32[q]
+    db_sizes: np.ndarray        # uint32[n]
+    a: np.ndarray               # int32[m]
+    b: np.ndarray               # int32[m]
+    shared: np.ndarray          # uint32[m]
+
+    def pairs(self) -> List[Tuple[int, int]]:
+        return list(zip(self.a.tolist(), self.b.tolist()))
+
+    def _containment(self, size) -> np.ndarray:
+        size = size.astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(size > 0, self.shared.astype(np.float64) / size, np.nan)
+
+    def containment_query(self) -> np.ndarray:
+        """shared / |S(query)|: the share of the query's sampled k-mers found in the db genome (NaN for an empty query)."""
+        return self._containment(self.query_sizes[self.a])
+
+    def containment_db(self) -> np.ndarray:
+        """shared / |S(db genome)| (NaN for an empty db genome)."""
+        return self._containment(self.db_sizes[self.b])
+
+    def identity(self) -> np.ndarray:
+        """The quantity the rule thresholds: the LARGER of the two containments to the power 1 / k where shared >= min_shared, else 0.0
+        (each side by _identity_of_counts, the very expression identity_thresholds bisects)."""
+        out = np.zeros(len(self.shared), dtype=np.float64)
+        for size in (self.query_sizes[self.a], self.db_sizes[self.b]):
+            ok = (self.shared >= self.options.min_shared) & (size > 0)
+            side = np.zeros(len(out), dtype=np.float64)
+            side[ok] = _identity_of_counts(self.shared[ok], size[ok], self.options.kmer)
+            out = np.maximum(out, side)
+        return out
+
+    def frame(self) -> pd.DataFrame:
+        """One row per kept cell: query, db (labels), shared, containment_query, containment_db, identity."""
+        ql, dl = np.array(list(self.query_labels), dtype=object), np.array(list(self.db_labels), dtype=object)
+        return pd.DataFrame({"query": ql[self.a] if len(self.a) else [], "db": dl[self.b] if len(self.b) else [], "shared": self.shared,
+                             "containment_query": self.containment_query(), "containment_db": self.containment_db(), "identity": self.identity()})
+
+    def best(self, top: int = 1) -> "SearchHits":
+        """Per query its `top` hits by identity, the best first, ties to the smaller db index (host numpy); a query without a hit has none."""
+        if isinstance(top, bool) or int(top) != top or int(top) < 1:
+            raise ValueError(f"top must be an integer >= 1, not {top!r}")
+        order = np.lexsort((self.b, -self.identity(), self.a))      # by query, then identity descending, then db index ascending
+        a = self.a[order]
+        first = np.searchsorted(a, a, side="left")                  # the first position of every entry's query
+        keep = order[np.arange(len(a)) - first < int(top)]
+        return self._replace(a=self.a[keep], b=self.b[keep], shared=self.shared[keep])
+
+
+def search_chunks(engine, query_ids, options) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """(query sizes, a, b, shared) of the queries against the engine's resident search index: chunks of band_rows queries, each counted
+    (Engine.screen_search_count), given its thresholds and selected; the chunk's row offset is added.  options.kmer and options.scale
+    must be the index's.  The index stays resident."""
+    options = check_options(options)
+    info = getattr(engine, "_search", None)
+    if not info or not info["n"]:
+        raise ValueError("no search index on this engine (call screen_search_index first)")
+    if (options.kmer, options.scale) != (info["kmer"], info["scale"]):
+        raise ValueError(f"the search index was built with kmer {info['kmer']} and scale {info['scale']}, not {options.kmer} and {options.scale}")
+    query_ids = [int(i) for i in query_ids]
+    rows = int(getattr(engine, "_band_rows", 0)) or default_search_rows(info["n"])
+    need_db = identity_thresholds(info["sizes"], options.kmer, options.min_identity, options.min_shared)
+    sizes, parts = [np.zeros(0, np.uint32)], [(np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint32))]
+    for c0 in range(0, len(query_ids), rows):
+        size = engine.screen_search_count(query_ids[c0:c0 + rows])
+        need_q = identity_thresholds(size, options.kmer, options.min_identity, options.min_shared)
+        a, b, s = engine.screen_search_select(need_q, need_db)
+        sizes.append(size)
+        parts.append((a + np.int32(c0), b, s))
+    return (np.concatenate(sizes), *(np.concatenate([p[i] for p in parts]) for i in range(3)))
+
+
+def search_labels(ids, labels, what: str) -> List[str]:
+    labels = [str(x) for x in (ids if labels is None else labels)]
+    if len(labels) != len(ids):
+        raise ValueError(f"{what} ids and labels must have the same length")
+    return labels
