@@ -525,6 +525,34 @@ int pg_screen_search_read(pg_ctx* ctx, int32_t* a_out, int32_t* b_out, uint32_t*
 int pg_screen_search_fetch(pg_ctx* ctx, uint32_t* out);
 int pg_screen_search_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
 
+/* ---- screen, the gather: a query decomposed into the collection's genomes.  For query i with Q = S(query i), R_0 = Q and
+ * round t = 0, 1, ...: left_t[b] = |R_t & S(b)|; the winner w = the SMALLEST b among those with the largest left_t[b]; the query stops
+ * when left_t[w] < need[i] or when it has max_ranks rows; otherwise the row (i, rank t, w, unique = left_t[w], total = hits[i][w]) is
+ * recorded and R_(t + 1) = R_t \ S(w).  The queries of a call are independent.  Integers only: unique never rises along a query's
+ * ranks, unique <= total, a winner's cell of `left` is 0 afterwards, and a query has at most min(n, max_ranks) rows.
+ * pg_screen_gather_count is pg_screen_search_count — the same limits, refusals, rectangle and statistics; select, read and fetch work on
+ * it as before — and also keeps the matched entries resident, one per (query, matched k-mer): at most the queries' keys, 8 bytes each.
+ * pg_screen_search_count keeps none: either count drops what the earlier one held, the entries and the gathered rows included.
+ * pg_screen_gather runs the rounds on a working copy of the rectangle and of the entries (the counted rectangle and the kept entries are
+ * never written: a selection, or another gather with other thresholds, may follow).  need: q uint32 >= 1, the smallest unique count worth
+ * a row; 1 <= max_ranks <= 65536; *n_rows_out = the rows of all queries.  PG_E_ARG, with any earlier result still readable: no resident
+ * search index; a latest count that kept no entries; q not the counted q; need NULL with q > 0; max_ranks out of range.  q = 0: no rows.
+ * pg_screen_gather_read copies the rows out, ordered by query, then rank: query_out, db_out int32 (positions in the count and the index
+ * call), unique_out, total_out uint32; the arrays may be NULL when there is no row.  pg_screen_gather_fetch copies `left` out (q x n
+ * uint32): what the rounds left of the rectangle.  Both are PG_E_ARG without a gather.
+ * pg_screen_gather_matched copies out, per query of the latest gather count, its kept entries = |S(query i) & the union of the db| (q
+ * uint32; PG_E_ARG without such a count): with it, the sum of a query's unique and what stayed unexplained add up to a known number.
+ * pg_screen_gather_last: counts_out[5] = matched entries M of the latest gather count | of the latest gather: rounds run (the last
+ * round in which a query was unfinished), rows, entries claimed, decrements issued.  ms_out[3] = the expansion of the entries (the
+ * count's extra stage) | arg-max + decide, claim (with the entries' compaction) of the latest gather.  All 0 without either.
+ * The gather's state goes with the next count, pg_screen_search_index_release and pg_destroy; it survives pg_clear_genomes. */
+int pg_screen_gather_count(pg_ctx* ctx, const int32_t* query_ids, uint32_t q, uint32_t* sizes_out);
+int pg_screen_gather(pg_ctx* ctx, const uint32_t* need, uint32_t q, uint32_t max_ranks, uint64_t* n_rows_out);
+int pg_screen_gather_read(pg_ctx* ctx, int32_t* query_out, int32_t* db_out, uint32_t* unique_out, uint32_t* total_out);
+int pg_screen_gather_fetch(pg_ctx* ctx, uint32_t* out);
+int pg_screen_gather_matched(pg_ctx* ctx, uint32_t* matched_out);
+int pg_screen_gather_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
+
 /* ---- classify: clique sweep over identity thresholds ------------------------------------------------------------------
  * The compute of `pyani classify`.  These calls read caller matrices only: they touch no genome, seed list or ANIm worker slot, so
  * they need no interlock with the pg_anim_pairs_enqueue / _fetch lanes and may run while enqueued ANIm calls are in flight (own

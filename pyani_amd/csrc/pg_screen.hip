@@ -54,6 +54,16 @@
 //   S2 screen_weight_kernel<SearchWeight> + an exclusive scan over the matched k-mers: m_q m_d items each
 //   S3 search_count_kernel  C3's balance by item (item_walk); item t -> (t / m_d, t % m_d), uint32 atomics into the rectangle
 //
+// pgscr_gather.inc — the GATHER: a query decomposed into the collection's genomes.  pg_screen_gather_count is the search's
+// count with a sink (QueryBack: G0 appends every matched (query, k-mer) entry per slice); pg_screen_gather runs greedy rounds on a copy of
+// the rectangle, in batches without a synchronisation between the rounds:
+//   G0 gather_expand_kernel item_walk over the matched runs, one item per query holder: entry = query << 48 | index position of the k-mer
+//   G1 gather_argmax_kernel a grid over (chunk of the row, query): 16-byte loads, wave and workgroup reduction of the packed key
+//                           count << 32 | ~b, one 64-bit atomic max per workgroup into best[query]
+//   G2 gather_decide_kernel one thread per query: a row recorded and the winner named, or the query finished; best reset
+//   G3 gather_claim_kernel  a wave per 64 entries: the winner looked up among the k-mer's holders (binary search), the claiming lanes
+//                           balloted, the whole wave walks each claimed k-mer's holders with uint32 atomic decrements along the row
+//
 // pgscr_components.inc — the COMPONENTS: which genomes belong together.  pg_screen_components (a list from the host) and
 // pg_screen_index_components (the bands' kept triples, where B5 left them on the device) hook a union-find forest that only atomics write
 // and sum two 64-bit counts per node; K1 ... K3 stand there with their state.
@@ -69,8 +79,8 @@
 
 namespace {
 
-// the stages whose milliseconds pg_screen_last, pg_screen_index_last, pg_screen_components_last and pg_screen_search_last report
-enum ScreenStage { ST_SCAN, ST_GROUP, ST_COUNT, ST_SELECT, ST_HOOK, ST_FLATTEN, ST_LOOKUP };
+// the stages whose milliseconds pg_screen_last, pg_screen_index_last, pg_screen_components_last, pg_screen_search_last and pg_screen_gather_last report
+enum ScreenStage { ST_SCAN, ST_GROUP, ST_COUNT, ST_SELECT, ST_HOOK, ST_FLATTEN, ST_LOOKUP, ST_EXPAND, ST_ARGMAX, ST_CLAIM };
 
 struct ScreenEvents {      // event pairs on the context's stream, summed per stage after the call's last synchronisation
   std::vector<hipEvent_t> ev;
@@ -123,3 +133,4 @@ hipError_t tmp_room(size_t& tmp_bytes, Query query) {
 #include "pgscr_index.inc"
 #include "pgscr_components.inc"
 #include "pgscr_search.inc"
+#include "pgscr_gather.inc"

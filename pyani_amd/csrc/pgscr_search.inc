@@ -33,7 +33,33 @@ struct SearchState {      // the resident search index of pg_screen_search_index
   uint64_t n_sel = 0;
   PgDevBuf<int32_t> d_a, d_b;
   PgDevBuf<uint32_t> d_s;
+  // the gather (DESIGN.md §16.5, pgscr_gather.inc): the matched entries of the latest pg_screen_gather_count and the latest decomposition
+  bool kept = false;                              // the latest count kept its entries
+  uint64_t M = 0;                                 // matched (query, k-mer) entries
+  PgDevBuf<unsigned long long> d_entry;           // M: query << GATHER_G_BITS | index position of the k-mer; never written after the count
+  PgDevBuf<uint32_t> d_matched;                   // q: the entries of each query = |S(query) & the union of the db|
+  bool gathered = false;
+  uint64_t n_rows = 0;
+  PgDevBuf<uint32_t> d_left;                      // q x n: what the latest pg_screen_gather left of the rectangle
+  PgDevBuf<int32_t> d_row_q, d_row_db;            // n_rows each, by query, then rank
+  PgDevBuf<uint32_t> d_row_unique, d_row_total;
+  void drop_gather() {
+    kept = gathered = false;
+    M = n_rows = 0;
+    d_entry.release(); d_matched.release(); d_left.release(); d_row_q.release(); d_row_db.release(); d_row_unique.release(); d_row_total.release();
+  }
 };
+
+// Where a count leaves its matched entries (pgscr_gather.inc): prepare once by the bound, per slice one more expansion over the matched runs.
+struct EntrySink {
+  PgDevBuf<unsigned long long> entry;
+  size_t cap = 0;
+  uint64_t M = 0;
+};
+struct QueryBack;
+int gather_sink_prepare(pg_ctx* ctx, EntrySink& sink, uint64_t total_keys);
+int gather_sink_slice(QueryBack& B, const SliceGroups& S, ScreenEvents& T, uint32_t nr, uint32_t na);
+int gather_sink_finish(pg_ctx* ctx, const EntrySink& sink, uint32_t q, PgDevBuf<uint32_t>& matched, ScreenEvents& T);
 
 // An array of the index that was sized by a bound and uses `need` elements moves into a block of exactly that many, unless the bound was
 // close (within a sixteenth: E is nearly the keys when few k-mers repeat inside a genome) or there is no room for the copy: then it stays.
@@ -190,10 +216,12 @@ struct QueryBack {
   PgDevBuf<uint32_t> run_first, active;
   PgDevBuf<unsigned long long> group, wts, off, d_sel;
   uint64_t lookups = 0, matched = 0, incr = 0;
-  int prepare(uint64_t, uint64_t slice_max, size_t, size_t& tmp_bytes) {
+  EntrySink* sink = nullptr;      // the gather's count: the matched entries go here as well
+  int prepare(uint64_t total_keys, uint64_t slice_max, size_t, size_t& tmp_bytes) {
     const size_t room = (size_t)slice_max + 1;
     hipStream_t st = ctx->stream;
     int rc;
+    if (sink && (rc = gather_sink_prepare(ctx, *sink, total_keys))) return rc;
     if ((rc = sk_malloc(ctx, head, room)) || (rc = sk_malloc(ctx, found, room)) || (rc = sk_malloc(ctx, run_first, room)) || (rc = sk_malloc(ctx, active, room)) ||
         (rc = sk_malloc(ctx, group, room)) || (rc = sk_malloc(ctx, wts, room)) || (rc = sk_malloc(ctx, off, room)) || (rc = sk_malloc(ctx, d_sel, 1)))
       return rc;
@@ -236,6 +264,7 @@ struct QueryBack {
     if (na > nr) return pg_fail(ctx, PG_E_INTERNAL, "screen: more matched k-mers than looked up");
     lookups += nr; matched += na;
     if (!na) return PG_OK;
+    if (sink) { int rc; if ((rc = gather_sink_slice(*this, S, T, (uint32_t)nr, (uint32_t)na))) return rc; }
     {
       ScreenEvents::Stage count(T, ST_COUNT, st);
       const SearchWeight weight{active.p, run_first.p, (uint32_t)nr, S.nu, I->D, group.p, I->d_start.p};
@@ -264,6 +293,7 @@ void pg_screen_search_drop(pg_ctx* ctx) {
   delete search_of(ctx);
   ctx->screen_search_state = nullptr;
   ctx->screen_search_stats = PgScreenSearchStats{};
+  ctx->screen_gather_stats = PgScreenGatherStats{};
 }
 
 extern "C" int pg_screen_search_index_release(pg_ctx* ctx) {
@@ -334,7 +364,8 @@ extern "C" int pg_screen_search_index(pg_ctx* ctx, const int32_t* genome_ids, ui
   return PG_OK;
 }
 
-extern "C" int pg_screen_search_count(pg_ctx* ctx, const int32_t* query_ids, uint32_t q, uint32_t* sizes_out) {
+// pg_screen_search_count and pg_screen_gather_count: one path; keep = the matched entries stay resident for pg_screen_gather
+static int search_count(pg_ctx* ctx, const int32_t* query_ids, uint32_t q, uint32_t* sizes_out, bool keep) {
   if (!ctx) return PG_E_ARG;
   SearchState* I = search_of(ctx);
   if (!I) return pg_fail(ctx, PG_E_ARG, "screen: no resident search index (call pg_screen_search_index first)");
@@ -347,10 +378,12 @@ extern "C" int pg_screen_search_count(pg_ctx* ctx, const int32_t* query_ids, uin
   I->counted = I->selected = false;
   I->n_sel = 0;
   I->d_rect.release(); I->d_a.release(); I->d_b.release(); I->d_s.release();
+  I->drop_gather();
+  ctx->screen_gather_stats = PgScreenGatherStats{};
   PgScreenSearchStats& L = ctx->screen_search_stats;
   L.query_keys = L.lookups = L.matched = L.increments = L.query_slices = 0;
   L.scan_ms = L.group_ms = L.lookup_ms = L.count_ms = L.select_ms = 0.0;
-  if (q == 0) { I->q = 0; I->counted = true; return PG_OK; }      // (a rectangle of no rows)
+  if (q == 0) { I->q = 0; I->counted = true; I->kept = keep; return PG_OK; }      // (a rectangle of no rows)
   if ((rc = pg_upload(ctx))) return rc;
   hipStream_t st = ctx->stream;
   PgDevBuf<uint32_t> rect, d_sizes;
@@ -358,8 +391,12 @@ extern "C" int pg_screen_search_count(pg_ctx* ctx, const int32_t* query_ids, uin
   PG_HIP(ctx, hipMemsetAsync(rect, 0, (size_t)q * I->n * 4, st));
   ScreenEvents T;
   FrontTotals tot;
+  EntrySink sink;
   QueryBack back{ctx, I, q, rect.p};
+  if (keep) back.sink = &sink;
+  PgDevBuf<uint32_t> matched;
   rc = screen_front(ctx, query_ids, q, I->kmer, I->scale, 0, 1, false, d_sizes, T, tot, back);
+  if (!rc && keep) rc = gather_sink_finish(ctx, sink, q, matched, T);
   hipError_t e = rc ? hipSuccess : hipMemcpyAsync(sizes_out, d_sizes, (size_t)q * 4, hipMemcpyDeviceToHost, st);
   const hipError_t es = hipStreamSynchronize(st);      // (on errors too: the back half's buffers and `rect` go with this scope)
   if (rc) return rc;
@@ -370,7 +407,19 @@ extern "C" int pg_screen_search_count(pg_ctx* ctx, const int32_t* query_ids, uin
   I->d_rect = std::move(rect);
   I->q = q;
   I->counted = true;
+  if (keep) {
+    I->kept = true;
+    I->M = sink.M;
+    I->d_entry = std::move(sink.entry);
+    I->d_matched = std::move(matched);
+    ctx->screen_gather_stats.entries = sink.M;
+    ctx->screen_gather_stats.expand_ms = T.ms(ST_EXPAND);
+  }
   return PG_OK;
+}
+
+extern "C" int pg_screen_search_count(pg_ctx* ctx, const int32_t* query_ids, uint32_t q, uint32_t* sizes_out) {
+  return search_count(ctx, query_ids, q, sizes_out, false);
 }
 
 extern "C" int pg_screen_search_fetch(pg_ctx* ctx, uint32_t* out) {

@@ -636,6 +636,60 @@ class Engine:
         query_sizes, a, b, shared = screen.search_chunks(self, query_ids, options)
         return screen.SearchHits(query_labels, list(self._search["labels"]), options, query_sizes, self._search["sizes"], a, b, shared)
 
+    # the gather: a query decomposed into the genomes of the resident collection
+    def screen_gather_count(self, query_ids) -> np.ndarray:
+        """pg_screen_gather_count: screen_search_count that also keeps the matched (query, k-mer) entries resident for
+        screen_gather_rows; returns the queries' sizes uint32[q].  select and fetch of the search work on its rectangle as before."""
+        a = self._ids(query_ids)
+        q = len(a)
+        sizes = np.zeros(q, dtype=np.uint32)
+        self._check(self.lib.pg_screen_gather_count(self._h, a.ctypes.data if q else None, q, sizes.ctypes.data if q else None))
+        self._search_q = q
+        return sizes
+
+    def screen_gather_rows(self, need, max_ranks: int = 65536) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """pg_screen_gather + pg_screen_gather_read: (query int32[r], db int32[r], unique uint32[r], total uint32[r]) of the greedy
+        decomposition of every counted query, ordered by query, then rank (pyani_gpu.h states the rounds).  need: uint32[q] >= 1."""
+        t = np.ascontiguousarray(need, dtype=np.uint32).reshape(-1)
+        r = ctypes.c_uint64(0)
+        self._check(self.lib.pg_screen_gather(self._h, t.ctypes.data if len(t) else None, len(t), int(max_ranks), ctypes.byref(r)))
+        qi, db = np.zeros(r.value, dtype=np.int32), np.zeros(r.value, dtype=np.int32)
+        unique, total = np.zeros(r.value, dtype=np.uint32), np.zeros(r.value, dtype=np.uint32)
+        self._check(self.lib.pg_screen_gather_read(self._h, *(x.ctypes.data if r.value else None for x in (qi, db, unique, total))))
+        return qi, db, unique, total
+
+    def screen_gather_matched(self) -> np.ndarray:
+        """pg_screen_gather_matched: uint32[q], the entries the latest gather count kept per query = |S(query) & the union of the db|."""
+        out = np.zeros(getattr(self, "_search_q", 0), dtype=np.uint32)
+        self._check(self.lib.pg_screen_gather_matched(self._h, out.ctypes.data if out.size else None))
+        return out
+
+    def screen_gather_fetch(self) -> np.ndarray:
+        """pg_screen_gather_fetch: what the latest gather left of the rectangle, uint32[q, n]."""
+        info = getattr(self, "_search", None)
+        out = np.zeros((getattr(self, "_search_q", 0), info["n"] if info else 0), dtype=np.uint32)
+        self._check(self.lib.pg_screen_gather_fetch(self._h, out.ctypes.data if out.size else None))
+        return out
+
+    def screen_gather_last(self) -> dict:
+        """pg_screen_gather_last: counts and stage milliseconds of the latest gather count and the latest gather."""
+        c = (ctypes.c_uint64 * 5)()
+        ms = (ctypes.c_double * 3)()
+        self._check(self.lib.pg_screen_gather_last(self._h, ctypes.addressof(c), ctypes.addressof(ms)))
+        return {"entries": int(c[0]), "rounds": int(c[1]), "rows": int(c[2]), "claimed": int(c[3]), "decrements": int(c[4]),
+                "expand_ms": float(ms[0]), "argmax_decide_ms": float(ms[1]), "claim_ms": float(ms[2])}
+
+    def screen_gather(self, query_ids, options, query_labels=None):
+        """What each of the resident genomes `query_ids` is MADE OF (pyani_amd.screen.GatherResult; options: a GatherOptions with the
+        index's kmer and scale): chunks of band_rows queries are counted against the resident search index with their entries kept,
+        given their thresholds and decomposed on the device.  The index stays resident: many gathers per index."""
+        from . import screen
+        options = screen.check_gather_options(options)
+        query_ids = [int(i) for i in query_ids]
+        query_labels = screen.search_labels(query_ids, query_labels, "query")
+        query_sizes, matched, qi, db, unique, total = screen.gather_chunks(self, query_ids, options)
+        return screen.GatherResult(query_labels, list(self._search["labels"]), options, query_sizes, self._search["sizes"], qi, db, unique, total, matched)
+
     # -- classify: clique sweep over identity thresholds (pyani_amd.classify drives these) -------------------------------------
     def classify_edges(self, identity: np.ndarray, coverage: np.ndarray, id_min: float = 0.8, cov_min: float = 0.5) -> Tuple[int, int]:
         """pg_classify_edges: the edges of build_graph_from_results (pyani_classify.py:90-111) from two n x n float64 matrices in one

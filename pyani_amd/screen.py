@@ -18,6 +18,10 @@ Which genomes BELONG TOGETHER is the last step: the connected
 the statement, Engine.screen_components / screen_index_components the kernels, ScreenComponents the table: one representative per
 component is the dereplicated set), had through the index without a single pair leaving the device (Engine.screen_components_of).
 
+New genomes against a resident collection: Engine.screen_search lists what each is RELATED TO (SearchHits), and
+Engine.screen_gather what each is MADE OF — the greedy minimum set of collection genomes that explains its k-mers (GatherOptions,
+GatherResult).
+
 An ESTIMATE for triage with its own frames: it is never written into an exact ANIm / ANIb matrix.  What this is modelled on: the
 sketch-then-align front ends of skani, sourmash and dRep; pyani itself has no such step.
 """
@@ -593,3 +597,126 @@ def search_labels(ids, labels, what: str) -> List[str]:
     if len(labels) != len(ids):
         raise ValueError(f"{what} ids and labels must have the same length")
     return labels
+
+
+# ---- the gather: a query decomposed into the collection's genomes ----------------------------------------------------------
+GATHER_MAX_RANKS = 65536
+
+
+class GatherOptions(NamedTuple):
+    """What a gather asks: a db genome is worth a row while it explains at least max(min_unique, ceil(min_fraction * |S(query)|)) of the
+    query's sampled k-mers that no better match has explained; at most max_ranks rows per query.  There is no default min_unique: two
+    unrelated 5 Mb genomes share about 50 sampled 16-mers by chance at scale 256, so the right floor depends on the genomes' size and
+    the scale."""
+    kmer: int
+    scale: int
+    min_unique: int
+    min_fraction: float = 0.0
+    max_ranks: int = GATHER_MAX_RANKS
+
+
+def check_gather_options(options) -> GatherOptions:
+    """A GatherOptions validated (no library call): kmer and scale as check_params, min_unique an integer >= 1, min_fraction a real number
+    in [0, 1], max_ranks an integer 1 ... 65536."""
+    if not isinstance(options, GatherOptions):
+        raise ValueError(f"gather options are a GatherOptions, not {options!r}")
+    kmer, scale = check_params(options.kmer, options.scale)
+    mu, mf, mr = options.min_unique, options.min_fraction, options.max_ranks
+    if isinstance(mu, bool) or not isinstance(mu, (int, np.integer)) or not 1 <= int(mu) < (1 << 32):
+        raise ValueError(f"min_unique must be an integer >= 1 (below 2^32), not {mu!r}")
+    if isinstance(mf, bool) or not isinstance(mf, (int, float, np.integer, np.floating)) or math.isnan(float(mf)) or not 0.0 <= float(mf) <= 1.0:
+        raise ValueError(f"min_fraction must be a number in [0, 1], not {mf!r}")
+    if isinstance(mr, bool) or not isinstance(mr, (int, np.integer)) or not 1 <= int(mr) <= GATHER_MAX_RANKS:
+        raise ValueError(f"max_ranks must be an integer 1 ... {GATHER_MAX_RANKS}, not {mr!r}")
+    return GatherOptions(kmer, scale, int(mu), float(mf), int(mr))
+
+
+def gather_thresholds(query_sizes, min_unique: int, min_fraction: float = 0.0) -> np.ndarray:
+    """need uint32[q] = max(min_unique, ceil(min_fraction * size)), floored at 1: the smallest unique count worth a row.  The product is
+    taken in float64 (sizes are below 2^32: exact operands) and rounded up."""
+    sizes = np.ascontiguousarray(query_sizes, dtype=np.uint32).reshape(-1)
+    if isinstance(min_unique, bool) or int(min_unique) != min_unique or not 0 <= int(min_unique) < (1 << 32):
+        raise ValueError(f"min_unique must be an integer 0 ... 2^32 - 1, not {min_unique!r}")
+    if isinstance(min_fraction, bool) or math.isnan(float(min_fraction)) or not 0.0 <= float(min_fraction) <= 1.0:
+        raise ValueError(f"min_fraction must be a number in [0, 1], not {min_fraction!r}")
+    part = np.ceil(float(min_fraction) * sizes.astype(np.float64)).astype(np.uint64)
+    return np.maximum(np.maximum(part, np.uint64(int(min_unique))), np.uint64(1)).astype(np.uint32)
+
+
+class GatherResult(NamedTuple):
+    """The rows of a gather (Engine.screen_gather), ordered by query, then rank: query = the position in `query_labels`, db = the position
+    in `db_labels`, unique = the query's k-mers this genome explains that no row before it explained, total = |S(query) & S(db)|.  An
+    ESTIMATE, as every frame of the screen."""
+    query_labels: List[str]
+    db_labels: List[str]
+    options: GatherOptions
+    query_sizes: np.ndarray     # uint32[q]
+    db_sizes: np.ndarray        # uint32[n]
+    query: np.ndarray           # int32[r]
+    db: np.ndarray              # int32[r]
+    unique: np.ndarray          # uint32[r]
+    total: np.ndarray           # uint32[r]
+    matched: np.ndarray         # uint32[q]: |S(query) & the union of the db|, the entries the count kept
+
+    def ranks(self) -> np.ndarray:
+        """The rank of every row inside its query, 0 first (the rows of a query stand together)."""
+        q = np.asarray(self.query)
+        return (np.arange(len(q)) - np.searchsorted(q, q, side="left")).astype(np.int64)
+
+    def frame(self) -> pd.DataFrame:
+        """One row per recorded genome: query, rank, db (labels), unique, total, f_unique_query = unique / |S(query)|, f_unique_cumulative
+        = its running sum inside the query, f_match = total / |S(db)|, identity = f_match ** (1 / k)."""
+        ql, dl = np.array(list(self.query_labels), dtype=object), np.array(list(self.db_labels), dtype=object)
+        qsize, dsize = self.query_sizes[self.query].astype(np.float64), self.db_sizes[self.db].astype(np.float64)
+        unique = self.unique.astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            f_unique = np.where(qsize > 0, unique / qsize, np.nan)
+            f_match = np.where(dsize > 0, self.total.astype(np.float64) / dsize, np.nan)
+        running = np.cumsum(self.unique.astype(np.int64))
+        first = np.searchsorted(self.query, self.query, side="left")
+        before = np.where(first > 0, running[np.maximum(first, 1) - 1], 0) if len(running) else running
+        with np.errstate(divide="ignore", invalid="ignore"):
+            f_running = np.where(qsize > 0, (running - before).astype(np.float64) / qsize, np.nan)
+        return pd.DataFrame({"query": ql[self.query] if len(self.query) else [], "rank": self.ranks(), "db": dl[self.db] if len(self.db) else [],
+                             "unique": self.unique, "total": self.total, "f_unique_query": f_unique, "f_unique_cumulative": f_running,
+                             "f_match": f_match, "identity": np.power(f_match, 1.0 / self.options.kmer)})
+
+    def summary(self) -> pd.DataFrame:
+        """One row per query: query, size, matched = |S(query) & the union of the db|, rows, explained = the sum of its rows' unique,
+        unexplained = matched - explained: the k-mers that matched the collection but stayed below the threshold (or beyond max_ranks)."""
+        q = len(self.query_labels)
+        rows = np.bincount(self.query, minlength=q).astype(np.int64)
+        explained = np.bincount(self.query, weights=self.unique.astype(np.float64), minlength=q).astype(np.int64)      # (sums below 2^53: exact)
+        matched = self.matched.astype(np.int64)
+        return pd.DataFrame({"query": list(self.query_labels), "size": self.query_sizes.astype(np.int64), "matched": matched, "rows": rows,
+                             "explained": explained, "unexplained": matched - explained})
+
+
+def gather_chunks(engine, query_ids, options):
+    """(query sizes, matched, query, db, unique, total) of the queries against the engine's resident search index: chunks of band_rows
+    queries, each counted with its entries kept (Engine.screen_gather_count), given its thresholds and decomposed; the chunk's row
+    offset is added.  options.kmer and options.scale must be the index's.  The index stays resident; the last chunk's rectangle, entries
+    and rows are dropped before this returns, on errors too (a count of no queries)."""
+    options = check_gather_options(options)
+    info = getattr(engine, "_search", None)
+    if not info or not info["n"]:
+        raise ValueError("no search index on this engine (call screen_search_index first)")
+    if (options.kmer, options.scale) != (info["kmer"], info["scale"]):
+        raise ValueError(f"the search index was built with kmer {info['kmer']} and scale {info['scale']}, not {options.kmer} and {options.scale}")
+    query_ids = [int(i) for i in query_ids]
+    rows = int(getattr(engine, "_band_rows", 0)) or default_search_rows(info["n"])
+    sizes, matched = [np.zeros(0, np.uint32)], [np.zeros(0, np.uint32)]
+    parts = [(np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint32), np.zeros(0, np.uint32))]
+    try:
+        for c0 in range(0, len(query_ids), rows):
+            size = engine.screen_gather_count(query_ids[c0:c0 + rows])
+            matched.append(engine.screen_gather_matched())
+            qi, db, unique, total = engine.screen_gather_rows(gather_thresholds(size, options.min_unique, options.min_fraction), options.max_ranks)
+            sizes.append(size)
+            parts.append((qi + np.int32(c0), db, unique, total))
+    finally:
+        try:
+            engine.screen_search_count([])
+        except Exception:      # (the first error is the one to report)
+            pass
+    return (np.concatenate(sizes), np.concatenate(matched), *(np.concatenate([p[i] for p in parts]) for i in range(4)))
