@@ -525,6 +525,29 @@ int pg_screen_search_read(pg_ctx* ctx, int32_t* a_out, int32_t* b_out, uint32_t*
 int pg_screen_search_fetch(pg_ctx* ctx, uint32_t* out);
 int pg_screen_search_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
 
+/* ---- screen, the search: genomes added to the resident index without a rebuild.  An index built from the list L of n
+ * genomes grows by m genomes of the store as it is NOW (genome_ids; none twice): afterwards the state is the one
+ * pg_screen_search_index(L ++ genome_ids) with the index's kmer and scale would leave — n' = n + m, added genome j is column n + j, D and
+ * E are the fresh build's, and every later count, selection, fetch and gather gives the fresh build's integers in the fresh build's order.
+ * Only the cut into slices may differ (nothing observable depends on it).  sizes_out: m uint32, the added genomes' sizes.
+ * The ids are NOT compared with the collection — the index knows positions, not ids: a genome added in two calls is two equal columns.
+ * So a collection larger than the genome store is indexed in batches: load, index, clear; load, add, clear; ...
+ * PG_E_ARG, before anything is touched (the index, the counted rectangle, the selection and the gather's state stay readable): no
+ * resident search index; n + m above 2^20 (checked before the ids are read); an id out of range or given twice; a NULL array with m > 0.
+ * m = 0 is PG_OK and changes nothing.  An accepted add with m >= 1 drops the counted rectangle, the selection and the gather's state, as
+ * a new count does (they were n wide).  The merged index is built BESIDE the old one, its arrays at their exact sizes (D' + 1, D' + 1,
+ * E' + 1), and takes its place only when the call has succeeded: on PG_E_NOMEM or any other failure after the checks the OLD index is
+ * resident and usable (its rectangle is gone by then).  While the call runs the device holds both, the staged keys of the batch (twice 8
+ * bytes each, and 22 bytes of work arrays) and 4 (D + 1) bytes; between calls never more than one index.
+ * After an add the index fields of pg_screen_search_last (keys — the sum over the build and the adds —, D, E, slices, bytes held)
+ * describe the merged index.
+ * pg_screen_search_add_last: the latest accepted add.  counts_out[6] = added genomes, keys scanned, new entries, new k-mers (absent
+ * before), matched k-mers (present before), accepted adds since the build.  ms_out[3] = scan, sort + group (the front's and the staged
+ * keys' sort into the index's order), merge (locate, scans, placement, the copy of the index) — HIP events; no pair spans a host
+ * synchronisation.  All 0 after a build, a release, or without an index. */
+int pg_screen_search_index_add(pg_ctx* ctx, const int32_t* genome_ids, uint32_t m, uint32_t* sizes_out);
+int pg_screen_search_add_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
+
 /* ---- screen, the gather: a query decomposed into the collection's genomes.  For query i with Q = S(query i), R_0 = Q and
  * round t = 0, 1, ...: left_t[b] = |R_t & S(b)|; the winner w = the SMALLEST b among those with the largest left_t[b]; the query stops
  * when left_t[w] < need[i] or when it has max_ranks rows; otherwise the row (i, rank t, w, unique = left_t[w], total = hits[i][w]) is

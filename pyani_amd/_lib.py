@@ -117,6 +117,8 @@ SIGNATURES = {
     "pg_screen_search_read": (_int, [_vp, _vp, _vp, _vp]),
     "pg_screen_search_fetch": (_int, [_vp, _vp]),
     "pg_screen_search_last": (_int, [_vp, _vp, _vp]),
+    "pg_screen_search_index_add": (_int, [_vp, _vp, _u32, _vp]),
+    "pg_screen_search_add_last": (_int, [_vp, _vp, _vp]),
     "pg_screen_gather_count": (_int, [_vp, _vp, _u32, _vp]),
     "pg_screen_gather": (_int, [_vp, _vp, _u32, _u32, _P(_u64)]),
     "pg_screen_gather_read": (_int, [_vp, _vp, _vp, _vp, _vp]),

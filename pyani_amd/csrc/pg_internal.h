@@ -65,6 +65,12 @@ struct PgScreenSearchStats {
   double select_ms = 0.0;                                                                // the latest selection
 };
 
+struct PgScreenSearchAddStats {      // pg_screen_search_add_last: the latest accepted pg_screen_search_index_add
+  uint64_t genomes = 0, keys = 0, entries = 0, new_kmers = 0, matched_kmers = 0;      // of the batch: k-mers absent from / present in the index before
+  uint64_t adds = 0;                                                                   // accepted adds since the build
+  double scan_ms = 0.0, group_ms = 0.0, merge_ms = 0.0;
+};
+
 struct PgScreenGatherStats {      // pg_screen_gather_last: the latest pg_screen_gather_count (entries, expand) and pg_screen_gather (the rest)
   uint64_t entries = 0, rounds = 0, rows = 0, claimed = 0, decrements = 0;
   double expand_ms = 0.0, argmax_ms = 0.0, claim_ms = 0.0;      // argmax_ms: arg-max + decide
@@ -139,6 +145,7 @@ struct pg_ctx {
   PgScreenComponentsStats screen_components_stats;      // pg_screen_components_last: the resident components' call
   void* screen_search_state = nullptr;          // resident search index of pg_screen_search_index and the latest rectangle counted against it (pg_screen.hip); independent of the three above and of the genome store
   PgScreenGatherStats screen_gather_stats;      // pg_screen_gather_last
+  PgScreenSearchAddStats screen_search_add_stats;      // pg_screen_search_add_last
   PgScreenSearchStats screen_search_stats;      // pg_screen_search_last: the resident search index, the latest count and selection over it
   double dist_ms[3] = {0.0, 0.0, 0.0};   // kernel milliseconds of the latest pg_dist_load / _hist / _kde while profiling is on (pg_dist_last_ms)
   std::mutex anim_mu, err_mu, prof_mu;

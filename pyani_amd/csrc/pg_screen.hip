@@ -54,6 +54,12 @@
 //   S2 screen_weight_kernel<SearchWeight> + an exclusive scan over the matched k-mers: m_q m_d items each
 //   S3 search_count_kernel  C3's balance by item (item_walk); item t -> (t / m_d, t % m_d), uint32 atomics into the rectangle
 //
+// pgscr_add.inc — genomes ADDED to the resident search index: pg_screen_search_index_add is screen_front over the new
+// genomes with a fourth back half (AddBack: the slices' distinct keys staged, the genome rebased behind the collection's) and a merge beside
+// the old index; A1 ... A8 stand there:
+//   A3 add_locate_kernel    one thread per distinct added k-mer: its position in the index, or where it goes
+//   A6 add_fill_old_kernel  the whole index streams through once, balanced by entry (item_walk over the starts)
+//
 // pgscr_gather.inc — the GATHER: a query decomposed into the collection's genomes.  pg_screen_gather_count is the search's
 // count with a sink (QueryBack: G0 appends every matched (query, k-mer) entry per slice); pg_screen_gather runs greedy rounds on a copy of
 // the rectangle, in batches without a synchronisation between the rounds:
@@ -79,8 +85,9 @@
 
 namespace {
 
-// the stages whose milliseconds pg_screen_last, pg_screen_index_last, pg_screen_components_last, pg_screen_search_last and pg_screen_gather_last report
-enum ScreenStage { ST_SCAN, ST_GROUP, ST_COUNT, ST_SELECT, ST_HOOK, ST_FLATTEN, ST_LOOKUP, ST_EXPAND, ST_ARGMAX, ST_CLAIM };
+// the stages whose milliseconds pg_screen_last, pg_screen_index_last, pg_screen_components_last, pg_screen_search_last, pg_screen_search_add_last and
+// pg_screen_gather_last report
+enum ScreenStage { ST_SCAN, ST_GROUP, ST_COUNT, ST_SELECT, ST_HOOK, ST_FLATTEN, ST_LOOKUP, ST_EXPAND, ST_ARGMAX, ST_CLAIM, ST_MERGE };
 
 struct ScreenEvents {      // event pairs on the context's stream, summed per stage after the call's last synchronisation
   std::vector<hipEvent_t> ev;
@@ -133,4 +140,5 @@ hipError_t tmp_room(size_t& tmp_bytes, Query query) {
 #include "pgscr_index.inc"
 #include "pgscr_components.inc"
 #include "pgscr_search.inc"
+#include "pgscr_add.inc"
 #include "pgscr_gather.inc"

@@ -76,6 +76,19 @@ int search_fit(pg_ctx* ctx, PgDevBuf<T>& b, size_t need) {
 
 SearchState* search_of(pg_ctx* ctx) { return static_cast<SearchState*>(ctx->screen_search_state); }
 
+// the rectangle, the selection and the gather state of an earlier count go, with their statistics: before a new count, and when the index grows
+void search_drop_counted(pg_ctx* ctx, SearchState* I) {
+  I->counted = I->selected = false;
+  I->q = 0;
+  I->n_sel = 0;
+  I->d_rect.release(); I->d_a.release(); I->d_b.release(); I->d_s.release();
+  I->drop_gather();
+  ctx->screen_gather_stats = PgScreenGatherStats{};
+  PgScreenSearchStats& L = ctx->screen_search_stats;
+  L.query_keys = L.lookups = L.matched = L.increments = L.query_slices = 0;
+  L.scan_ms = L.group_ms = L.lookup_ms = L.count_ms = L.select_ms = 0.0;
+}
+
 // u: the nu distinct keys of a slice, sorted.  head[i] = entry i is the first of its k-mer (EVERY k-mer: the front's marks cover only the
 // ones held by two or more genomes); member_out[i] = its genome, where an output is given.
 __global__ __launch_bounds__(256) void search_mark_kernel(const unsigned long long* __restrict__ u, uint64_t nu, uint8_t* __restrict__ head,
@@ -293,6 +306,7 @@ void pg_screen_search_drop(pg_ctx* ctx) {
   delete search_of(ctx);
   ctx->screen_search_state = nullptr;
   ctx->screen_search_stats = PgScreenSearchStats{};
+  ctx->screen_search_add_stats = PgScreenSearchAddStats{};
   ctx->screen_gather_stats = PgScreenGatherStats{};
 }
 
@@ -374,15 +388,8 @@ static int search_count(pg_ctx* ctx, const int32_t* query_ids, uint32_t q, uint3
   int rc;
   if ((rc = screen_check(ctx, query_ids, q, I->kmer, I->scale, 0, 1, sizes_out, false, nullptr, rows, too_many.c_str()))) return rc;
   PG_HIP(ctx, hipSetDevice(ctx->device));
-  // the rectangle and the selection of an earlier count go before the new one is made
-  I->counted = I->selected = false;
-  I->n_sel = 0;
-  I->d_rect.release(); I->d_a.release(); I->d_b.release(); I->d_s.release();
-  I->drop_gather();
-  ctx->screen_gather_stats = PgScreenGatherStats{};
+  search_drop_counted(ctx, I);      // the rectangle and the selection of an earlier count go before the new one is made
   PgScreenSearchStats& L = ctx->screen_search_stats;
-  L.query_keys = L.lookups = L.matched = L.increments = L.query_slices = 0;
-  L.scan_ms = L.group_ms = L.lookup_ms = L.count_ms = L.select_ms = 0.0;
   if (q == 0) { I->q = 0; I->counted = true; I->kept = keep; return PG_OK; }      // (a rectangle of no rows)
   if ((rc = pg_upload(ctx))) return rc;
   hipStream_t st = ctx->stream;

@@ -582,6 +582,34 @@ class Engine:
         self._search_q = 0
         return sizes
 
+    def screen_search_index_add(self, ids, labels=None) -> np.ndarray:
+        """pg_screen_search_index_add: the genomes `ids` (of the store as it is now) join the resident search index as its last columns,
+        without a rebuild: the state is the one screen_search_index over the old list + `ids` would leave.  Returns
+        their sizes uint32[m].  The counted rectangle goes; the index's kmer, scale and earlier columns stay.  A collection larger than
+        the genome store is indexed in batches: load, index, clear_genomes; load, add, clear_genomes; ...  labels: as for
+        screen_search_index."""
+        from . import screen
+        a = self._ids(ids)
+        m = len(a)
+        labels = screen.search_labels(a.tolist(), labels, "db")
+        info = getattr(self, "_search", None)
+        sizes = np.zeros(m if m <= (1 << 20) else 0, dtype=np.uint32)      # (beyond: refused before anything is read)
+        # (a failure leaves the old index resident, refused arguments its rectangle too: nothing recorded here changes)
+        self._check(self.lib.pg_screen_search_index_add(self._h, a.ctypes.data if m else None, m, sizes.ctypes.data if sizes.size else None))
+        if m:
+            self._search = dict(info, n=info["n"] + m, sizes=np.concatenate([info["sizes"], sizes]), labels=list(info["labels"]) + labels)
+            self._search_q = 0
+        return sizes
+
+    def screen_search_add_last(self) -> dict:
+        """pg_screen_search_add_last: counts and stage milliseconds of the latest accepted screen_search_index_add (zeros after a build
+        or a release)."""
+        c = (ctypes.c_uint64 * 6)()
+        ms = (ctypes.c_double * 3)()
+        self._check(self.lib.pg_screen_search_add_last(self._h, ctypes.addressof(c), ctypes.addressof(ms)))
+        return {"genomes": int(c[0]), "keys": int(c[1]), "entries": int(c[2]), "new_kmers": int(c[3]), "matched_kmers": int(c[4]), "adds": int(c[5]),
+                "scan_ms": float(ms[0]), "sort_group_ms": float(ms[1]), "merge_ms": float(ms[2])}
+
     def screen_search_count(self, query_ids) -> np.ndarray:
         """pg_screen_search_count: the rectangle of the resident genomes `query_ids` (at most the band's rows: screen_set_band) against the
         search index stays on the device; returns the queries' sizes uint32[q]."""

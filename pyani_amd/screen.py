@@ -513,6 +513,45 @@ def merge_search_parts(parts) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     return a[order], b[order], s[order]
 
 
+def merge_search_index(kmer, start, member, new_kmer, new_member):
+    """THE STATEMENT of the search index's growth (the device's steps 3 to 5) on arrays, for an index of ONE slice: the
+    index (kmer uint32[D] ascending, start int64[D + 1], member uint32[E], ascending inside a k-mer) and the entries of the added genomes
+    (new_kmer, new_member, sorted by k-mer, then member; every new member larger than every old one) -> (kmer', start', member', new
+    k-mers, matched k-mers).  An added k-mer is looked up (lower bound p); an absent one is ranked among the absent (a) and goes to p + a,
+    an old k-mer g moves up by the absent ones with p <= g, and the new entries go behind their k-mer's old holders — nothing is sorted."""
+    kmer, start, member = np.asarray(kmer, dtype=np.uint32), np.asarray(start, dtype=np.int64), np.asarray(member, dtype=np.uint32)
+    new_kmer, new_member = np.asarray(new_kmer, dtype=np.uint32), np.asarray(new_member, dtype=np.uint32)
+    d, e, nk = len(kmer), len(member), len(new_kmer)
+    old_count = np.diff(start)
+    head = np.ones(nk, dtype=bool)
+    head[1:] = new_kmer[1:] != new_kmer[:-1]
+    run_first = np.flatnonzero(head)
+    run_len = np.diff(np.append(run_first, nk))
+    canon = new_kmer[run_first]
+    p = np.searchsorted(kmer, canon, side="left")
+    found = np.zeros(len(canon), dtype=bool)
+    inside = p < d
+    found[inside] = kmer[p[inside]] == canon[inside]
+    absent = ~found
+    a = np.cumsum(absent) - absent                                        # the absent runs before each run
+    shift = np.cumsum(np.bincount(p[absent], minlength=d + 1))[:d]        # the absent runs that go before each old k-mer
+    d_new = d + int(absent.sum())
+    old_pos, run_pos = np.arange(d) + shift, p + a
+    kmer_new, count = np.zeros(d_new, dtype=np.uint32), np.zeros(d_new, dtype=np.int64)
+    kmer_new[old_pos], count[old_pos] = kmer, old_count
+    kmer_new[run_pos[absent]] = canon[absent]
+    count[run_pos] += run_len
+    start_new = np.concatenate([[0], np.cumsum(count)]).astype(np.int64)
+    member_new = np.zeros(e + nk, dtype=np.uint32)
+    of_entry = np.repeat(np.arange(d), old_count)
+    member_new[np.arange(e) + (start_new[old_pos] - start[:d])[of_entry]] = member
+    behind = np.zeros(len(canon), dtype=np.int64)
+    behind[found] = old_count[p[found]]
+    of_key = np.repeat(np.arange(len(canon)), run_len)
+    member_new[(start_new[run_pos] + behind)[of_key] + np.arange(nk) - run_first[of_key]] = new_member
+    return kmer_new, start_new, member_new, int(absent.sum()), int(found.sum())
+
+
 class SearchHits(NamedTuple):
     """The cells a search kept (Engine.screen_search), row-major: a = the position in `query_labels`, b = the position in `db_labels`,
     shared = |S(query a) & S(db b)|.  An ESTIMATE, as every frame of the screen."""

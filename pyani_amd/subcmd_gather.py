@@ -26,7 +26,7 @@ import pandas as pd
 from . import anim, files, screen as screen_mod
 from .engine import Engine, default_engine
 from .subcmd_screen import OUTDIR
-from .subcmd_search import _stems
+from .subcmd_search import _stems, check_db_batch, load_db
 
 EXACT = (None, "anim")
 
@@ -48,11 +48,13 @@ def gather_tab_path(outdir, name: str) -> Path:
 def run_screen_gather(db_dir, query_dir, outdir=None, min_unique: Optional[int] = None, kmer: int = screen_mod.DEFAULT_KMER,
                       scale: int = screen_mod.DEFAULT_SCALE, min_fraction: float = 0.0, max_ranks: int = screen_mod.GATHER_MAX_RANKS,
                       exact: Optional[str] = None, write_output: bool = False, engine: Optional[Engine] = None,
-                      devices: Optional[List[int]] = None, workers: Optional[int] = None) -> GatherRun:
+                      devices: Optional[List[int]] = None, workers: Optional[int] = None, db_batch: Optional[int] = None) -> GatherRun:
     """Every FASTA file of `query_dir` decomposed into the genomes of `db_dir`.  min_unique is required (there is no default threshold:
     about 50 sampled 16-mers are shared by chance between two unrelated 5 Mb genomes at scale 256); outdir is needed for write_output
     only.  devices / workers are refused: a gather runs on a single engine.  An engine holds ONE search index: one already resident on a
-    caller's `engine` is replaced by the one of `db_dir`, and the engine holds none when this returns (released on errors too)."""
+    caller's `engine` is replaced by the one of `db_dir`, and the engine holds none when this returns (released on errors too).
+    db_batch: the collection goes through the store that many files at a time, each batch after the first ADDED to the resident index
+    (run_screen_search's text); the result does not change."""
     if min_unique is None:
         raise ValueError("run_screen_gather needs min_unique= (there is no default threshold)")
     if write_output and outdir is None:
@@ -62,10 +64,11 @@ def run_screen_gather(db_dir, query_dir, outdir=None, min_unique: Optional[int] 
     if devices is not None or workers:
         raise ValueError("a gather runs on a single engine: devices= / workers= are not supported (the winner's k-mers live on one device)")
     options = screen_mod.check_gather_options(screen_mod.GatherOptions(kmer, scale, min_unique, min_fraction, max_ranks))
-    return _run(db_dir, query_dir, outdir, options, exact, write_output, engine or default_engine())
+    db_batch = check_db_batch(db_batch, exact, engine, None, None)
+    return _run(db_dir, query_dir, outdir, options, exact, write_output, engine or default_engine(), db_batch)
 
 
-def _run(db_dir, query_dir, outdir, options, exact, write_output, eng) -> GatherRun:
+def _run(db_dir, query_dir, outdir, options, exact, write_output, eng, db_batch=None) -> GatherRun:
     db_paths, q_paths = files.get_fasta_paths(Path(db_dir)), files.get_fasta_paths(Path(query_dir))
     db_stems, q_stems = _stems(db_paths, "db"), _stems(q_paths, "query")
     scratch_store = eng.genome_count() == 0
@@ -73,10 +76,7 @@ def _run(db_dir, query_dir, outdir, options, exact, write_output, eng) -> Gather
     q_len: Dict[str, int] = {}
     results = None
     try:
-        db_ids = np.zeros(len(db_paths), dtype=np.int64)
-        for k, (p, (gid, total, _)) in enumerate(zip(db_paths, eng.add_fasta_batch(db_paths))):
-            db_ids[k], db_len[p.stem] = gid, total
-        eng.screen_search_index(db_ids.tolist(), options.kmer, options.scale, labels=db_stems)
+        db_ids = load_db(eng, db_paths, db_stems, options, db_batch, db_len)
         if exact is None and scratch_store:      # the index names the collection by position only: its sequences make room for the queries
             eng.clear_genomes()
         q_ids = np.zeros(len(q_paths), dtype=np.int64)

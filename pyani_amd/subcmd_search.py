@@ -10,6 +10,10 @@ the identity and coverage of both directions are added to the hits' table.  The 
 files: `<outdir>/screen_output/search_hits.tab` (every kept cell) and `search_best.tab` (per query its `top` hits, default 1).
 OUT OF SCOPE: ANIb as exact=, saving an index, recovery, collective runs.  Single-process: one engine, or several GPUs of this node
 (devices / workers: the collection is dealt over them, MultiEngine.screen_search_index).
+
+db_batch=N: the collection is loaded N files at a time — the first batch is indexed, every later one ADDED to the
+resident index (Engine.screen_search_index_add), the store cleared after each — so a collection larger than the genome arena can be
+searched.  Only for a run that owns the store, on a single Engine, without exact= (the sequences are gone).  The result is the same.
 """
 from pathlib import Path
 from typing import Dict, List, NamedTuple, Optional, Tuple
@@ -45,14 +49,58 @@ def _stems(paths, what: str) -> List[str]:
     return stems
 
 
+def check_db_batch(db_batch, exact, engine, devices, workers) -> Optional[int]:
+    """The db_batch= of run_screen_search and run_screen_gather, checked before a file is read or an engine is made: None, or an integer
+    >= 1 on a single Engine whose store is empty, without exact=."""
+    if db_batch is None:
+        return None
+    if isinstance(db_batch, bool) or not isinstance(db_batch, (int, np.integer)) or int(db_batch) < 1:
+        raise ValueError(f"db_batch must be an integer >= 1, not {db_batch!r}")
+    if exact is not None:
+        raise ValueError("db_batch clears the store after every batch: exact= needs the collection's sequences and cannot go with it")
+    if devices is not None or workers or (engine is not None and not isinstance(engine, Engine)):
+        raise ValueError("db_batch runs on a single Engine: a collection dealt over several devices cannot be added to")
+    if engine is not None and engine.genome_count() != 0:
+        raise ValueError("db_batch clears the genome store after every batch: it needs an engine whose store is empty")
+    return int(db_batch)
+
+
+def load_db(eng, db_paths, db_stems, options, db_batch, db_len) -> np.ndarray:
+    """The collection's files loaded and the search index built: in one piece (returns the genomes' ids), or db_batch files at a time
+    through a store cleared after every batch (the ids are gone with the sequences: positions are returned)."""
+    if db_batch is None:
+        db_ids = np.zeros(len(db_paths), dtype=np.int64)
+        for k, (p, (gid, total, _)) in enumerate(zip(db_paths, eng.add_fasta_batch(db_paths))):
+            db_ids[k], db_len[p.stem] = gid, total
+        eng.screen_search_index(db_ids.tolist(), options.kmer, options.scale, labels=db_stems)
+        return db_ids
+    if eng.genome_count() != 0:      # (the default engine is known only now)
+        raise ValueError("db_batch clears the genome store after every batch: it needs an engine whose store is empty")
+    if not db_paths:
+        eng.screen_search_index([], options.kmer, options.scale, labels=[])
+    for lo in range(0, len(db_paths), db_batch):
+        paths, stems = db_paths[lo:lo + db_batch], db_stems[lo:lo + db_batch]
+        ids = []
+        for p, (gid, total, _) in zip(paths, eng.add_fasta_batch(paths)):
+            ids.append(gid)
+            db_len[p.stem] = total
+        if lo == 0:
+            eng.screen_search_index(ids, options.kmer, options.scale, labels=stems)
+        else:
+            eng.screen_search_index_add(ids, labels=stems)
+        eng.clear_genomes()
+    return np.arange(len(db_paths), dtype=np.int64)
+
+
 def run_screen_search(db_dir, query_dir, outdir=None, min_identity: Optional[float] = None, kmer: int = screen_mod.DEFAULT_KMER,
                       scale: int = screen_mod.DEFAULT_SCALE, min_shared: int = screen_mod.DEFAULT_MIN_SHARED, top: Optional[int] = None,
                       exact: Optional[str] = None, write_output: bool = False, engine: Optional[Engine] = None,
-                      devices: Optional[List[int]] = None, workers: Optional[int] = None) -> SearchRun:
+                      devices: Optional[List[int]] = None, workers: Optional[int] = None, db_batch: Optional[int] = None) -> SearchRun:
     """Every FASTA file of `query_dir` placed against the collection of `db_dir`.  min_identity is required (there is no default
     threshold); outdir is needed for write_output only; devices / workers: several GPUs of this node, ignored when `engine` is given.
     An engine holds ONE search index: a search index already resident on a caller's `engine` is replaced by the one of `db_dir`, and
-    the engine holds none when this returns (released on errors too)."""
+    the engine holds none when this returns (released on errors too).  db_batch: the collection goes through the store that many files
+    at a time (the module's text); the result does not change."""
     if min_identity is None:
         raise ValueError("run_screen_search needs min_identity= (there is no default threshold)")
     if write_output and outdir is None:
@@ -62,13 +110,14 @@ def run_screen_search(db_dir, query_dir, outdir=None, min_identity: Optional[flo
     if top is not None and (isinstance(top, bool) or int(top) != top or int(top) < 1):
         raise ValueError(f"top must be an integer >= 1, not {top!r}")
     options = screen_mod.check_options(screen_mod.ScreenOptions(min_identity, kmer, scale, min_shared))
+    db_batch = check_db_batch(db_batch, exact, engine, devices, workers)
     own = None
     if engine is None and (devices is not None or workers):
         from . import multi
         engine = multi.engine_for(devices, workers)
         own = engine if isinstance(engine, multi.MultiEngine) else None
     try:
-        return _run(db_dir, query_dir, outdir, options, int(top or 1), exact, write_output, engine or default_engine())
+        return _run(db_dir, query_dir, outdir, options, int(top or 1), exact, write_output, engine or default_engine(), db_batch)
     finally:
         if own is not None:
             own.close()
@@ -78,7 +127,7 @@ def _coverage(aln: int, length: int) -> float:
     return aln / length if length else float("nan")
 
 
-def _run(db_dir, query_dir, outdir, options, top, exact, write_output, eng) -> SearchRun:
+def _run(db_dir, query_dir, outdir, options, top, exact, write_output, eng, db_batch=None) -> SearchRun:
     db_paths, q_paths = files.get_fasta_paths(Path(db_dir)), files.get_fasta_paths(Path(query_dir))
     db_stems, q_stems = _stems(db_paths, "db"), _stems(q_paths, "query")
     scratch_store = eng.genome_count() == 0
@@ -86,10 +135,7 @@ def _run(db_dir, query_dir, outdir, options, top, exact, write_output, eng) -> S
     q_len: Dict[str, int] = {}
     results = None
     try:
-        db_ids = np.zeros(len(db_paths), dtype=np.int64)
-        for k, (p, (gid, total, _)) in enumerate(zip(db_paths, eng.add_fasta_batch(db_paths))):
-            db_ids[k], db_len[p.stem] = gid, total
-        eng.screen_search_index(db_ids.tolist(), options.kmer, options.scale, labels=db_stems)
+        db_ids = load_db(eng, db_paths, db_stems, options, db_batch, db_len)
         if exact is None and scratch_store:      # the index names the collection by position only: its sequences make room for the queries
             eng.clear_genomes()
         q_ids = np.zeros(len(q_paths), dtype=np.int64)
