@@ -548,6 +548,49 @@ int pg_screen_search_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
 int pg_screen_search_index_add(pg_ctx* ctx, const int32_t* genome_ids, uint32_t m, uint32_t* sizes_out);
 int pg_screen_search_add_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
 
+/* ---- screen, the search: the resident index exported, imported and shrunk — with the build and the add, the operations
+ * of a database one maintains.  The index is six plain arrays and seven numbers:
+ *   shape[7] = n, kmer, scale, D (distinct k-mers), E (entries), n_slices S, keys (the scan count pg_screen_search_last reports)
+ *   kmer uint32[D], start uint64[D + 1], member uint32[E], slice_first uint64[S + 1], bin_slice uint32[4096]
+ * (the sixth array, the genomes' sizes, is a function of member: it is never stored on the device and never believed).
+ * pg_screen_search_index_shape and pg_screen_search_index_export copy these out and change nothing: the counted rectangle, the selection
+ * and the gather's state stay.  PG_E_ARG without a resident index.
+ * pg_screen_search_index_import uploads arrays that a FILE supplied and leaves exactly the state the exporting context had: every later
+ * count, selection, fetch, gather and add gives the same integers in the same order, and the index fields of pg_screen_search_last (keys,
+ * D, E, slices) are the exporter's; the arrays sit at their exact sizes: bytes held = 12 (D + 1) + 4 (E + 1) + 8 (S + 1) + 4 * 4096.
+ * sizes_out: n uint32, COMPUTED from the entries (a count per column).  Nothing of the file is trusted.  The host checks, before anything
+ * is uploaded: n <= 2^20, 8 <= kmer <= 16, scale a power of two <= 65536, E >= D, S <= 4096; n = 0 needs D = E = 0 and leaves no index
+ * (an earlier one is released, as pg_screen_search_index does); slice_first[0] = 0, non-decreasing, slice_first[S] = D; every bin_slice
+ * value < S or 0xFFFFFFFF (no slice).  Then the device validates every invariant the build guarantees, in an order in which no pass
+ * indexes by a value an earlier pass has not validated: start[0] = 0, start[D] = E, start strictly increasing (every k-mer has a holder);
+ * every k-mer < 4^kmer, sampled under scale, in the slice its bin names, strictly ascending inside a slice; only when the starts are sound
+ * are the entries walked by them: every member < n, strictly ascending inside a k-mer.  One counter per kind is read back once; a nonzero
+ * one is PG_E_ARG and the message names the first violated invariant and its count.  The imported index is built BESIDE any resident one
+ * and takes its place only on success: after any refusal the old index and its rectangle are resident and usable, after any other failure
+ * the old index.  ms_out[1] of pg_screen_search_last (sort + group of the build) holds the validation's milliseconds for an imported index,
+ * ms_out[0] is 0.
+ * pg_screen_search_index_remove takes m columns (current call indices; each < n, none twice) out of the index: afterwards the state is
+ * the one pg_screen_search_index over the list without those genomes would leave — n' = n - m, surviving column c becomes c - (removed
+ * columns below c), D' and E' are the fresh build's, holders ascend inside a k-mer, k-mers with no holder left are gone.  As for the add
+ * only the cut into slices may differ: the directory keeps its slice count with slice_first rebased, and a slice may become empty.
+ * PG_E_ARG before anything is touched: no resident index; a NULL array with m > 0; a column >= n or given twice.  m = 0 is PG_OK and
+ * changes nothing.  Removing every column releases the index, as a build of no genome leaves none.  An accepted remove drops the counted
+ * rectangle, the selection and the gather's state; the new index is built beside the old one at its exact sizes and replaces it on
+ * success: on PG_E_NOMEM the old one is still resident.  While the call runs the device holds both, 8 (E + 1) + 8 (D + 1) + 4 n bytes of
+ * positions and the scans' temporary storage.  The old entries are read twice and written once.  The `keys` field of
+ * pg_screen_search_last is a HISTORICAL scan count (the build's and the adds'): a remove does not change it; D, E and the bytes held
+ * describe the shrunk index.
+ * pg_screen_search_remove_last: the latest accepted remove.  counts_out[4] = removed genomes, removed entries, removed k-mers, accepted
+ * removes since the build or the import.  ms_out[2] = mark + scans, compaction (HIP events; no pair spans a host synchronisation).  All 0
+ * after a build, an import, a release, or without an index. */
+int pg_screen_search_index_shape(pg_ctx* ctx, uint64_t* shape_out);
+int pg_screen_search_index_export(pg_ctx* ctx, uint32_t* kmer_out, uint64_t* start_out, uint32_t* member_out, uint64_t* slice_first_out,
+                                  uint32_t* bin_slice_out);
+int pg_screen_search_index_import(pg_ctx* ctx, const uint64_t* shape, const uint32_t* kmer, const uint64_t* start, const uint32_t* member,
+                                  const uint64_t* slice_first, const uint32_t* bin_slice, uint32_t* sizes_out);
+int pg_screen_search_index_remove(pg_ctx* ctx, const uint32_t* columns, uint32_t m);
+int pg_screen_search_remove_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
+
 /* ---- screen, the gather: a query decomposed into the collection's genomes.  For query i with Q = S(query i), R_0 = Q and
  * round t = 0, 1, ...: left_t[b] = |R_t & S(b)|; the winner w = the SMALLEST b among those with the largest left_t[b]; the query stops
  * when left_t[w] < need[i] or when it has max_ranks rows; otherwise the row (i, rank t, w, unique = left_t[w], total = hits[i][w]) is

@@ -119,6 +119,11 @@ SIGNATURES = {
     "pg_screen_search_last": (_int, [_vp, _vp, _vp]),
     "pg_screen_search_index_add": (_int, [_vp, _vp, _u32, _vp]),
     "pg_screen_search_add_last": (_int, [_vp, _vp, _vp]),
+    "pg_screen_search_index_shape": (_int, [_vp, _vp]),
+    "pg_screen_search_index_export": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "pg_screen_search_index_import": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pg_screen_search_index_remove": (_int, [_vp, _vp, _u32]),
+    "pg_screen_search_remove_last": (_int, [_vp, _vp, _vp]),
     "pg_screen_gather_count": (_int, [_vp, _vp, _u32, _vp]),
     "pg_screen_gather": (_int, [_vp, _vp, _u32, _u32, _P(_u64)]),
     "pg_screen_gather_read": (_int, [_vp, _vp, _vp, _vp, _vp]),

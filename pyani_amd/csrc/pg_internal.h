@@ -65,6 +65,12 @@ struct PgScreenSearchStats {
   double select_ms = 0.0;                                                                // the latest selection
 };
 
+struct PgScreenSearchRemoveStats {      // pg_screen_search_remove_last: the latest accepted pg_screen_search_index_remove
+  uint64_t genomes = 0, entries = 0, kmers = 0;      // removed columns, entries, k-mers (those whose last holder went)
+  uint64_t removes = 0;                              // accepted removes since the build or the import
+  double mark_ms = 0.0, compact_ms = 0.0;            // the two scans; placement, the copy of the entries, the directory
+};
+
 struct PgScreenSearchAddStats {      // pg_screen_search_add_last: the latest accepted pg_screen_search_index_add
   uint64_t genomes = 0, keys = 0, entries = 0, new_kmers = 0, matched_kmers = 0;      // of the batch: k-mers absent from / present in the index before
   uint64_t adds = 0;                                                                   // accepted adds since the build
@@ -146,6 +152,7 @@ struct pg_ctx {
   void* screen_search_state = nullptr;          // resident search index of pg_screen_search_index and the latest rectangle counted against it (pg_screen.hip); independent of the three above and of the genome store
   PgScreenGatherStats screen_gather_stats;      // pg_screen_gather_last
   PgScreenSearchAddStats screen_search_add_stats;      // pg_screen_search_add_last
+  PgScreenSearchRemoveStats screen_search_remove_stats;      // pg_screen_search_remove_last
   PgScreenSearchStats screen_search_stats;      // pg_screen_search_last: the resident search index, the latest count and selection over it
   double dist_ms[3] = {0.0, 0.0, 0.0};   // kernel milliseconds of the latest pg_dist_load / _hist / _kde while profiling is on (pg_dist_last_ms)
   std::mutex anim_mu, err_mu, prof_mu;

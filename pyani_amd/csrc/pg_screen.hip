@@ -60,6 +60,13 @@
 //   A3 add_locate_kernel    one thread per distinct added k-mer: its position in the index, or where it goes
 //   A6 add_fill_old_kernel  the whole index streams through once, balanced by entry (item_walk over the starts)
 //
+// pgscr_store.inc — the resident search index EXPORTED, IMPORTED and SHRUNK: pg_screen_search_index_export copies the
+// arrays out; pg_screen_search_index_import uploads arrays a file supplied and validates every invariant of the build before anything may
+// index by them; pg_screen_search_index_remove compacts the index without some columns, beside the old one; V1, V2, R1 ... R5 stand there:
+//   V1 store_check_kmer_kernel   one thread per k-mer: the starts strictly increasing up to E; the k-mer sampled, in its bin's slice, ascending
+//   V2 store_check_member_kernel only after V1 found the starts sound: item_walk over them; member < n, ascending, the sizes' histogram
+//   R4 remove_fill_kernel        member'[pos[t]] = new_of[member[t]]: the second and last read of the old entries
+//
 // pgscr_gather.inc — the GATHER: a query decomposed into the collection's genomes.  pg_screen_gather_count is the search's
 // count with a sink (QueryBack: G0 appends every matched (query, k-mer) entry per slice); pg_screen_gather runs greedy rounds on a copy of
 // the rectangle, in batches without a synchronisation between the rounds:
@@ -85,9 +92,9 @@
 
 namespace {
 
-// the stages whose milliseconds pg_screen_last, pg_screen_index_last, pg_screen_components_last, pg_screen_search_last, pg_screen_search_add_last and
-// pg_screen_gather_last report
-enum ScreenStage { ST_SCAN, ST_GROUP, ST_COUNT, ST_SELECT, ST_HOOK, ST_FLATTEN, ST_LOOKUP, ST_EXPAND, ST_ARGMAX, ST_CLAIM, ST_MERGE };
+// the stages whose milliseconds pg_screen_last, pg_screen_index_last, pg_screen_components_last, pg_screen_search_last, pg_screen_search_add_last,
+// pg_screen_search_remove_last and pg_screen_gather_last report
+enum ScreenStage { ST_SCAN, ST_GROUP, ST_COUNT, ST_SELECT, ST_HOOK, ST_FLATTEN, ST_LOOKUP, ST_EXPAND, ST_ARGMAX, ST_CLAIM, ST_MERGE, ST_CHECK, ST_MARK, ST_COMPACT };
 
 struct ScreenEvents {      // event pairs on the context's stream, summed per stage after the call's last synchronisation
   std::vector<hipEvent_t> ev;
@@ -141,4 +148,5 @@ hipError_t tmp_room(size_t& tmp_bytes, Query query) {
 #include "pgscr_components.inc"
 #include "pgscr_search.inc"
 #include "pgscr_add.inc"
+#include "pgscr_store.inc"
 #include "pgscr_gather.inc"

@@ -307,6 +307,7 @@ void pg_screen_search_drop(pg_ctx* ctx) {
   ctx->screen_search_state = nullptr;
   ctx->screen_search_stats = PgScreenSearchStats{};
   ctx->screen_search_add_stats = PgScreenSearchAddStats{};
+  ctx->screen_search_remove_stats = PgScreenSearchRemoveStats{};
   ctx->screen_gather_stats = PgScreenGatherStats{};
 }
 

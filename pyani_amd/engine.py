@@ -610,6 +610,112 @@ class Engine:
         return {"genomes": int(c[0]), "keys": int(c[1]), "entries": int(c[2]), "new_kmers": int(c[3]), "matched_kmers": int(c[4]), "adds": int(c[5]),
                 "scan_ms": float(ms[0]), "sort_group_ms": float(ms[1]), "merge_ms": float(ms[2])}
 
+    # the search index exported, imported and shrunk
+    def screen_search_index_shape(self) -> Tuple[int, int, int, int, int, int, int]:
+        """pg_screen_search_index_shape: (n, kmer, scale, D, E, n_slices, keys) of the resident search index."""
+        s = (ctypes.c_uint64 * 7)()
+        self._check(self.lib.pg_screen_search_index_shape(self._h, ctypes.addressof(s)))
+        return tuple(int(x) for x in s)
+
+    def screen_search_index_export(self):
+        """pg_screen_search_index_shape + _export: (shape, (kmer uint32[D], start uint64[D + 1], member uint32[E], slice_first
+        uint64[n_slices + 1], bin_slice uint32[4096])) of the resident search index.  Nothing resident changes."""
+        shape = self.screen_search_index_shape()
+        _, _, _, d, e, s, _ = shape
+        arrays = (np.zeros(d, dtype=np.uint32), np.zeros(d + 1, dtype=np.uint64), np.zeros(e, dtype=np.uint32), np.zeros(s + 1, dtype=np.uint64),
+                  np.zeros(4096, dtype=np.uint32))
+        self._check(self.lib.pg_screen_search_index_export(self._h, *(x.ctypes.data if x.size else None for x in arrays)))
+        return shape, arrays
+
+    def screen_search_index_import(self, shape, arrays, labels=None) -> np.ndarray:
+        """pg_screen_search_index_import: the arrays of an export (or of a file) become the resident search index after the device has
+        validated every invariant of a built index (pyani_amd.screen.check_search_index states them); returns the sizes uint32[n] the
+        device COMPUTED from the entries.  A refusal (PG_E_ARG) leaves an earlier index, its rectangle and this engine's record as
+        they were.  labels: as for screen_search_index (default: the positions)."""
+        from . import screen
+        shape = tuple(int(x) for x in shape)
+        if len(shape) != 7 or min(shape) < 0:
+            raise ValueError("the shape of a search index is (n, kmer, scale, D, E, n_slices, keys)")
+        n, kmer, scale, d, e, s, _ = shape
+        labels = screen.search_labels(list(range(n)), labels, "db")
+        kinds = (np.uint32, np.uint64, np.uint32, np.uint64, np.uint32)
+        arrays = tuple(np.ascontiguousarray(x, dtype=t).reshape(-1) for x, t in zip(arrays, kinds))
+        if tuple(len(x) for x in arrays) != (d, d + 1, e, s + 1, 4096):
+            raise ValueError(f"the arrays of a search index of shape {shape} have {d}, {d + 1}, {e}, {s + 1} and 4096 elements, not {[len(x) for x in arrays]}")
+        sizes = np.zeros(n if n <= (1 << 20) else 0, dtype=np.uint32)
+        c_shape = (ctypes.c_uint64 * 7)(*shape)
+        # (a failure leaves the old index resident, a refusal its rectangle too: nothing recorded here changes)
+        self._check(self.lib.pg_screen_search_index_import(self._h, ctypes.addressof(c_shape), *(x.ctypes.data if x.size else None for x in arrays),
+                                                           sizes.ctypes.data if sizes.size else None))
+        self._search = {"n": n, "kmer": kmer, "scale": scale, "sizes": sizes, "labels": labels} if n else None      # (n = 0 leaves no index)
+        self._search_q = 0
+        return sizes
+
+    def screen_search_index_save(self, path, lengths=None) -> int:
+        """The resident search index written to one file (pyani_amd.screen.write_search_index; DESIGN.md §16.7 has the layout) with the
+        labels and sizes this engine recorded; lengths: the genomes' lengths, uint64[n] (default zeros).  Returns the file's bytes."""
+        from . import screen
+        info = getattr(self, "_search", None)
+        if not info:
+            raise ValueError("no search index on this engine (call screen_search_index first)")
+        shape, arrays = self.screen_search_index_export()
+        return screen.write_search_index(path, shape, arrays, info["sizes"], info["labels"], lengths)
+
+    def screen_search_index_load(self, path):
+        """The search index of a file becomes the resident one: read (np.memmap), imported and validated on the device, and the sizes
+        the device computed compared with the stored ones — a mismatch is a ValueError and the index is released.  Returns (sizes,
+        labels, lengths).  This engine's record changes after success only."""
+        from . import screen
+        f = screen.read_search_index(path)
+        return self.screen_search_index_adopt(f, str(path))
+
+    def screen_search_index_adopt(self, f, path="the search index file"):
+        """screen_search_index_load behind the read: f = pyani_amd.screen.read_search_index(path), for a caller that looks at the header
+        before anything is uploaded."""
+        sizes = self.screen_search_index_import(f.shape, f.arrays, labels=f.labels)
+        if not np.array_equal(sizes, np.asarray(f.sizes, dtype=np.uint32)):
+            self.screen_search_index_release()
+            raise ValueError(f"{path}: the stored sizes of {int(np.count_nonzero(sizes != f.sizes))} genomes are not the entries the index holds for them")
+        return sizes, list(f.labels), np.array(f.lengths, dtype=np.uint64)
+
+    def screen_search_index_remove(self, which) -> None:
+        """pg_screen_search_index_remove: the columns `which` — positions (integers) or labels (strings) — leave the resident search
+        index without a rebuild: the state is the one screen_search_index over the list without them would leave,
+        the later columns move down.  An unknown label, and a label that two columns hold, are ValueErrors.  The counted rectangle
+        goes.  Removing every column releases the index.  This engine's record shrinks after success only."""
+        info = getattr(self, "_search", None)
+        which = list(which)
+        cols = []
+        for w in which:
+            if isinstance(w, str):
+                if not info:
+                    raise ValueError("no search index on this engine (call screen_search_index first)")
+                at = [i for i, x in enumerate(info["labels"]) if x == w]
+                if len(at) != 1:
+                    raise ValueError(f"the label {w!r} is held by {len(at)} columns of the search index" if at else f"no column of the search index has the label {w!r}")
+                cols.append(at[0])
+            elif isinstance(w, (bool, float)) or int(w) != w or not 0 <= int(w) < (1 << 32):
+                raise ValueError(f"a column to remove is a position or a label, not {w!r}")
+            else:
+                cols.append(int(w))
+        a = np.array(cols, dtype=np.uint32)
+        m = len(a)
+        self._check(self.lib.pg_screen_search_index_remove(self._h, a.ctypes.data if m else None, m))
+        if m:
+            keep = np.ones(info["n"], dtype=bool)
+            keep[a] = False
+            left = int(keep.sum())
+            self._search = dict(info, n=left, sizes=info["sizes"][keep], labels=[x for x, k in zip(info["labels"], keep) if k]) if left else None
+            self._search_q = 0
+
+    def screen_search_remove_last(self) -> dict:
+        """pg_screen_search_remove_last: counts and stage milliseconds of the latest accepted screen_search_index_remove (zeros after a
+        build, a load or a release)."""
+        c = (ctypes.c_uint64 * 4)()
+        ms = (ctypes.c_double * 2)()
+        self._check(self.lib.pg_screen_search_remove_last(self._h, ctypes.addressof(c), ctypes.addressof(ms)))
+        return {"genomes": int(c[0]), "entries": int(c[1]), "kmers": int(c[2]), "removes": int(c[3]), "mark_ms": float(ms[0]), "compact_ms": float(ms[1])}
+
     def screen_search_count(self, query_ids) -> np.ndarray:
         """pg_screen_search_count: the rectangle of the resident genomes `query_ids` (at most the band's rows: screen_set_band) against the
         search index stays on the device; returns the queries' sizes uint32[q]."""
@@ -640,7 +746,9 @@ class Engine:
         return out
 
     def screen_search_last(self) -> dict:
-        """pg_screen_search_last: counts and stage milliseconds of the resident search index, the latest count and the latest selection."""
+        """pg_screen_search_last: counts and stage milliseconds of the resident search index, the latest count and the latest selection.
+        For an index that was loaded (screen_search_index_import) index_sort_group_ms holds the validation's milliseconds and
+        index_scan_ms is 0; `keys` is a historical scan count that a remove does not change."""
         c = (ctypes.c_uint64 * 10)()
         ms = (ctypes.c_double * 7)()
         self._check(self.lib.pg_screen_search_last(self._h, ctypes.addressof(c), ctypes.addressof(ms)))

@@ -372,6 +372,16 @@ class MultiEngine:
             e.screen_search_index_release()
         self._search, self._search_ranges = None, []
 
+    # the index on disk and the remove are a single Engine's: here the collection is dealt in ranges of columns, one index each
+    def screen_search_index_save(self, path, lengths=None):
+        raise ValueError("a search index dealt over several devices cannot be saved: build it on a single Engine")
+
+    def screen_search_index_load(self, path):
+        raise ValueError("a search index file is loaded on a single Engine, not dealt over several devices")
+
+    def screen_search_index_remove(self, which):
+        raise ValueError("a search index dealt over several devices cannot be shrunk: remove on a single Engine")
+
     def screen_components(self, a, b, shared=None, n: int = 0):
         """Engine.screen_components on the first engine (a list call has nothing to divide)."""
         return self.engines[0].screen_components(a, b, shared, n=n)

@@ -552,6 +552,237 @@ def merge_search_index(kmer, start, member, new_kmer, new_member):
     return kmer_new, start_new, member_new, int(absent.sum()), int(found.sum())
 
 
+def remove_from_search_index(kmer, start, member, n, columns):
+    """THE STATEMENT of the search index's shrinking on arrays, for an index of ONE slice: the index of n genomes (kmer
+    uint32[D] ascending, start int64[D + 1], member uint32[E], ascending inside a k-mer) without the columns `columns` (each < n, none
+    twice) -> (kmer', start', member', removed entries, removed k-mers).  A surviving column c becomes c - (removed columns below c);
+    the surviving entries keep their order, a k-mer whose last holder went is dropped — nothing is sorted."""
+    kmer, start, member = np.asarray(kmer, dtype=np.uint32), np.asarray(start, dtype=np.int64), np.asarray(member, dtype=np.uint32)
+    columns = np.asarray(columns, dtype=np.int64).reshape(-1)
+    n = int(n)
+    if len(columns) and (columns.min() < 0 or columns.max() >= n):
+        raise ValueError(f"a column to remove is not in an index of {n} genomes")
+    if len(np.unique(columns)) != len(columns):
+        raise ValueError("a column to remove is given twice")
+    keep = np.ones(n, dtype=bool)
+    keep[columns] = False
+    new_of = np.cumsum(keep) - keep                                      # the kept columns below each column
+    alive = keep[member] if len(member) else np.zeros(0, dtype=bool)
+    pos = np.concatenate([[0], np.cumsum(alive)]).astype(np.int64)       # the entries' new positions; pos[E] = E'
+    count = pos[start[1:]] - pos[start[:-1]]                             # the holders each k-mer keeps
+    kept = count > 0
+    start_new = np.concatenate([pos[start[:-1]][kept], pos[-1:]]).astype(np.int64)
+    member_new = new_of[member[alive]].astype(np.uint32)
+    return kmer[kept], start_new, member_new, int(len(member) - len(member_new)), int(len(kmer) - int(kept.sum()))
+
+
+# ---- the search index on disk (DESIGN.md §16.7) -------------------------------------------------------------------------------------------
+N_BINS = 4096                       # pgscr::N_BINS: the slice bins of a sampled k-mer
+SEARCH_NO_SLICE = 0xFFFFFFFF        # bin_slice of a bin that no slice covers
+
+
+def mix32(h) -> np.ndarray:
+    """pgs::mix32 (pg_sketch_core.h) on uint32 arrays: murmur3's finaliser."""
+    h = np.array(h, dtype=np.uint32, copy=True).reshape(-1)
+    with np.errstate(over="ignore"):
+        h ^= h >> np.uint32(16)
+        h *= np.uint32(0x85EBCA6B)
+        h ^= h >> np.uint32(13)
+        h *= np.uint32(0xC2B2AE35)
+        h ^= h >> np.uint32(16)
+    return h
+
+
+def log2_scale(scale: int) -> int:
+    return int(scale).bit_length() - 1
+
+
+def kmer_sampled(canon, scale: int) -> np.ndarray:
+    """pgs::sampled: the FracMinHash rule, mix32(canon) & (scale - 1) == 0."""
+    return (mix32(canon) & np.uint32(int(scale) - 1)) == 0
+
+
+def kmer_bin(canon, scale: int) -> np.ndarray:
+    """pgscr::bin_of (pg_screen_core.h): (mix32(canon) >> log2(scale)) & 4095, the hash bits above the ones the sampling reads."""
+    return (mix32(canon) >> np.uint32(log2_scale(scale))) & np.uint32(N_BINS - 1)
+
+
+SEARCH_INDEX_INVARIANTS = {
+    "shape": "the shape is out of range (n <= 2^20, 8 <= kmer <= 16, scale a power of two <= 65536, E >= D, slices <= 4096, n = 0 with D = E = 0)",
+    "lengths": "an array has not the length its shape gives",
+    "slice_first": "slice_first does not begin at 0, ascend and end at D",
+    "bin_slice": "a bin names a slice that is not there",
+    "start0": "start[0] is not 0",
+    "start_end": "start[D] is not E",
+    "start_order": "start is not strictly increasing",
+    "kmer_range": "k-mers are not below 4^kmer",
+    "kmer_sampled": "k-mers are not sampled under the scale",
+    "kmer_slice": "k-mers stand outside the slice of their bin",
+    "kmer_order": "k-mers are not strictly ascending inside a slice",
+    "member_range": "members are not below n",
+    "member_order": "members are not strictly ascending inside a k-mer",
+}
+
+
+def check_search_index(shape, kmer, start, member, slice_first, bin_slice) -> List[str]:
+    """THE STATEMENT of the import's validation (pg_screen_search_index_import): the texts (values of SEARCH_INDEX_INVARIANTS, each followed
+    by its count where it has one) of EVERY invariant of a built search index that the arrays violate; [] for a sound index.  shape = (n,
+    kmer, scale, D, E, n_slices, keys).  As on the device nothing is indexed by a value that was not checked first: a violated host check
+    ends the list, and the entries are walked only when the starts are sound."""
+    inv = SEARCH_INDEX_INVARIANTS
+    n, k, scale, d, e, s = (int(x) for x in list(shape)[:6])
+    kmer, member, bin_slice = (np.asarray(x, dtype=np.uint32).reshape(-1) for x in (kmer, member, bin_slice))
+    start, slice_first = (np.asarray(x, dtype=np.uint64).reshape(-1) for x in (start, slice_first))
+    if n > INDEX_MAX_GENOMES or not 8 <= k <= 16 or not (1 <= scale <= 65536 and scale & (scale - 1) == 0) or e < d or s > N_BINS or (n == 0 and (d or e)):
+        return [inv["shape"]]
+    if (len(kmer), len(start), len(member), len(slice_first), len(bin_slice)) != (d, d + 1, e, s + 1, N_BINS):
+        return [inv["lengths"]]
+    if n == 0:
+        return []
+    host = []
+    if slice_first[0] != 0 or (np.diff(slice_first.astype(np.int64)) < 0).any() or slice_first[s] != d:
+        host.append(inv["slice_first"])
+    if ((bin_slice >= s) & (bin_slice != SEARCH_NO_SLICE)).any():
+        host.append(inv["bin_slice"])
+    if host:
+        return host
+    out = []
+
+    def count(name, bad):
+        c = int(np.count_nonzero(bad))
+        if c:
+            out.append(f"{inv[name]} ({c} of them)")
+
+    count("start0", start[:1] != 0)
+    count("start_end", start[d:] != e)
+    order = ~(start[:-1] < start[1:])
+    count("start_order", order)
+    count("kmer_range", kmer.astype(np.uint64) >= (np.uint64(1) << np.uint64(2 * k)))
+    count("kmer_sampled", ~kmer_sampled(kmer, scale))
+    g = np.arange(d, dtype=np.uint64)
+    of = np.searchsorted(slice_first[:s], g, side="right").astype(np.int64) - 1      # the last slice that begins at or before g
+    count("kmer_slice", bin_slice[kmer_bin(kmer, scale)].astype(np.int64) != of)
+    if d:
+        first_of_slice = g == slice_first[of]
+        count("kmer_order", ~first_of_slice[1:] & (kmer[:-1] >= kmer[1:]))
+    if start[0] == 0 and start[d] == e and not order.any() and e:
+        count("member_range", member >= n)
+        first_of_kmer = np.zeros(e, dtype=bool)
+        first_of_kmer[start[:-1].astype(np.int64)] = True
+        count("member_order", ~first_of_kmer[1:] & (member[:-1] >= member[1:]))
+    return out
+
+
+def search_index_sizes(member, n: int) -> np.ndarray:
+    """sizes uint32[n] of an index's genomes: the entries per column, as the import computes them."""
+    return np.bincount(np.asarray(member, dtype=np.int64), minlength=int(n)).astype(np.uint32)
+
+
+SEARCH_FILE_MAGIC = b"PYANISX\0"
+SEARCH_FILE_VERSION = 1
+SEARCH_FILE_PROBE_INPUT = 0x9E3779B9          # the probe word of the header is mix32 of this: another hash refuses the file
+SEARCH_FILE_ALIGN = 64
+# the header: magic 8s | version, kmer, scale, n, N_BINS, n_slices uint32 | probe uint32, reserved uint32 | D, E, keys, labels' bytes uint64
+_SEARCH_HEADER = np.dtype([("magic", "S8"), ("version", "<u4"), ("kmer", "<u4"), ("scale", "<u4"), ("n", "<u4"), ("n_bins", "<u4"), ("n_slices", "<u4"),
+                           ("probe", "<u4"), ("reserved", "<u4"), ("D", "<u8"), ("E", "<u8"), ("keys", "<u8"), ("label_bytes", "<u8")])
+
+
+def search_file_probe() -> int:
+    return int(mix32(np.array([SEARCH_FILE_PROBE_INPUT], dtype=np.uint32))[0])
+
+
+def _search_file_layout(n, d, e, s, label_bytes):
+    """[(name, dtype, count, offset)] of the file's arrays, each at the next multiple of 64 bytes behind the one before, and the file's size."""
+    at = _SEARCH_HEADER.itemsize
+    out = []
+    for name, dtype, count in (("sizes", "<u4", n), ("lengths", "<u8", n), ("kmer", "<u4", d), ("start", "<u8", d + 1), ("member", "<u4", e),
+                               ("slice_first", "<u8", s + 1), ("bin_slice", "<u4", N_BINS), ("labels", "u1", label_bytes)):
+        at = -(-at // SEARCH_FILE_ALIGN) * SEARCH_FILE_ALIGN
+        out.append((name, np.dtype(dtype), int(count), at))
+        at += int(count) * np.dtype(dtype).itemsize
+    return out, at
+
+
+def write_search_index(path, shape, arrays, sizes, labels, lengths) -> int:
+    """One little-endian file of a search index (DESIGN.md §16.7 has the layout): shape = (n, kmer, scale, D, E, n_slices, keys), arrays =
+    (kmer, start, member, slice_first, bin_slice) as Engine.screen_search_index_export gives them, sizes uint32[n], the n labels (a label
+    with a newline is a ValueError), lengths uint64[n] (the genomes' lengths; None: zeros).  Written to path + ".tmp" and renamed on
+    success: a failure part-way leaves no file at `path` and none at path + ".tmp".  Returns the file's bytes."""
+    import os
+    n, k, scale, d, e, s, keys = (int(x) for x in shape)
+    labels = [str(x) for x in labels]
+    if any("\n" in x for x in labels):
+        raise ValueError("a label with a newline cannot be stored in a search index file")
+    lengths = np.zeros(n, dtype=np.uint64) if lengths is None else np.asarray(lengths, dtype=np.uint64).reshape(-1)
+    blob = "\n".join(labels).encode("utf-8")
+    given = dict(zip(("kmer", "start", "member", "slice_first", "bin_slice"), arrays), sizes=sizes, lengths=lengths, labels=np.frombuffer(blob, dtype=np.uint8))
+    layout, total = _search_file_layout(n, d, e, s, len(blob))
+    if len(labels) != n:
+        raise ValueError(f"{len(labels)} labels for a search index of {n} genomes")
+    for name, dtype, count, _ in layout:
+        if len(given[name]) != count:
+            raise ValueError(f"the array {name} has {len(given[name])} elements where the shape gives {count}")
+    head = np.zeros(1, dtype=_SEARCH_HEADER)
+    head["magic"], head["version"], head["kmer"], head["scale"], head["n"], head["n_bins"], head["n_slices"] = SEARCH_FILE_MAGIC, SEARCH_FILE_VERSION, k, scale, n, N_BINS, s
+    head["probe"], head["D"], head["E"], head["keys"], head["label_bytes"] = search_file_probe(), d, e, keys, len(blob)
+    tmp = str(path) + ".tmp"
+    try:
+        with open(tmp, "wb") as f:
+            f.write(head.tobytes())
+            for name, dtype, count, at in layout:
+                f.write(b"\0" * (at - f.tell()))
+                np.ascontiguousarray(given[name], dtype=dtype).tofile(f)
+            if f.tell() != total:
+                raise OSError(f"wrote {f.tell()} bytes of a search index file of {total}")
+        os.replace(tmp, str(path))
+    except BaseException:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        raise
+    return total
+
+
+class SearchIndexFile(NamedTuple):
+    """What read_search_index gives: the arrays are read-only np.memmap views of the file (a 12 GB index is not held twice on the host)."""
+    shape: Tuple[int, int, int, int, int, int, int]      # n, kmer, scale, D, E, n_slices, keys
+    arrays: Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]      # kmer, start, member, slice_first, bin_slice
+    sizes: np.ndarray           # uint32[n], as STORED: the import computes them again and the two are compared
+    labels: List[str]
+    lengths: np.ndarray         # uint64[n]
+
+
+def read_search_index(path) -> SearchIndexFile:
+    """The file write_search_index wrote, through np.memmap.  ValueError, naming what is wrong: a wrong magic, version, N_BINS or probe
+    word, a file shorter or longer than its header implies, a label count other than n.  The CONTENT of the arrays is not judged here:
+    the import validates it on the device (check_search_index states how)."""
+    import os
+    path = str(path)
+    size = os.path.getsize(path)
+    if size < _SEARCH_HEADER.itemsize:
+        raise ValueError(f"{path}: {size} bytes are too few for the header of a search index file")
+    head = np.fromfile(path, dtype=_SEARCH_HEADER, count=1)[0]
+    if bytes(head["magic"]).ljust(8, b"\0") != SEARCH_FILE_MAGIC:
+        raise ValueError(f"{path}: not a search index file (wrong magic)")
+    if int(head["version"]) != SEARCH_FILE_VERSION:
+        raise ValueError(f"{path}: search index file of version {int(head['version'])}, not {SEARCH_FILE_VERSION}")
+    if int(head["n_bins"]) != N_BINS:
+        raise ValueError(f"{path}: search index file with {int(head['n_bins'])} slice bins (N_BINS), not {N_BINS}")
+    if int(head["probe"]) != search_file_probe():
+        raise ValueError(f"{path}: the probe word of the file is not this build's hash of its constant: the file's k-mers were sampled by another hash")
+    n, k, scale, s = (int(head[x]) for x in ("n", "kmer", "scale", "n_slices"))
+    d, e, keys, label_bytes = (int(head[x]) for x in ("D", "E", "keys", "label_bytes"))
+    layout, total = _search_file_layout(n, d, e, s, label_bytes)
+    if size != total:
+        raise ValueError(f"{path}: {size} bytes where the header implies {total}: the file is {'shorter' if size < total else 'longer'} than its header says")
+    got = {name: (np.memmap(path, dtype=dtype, mode="r", offset=at, shape=(count,)) if count else np.zeros(0, dtype=dtype)) for name, dtype, count, at in layout}
+    blob = bytes(got["labels"])
+    labels = blob.decode("utf-8").split("\n") if n else []
+    if len(labels) != n or (n == 0 and blob):
+        raise ValueError(f"{path}: {len(labels) if n else 1} labels for {n} genomes")
+    return SearchIndexFile((n, k, scale, d, e, s, keys), (got["kmer"], got["start"], got["member"], got["slice_first"], got["bin_slice"]), got["sizes"], labels,
+                           got["lengths"])
+
+
 class SearchHits(NamedTuple):
     """The cells a search kept (Engine.screen_search), row-major: a = the position in `query_labels`, b = the position in `db_labels`,
     shared = |S(query a) & S(db b)|.  An ESTIMATE, as every frame of the screen."""

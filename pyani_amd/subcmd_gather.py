@@ -15,7 +15,9 @@ before the queries are loaded.  With exact="anim" ONE anim_pairs call aligns (db
 rows only, and each member's identity and coverage (of the member) are added to the rows' table.  The screen's own numbers stay an
 ESTIMATE with its own files: `<outdir>/screen_output/gather_rows.tab` (one line per recorded genome) and `gather_summary.tab` (one per
 query).  A single engine only.  OUT OF SCOPE: a MultiEngine gather (the winner's k-mers live on one device: every round would need an
-exchange), abundance weighting, an index on disk, ANIb as exact=.
+exchange), abundance weighting, exact= from an index file, ANIb as exact=.
+
+index=PATH: a saved search index takes the place of reading `db_dir` (None then), as for run_screen_search.
 """
 from pathlib import Path
 from typing import Dict, List, NamedTuple, Optional, Tuple
@@ -26,7 +28,7 @@ import pandas as pd
 from . import anim, files, screen as screen_mod
 from .engine import Engine, default_engine
 from .subcmd_screen import OUTDIR
-from .subcmd_search import _stems, check_db_batch, load_db
+from .subcmd_search import _stems, check_db_batch, check_index, load_db, load_index
 
 EXACT = (None, "anim")
 
@@ -48,13 +50,15 @@ def gather_tab_path(outdir, name: str) -> Path:
 def run_screen_gather(db_dir, query_dir, outdir=None, min_unique: Optional[int] = None, kmer: int = screen_mod.DEFAULT_KMER,
                       scale: int = screen_mod.DEFAULT_SCALE, min_fraction: float = 0.0, max_ranks: int = screen_mod.GATHER_MAX_RANKS,
                       exact: Optional[str] = None, write_output: bool = False, engine: Optional[Engine] = None,
-                      devices: Optional[List[int]] = None, workers: Optional[int] = None, db_batch: Optional[int] = None) -> GatherRun:
+                      devices: Optional[List[int]] = None, workers: Optional[int] = None, db_batch: Optional[int] = None,
+                      index=None) -> GatherRun:
     """Every FASTA file of `query_dir` decomposed into the genomes of `db_dir`.  min_unique is required (there is no default threshold:
     about 50 sampled 16-mers are shared by chance between two unrelated 5 Mb genomes at scale 256); outdir is needed for write_output
     only.  devices / workers are refused: a gather runs on a single engine.  An engine holds ONE search index: one already resident on a
     caller's `engine` is replaced by the one of `db_dir`, and the engine holds none when this returns (released on errors too).
     db_batch: the collection goes through the store that many files at a time, each batch after the first ADDED to the resident index
-    (run_screen_search's text); the result does not change."""
+    (run_screen_search's text); the result does not change.  index: the path of a saved search index in place of
+    `db_dir` (None then): labels, lengths and every table column come from the file; without exact= and db_batch=."""
     if min_unique is None:
         raise ValueError("run_screen_gather needs min_unique= (there is no default threshold)")
     if write_output and outdir is None:
@@ -64,19 +68,23 @@ def run_screen_gather(db_dir, query_dir, outdir=None, min_unique: Optional[int] 
     if devices is not None or workers:
         raise ValueError("a gather runs on a single engine: devices= / workers= are not supported (the winner's k-mers live on one device)")
     options = screen_mod.check_gather_options(screen_mod.GatherOptions(kmer, scale, min_unique, min_fraction, max_ranks))
+    index = check_index(index, db_dir, exact, db_batch, engine, None, None)
     db_batch = check_db_batch(db_batch, exact, engine, None, None)
-    return _run(db_dir, query_dir, outdir, options, exact, write_output, engine or default_engine(), db_batch)
+    return _run(db_dir, query_dir, outdir, options, exact, write_output, engine or default_engine(), db_batch, index)
 
 
-def _run(db_dir, query_dir, outdir, options, exact, write_output, eng, db_batch=None) -> GatherRun:
-    db_paths, q_paths = files.get_fasta_paths(Path(db_dir)), files.get_fasta_paths(Path(query_dir))
+def _run(db_dir, query_dir, outdir, options, exact, write_output, eng, db_batch=None, index=None) -> GatherRun:
+    db_paths, q_paths = files.get_fasta_paths(Path(db_dir)) if index is None else [], files.get_fasta_paths(Path(query_dir))
     db_stems, q_stems = _stems(db_paths, "db"), _stems(q_paths, "query")
     scratch_store = eng.genome_count() == 0
     db_len: Dict[str, int] = {}
     q_len: Dict[str, int] = {}
     results = None
     try:
-        db_ids = load_db(eng, db_paths, db_stems, options, db_batch, db_len)
+        if index is None:
+            db_ids = load_db(eng, db_paths, db_stems, options, db_batch, db_len)
+        else:
+            db_ids, db_stems = load_index(eng, index, options, db_len)
         if exact is None and scratch_store:      # the index names the collection by position only: its sequences make room for the queries
             eng.clear_genomes()
         q_ids = np.zeros(len(q_paths), dtype=np.int64)

@@ -8,12 +8,16 @@ before the queries are loaded (the index survives pg_clear_genomes).  With exact
 both directions — built from the SearchHits arrays, the query as nucmer's reference for the forward direction, as in run_anim — and
 the identity and coverage of both directions are added to the hits' table.  The screen's own numbers stay an ESTIMATE with its own
 files: `<outdir>/screen_output/search_hits.tab` (every kept cell) and `search_best.tab` (per query its `top` hits, default 1).
-OUT OF SCOPE: ANIb as exact=, saving an index, recovery, collective runs.  Single-process: one engine, or several GPUs of this node
+OUT OF SCOPE: ANIb as exact=, exact= from an index file, recovery, collective runs.  Single-process: one engine, or several GPUs of this node
 (devices / workers: the collection is dealt over them, MultiEngine.screen_search_index).
 
 db_batch=N: the collection is loaded N files at a time — the first batch is indexed, every later one ADDED to the
 resident index (Engine.screen_search_index_add), the store cleared after each — so a collection larger than the genome arena can be
 searched.  Only for a run that owns the store, on a single Engine, without exact= (the sequences are gone).  The result is the same.
+
+index=PATH: a search index saved by subcmd_searchdb.run_screen_index_build (or Engine.screen_search_index_save) takes
+the place of reading `db_dir`, which must then be None: the db labels, lengths and every table column come from the file, and not a
+FASTA file of the collection is read.  On a single Engine, without exact= (the file holds no sequence) and without db_batch=.
 """
 from pathlib import Path
 from typing import Dict, List, NamedTuple, Optional, Tuple
@@ -65,6 +69,36 @@ def check_db_batch(db_batch, exact, engine, devices, workers) -> Optional[int]:
     return int(db_batch)
 
 
+def check_index(index, db_dir, exact, db_batch, engine, devices, workers) -> Optional[str]:
+    """The index= of run_screen_search and run_screen_gather, checked before a file is read or an engine is made: None (then db_dir is
+    needed), or the path of a saved search index in place of db_dir, on a single Engine, without exact= and db_batch=."""
+    if index is None:
+        if db_dir is None:
+            raise ValueError("a collection is needed: db_dir=, or index= with a saved search index")
+        return None
+    if db_dir is not None:
+        raise ValueError("index= takes the place of db_dir: give one of them (db_dir=None with index=)")
+    if exact is not None:
+        raise ValueError("index= holds no sequence of the collection: exact= needs db_dir")
+    if db_batch is not None:
+        raise ValueError("index= reads no file of a collection: db_batch= goes with db_dir")
+    if devices is not None or workers or (engine is not None and not isinstance(engine, Engine)):
+        raise ValueError("index= runs on a single Engine: a saved search index is not dealt over several devices")
+    return str(index)
+
+
+def load_index(eng, index, options, db_len):
+    """The saved search index `index` made resident on `eng` in place of load_db: (positions, db labels); db_len is filled from the file.
+    A file of another kmer or scale than the options' is a ValueError after its header is read and before anything is uploaded."""
+    f = screen_mod.read_search_index(index)
+    if (f.shape[1], f.shape[2]) != (options.kmer, options.scale):
+        raise ValueError(f"{index}: the search index was built with kmer {f.shape[1]} and scale {f.shape[2]}, not {options.kmer} and {options.scale}")
+    _, labels, lengths = eng.screen_search_index_adopt(f, index)
+    for stem, length in zip(labels, lengths.tolist()):
+        db_len[stem] = int(length)
+    return np.arange(len(labels), dtype=np.int64), labels
+
+
 def load_db(eng, db_paths, db_stems, options, db_batch, db_len) -> np.ndarray:
     """The collection's files loaded and the search index built: in one piece (returns the genomes' ids), or db_batch files at a time
     through a store cleared after every batch (the ids are gone with the sequences: positions are returned)."""
@@ -95,12 +129,14 @@ def load_db(eng, db_paths, db_stems, options, db_batch, db_len) -> np.ndarray:
 def run_screen_search(db_dir, query_dir, outdir=None, min_identity: Optional[float] = None, kmer: int = screen_mod.DEFAULT_KMER,
                       scale: int = screen_mod.DEFAULT_SCALE, min_shared: int = screen_mod.DEFAULT_MIN_SHARED, top: Optional[int] = None,
                       exact: Optional[str] = None, write_output: bool = False, engine: Optional[Engine] = None,
-                      devices: Optional[List[int]] = None, workers: Optional[int] = None, db_batch: Optional[int] = None) -> SearchRun:
+                      devices: Optional[List[int]] = None, workers: Optional[int] = None, db_batch: Optional[int] = None,
+                      index=None) -> SearchRun:
     """Every FASTA file of `query_dir` placed against the collection of `db_dir`.  min_identity is required (there is no default
     threshold); outdir is needed for write_output only; devices / workers: several GPUs of this node, ignored when `engine` is given.
     An engine holds ONE search index: a search index already resident on a caller's `engine` is replaced by the one of `db_dir`, and
     the engine holds none when this returns (released on errors too).  db_batch: the collection goes through the store that many files
-    at a time (the module's text); the result does not change."""
+    at a time (the module's text); the result does not change.  index: the path of a saved search index in place of `db_dir` (None
+    then; the module's text)."""
     if min_identity is None:
         raise ValueError("run_screen_search needs min_identity= (there is no default threshold)")
     if write_output and outdir is None:
@@ -110,6 +146,7 @@ def run_screen_search(db_dir, query_dir, outdir=None, min_identity: Optional[flo
     if top is not None and (isinstance(top, bool) or int(top) != top or int(top) < 1):
         raise ValueError(f"top must be an integer >= 1, not {top!r}")
     options = screen_mod.check_options(screen_mod.ScreenOptions(min_identity, kmer, scale, min_shared))
+    index = check_index(index, db_dir, exact, db_batch, engine, devices, workers)
     db_batch = check_db_batch(db_batch, exact, engine, devices, workers)
     own = None
     if engine is None and (devices is not None or workers):
@@ -117,7 +154,7 @@ def run_screen_search(db_dir, query_dir, outdir=None, min_identity: Optional[flo
         engine = multi.engine_for(devices, workers)
         own = engine if isinstance(engine, multi.MultiEngine) else None
     try:
-        return _run(db_dir, query_dir, outdir, options, int(top or 1), exact, write_output, engine or default_engine(), db_batch)
+        return _run(db_dir, query_dir, outdir, options, int(top or 1), exact, write_output, engine or default_engine(), db_batch, index)
     finally:
         if own is not None:
             own.close()
@@ -127,15 +164,18 @@ def _coverage(aln: int, length: int) -> float:
     return aln / length if length else float("nan")
 
 
-def _run(db_dir, query_dir, outdir, options, top, exact, write_output, eng, db_batch=None) -> SearchRun:
-    db_paths, q_paths = files.get_fasta_paths(Path(db_dir)), files.get_fasta_paths(Path(query_dir))
+def _run(db_dir, query_dir, outdir, options, top, exact, write_output, eng, db_batch=None, index=None) -> SearchRun:
+    db_paths, q_paths = files.get_fasta_paths(Path(db_dir)) if index is None else [], files.get_fasta_paths(Path(query_dir))
     db_stems, q_stems = _stems(db_paths, "db"), _stems(q_paths, "query")
     scratch_store = eng.genome_count() == 0
     db_len: Dict[str, int] = {}
     q_len: Dict[str, int] = {}
     results = None
     try:
-        db_ids = load_db(eng, db_paths, db_stems, options, db_batch, db_len)
+        if index is None:
+            db_ids = load_db(eng, db_paths, db_stems, options, db_batch, db_len)
+        else:
+            db_ids, db_stems = load_index(eng, index, options, db_len)
         if exact is None and scratch_store:      # the index names the collection by position only: its sequences make room for the queries
             eng.clear_genomes()
         q_ids = np.zeros(len(q_paths), dtype=np.int64)
