@@ -619,6 +619,34 @@ int pg_screen_gather_fetch(pg_ctx* ctx, uint32_t* out);
 int pg_screen_gather_matched(pg_ctx* ctx, uint32_t* matched_out);
 int pg_screen_gather_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
 
+/* ---- screen, the gather's abundances: per-row statistics of the k-mers' multiplicities.  a(i, x) = the number of
+ * windows of query i, over all its records, that the scan samples and whose canonical k-mer is x (uint32).  W[i] = the sum of a(i, x)
+ * over x in S(query i); MW[i] = the same sum over the matched entries of query i.  Abundance does not move a winner: the rounds, the
+ * rows and their order are pg_screen_gather's.  The matched entry (i, x) belongs to the row of the SMALLEST rank among the holders of x
+ * that won in query i, and to no row if none of them won: row (i, t) owns exactly the `unique` k-mers it claimed.  Over the sorted
+ * multiplicities a_0 <= ... <= a_(m - 1) of a row's k-mers (m = unique): sum, sumsq = the sum of squares as two uint64 words (lo, hi),
+ * min, max, and median2 = a_((m - 1) / 2) + a_(m / 2) (integer division): twice the median, exact for both parities.  Integers only.
+ * pg_screen_gather_count_abund IS pg_screen_gather_count — the same limits, refusals, rectangle, sizes, entries and statistics; select,
+ * read, fetch, pg_screen_gather and pg_screen_gather_matched work on it unchanged — and also keeps a(i, x) of every entry (4 bytes each)
+ * and copies W out: weight_out, q uint64 (may be NULL when q = 0).
+ * pg_screen_gather_abund runs the pass over the latest gather of such a count; *n_rows_out = the gather's rows.  PG_E_ARG, with any
+ * earlier result still readable: no resident search index; a latest count that kept no abundances; no pg_screen_gather since that
+ * count.  PG_E_NOMEM (the message names the size) when the pass's q x n uint32 rank table does not fit; PG_E_INTERNAL when one of the
+ * pass's own checks fails; either leaves the earlier results readable.  q = 0 or no rows: 0 rows.  Every pg_screen_gather drops the
+ * statistics of the gather before it: run the pass again after it.
+ * pg_screen_gather_abund_read copies the statistics out, in the rows' order: sum_out uint64[r], sumsq_out uint64[2 r] (row j: words 2 j
+ * = lo, 2 j + 1 = hi), median2_out uint64[r], min_out, max_out uint32[r]; the arrays may be NULL when there is no row.  PG_E_ARG
+ * without a pass.  pg_screen_gather_abund_matched copies MW out (q uint64; PG_E_ARG without such a count).
+ * pg_screen_gather_abund_last: counts_out[4] = of the latest pass: entries that belong to a row, entries that belong to none, holders
+ * walked, bytes of the rank table.  ms_out[4] = the weights of the latest abundance count (its extra stage beside the expansion) | of the
+ * latest pass: rank table + attribute, sort, row statistics.  All 0 without either.
+ * The state goes and stays as the gather's does. */
+int pg_screen_gather_count_abund(pg_ctx* ctx, const int32_t* query_ids, uint32_t q, uint32_t* sizes_out, uint64_t* weight_out);
+int pg_screen_gather_abund(pg_ctx* ctx, uint64_t* n_rows_out);
+int pg_screen_gather_abund_read(pg_ctx* ctx, uint64_t* sum_out, uint64_t* sumsq_out, uint64_t* median2_out, uint32_t* min_out, uint32_t* max_out);
+int pg_screen_gather_abund_matched(pg_ctx* ctx, uint64_t* matched_weight_out);
+int pg_screen_gather_abund_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
+
 /* ---- classify: clique sweep over identity thresholds ------------------------------------------------------------------
  * The compute of `pyani classify`.  These calls read caller matrices only: they touch no genome, seed list or ANIm worker slot, so
  * they need no interlock with the pg_anim_pairs_enqueue / _fetch lanes and may run while enqueued ANIm calls are in flight (own

@@ -130,6 +130,11 @@ SIGNATURES = {
     "pg_screen_gather_fetch": (_int, [_vp, _vp]),
     "pg_screen_gather_matched": (_int, [_vp, _vp]),
     "pg_screen_gather_last": (_int, [_vp, _vp, _vp]),
+    "pg_screen_gather_count_abund": (_int, [_vp, _vp, _u32, _vp, _vp]),
+    "pg_screen_gather_abund": (_int, [_vp, _P(_u64)]),
+    "pg_screen_gather_abund_read": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "pg_screen_gather_abund_matched": (_int, [_vp, _vp]),
+    "pg_screen_gather_abund_last": (_int, [_vp, _vp, _vp]),
     "pg_classify_edges": (_int, [_vp, _vp, _vp, _u32, ctypes.c_double, ctypes.c_double, _P(_u64), _P(_u32)]),
     "pg_classify_edge_identities": (_int, [_vp, _vp, _u64]),
     "pg_classify_sweep": (_int, [_vp, _vp, _u64, _vp, _vp, _vp]),

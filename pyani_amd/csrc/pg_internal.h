@@ -82,6 +82,11 @@ struct PgScreenGatherStats {      // pg_screen_gather_last: the latest pg_screen
   double expand_ms = 0.0, argmax_ms = 0.0, claim_ms = 0.0;      // argmax_ms: arg-max + decide
 };
 
+struct PgScreenGatherAbundStats {      // pg_screen_gather_abund_last: the latest pg_screen_gather_count_abund (weight) and pg_screen_gather_abund (the rest)
+  uint64_t attributed = 0, unattributed = 0, walked = 0, rank_bytes = 0;      // entries that belong to a row | to none; holders walked; bytes of the rank table
+  double weight_ms = 0.0, attribute_ms = 0.0, sort_ms = 0.0, stats_ms = 0.0;
+};
+
 struct pg_ctx {
   ~pg_ctx();   // destroys the streams (pg_api.cpp); the buffers below free themselves
   int device = 0;
@@ -151,6 +156,7 @@ struct pg_ctx {
   PgScreenComponentsStats screen_components_stats;      // pg_screen_components_last: the resident components' call
   void* screen_search_state = nullptr;          // resident search index of pg_screen_search_index and the latest rectangle counted against it (pg_screen.hip); independent of the three above and of the genome store
   PgScreenGatherStats screen_gather_stats;      // pg_screen_gather_last
+  PgScreenGatherAbundStats screen_gather_abund_stats;      // pg_screen_gather_abund_last
   PgScreenSearchAddStats screen_search_add_stats;      // pg_screen_search_add_last
   PgScreenSearchRemoveStats screen_search_remove_stats;      // pg_screen_search_remove_last
   PgScreenSearchStats screen_search_stats;      // pg_screen_search_last: the resident search index, the latest count and selection over it

@@ -77,6 +77,12 @@
 //   G3 gather_claim_kernel  a wave per 64 entries: the winner looked up among the k-mer's holders (binary search), the claiming lanes
 //                           balloted, the whole wave walks each claimed k-mer's holders with uint32 atomic decrements along the row
 //
+// pgscr_abund.inc — the gather's ABUNDANCES: pg_screen_gather_count_abund is the gather's count over a front half that
+// run-length encodes the sorted keys (every entry keeps how many times its query holds the k-mer); pg_screen_gather_abund follows a
+// pg_screen_gather and gives every recorded row the statistics of those multiplicities; W1 ... W4 stand there:
+//   W2 abund_attribute_kernel a wave per 64 entries: the whole wave walks each live entry's holders for the smallest rank that won
+//   W4 abund_stats_kernel     a workgroup per 4096 sorted keys of a row: integer sums by atomics, the squares' carry from the old value
+//
 // pgscr_components.inc — the COMPONENTS: which genomes belong together.  pg_screen_components (a list from the host) and
 // pg_screen_index_components (the bands' kept triples, where B5 left them on the device) hook a union-find forest that only atomics write
 // and sum two 64-bit counts per node; K1 ... K3 stand there with their state.
@@ -94,7 +100,7 @@ namespace {
 
 // the stages whose milliseconds pg_screen_last, pg_screen_index_last, pg_screen_components_last, pg_screen_search_last, pg_screen_search_add_last,
 // pg_screen_search_remove_last and pg_screen_gather_last report
-enum ScreenStage { ST_SCAN, ST_GROUP, ST_COUNT, ST_SELECT, ST_HOOK, ST_FLATTEN, ST_LOOKUP, ST_EXPAND, ST_ARGMAX, ST_CLAIM, ST_MERGE, ST_CHECK, ST_MARK, ST_COMPACT };
+enum ScreenStage { ST_SCAN, ST_GROUP, ST_COUNT, ST_SELECT, ST_HOOK, ST_FLATTEN, ST_LOOKUP, ST_EXPAND, ST_ARGMAX, ST_CLAIM, ST_MERGE, ST_CHECK, ST_MARK, ST_COMPACT, ST_WEIGHT, ST_ATTRIBUTE, ST_SORT, ST_STATS };
 
 struct ScreenEvents {      // event pairs on the context's stream, summed per stage after the call's last synchronisation
   std::vector<hipEvent_t> ev;
@@ -150,3 +156,4 @@ hipError_t tmp_room(size_t& tmp_bytes, Query query) {
 #include "pgscr_add.inc"
 #include "pgscr_store.inc"
 #include "pgscr_gather.inc"
+#include "pgscr_abund.inc"

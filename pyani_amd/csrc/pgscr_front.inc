@@ -232,6 +232,7 @@ struct SliceGroups {      // one slice, sorted and grouped, on the device: what 
   const uint32_t* first;            // the first and the last entry of each of the ng k-mers held by >= 2 genomes
   const uint32_t* last;
   uint64_t ng;
+  const uint32_t* mult;             // with_mult: the times the fill pass appended each distinct key (its run in the sorted keys); else nullptr
   void* tmp;                        // temporary storage of the library calls: what the front half needs, and what prepare() asked for
   size_t tmp_bytes;
   uint32_t bin_lo, bin_hi;          // the slice's bins [bin_lo, bin_hi)
@@ -239,14 +240,21 @@ struct SliceGroups {      // one slice, sorted and grouped, on the device: what 
 
 struct FrontTotals { uint64_t keys = 0, distinct = 0, groups = 0, slices = 0; };
 
+struct AsU64 {      // a run length read as a 64-bit term of a sum
+  __host__ __device__ __forceinline__ unsigned long long operator()(uint32_t x) const { return x; }
+};
+
 // The FRONT HALF of a screen of checked arguments (n >= 1), shared by the dense calls and the index: the count pass, slices of whole bins
 // under the budget, and per slice the fill pass, the radix sort, Unique and the head kernel's sizes and first / last marks (C1, C2).
 // What becomes of a grouped slice is the back half's: back.prepare(all keys, keys of the largest slice, its bound of groups, tmp bytes to
 // raise) once before the first slice, back.slice(S, T) per slice.  d_sizes (the caller's, empty) holds the finished sizes on return.
 // wide_head: screen_head_kernel<true> (any n, bit 2 of the flags) instead of the LDS histogram of at most MAX_GENOMES genomes.
+// with_mult (the abundance count of the gather, DESIGN.md §16.8; off for every other caller): the sorted keys go through
+// DeviceRunLengthEncode::Encode in place of Unique — the same distinct keys, and SliceGroups::mult = the length of each one's run.  A
+// k-mer lies in one bin, a bin in one slice and a slice holds at most 2^30 keys: a run length never reaches the uint32's end.
 template <typename Back>
 int screen_front(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kmer, int32_t scale, uint32_t part, uint32_t n_parts, bool wide_head,
-                 PgDevBuf<uint32_t>& d_sizes, ScreenEvents& T, FrontTotals& tot, Back& back) {
+                 PgDevBuf<uint32_t>& d_sizes, ScreenEvents& T, FrontTotals& tot, Back& back, bool with_mult = false) {
   int rc;
   const auto scan_count = screen_scan_of<false>(kmer);
   const auto scan_fill = screen_scan_of<true>(kmer);
@@ -307,16 +315,19 @@ int screen_front(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kme
   tot.keys = total_keys; tot.slices = slices.size();
   if (!slices.empty()) {
     PgDevBuf<unsigned long long> keys_a, keys_b;
-    PgDevBuf<uint32_t> first, last;
+    PgDevBuf<uint32_t> first, last, mult;
     PgDevBuf<uint8_t> flags, tmp;
     const size_t max_groups = (size_t)(slice_max / 2 + 2);
     if ((rc = sk_malloc(ctx, keys_a, (size_t)slice_max + 1)) || (rc = sk_malloc(ctx, keys_b, (size_t)slice_max + 1)) ||
         (rc = sk_malloc(ctx, flags, (size_t)slice_max + 1)) || (rc = sk_malloc(ctx, first, max_groups)) || (rc = sk_malloc(ctx, last, max_groups)))
       return rc;
+    if (with_mult && (rc = sk_malloc(ctx, mult, (size_t)slice_max + 1))) return rc;
     // temporary storage of the library calls: the largest any of them asks for at the largest slice
     const int end_bit = 32 + 2 * kmer;
     unsigned long long* d_nu = d_counters.p + 1;
     unsigned long long* d_ng = d_counters.p + 2;
+    unsigned long long* d_runs = d_counters.p + 3;      // with_mult: the sum of a slice's run lengths
+    hipcub::TransformInputIterator<unsigned long long, AsU64, const uint32_t*> run_len((const uint32_t*)mult.p, AsU64{});
     hipcub::CountingInputIterator<uint32_t> counting(0u);
     hipcub::TransformInputIterator<uint8_t, FlagBit, const uint8_t*> is_first(flags.p, FlagBit{0u}), is_last(flags.p, FlagBit{1u});
     size_t tmp_bytes = 0;
@@ -325,6 +336,11 @@ int screen_front(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kme
     PG_HIP(ctx, tmp_room(tmp_bytes, [&](size_t& b) {
       return hipcub::DeviceSelect::Unique(nullptr, b, (const unsigned long long*)keys_b.p, keys_a.p, d_nu, (int64_t)slice_max, st); }));
     PG_HIP(ctx, tmp_room(tmp_bytes, [&](size_t& b) { return hipcub::DeviceSelect::Flagged(nullptr, b, counting, is_first, first.p, d_ng, (int64_t)slice_max, st); }));
+    if (with_mult) {
+      PG_HIP(ctx, tmp_room(tmp_bytes, [&](size_t& b) {
+        return hipcub::DeviceRunLengthEncode::Encode(nullptr, b, (const unsigned long long*)keys_b.p, keys_a.p, mult.p, d_nu, (int)slice_max, st); }));
+      PG_HIP(ctx, tmp_room(tmp_bytes, [&](size_t& b) { return hipcub::DeviceReduce::Sum(nullptr, b, run_len, d_runs, (int)slice_max, st); }));
+    }
     if ((rc = back.prepare(total_keys, slice_max, max_groups, tmp_bytes))) return rc;
     if ((rc = sk_malloc(ctx, tmp, tmp_bytes + 16))) return rc;
 
@@ -337,19 +353,30 @@ int screen_front(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kme
       }
       PG_HIP(ctx, hipGetLastError());
       unsigned long long cnt[3] = {0, 0, 0};      // cursor, distinct, groups
+      unsigned long long runs = 0;
       uint64_t nu = 0;
       {      // sort, drop a genome's repeats, mark the groups
         ScreenEvents::Stage group(T, ST_GROUP, st);
         size_t tb = tmp_bytes;
         PG_HIP(ctx, hipcub::DeviceRadixSort::SortKeys((void*)tmp.p, tb, (const unsigned long long*)keys_a.p, keys_b.p, (int64_t)S.keys, 0, end_bit, st));
         tb = tmp_bytes;
-        PG_HIP(ctx, hipcub::DeviceSelect::Unique((void*)tmp.p, tb, (const unsigned long long*)keys_b.p, keys_a.p, d_nu, (int64_t)S.keys, st));
+        if (!with_mult) {
+          PG_HIP(ctx, hipcub::DeviceSelect::Unique((void*)tmp.p, tb, (const unsigned long long*)keys_b.p, keys_a.p, d_nu, (int64_t)S.keys, st));
+        } else {      // the distinct keys with the length of each one's run
+          PG_HIP(ctx, hipcub::DeviceRunLengthEncode::Encode((void*)tmp.p, tb, (const unsigned long long*)keys_b.p, keys_a.p, mult.p, d_nu, (int)S.keys, st));
+        }
         PG_HIP(ctx, hipMemcpyAsync(cnt, d_counters, 2 * 8, hipMemcpyDeviceToHost, st));
         PG_HIP(ctx, hipStreamSynchronize(st));
         if (cnt[0] != S.keys)
           return pg_fail(ctx, PG_E_INTERNAL, "screen: the fill pass appended " + std::to_string(cnt[0]) + " keys where the count pass saw " + std::to_string(S.keys));
         nu = cnt[1];
         tot.distinct += nu;
+        if (with_mult) {      // every key of the slice lies in exactly one run
+          if (nu > S.keys) return pg_fail(ctx, PG_E_INTERNAL, "screen: more runs than keys in a slice");
+          tb = tmp_bytes;
+          PG_HIP(ctx, hipcub::DeviceReduce::Sum((void*)tmp.p, tb, run_len, d_runs, (int)nu, st));
+          PG_HIP(ctx, hipMemcpyAsync(&runs, d_runs, 8, hipMemcpyDeviceToHost, st));
+        }
         hipLaunchKernelGGL(wide_head ? screen_head_kernel<true> : screen_head_kernel<false>, dim3(grid_for(nu, 256 * 16, cu_blocks)), dim3(256), 0, st,
                            (const unsigned long long*)keys_a.p, nu, n, d_sizes.p, flags.p);
         PG_HIP(ctx, hipGetLastError());
@@ -361,9 +388,11 @@ int screen_front(pg_ctx* ctx, const int32_t* genome_ids, uint32_t n, int32_t kme
       }
       PG_HIP(ctx, hipStreamSynchronize(st));
       const uint64_t ng = cnt[2];
+      if (with_mult && runs != S.keys)
+        return pg_fail(ctx, PG_E_INTERNAL, "screen: the runs of a slice hold " + std::to_string(runs) + " keys where the fill pass appended " + std::to_string(S.keys));
       if (ng + 1 > max_groups) return pg_fail(ctx, PG_E_INTERNAL, "screen: more groups than half the keys");
       tot.groups += ng;
-      const SliceGroups G{keys_a.p, nu, flags.p, first.p, last.p, ng, (void*)tmp.p, tmp_bytes, S.lo, S.hi};
+      const SliceGroups G{keys_a.p, nu, flags.p, first.p, last.p, ng, with_mult ? (const uint32_t*)mult.p : nullptr, (void*)tmp.p, tmp_bytes, S.lo, S.hi};
       if ((rc = back.slice(G, T))) return rc;
     }
   }

@@ -32,11 +32,14 @@ struct EntryWeight {      // G0: the items of the i-th matched run: its query ho
 };
 
 // G0 expand: item t of matched run r = its t-th query holder; entry[off[run] + t] = query << 48 | group[r].  The caller filled the range
-// with GATHER_DEAD, so an item that fails a check leaves a dead entry, never an unwritten one.
+// with GATHER_DEAD, so an item that fails a check leaves a dead entry, never an unwritten one.  WEIGHTED (the abundance count, DESIGN.md
+// §16.8): abund[off[run] + t] = mult[that holder's key], the times the query holds the k-mer; its range was filled with 0.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void gather_expand_kernel(const unsigned long long* __restrict__ u, uint64_t nu, const uint32_t* __restrict__ run_first, uint32_t nr,
                                                              const uint32_t* __restrict__ active, const unsigned long long* __restrict__ group, uint64_t D,
                                                              const unsigned long long* __restrict__ off, uint32_t na, unsigned long long P, unsigned long long per,
-                                                             uint32_t q, unsigned long long* __restrict__ entry) {
+                                                             uint32_t q, unsigned long long* __restrict__ entry, const uint32_t* __restrict__ mult,
+                                                             uint32_t* __restrict__ abund) {
   item_walk<uint32_t>(off, na, P, per, [=](uint32_t ga, unsigned long long t) {
     const uint32_t r = active[ga];
     if (r >= nr) return;
@@ -46,9 +49,45 @@ __global__ __launch_bounds__(256) void gather_expand_kernel(const unsigned long 
     const unsigned long long at = off[ga] + t;
     if (sq + t < eq && eq <= nu && at < P) {
       const uint32_t qi = (uint32_t)u[sq + t];
-      if (qi < q) entry[at] = ((unsigned long long)qi << GATHER_G_BITS) | g;
+      if (qi < q) {
+        entry[at] = ((unsigned long long)qi << GATHER_G_BITS) | g;
+        if (WEIGHTED) abund[at] = mult[sq + t];
+      }
     }
   });
+}
+
+// The sums of the abundance count, one per query: item i of `src` adds src.weight(i) to sum[src.query(i)] where that query is below q.  Through
+// 64-bit sums in LDS for the first WEIGHT_LDS queries (a call of one query would otherwise send every key to one word of HBM), one atomic
+// in HBM per query and workgroup; the queries beyond go to HBM directly.
+constexpr uint32_t WEIGHT_LDS = 4096;
+struct KeyWeight {        // the distinct keys of a slice: the key's genome, the length of its run
+  const unsigned long long* u;
+  const uint32_t* mult;
+  __device__ uint32_t query(uint64_t i) const { return (uint32_t)u[i]; }
+  __device__ uint32_t weight(uint64_t i) const { return mult[i]; }
+};
+struct EntryAbund {       // the kept entries: the entry's query, its abundance (a dead entry has none)
+  const unsigned long long* entry;
+  const uint32_t* abund;
+  __device__ uint32_t query(uint64_t i) const { const unsigned long long x = entry[i]; return x == GATHER_DEAD ? GATHER_NONE : (uint32_t)(x >> GATHER_G_BITS); }
+  __device__ uint32_t weight(uint64_t i) const { return abund[i]; }
+};
+template <typename Src>
+__global__ __launch_bounds__(256) void gather_weight_kernel(Src src, uint64_t n_items, uint32_t q, unsigned long long* __restrict__ sum) {
+  __shared__ unsigned long long lsum[WEIGHT_LDS];
+  const uint32_t in_lds = q < WEIGHT_LDS ? q : WEIGHT_LDS;
+  for (uint32_t i = threadIdx.x; i < in_lds; i += blockDim.x) lsum[i] = 0ull;
+  __syncthreads();
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_items; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t qi = src.query(i);
+    if (qi >= q) continue;
+    const unsigned long long w = src.weight(i);
+    if (qi < in_lds) atomicAdd(&lsum[qi], w); else atomicAdd(&sum[qi], w);
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < in_lds; i += blockDim.x)
+    if (lsum[i]) atomicAdd(&sum[i], lsum[i]);
 }
 
 // matched[i] = the entries of query i, through a histogram in LDS (q <= the band's rows, 8192: 32 KB)
@@ -251,6 +290,19 @@ int gather_sink_prepare(pg_ctx* ctx, EntrySink& sink, uint64_t total_keys) {
   sink.M = 0;
   if (sk_malloc(ctx, sink.entry, sink.cap + 1))
     return pg_fail(ctx, PG_E_NOMEM, "screen: no device memory for up to " + std::to_string(sink.cap) + " matched entries of a gather (8 bytes each)");
+  if (sink.weighted && sk_malloc(ctx, sink.abund, sink.cap + 1))
+    return pg_fail(ctx, PG_E_NOMEM, "screen: no device memory for the abundances of up to " + std::to_string(sink.cap) + " matched entries of a gather (4 bytes each)");
+  return PG_OK;
+}
+
+// The abundance count, per slice: every distinct key's multiplicity goes into its query's weight W.
+int gather_sink_weight(QueryBack& B, const SliceGroups& S, ScreenEvents& T) {
+  pg_ctx* ctx = B.ctx;
+  if (!S.mult) return pg_fail(ctx, PG_E_INTERNAL, "screen: an abundance count over a front half that kept no multiplicities");
+  ScreenEvents::Stage weight(T, ST_WEIGHT, ctx->stream);
+  hipLaunchKernelGGL(gather_weight_kernel<KeyWeight>, dim3(grid_for(S.nu, 256 * 16, (uint32_t)ctx->num_cu * 4u)), dim3(256), 0, ctx->stream, KeyWeight{S.u, S.mult}, S.nu,
+                     B.q, B.sink->weight.p);
+  PG_HIP(ctx, hipGetLastError());
   return PG_OK;
 }
 
@@ -275,25 +327,41 @@ int gather_sink_slice(QueryBack& B, const SliceGroups& S, ScreenEvents& T, uint3
   const unsigned long long per = items_per_workgroup(ctx, P);
   ScreenEvents::Stage expand(T, ST_EXPAND, st);
   PG_HIP(ctx, hipMemsetAsync(sink.entry.p + sink.M, 0xFF, (size_t)P * 8, st));
-  hipLaunchKernelGGL(gather_expand_kernel, dim3((uint32_t)((P + per - 1) / per)), dim3(256), 0, st, S.u, S.nu, (const uint32_t*)B.run_first.p, nr,
-                     (const uint32_t*)B.active.p, (const unsigned long long*)B.group.p, B.I->D, (const unsigned long long*)B.off.p, na, P, per, B.q,
-                     sink.entry.p + sink.M);
+  if (!sink.weighted) {
+    hipLaunchKernelGGL(gather_expand_kernel<false>, dim3((uint32_t)((P + per - 1) / per)), dim3(256), 0, st, S.u, S.nu, (const uint32_t*)B.run_first.p, nr,
+                       (const uint32_t*)B.active.p, (const unsigned long long*)B.group.p, B.I->D, (const unsigned long long*)B.off.p, na, P, per, B.q,
+                       sink.entry.p + sink.M, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+  } else {      // (the abundances in step with the entries)
+    if (!S.mult) return pg_fail(ctx, PG_E_INTERNAL, "screen: an abundance count over a front half that kept no multiplicities");
+    PG_HIP(ctx, hipMemsetAsync(sink.abund.p + sink.M, 0, (size_t)P * 4, st));
+    hipLaunchKernelGGL(gather_expand_kernel<true>, dim3((uint32_t)((P + per - 1) / per)), dim3(256), 0, st, S.u, S.nu, (const uint32_t*)B.run_first.p, nr,
+                       (const uint32_t*)B.active.p, (const unsigned long long*)B.group.p, B.I->D, (const unsigned long long*)B.off.p, na, P, per, B.q,
+                       sink.entry.p + sink.M, S.mult, sink.abund.p + sink.M);
+  }
   PG_HIP(ctx, hipGetLastError());
   sink.M += P;
   return PG_OK;
 }
 
 // after the last slice: the entries of every query counted
-int gather_sink_finish(pg_ctx* ctx, const EntrySink& sink, uint32_t q, PgDevBuf<uint32_t>& matched, ScreenEvents& T) {
+int gather_sink_finish(pg_ctx* ctx, EntrySink& sink, uint32_t q, PgDevBuf<uint32_t>& matched, ScreenEvents& T) {
   hipStream_t st = ctx->stream;
   int rc;
   if (q > pgscr::MAX_BAND_ROWS) return pg_fail(ctx, PG_E_INTERNAL, "screen: more queries than a band has rows");
   if ((rc = pg_dev_alloc(ctx, "screen", matched, q, "the queries' matched counts"))) return rc;
-  ScreenEvents::Stage expand(T, ST_EXPAND, st);
-  PG_HIP(ctx, hipMemsetAsync(matched, 0, (size_t)q * 4, st));
-  if (sink.M) {
-    hipLaunchKernelGGL(gather_matched_kernel, dim3(grid_for(sink.M, 256 * 16, (uint32_t)ctx->num_cu * 4u)), dim3(256), 0, st, (const unsigned long long*)sink.entry.p, sink.M, q,
-                       matched.p);
+  {
+    ScreenEvents::Stage expand(T, ST_EXPAND, st);
+    PG_HIP(ctx, hipMemsetAsync(matched, 0, (size_t)q * 4, st));
+    if (sink.M) {
+      hipLaunchKernelGGL(gather_matched_kernel, dim3(grid_for(sink.M, 256 * 16, (uint32_t)ctx->num_cu * 4u)), dim3(256), 0, st, (const unsigned long long*)sink.entry.p, sink.M, q,
+                         matched.p);
+      PG_HIP(ctx, hipGetLastError());
+    }
+  }
+  if (sink.weighted && sink.M) {      // MW: the abundances of every query's entries
+    ScreenEvents::Stage weight(T, ST_WEIGHT, st);
+    hipLaunchKernelGGL(gather_weight_kernel<EntryAbund>, dim3(grid_for(sink.M, 256 * 16, (uint32_t)ctx->num_cu * 4u)), dim3(256), 0, st,
+                       EntryAbund{sink.entry.p, sink.abund.p}, sink.M, q, sink.matched_weight.p);
     PG_HIP(ctx, hipGetLastError());
   }
   return PG_OK;
@@ -422,7 +490,7 @@ int gather_run(pg_ctx* ctx, SearchState* I, const uint32_t* need, uint32_t q, ui
 }  // namespace
 
 extern "C" int pg_screen_gather_count(pg_ctx* ctx, const int32_t* query_ids, uint32_t q, uint32_t* sizes_out) {
-  return search_count(ctx, query_ids, q, sizes_out, true);
+  return search_count(ctx, query_ids, q, sizes_out, KEEP_ENTRIES);
 }
 
 extern "C" int pg_screen_gather(pg_ctx* ctx, const uint32_t* need, uint32_t q, uint32_t max_ranks, uint64_t* n_rows_out) {
@@ -438,6 +506,7 @@ extern "C" int pg_screen_gather(pg_ctx* ctx, const uint32_t* need, uint32_t q, u
   if (q == 0) {      // (no rows)
     I->gathered = true;
     I->n_rows = 0;
+    I->drop_abund_rows();
     I->d_left.release(); I->d_row_q.release(); I->d_row_db.release(); I->d_row_unique.release(); I->d_row_total.release();
     L.rounds = L.rows = L.claimed = L.decrements = 0;
     L.argmax_ms = L.claim_ms = 0.0;
@@ -468,6 +537,7 @@ extern "C" int pg_screen_gather(pg_ctx* ctx, const uint32_t* need, uint32_t q, u
   I->d_row_q = std::move(W.row_q); I->d_row_db = std::move(W.row_db); I->d_row_unique = std::move(W.row_unique); I->d_row_total = std::move(W.row_total);
   I->n_rows = n_rows;
   I->gathered = true;
+  I->drop_abund_rows();      // (statistics of an earlier gather's rows)
   L.rounds = ctl[GC_ROUNDS]; L.rows = n_rows; L.claimed = ctl[GC_CLAIMED]; L.decrements = ctl[GC_DECR];
   L.argmax_ms = T.ms(ST_ARGMAX); L.claim_ms = T.ms(ST_CLAIM);
   *n_rows_out = n_rows;

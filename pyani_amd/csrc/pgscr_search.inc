@@ -43,10 +43,26 @@ struct SearchState {      // the resident search index of pg_screen_search_index
   PgDevBuf<uint32_t> d_left;                      // q x n: what the latest pg_screen_gather left of the rectangle
   PgDevBuf<int32_t> d_row_q, d_row_db;            // n_rows each, by query, then rank
   PgDevBuf<uint32_t> d_row_unique, d_row_total;
+  // the abundances (DESIGN.md §16.8, pgscr_abund.inc): what pg_screen_gather_count_abund keeps beside the entries, and the latest pass
+  bool abund_kept = false;                        // the latest count kept the abundances
+  PgDevBuf<uint32_t> d_abund;                     // M: a(query, k-mer) of entry e, parallel to d_entry; never written after the count
+  PgDevBuf<unsigned long long> d_weight;          // q: W, the sampled occurrences of each query
+  PgDevBuf<unsigned long long> d_matched_weight;  // q: MW, the abundances of each query's entries summed
+  bool abund_done = false;                        // a pg_screen_gather_abund over the latest gather
+  uint64_t n_abund_rows = 0;
+  PgDevBuf<unsigned long long> d_ab_sum, d_ab_sumsq, d_ab_median2;      // n_rows, 2 n_rows (lo, hi), n_rows
+  PgDevBuf<uint32_t> d_ab_min, d_ab_max;
+  void drop_abund_rows() {      // with every new gather: the statistics are of the rows they were made from
+    abund_done = false;
+    n_abund_rows = 0;
+    d_ab_sum.release(); d_ab_sumsq.release(); d_ab_median2.release(); d_ab_min.release(); d_ab_max.release();
+  }
   void drop_gather() {
-    kept = gathered = false;
+    kept = gathered = abund_kept = false;
     M = n_rows = 0;
     d_entry.release(); d_matched.release(); d_left.release(); d_row_q.release(); d_row_db.release(); d_row_unique.release(); d_row_total.release();
+    d_abund.release(); d_weight.release(); d_matched_weight.release();
+    drop_abund_rows();
   }
 };
 
@@ -55,11 +71,16 @@ struct EntrySink {
   PgDevBuf<unsigned long long> entry;
   size_t cap = 0;
   uint64_t M = 0;
+  // the abundance count (DESIGN.md §16.8): abund[e] = the multiplicity of entry e; weight, matched_weight: q sums, the caller's, zeroed
+  bool weighted = false;
+  PgDevBuf<uint32_t> abund;
+  PgDevBuf<unsigned long long> weight, matched_weight;
 };
 struct QueryBack;
+int gather_sink_weight(QueryBack& B, const SliceGroups& S, ScreenEvents& T);
 int gather_sink_prepare(pg_ctx* ctx, EntrySink& sink, uint64_t total_keys);
 int gather_sink_slice(QueryBack& B, const SliceGroups& S, ScreenEvents& T, uint32_t nr, uint32_t na);
-int gather_sink_finish(pg_ctx* ctx, const EntrySink& sink, uint32_t q, PgDevBuf<uint32_t>& matched, ScreenEvents& T);
+int gather_sink_finish(pg_ctx* ctx, EntrySink& sink, uint32_t q, PgDevBuf<uint32_t>& matched, ScreenEvents& T);
 
 // An array of the index that was sized by a bound and uses `need` elements moves into a block of exactly that many, unless the bound was
 // close (within a sixteenth: E is nearly the keys when few k-mers repeat inside a genome) or there is no room for the copy: then it stays.
@@ -84,6 +105,7 @@ void search_drop_counted(pg_ctx* ctx, SearchState* I) {
   I->d_rect.release(); I->d_a.release(); I->d_b.release(); I->d_s.release();
   I->drop_gather();
   ctx->screen_gather_stats = PgScreenGatherStats{};
+  ctx->screen_gather_abund_stats = PgScreenGatherAbundStats{};
   PgScreenSearchStats& L = ctx->screen_search_stats;
   L.query_keys = L.lookups = L.matched = L.increments = L.query_slices = 0;
   L.scan_ms = L.group_ms = L.lookup_ms = L.count_ms = L.select_ms = 0.0;
@@ -250,6 +272,7 @@ struct QueryBack {
     const uint32_t cu_blocks = (uint32_t)ctx->num_cu * 8u;
     hipcub::CountingInputIterator<uint32_t> counting(0u);
     unsigned long long nr = 0, na = 0, P = 0;
+    if (sink && sink->weighted) { int rc; if ((rc = gather_sink_weight(*this, S, T))) return rc; }      // (every key of the slice, matched or not)
     // Each stage is timed in pieces that end before the host waits for a count, so that no event pair spans a synchronisation: the
     // lookup stage = the mark, the runs' compaction, the lookup kernel and the matched runs' compaction; the count stage = the weights,
     // their scan and the count kernel.
@@ -309,6 +332,7 @@ void pg_screen_search_drop(pg_ctx* ctx) {
   ctx->screen_search_add_stats = PgScreenSearchAddStats{};
   ctx->screen_search_remove_stats = PgScreenSearchRemoveStats{};
   ctx->screen_gather_stats = PgScreenGatherStats{};
+  ctx->screen_gather_abund_stats = PgScreenGatherAbundStats{};
 }
 
 extern "C" int pg_screen_search_index_release(pg_ctx* ctx) {
@@ -379,8 +403,11 @@ extern "C" int pg_screen_search_index(pg_ctx* ctx, const int32_t* genome_ids, ui
   return PG_OK;
 }
 
-// pg_screen_search_count and pg_screen_gather_count: one path; keep = the matched entries stay resident for pg_screen_gather
-static int search_count(pg_ctx* ctx, const int32_t* query_ids, uint32_t q, uint32_t* sizes_out, bool keep) {
+// pg_screen_search_count, pg_screen_gather_count and pg_screen_gather_count_abund: one path.  keep = KEEP_ENTRIES: the matched entries stay
+// resident for pg_screen_gather; KEEP_ABUND: so do their abundances and the queries' weights, for pg_screen_gather_abund (weight_out: q
+// uint64, W).
+enum SearchKeep { KEEP_NONE, KEEP_ENTRIES, KEEP_ABUND };
+static int search_count(pg_ctx* ctx, const int32_t* query_ids, uint32_t q, uint32_t* sizes_out, SearchKeep keep, uint64_t* weight_out = nullptr) {
   if (!ctx) return PG_E_ARG;
   SearchState* I = search_of(ctx);
   if (!I) return pg_fail(ctx, PG_E_ARG, "screen: no resident search index (call pg_screen_search_index first)");
@@ -388,10 +415,11 @@ static int search_count(pg_ctx* ctx, const int32_t* query_ids, uint32_t q, uint3
   const std::string too_many = "screen: " + std::to_string(q) + " queries in one count, more than the band's " + std::to_string(rows) + " rows (pg_screen_set_band)";
   int rc;
   if ((rc = screen_check(ctx, query_ids, q, I->kmer, I->scale, 0, 1, sizes_out, false, nullptr, rows, too_many.c_str()))) return rc;
+  if (keep == KEEP_ABUND && q && !weight_out) return pg_fail(ctx, PG_E_ARG, "bad argument");
   PG_HIP(ctx, hipSetDevice(ctx->device));
   search_drop_counted(ctx, I);      // the rectangle and the selection of an earlier count go before the new one is made
   PgScreenSearchStats& L = ctx->screen_search_stats;
-  if (q == 0) { I->q = 0; I->counted = true; I->kept = keep; return PG_OK; }      // (a rectangle of no rows)
+  if (q == 0) { I->q = 0; I->counted = true; I->kept = keep != KEEP_NONE; I->abund_kept = keep == KEEP_ABUND; return PG_OK; }      // (a rectangle of no rows)
   if ((rc = pg_upload(ctx))) return rc;
   hipStream_t st = ctx->stream;
   PgDevBuf<uint32_t> rect, d_sizes;
@@ -402,14 +430,26 @@ static int search_count(pg_ctx* ctx, const int32_t* query_ids, uint32_t q, uint3
   EntrySink sink;
   QueryBack back{ctx, I, q, rect.p};
   if (keep) back.sink = &sink;
+  if (keep == KEEP_ABUND) {
+    sink.weighted = true;
+    if ((rc = pg_dev_alloc(ctx, "screen", sink.weight, q, "the queries' weights")) || (rc = pg_dev_alloc(ctx, "screen", sink.matched_weight, q, "the queries' weights"))) return rc;
+    PG_HIP(ctx, hipMemsetAsync(sink.weight, 0, (size_t)q * 8, st));
+    PG_HIP(ctx, hipMemsetAsync(sink.matched_weight, 0, (size_t)q * 8, st));
+  }
   PgDevBuf<uint32_t> matched;
-  rc = screen_front(ctx, query_ids, q, I->kmer, I->scale, 0, 1, false, d_sizes, T, tot, back);
+  rc = screen_front(ctx, query_ids, q, I->kmer, I->scale, 0, 1, false, d_sizes, T, tot, back, keep == KEEP_ABUND);
   if (!rc && keep) rc = gather_sink_finish(ctx, sink, q, matched, T);
   hipError_t e = rc ? hipSuccess : hipMemcpyAsync(sizes_out, d_sizes, (size_t)q * 4, hipMemcpyDeviceToHost, st);
+  if (!rc && e == hipSuccess && keep == KEEP_ABUND) e = hipMemcpyAsync(weight_out, sink.weight, (size_t)q * 8, hipMemcpyDeviceToHost, st);
   const hipError_t es = hipStreamSynchronize(st);      // (on errors too: the back half's buffers and `rect` go with this scope)
   if (rc) return rc;
   PG_HIP(ctx, e);
   PG_HIP(ctx, es);
+  if (keep == KEEP_ABUND) {      // every key the fill pass appended is an occurrence of exactly one query
+    unsigned long long all = 0;
+    for (uint32_t i = 0; i < q; ++i) all += weight_out[i];
+    if (all != tot.keys) return pg_fail(ctx, PG_E_INTERNAL, "screen: the queries' weights add up to " + std::to_string(all) + " where the scan took " + std::to_string(tot.keys) + " keys");
+  }
   L.query_keys = tot.keys; L.lookups = back.lookups; L.matched = back.matched; L.increments = back.incr; L.query_slices = tot.slices;
   L.scan_ms = T.ms(ST_SCAN); L.group_ms = T.ms(ST_GROUP); L.lookup_ms = T.ms(ST_LOOKUP); L.count_ms = T.ms(ST_COUNT);
   I->d_rect = std::move(rect);
@@ -423,11 +463,18 @@ static int search_count(pg_ctx* ctx, const int32_t* query_ids, uint32_t q, uint3
     ctx->screen_gather_stats.entries = sink.M;
     ctx->screen_gather_stats.expand_ms = T.ms(ST_EXPAND);
   }
+  if (keep == KEEP_ABUND) {
+    I->abund_kept = true;
+    I->d_abund = std::move(sink.abund);
+    I->d_weight = std::move(sink.weight);
+    I->d_matched_weight = std::move(sink.matched_weight);
+    ctx->screen_gather_abund_stats.weight_ms = T.ms(ST_WEIGHT);
+  }
   return PG_OK;
 }
 
 extern "C" int pg_screen_search_count(pg_ctx* ctx, const int32_t* query_ids, uint32_t q, uint32_t* sizes_out) {
-  return search_count(ctx, query_ids, q, sizes_out, false);
+  return search_count(ctx, query_ids, q, sizes_out, KEEP_NONE);
 }
 
 extern "C" int pg_screen_search_fetch(pg_ctx* ctx, uint32_t* out) {

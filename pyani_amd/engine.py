@@ -773,15 +773,48 @@ class Engine:
         return screen.SearchHits(query_labels, list(self._search["labels"]), options, query_sizes, self._search["sizes"], a, b, shared)
 
     # the gather: a query decomposed into the genomes of the resident collection
-    def screen_gather_count(self, query_ids) -> np.ndarray:
+    def screen_gather_count(self, query_ids, abundance: bool = False):
         """pg_screen_gather_count: screen_search_count that also keeps the matched (query, k-mer) entries resident for
-        screen_gather_rows; returns the queries' sizes uint32[q].  select and fetch of the search work on its rectangle as before."""
+        screen_gather_rows; returns the queries' sizes uint32[q].  select and fetch of the search work on its rectangle as before.
+        abundance=True (pg_screen_gather_count_abund): the same count, which also keeps every entry's multiplicity
+        for screen_gather_abundance; returns (sizes uint32[q], weight uint64[q]: the queries' sampled occurrences W)."""
         a = self._ids(query_ids)
         q = len(a)
         sizes = np.zeros(q, dtype=np.uint32)
+        if abundance:
+            weight = np.zeros(q, dtype=np.uint64)
+            self._check(self.lib.pg_screen_gather_count_abund(self._h, a.ctypes.data if q else None, q, sizes.ctypes.data if q else None,
+                                                              weight.ctypes.data if q else None))
+            self._search_q = q
+            return sizes, weight
         self._check(self.lib.pg_screen_gather_count(self._h, a.ctypes.data if q else None, q, sizes.ctypes.data if q else None))
         self._search_q = q
         return sizes
+
+    def screen_gather_abundance(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """pg_screen_gather_abund + pg_screen_gather_abund_read, after screen_gather_rows over a count with abundance=True: (sum
+        uint64[r], sumsq uint64[r, 2] = (lo, hi) words, median2 uint64[r], min uint32[r], max uint32[r]) of the multiplicities of the
+        k-mers each recorded row claimed, in the rows' order (pyani_gpu.h states them)."""
+        r = ctypes.c_uint64(0)
+        self._check(self.lib.pg_screen_gather_abund(self._h, ctypes.byref(r)))
+        total, sumsq, median2 = np.zeros(r.value, dtype=np.uint64), np.zeros((r.value, 2), dtype=np.uint64), np.zeros(r.value, dtype=np.uint64)
+        low, high = np.zeros(r.value, dtype=np.uint32), np.zeros(r.value, dtype=np.uint32)
+        self._check(self.lib.pg_screen_gather_abund_read(self._h, *(x.ctypes.data if r.value else None for x in (total, sumsq, median2, low, high))))
+        return total, sumsq, median2, low, high
+
+    def screen_gather_abundance_matched(self) -> np.ndarray:
+        """pg_screen_gather_abund_matched: uint64[q], MW = the multiplicities of each query's kept entries, summed."""
+        out = np.zeros(getattr(self, "_search_q", 0), dtype=np.uint64)
+        self._check(self.lib.pg_screen_gather_abund_matched(self._h, out.ctypes.data if out.size else None))
+        return out
+
+    def screen_gather_abundance_last(self) -> dict:
+        """pg_screen_gather_abund_last: counts and stage milliseconds of the latest abundance count and the latest abundance pass."""
+        c = (ctypes.c_uint64 * 4)()
+        ms = (ctypes.c_double * 4)()
+        self._check(self.lib.pg_screen_gather_abund_last(self._h, ctypes.addressof(c), ctypes.addressof(ms)))
+        return {"attributed": int(c[0]), "unattributed": int(c[1]), "holders_walked": int(c[2]), "rank_table_bytes": int(c[3]),
+                "weight_ms": float(ms[0]), "attribute_ms": float(ms[1]), "sort_ms": float(ms[2]), "stats_ms": float(ms[3])}
 
     def screen_gather_rows(self, need, max_ranks: int = 65536) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """pg_screen_gather + pg_screen_gather_read: (query int32[r], db int32[r], unique uint32[r], total uint32[r]) of the greedy
@@ -823,8 +856,8 @@ class Engine:
         options = screen.check_gather_options(options)
         query_ids = [int(i) for i in query_ids]
         query_labels = screen.search_labels(query_ids, query_labels, "query")
-        query_sizes, matched, qi, db, unique, total = screen.gather_chunks(self, query_ids, options)
-        return screen.GatherResult(query_labels, list(self._search["labels"]), options, query_sizes, self._search["sizes"], qi, db, unique, total, matched)
+        query_sizes, matched, qi, db, unique, total, *abund = screen.gather_chunks(self, query_ids, options)
+        return screen.GatherResult(query_labels, list(self._search["labels"]), options, query_sizes, self._search["sizes"], qi, db, unique, total, matched, *abund)
 
     # -- classify: clique sweep over identity thresholds (pyani_amd.classify drives these) -------------------------------------
     def classify_edges(self, identity: np.ndarray, coverage: np.ndarray, id_min: float = 0.8, cov_min: float = 0.5) -> Tuple[int, int]:

@@ -877,17 +877,19 @@ class GatherOptions(NamedTuple):
     """What a gather asks: a db genome is worth a row while it explains at least max(min_unique, ceil(min_fraction * |S(query)|)) of the
     query's sampled k-mers that no better match has explained; at most max_ranks rows per query.  There is no default min_unique: two
     unrelated 5 Mb genomes share about 50 sampled 16-mers by chance at scale 256, so the right floor depends on the genomes' size and
-    the scale."""
+    the scale.  abundance: the count also keeps how many times the query holds each matched k-mer, and every row gets
+    the statistics of the multiplicities of the k-mers it claimed; the rows themselves do not change."""
     kmer: int
     scale: int
     min_unique: int
     min_fraction: float = 0.0
     max_ranks: int = GATHER_MAX_RANKS
+    abundance: bool = False
 
 
 def check_gather_options(options) -> GatherOptions:
     """A GatherOptions validated (no library call): kmer and scale as check_params, min_unique an integer >= 1, min_fraction a real number
-    in [0, 1], max_ranks an integer 1 ... 65536."""
+    in [0, 1], max_ranks an integer 1 ... 65536, abundance a bool."""
     if not isinstance(options, GatherOptions):
         raise ValueError(f"gather options are a GatherOptions, not {options!r}")
     kmer, scale = check_params(options.kmer, options.scale)
@@ -898,7 +900,9 @@ def check_gather_options(options) -> GatherOptions:
         raise ValueError(f"min_fraction must be a number in [0, 1], not {mf!r}")
     if isinstance(mr, bool) or not isinstance(mr, (int, np.integer)) or not 1 <= int(mr) <= GATHER_MAX_RANKS:
         raise ValueError(f"max_ranks must be an integer 1 ... {GATHER_MAX_RANKS}, not {mr!r}")
-    return GatherOptions(kmer, scale, int(mu), float(mf), int(mr))
+    if not isinstance(options.abundance, (bool, np.bool_)):
+        raise ValueError(f"abundance must be True or False, not {options.abundance!r}")
+    return GatherOptions(kmer, scale, int(mu), float(mf), int(mr), bool(options.abundance))
 
 
 def gather_thresholds(query_sizes, min_unique: int, min_fraction: float = 0.0) -> np.ndarray:
@@ -927,6 +931,17 @@ class GatherResult(NamedTuple):
     unique: np.ndarray          # uint32[r]
     total: np.ndarray           # uint32[r]
     matched: np.ndarray         # uint32[q]: |S(query) & the union of the db|, the entries the count kept
+    # options.abundance only (None otherwise): a(i, x) = the times query i holds the sampled k-mer x
+    query_weight: Optional[np.ndarray] = None       # uint64[q]: W, the sum of a over S(query)
+    matched_weight: Optional[np.ndarray] = None     # uint64[q]: MW, the sum of a over the matched entries
+    sum_abund: Optional[np.ndarray] = None          # uint64[r]: over the k-mers the row claimed (`unique` of them): the sum of a,
+    sumsq_abund: Optional[np.ndarray] = None        # object[r]: the sum of a^2 as Python ints (sumsq_words joins the library's two words),
+    median2_abund: Optional[np.ndarray] = None      # uint64[r]: twice the median,
+    min_abund: Optional[np.ndarray] = None          # uint32[r]
+    max_abund: Optional[np.ndarray] = None          # uint32[r]
+
+    def has_abundance(self) -> bool:
+        return self.sum_abund is not None
 
     def ranks(self) -> np.ndarray:
         """The rank of every row inside its query, 0 first (the rows of a query stand together)."""
@@ -947,9 +962,13 @@ class GatherResult(NamedTuple):
         before = np.where(first > 0, running[np.maximum(first, 1) - 1], 0) if len(running) else running
         with np.errstate(divide="ignore", invalid="ignore"):
             f_running = np.where(qsize > 0, (running - before).astype(np.float64) / qsize, np.nan)
-        return pd.DataFrame({"query": ql[self.query] if len(self.query) else [], "rank": self.ranks(), "db": dl[self.db] if len(self.db) else [],
-                             "unique": self.unique, "total": self.total, "f_unique_query": f_unique, "f_unique_cumulative": f_running,
-                             "f_match": f_match, "identity": np.power(f_match, 1.0 / self.options.kmer)})
+        frame = pd.DataFrame({"query": ql[self.query] if len(self.query) else [], "rank": self.ranks(), "db": dl[self.db] if len(self.db) else [],
+                              "unique": self.unique, "total": self.total, "f_unique_query": f_unique, "f_unique_cumulative": f_running,
+                              "f_match": f_match, "identity": np.power(f_match, 1.0 / self.options.kmer)})
+        if self.has_abundance():      # with the abundances: average_abund, median_abund, std_abund, f_unique_weighted, f_weighted_cumulative
+            for name, column in abundance_columns(self.query, self.unique, self.sum_abund, self.sumsq_abund, self.median2_abund, self.query_weight).items():
+                frame[name] = column
+        return frame
 
     def summary(self) -> pd.DataFrame:
         """One row per query: query, size, matched = |S(query) & the union of the db|, rows, explained = the sum of its rows' unique,
@@ -958,15 +977,59 @@ class GatherResult(NamedTuple):
         rows = np.bincount(self.query, minlength=q).astype(np.int64)
         explained = np.bincount(self.query, weights=self.unique.astype(np.float64), minlength=q).astype(np.int64)      # (sums below 2^53: exact)
         matched = self.matched.astype(np.int64)
-        return pd.DataFrame({"query": list(self.query_labels), "size": self.query_sizes.astype(np.int64), "matched": matched, "rows": rows,
-                             "explained": explained, "unexplained": matched - explained})
+        frame = pd.DataFrame({"query": list(self.query_labels), "size": self.query_sizes.astype(np.int64), "matched": matched, "rows": rows,
+                              "explained": explained, "unexplained": matched - explained})
+        if self.has_abundance():      # weight = W, matched_weight = MW, explained_weight = the rows' sum_abund, unexplained_weight = MW - that
+            told = [0] * q
+            for i, x in zip(self.query.tolist(), self.sum_abund.tolist()):
+                told[i] += int(x)
+            frame["weight"] = np.asarray(self.query_weight, dtype=np.uint64)
+            frame["matched_weight"] = np.asarray(self.matched_weight, dtype=np.uint64)
+            frame["explained_weight"] = np.array(told, dtype=np.uint64)
+            frame["unexplained_weight"] = np.array([int(m) - t for m, t in zip(self.matched_weight.tolist(), told)], dtype=np.uint64)
+        return frame
+
+
+def sumsq_words(words) -> np.ndarray:
+    """The sums of squares of pg_screen_gather_abund_read, uint64[r, 2] = (lo, hi) words, as an object array of Python ints."""
+    words = np.asarray(words, dtype=np.uint64).reshape(-1, 2)
+    out = np.empty(len(words), dtype=object)
+    for j, (lo, hi) in enumerate(words.tolist()):
+        out[j] = int(lo) + (int(hi) << 64)
+    return out
+
+
+def abundance_columns(query, unique, sum_abund, sumsq_abund, median2_abund, query_weight) -> dict:
+    """The float columns of a gather's abundances from its integers, with Python integers throughout (true division of two ints is
+    correctly rounded, so every column is a fixed function of the integers): average_abund = sum / m, median_abund = median2 / 2,
+    std_abund = sqrt((m sumsq - sum^2) / m^2) (the population form, as numpy.std), f_unique_weighted = sum / W[query],
+    f_weighted_cumulative = (the sum of `sum` over the query's rows so far) / W[query].  m = unique; NaN where a divisor is 0."""
+    nan = float("nan")
+    average, median, std, f_weighted, f_running = [], [], [], [], []
+    running, before = 0, None
+    weight = [int(w) for w in np.asarray(query_weight).tolist()]
+    for i, m, total, sq, med2 in zip(np.asarray(query).tolist(), np.asarray(unique).tolist(), np.asarray(sum_abund).tolist(), list(sumsq_abund),
+                                     np.asarray(median2_abund).tolist()):
+        m, total, sq, med2 = int(m), int(total), int(sq), int(med2)
+        running = total if i != before else running + total
+        before = i
+        average.append(total / m if m else nan)
+        median.append(med2 / 2)
+        std.append(math.sqrt((m * sq - total * total) / (m * m)) if m and m * sq >= total * total else nan)
+        f_weighted.append(total / weight[i] if weight[i] else nan)
+        f_running.append(running / weight[i] if weight[i] else nan)
+    return {"average_abund": np.array(average, dtype=np.float64), "median_abund": np.array(median, dtype=np.float64),
+            "std_abund": np.array(std, dtype=np.float64), "f_unique_weighted": np.array(f_weighted, dtype=np.float64),
+            "f_weighted_cumulative": np.array(f_running, dtype=np.float64)}
 
 
 def gather_chunks(engine, query_ids, options):
     """(query sizes, matched, query, db, unique, total) of the queries against the engine's resident search index: chunks of band_rows
     queries, each counted with its entries kept (Engine.screen_gather_count), given its thresholds and decomposed; the chunk's row
     offset is added.  options.kmer and options.scale must be the index's.  The index stays resident; the last chunk's rectangle, entries
-    and rows are dropped before this returns, on errors too (a count of no queries)."""
+    and rows are dropped before this returns, on errors too (a count of no queries).  With options.abundance seven more follow, in the
+    order of GatherResult's trailing fields: every chunk is counted with its abundances kept and the abundance pass runs after its
+    rounds (the pass's rank table is a third array of the rectangle's size beside the rectangle and its working copy)."""
     options = check_gather_options(options)
     info = getattr(engine, "_search", None)
     if not info or not info["n"]:
@@ -977,11 +1040,20 @@ def gather_chunks(engine, query_ids, options):
     rows = int(getattr(engine, "_band_rows", 0)) or default_search_rows(info["n"])
     sizes, matched = [np.zeros(0, np.uint32)], [np.zeros(0, np.uint32)]
     parts = [(np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.uint32), np.zeros(0, np.uint32))]
+    weights = [(np.zeros(0, np.uint64), np.zeros(0, np.uint64))]
+    stats = [(np.zeros(0, np.uint64), np.zeros(0, object), np.zeros(0, np.uint64), np.zeros(0, np.uint32), np.zeros(0, np.uint32))]
     try:
         for c0 in range(0, len(query_ids), rows):
-            size = engine.screen_gather_count(query_ids[c0:c0 + rows])
+            if options.abundance:
+                size, weight = engine.screen_gather_count(query_ids[c0:c0 + rows], abundance=True)
+                weights.append((weight, engine.screen_gather_abundance_matched()))
+            else:
+                size = engine.screen_gather_count(query_ids[c0:c0 + rows])
             matched.append(engine.screen_gather_matched())
             qi, db, unique, total = engine.screen_gather_rows(gather_thresholds(size, options.min_unique, options.min_fraction), options.max_ranks)
+            if options.abundance:
+                a_sum, a_sumsq, a_median2, a_min, a_max = engine.screen_gather_abundance()
+                stats.append((a_sum, sumsq_words(a_sumsq), a_median2, a_min, a_max))
             sizes.append(size)
             parts.append((qi + np.int32(c0), db, unique, total))
     finally:
@@ -989,4 +1061,7 @@ def gather_chunks(engine, query_ids, options):
             engine.screen_search_count([])
         except Exception:      # (the first error is the one to report)
             pass
-    return (np.concatenate(sizes), np.concatenate(matched), *(np.concatenate([p[i] for p in parts]) for i in range(4)))
+    plain = (np.concatenate(sizes), np.concatenate(matched), *(np.concatenate([p[i] for p in parts]) for i in range(4)))
+    if not options.abundance:
+        return plain
+    return (*plain, *(np.concatenate([w[i] for w in weights]) for i in range(2)), *(np.concatenate([t[i] for t in stats]) for i in range(5)))

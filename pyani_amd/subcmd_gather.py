@@ -14,8 +14,16 @@ Without exact= the collection's sequences are not needed after the index is buil
 before the queries are loaded.  With exact="anim" ONE anim_pairs call aligns (db genome as nucmer's reference, query) for the recorded
 rows only, and each member's identity and coverage (of the member) are added to the rows' table.  The screen's own numbers stay an
 ESTIMATE with its own files: `<outdir>/screen_output/gather_rows.tab` (one line per recorded genome) and `gather_summary.tab` (one per
-query).  A single engine only.  OUT OF SCOPE: a MultiEngine gather (the winner's k-mers live on one device: every round would need an
-exchange), abundance weighting, exact= from an index file, ANIb as exact=.
+query).  A single engine only.
+
+abundance=True: a query of reads holds a member's k-mers as many times as it covers them, and sourmash gather's
+abundance columns say how much of the sample each member accounts for.  The count then also keeps how many times the query holds each
+matched k-mer, and every row gets the statistics of the multiplicities of the k-mers it claimed: average_abund, median_abund, std_abund,
+f_unique_weighted, f_weighted_cumulative in the rows' table, weight, matched_weight, explained_weight, unexplained_weight in the
+summary.  Abundance does not move a winner (as in sourmash): the rows, their order, unique and total are the unweighted gather's.
+
+OUT OF SCOPE: a MultiEngine gather (the winner's k-mers live on one device: every round would need an exchange), FASTQ ingest (reads
+come in as FASTA), a weighted CHOICE of winners (sourmash does not do it either), exact= from an index file, ANIb as exact=.
 
 index=PATH: a saved search index takes the place of reading `db_dir` (None then), as for run_screen_search.
 """
@@ -51,14 +59,15 @@ def run_screen_gather(db_dir, query_dir, outdir=None, min_unique: Optional[int] 
                       scale: int = screen_mod.DEFAULT_SCALE, min_fraction: float = 0.0, max_ranks: int = screen_mod.GATHER_MAX_RANKS,
                       exact: Optional[str] = None, write_output: bool = False, engine: Optional[Engine] = None,
                       devices: Optional[List[int]] = None, workers: Optional[int] = None, db_batch: Optional[int] = None,
-                      index=None) -> GatherRun:
+                      index=None, abundance: bool = False) -> GatherRun:
     """Every FASTA file of `query_dir` decomposed into the genomes of `db_dir`.  min_unique is required (there is no default threshold:
     about 50 sampled 16-mers are shared by chance between two unrelated 5 Mb genomes at scale 256); outdir is needed for write_output
     only.  devices / workers are refused: a gather runs on a single engine.  An engine holds ONE search index: one already resident on a
     caller's `engine` is replaced by the one of `db_dir`, and the engine holds none when this returns (released on errors too).
     db_batch: the collection goes through the store that many files at a time, each batch after the first ADDED to the resident index
     (run_screen_search's text); the result does not change.  index: the path of a saved search index in place of
-    `db_dir` (None then): labels, lengths and every table column come from the file; without exact= and db_batch=."""
+    `db_dir` (None then): labels, lengths and every table column come from the file; without exact= and db_batch=.  abundance: the
+    abundance columns are added to both tables (the module's text); with it off both are what they were without the option."""
     if min_unique is None:
         raise ValueError("run_screen_gather needs min_unique= (there is no default threshold)")
     if write_output and outdir is None:
@@ -67,7 +76,7 @@ def run_screen_gather(db_dir, query_dir, outdir=None, min_unique: Optional[int] 
         raise ValueError(f"exact must be one of {EXACT}, not {exact!r}")
     if devices is not None or workers:
         raise ValueError("a gather runs on a single engine: devices= / workers= are not supported (the winner's k-mers live on one device)")
-    options = screen_mod.check_gather_options(screen_mod.GatherOptions(kmer, scale, min_unique, min_fraction, max_ranks))
+    options = screen_mod.check_gather_options(screen_mod.GatherOptions(kmer, scale, min_unique, min_fraction, max_ranks, abundance))
     index = check_index(index, db_dir, exact, db_batch, engine, None, None)
     db_batch = check_db_batch(db_batch, exact, engine, None, None)
     return _run(db_dir, query_dir, outdir, options, exact, write_output, engine or default_engine(), db_batch, index)
