@@ -190,6 +190,30 @@ int pg_anim_counters(pg_ctx* ctx, uint64_t* out, int reset);
 int pg_anim_forced_rects(pg_ctx* ctx, int32_t ref_id, int32_t qry_id, int strand, uint32_t n, const int32_t* rects, int32_t* errors,
                          int32_t* w_used, int32_t* status);
 
+/* Caller-chosen TRIMMED searches on the extender's search engines (MUMmer's own band: cut 600 below the best score, broken 200
+ * anti-diagonals after it — the match-to-match gaps, forward extensions, backward searches and the walks' own calls), so that tests can
+ * put a search on a window move, a window misfit, the break length, a stream end or a size class of the lane kernels instead of
+ * waiting for a genome pair to produce one.  The sibling of pg_anim_forced_rects, with its conventions: two resident genomes and one
+ * query strand; honoured only under PYANI_DEV_KNOBS=1 (PG_E_ARG without it); not while enqueued calls are in flight.
+ * searches[5 n]: (A0, B0, tA, tB, m_o) per search — start and target as stream positions (both inclusive, B in the coordinates of
+ * the query strand), m_o one of PG_SEARCH_FORWARD_ALIGN, PG_SEARCH_BACKWARD_SEARCH, each with or without PG_SEARCH_OPTIMAL_BIT
+ * (without: the target corner is the finish if the matrix was walked to its end; with: the best cell is).
+ * engine: which product code runs —
+ *   PG_SEARCH_PREPASS      the pre-pass kernels' engine (256-diagonal window only) calling its align(), one wave per search, items taken
+ *                          from a cursor in the chunk sizes of the gap, forward and backward kernels; a band the window does not hold
+ *                          (the engine's overflow: left to the walk in a batch) is held = 0
+ *   PG_SEARCH_WALK         the walks' engine calling its align(): 256 diagonals, then 512, then the wave's slice of global memory
+ *   PG_SEARCH_RUNG_256 / _RUNG_512 / _RUNG_GLOBAL   one rung of that ladder called directly, held = its own verdict
+ *   PG_SEARCH_LANES        FORWARD_ALIGN only: every search as a match-to-match gap (a chain of two one-base matches, start and target)
+ *                          through the batch's gap launches — gap list, the three one-gap-per-lane kernels (sides up to 16 / 32 / 59),
+ *                          and the wave kernel for every gap that is not small
+ * out[5 n]: endA, endB, errors, reached, held per search; held = 0: the engine asked for did not hold the band, the other fields are 0.
+ * PG_E_ARG (one bad search refuses the call) for a search with the forced bit or any other mode, a position outside its stream, a
+ * target on the wrong side of the start for the direction, a side above 10 000 bases (MAX_ALIGNMENT_LENGTH), a bad id, strand or engine. */
+enum { PG_SEARCH_PREPASS = 0, PG_SEARCH_WALK = 1, PG_SEARCH_RUNG_256 = 2, PG_SEARCH_RUNG_512 = 3, PG_SEARCH_RUNG_GLOBAL = 4, PG_SEARCH_LANES = 5 };
+enum { PG_SEARCH_FORWARD_ALIGN = 1, PG_SEARCH_BACKWARD_SEARCH = 2, PG_SEARCH_OPTIMAL_BIT = 8 };
+int pg_anim_searches(pg_ctx* ctx, int32_t ref_id, int32_t qry_id, int strand, int engine, uint32_t n, const int32_t* searches, int32_t* out);
+
 /* Work-memory budget of pg_anim_pairs: at most max_pairs ordered pairs and max_matches exact matches in flight (about 384 bytes
  * of device scratch per match, grown on demand; default 131072 pairs / 512 Mi matches, split over the context's two workers =
  * launches of up to 65536 pairs / 256 Mi matches, ~68 GB each).  Larger calls are split transparently; results do not depend on

@@ -60,6 +60,8 @@ static int EXP_BAND_SHIFT = 1;    //   ... centred between the start diagonal an
 static int STATS = 0;
 static long stat_maxw = 0, stat_cells = 0, stat_diags = 0, stat_forced_cells = 0, stat_hist[64];
 static const long NEG = -(1L << 40);
+static long stat_best_cells = 0;   // --searches: cells of the latest engine call that held its final best score (>= 2: the tie rules decided the finish)
+static long stat_tied_diagonals = 0;   // ... and its anti-diagonals whose best score was shared by two or more cells
 enum { DELETE = 0, INSERT = 1, MATCH = 2, NONE = 3 };   // DELETE consumes a B base, INSERT an A base
 enum { DIRECTION_BIT = 1, SEARCH_BIT = 2, FORCED_BIT = 4, OPTIMAL_BIT = 8 };
 static const unsigned FORWARD_ALIGN = 1, FORCED_FORWARD_ALIGN = 5, BACKWARD_SEARCH = 2;
@@ -106,6 +108,7 @@ static bool align_engine(const Seq& A, long Astart, long& Aend, const Seq& B, lo
   Diag.push_back(Diagonal{0, 0, std::vector<Node>(1)});
   Diag[0].I[0] = Node{{NEG, NEG, 0}, {NONE, NONE, NONE}, MATCH};
   long high_score = NEG * 2, FinishCt = 0, FinishJ = 0;
+  stat_best_cells = 0; stat_tied_diagonals = 0;
   long jlo = 0, jhi = 1;     // band of the next anti-diagonal, in j
   long Dct;
   for (Dct = 1; Dct <= N + M && (forced || Dct - FinishCt <= BREAK_LEN) && jlo <= jhi; ++Dct) {
@@ -124,6 +127,7 @@ static bool align_engine(const Seq& A, long Astart, long& Aend, const Seq& B, lo
     Diagonal& cur = Diag[Dct];
     const Diagonal& p1 = Diag[Dct - 1];
     const Diagonal* p2 = Dct >= 2 ? &Diag[Dct - 2] : nullptr;
+    long diag_best = NEG * 2, diag_best_cells = 0;
     for (long j = lo; j <= hi; ++j) {
       const long i = Dct - j;
       Node& c = cur.I[j - lo];
@@ -144,8 +148,13 @@ static bool align_engine(const Seq& A, long Astart, long& Aend, const Seq& B, lo
         c.used[MATCH] = p.mx;
       } else { c.v[MATCH] = NEG; c.used[MATCH] = NONE; }
       c.mx = max_state(c);
-      if (c.v[c.mx] > NEG / 2 && sc_of(c.v[c.mx]) >= sc_of(high_score)) { high_score = c.v[c.mx]; FinishCt = Dct; FinishJ = j; }
+      if (c.v[c.mx] > NEG / 2 && sc_of(c.v[c.mx]) >= sc_of(high_score)) {
+        stat_best_cells = sc_of(c.v[c.mx]) > sc_of(high_score) ? 1 : stat_best_cells + 1;
+        high_score = c.v[c.mx]; FinishCt = Dct; FinishJ = j;
+      }
+      if (c.v[c.mx] > NEG / 2) { if (sc_of(c.v[c.mx]) > sc_of(diag_best)) { diag_best = c.v[c.mx]; diag_best_cells = 1; } else if (sc_of(c.v[c.mx]) == sc_of(diag_best)) ++diag_best_cells; }
     }
+    if (diag_best_cells >= 2) ++stat_tied_diagonals;
     if (!keep_all && Dct >= 2) { std::vector<Node>().swap(Diag[Dct - 2].I); if (!STORED_BOUNDS) {} }
     // trim hopeless cells from the edges
     long tlo = lo, thi = hi;
@@ -515,11 +524,60 @@ static void mgaps(std::vector<Mem>& mem, std::vector<std::vector<Match>>& cluste
   }
 }
 
+
+// ---- --searches: the engine alone on directed searches (tests/search_cases.py) -----------------------------------------------------
+// stdin: <number of cases>, then per case: <name> <strand 0|1> <number of searches> / <reference sequence> / <query sequence as stored>
+// / one line "A0 B0 tA tB m_o" per search — 0-based positions, B in the coordinates of the strand, m_o = 1, 9, 2 or 10 (FORWARD_ALIGN,
+// BACKWARD_SEARCH, with or without OPTIMAL_BIT).  stdout, one line per search: <name> <k> <endA> <endB> <errors> <reached> <ties> <tied diagonals>:
+// 0-based finish, the errors of the path to it (columns that are not a match of two equal bases A, C, G, T; a backward search is run
+// with its path kept: SEARCH_BIT only says that nobody wants it), how many cells held the final best score, and on how many
+// anti-diagonals two or more cells shared that anti-diagonal's best score.
+static int searches_main() {
+  char word[256];
+  long n_cases = 0;
+  if (scanf("%ld", &n_cases) != 1) return 2;
+  auto read_seq = [](std::string& out) {      // 1-based: a pad in front
+    out.assign(1, '\0');
+    int ch;
+    while ((ch = getchar()) != EOF && (ch == ' ' || ch == '\n' || ch == '\r' || ch == '\t')) {}
+    for (; ch != EOF && ch != ' ' && ch != '\n' && ch != '\r' && ch != '\t'; ch = getchar()) out.push_back((char)ch);
+    return out.size() > 1;
+  };
+  for (long ci = 0; ci < n_cases; ++ci) {
+    int strand = 0;
+    long ns = 0;
+    std::string a, b;
+    if (scanf("%255s %d %ld", word, &strand, &ns) != 3 || !read_seq(a) || !read_seq(b)) { fprintf(stderr, "nucmer_oracle --searches: malformed input\n"); return 2; }
+    const std::string bs = strand ? revcomp(b) : b;
+    const Seq A{a.data(), (long)a.size() - 1}, B{bs.data(), (long)bs.size() - 1};
+    for (long k = 0; k < ns; ++k) {
+      long A0, B0, tA, tB;
+      unsigned m_o;
+      if (scanf("%ld %ld %ld %ld %u", &A0, &B0, &tA, &tB, &m_o) != 5) { fprintf(stderr, "nucmer_oracle --searches: malformed input\n"); return 2; }
+      const bool fwd = m_o & DIRECTION_BIT;
+      if ((m_o & ~(unsigned)(DIRECTION_BIT | SEARCH_BIT | OPTIMAL_BIT)) || fwd == (bool)(m_o & SEARCH_BIT) || A0 < 0 || tA < 0 || B0 < 0 || tB < 0 || A0 >= A.len ||
+          tA >= A.len || B0 >= B.len || tB >= B.len || (fwd ? tA < A0 || tB < B0 : tA > A0 || tB > B0)) { fprintf(stderr, "nucmer_oracle --searches: bad search\n"); return 2; }
+      long eA = tA + 1, eB = tB + 1;
+      std::string ops;
+      const bool reached = align_engine(A, A0 + 1, eA, B, B0 + 1, eB, &ops, m_o & ~(unsigned)SEARCH_BIT);
+      const long ties = stat_best_cells, tied = stat_tied_diagonals;
+      long i = 0, j = 0, errors = 0;
+      for (char op : ops) {
+        if (op == 'M') { ++i; ++j; if (!same_base(A.at(fwd ? A0 + i : A0 + 2 - i), B.at(fwd ? B0 + j : B0 + 2 - j))) ++errors; }
+        else { if (op == 'I') ++i; else ++j; ++errors; }
+      }
+      if ((fwd ? A0 + i : A0 + 2 - i) != eA || (fwd ? B0 + j : B0 + 2 - j) != eB) { fprintf(stderr, "nucmer_oracle --searches: the path does not end on the finish\n"); return 3; }
+      printf("%s %ld %ld %ld %ld %d %ld %ld\n", word, k, eA - 1, eB - 1, errors, reached ? 1 : 0, ties, tied);
+    }
+  }
+  return 0;
+}
 }  // namespace nuc
 
 int main(int argc, char** argv) {
   using namespace nuc;
-  if (argc < 3) { fprintf(stderr, "usage: nucmer_oracle ref.fna qry.fna [--maxmatch] [--delta]\n"); return 2; }
+  if (argc == 2 && !strcmp(argv[1], "--searches")) return searches_main();
+  if (argc < 3) { fprintf(stderr, "usage: nucmer_oracle ref.fna qry.fna [--maxmatch] [--delta]  |  nucmer_oracle --searches < cases\n"); return 2; }
   bool maxmatch = false, delta = false;
   for (int i = 3; i < argc; ++i) { if (!strcmp(argv[i], "--maxmatch")) maxmatch = true; if (!strcmp(argv[i], "--delta")) delta = true; }
   if (const char* e = getenv("NUC_MAX_DIFF")) MAX_DIFF = atol(e);

@@ -74,6 +74,7 @@ SIGNATURES = {
     "pg_anim_set_extender": (_int, [_vp, _int]),
     "pg_anim_counters": (_int, [_vp, _vp, _int]),
     "pg_anim_forced_rects": (_int, [_vp, _i32, _i32, _int, _u32, _vp, _vp, _vp, _vp]),
+    "pg_anim_searches": (_int, [_vp, _i32, _i32, _int, _int, _u32, _vp, _vp]),
     "pg_anim_pair_alignments": (_int, [_vp, _i32, _i32, _vp, _u32, _P(_u32)]),
     "pg_anim_alignments_batch": (_int, [_vp, _vp, _vp, _u64, _int, _int, _vp, _P(_u64)]),
     "pg_anim_alignments_read": (_int, [_vp, _vp, _vp, _vp]),

@@ -1051,6 +1051,30 @@ static void launch_forced(pg_ctx* ctx, const RefDesc* refs_d, const UnitDesc* un
                      cur + PNC_STRIPS_CUR, pn_n, gscratch, wide + 2 * (size_t)req_cap, cur + PNC_STRIPS_N);
 }
 
+// The match-to-match alignments of a work list of (unit, chain): the small gaps one LANE each by size class (tasks: 4 * task_cap
+// slots — three lane classes, then the list the wave engine takes), the rest one wave each; with the lane kernels off
+// (PYANI_ANIM_GAP_LANES=0) every gap on the wave engine, which needs gscratch for diag_only_waves(ctx) waves.  cur: the zeroed
+// cursor words.  Called by the batch's extension stage and by pg_anim_searches_run (development: caller-chosen gaps).
+static void launch_gaps(pg_ctx* ctx, const RefDesc* refs_d, const UnitDesc* units_d, const ClusterOut& O, const uint2* wl, uint32_t n_wl, PnGapTask* tasks,
+                        size_t task_cap, uint32_t* cur, pgn::PnGap* gaps, uint32_t* gscratch) {
+  const uint32_t pn_waves_pre = diag_only_waves(ctx);
+  const int lane_small = ctx->anim_gap_lanes;
+  if (lane_small) {     // small gaps: one LANE each, by size class
+    hipLaunchKernelGGL(anim_postnuc_gaplist_kernel, dim3((n_wl + 255) / 256), dim3(256), 0, cur_stream(ctx), units_d, O, wl, n_wl, tasks, task_cap,
+                       cur + PNC_GAP_LANE);
+    const dim3 lg((uint32_t)ctx->num_cu * 8u);
+    hipLaunchKernelGGL((anim_postnuc_gaplane_kernel<16>), lg, dim3(64), 0, cur_stream(ctx), refs_d, units_d, O, tasks, cur + PNC_GAP_LANE, gaps);
+    hipLaunchKernelGGL((anim_postnuc_gaplane_kernel<32>), lg, dim3(64), 0, cur_stream(ctx), refs_d, units_d, O, tasks + task_cap, cur + PNC_GAP_LANE + 1, gaps);
+    hipLaunchKernelGGL((anim_postnuc_gaplane_kernel<PN_SMALL>), lg, dim3(64), 0, cur_stream(ctx), refs_d, units_d, O, tasks + 2 * task_cap, cur + PNC_GAP_LANE + 2, gaps);
+  }
+  if (lane_small)
+    hipLaunchKernelGGL(anim_postnuc_gapbig_kernel, dim3(pn_waves_pre), dim3(64), 0, cur_stream(ctx), refs_d, units_d, O, cur + PNC_GAP_BIG, gaps,
+                       tasks + 3 * task_cap, cur + PNC_GAP_WAVE);
+  else
+    hipLaunchKernelGGL(anim_postnuc_gap_kernel, dim3(pn_waves_pre), dim3(64), 0, cur_stream(ctx), refs_d, units_d, O, wl, n_wl, cur + PNC_GAP_BIG, gaps,
+                       gscratch);
+}
+
 // A4x: MUMmer's own extension algorithm — the (unit, chain) work list, the pre-passes over it (match-to-match gaps, forward
 // extensions, backward searches), the pairs' walks on persistent waves, then the forced re-alignments the walks deferred.
 static int extend_stage(Batch& B) {
@@ -1102,21 +1126,7 @@ static int extend_stage(Batch& B) {
     PG_HIP(ctx, hipMemcpyAsync(A->choff_d, B.choff.data(), B.choff.size() * 4, hipMemcpyHostToDevice, cur_stream(ctx)));
     hipLaunchKernelGGL(anim_wl_kernel, dim3(n_units), dim3(64), 0, cur_stream(ctx), A->choff_d, A->wl_d);
     pg_prof_begin(ctx, PG_K_ANIM_GAPS);
-    const int lane_small = ctx->anim_gap_lanes;
-    if (lane_small) {     // small gaps: one LANE each, by size class
-      hipLaunchKernelGGL(anim_postnuc_gaplist_kernel, dim3((uint32_t)((n_wl + 255) / 256)), dim3(256), 0, cur_stream(ctx), A->units_d, O, A->wl_d,
-                         (uint32_t)n_wl, A->pn_tasks, task_cap, cur + PNC_GAP_LANE);
-      const dim3 lg((uint32_t)ctx->num_cu * 8u);
-      hipLaunchKernelGGL((anim_postnuc_gaplane_kernel<16>), lg, dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, O, A->pn_tasks, cur + PNC_GAP_LANE, A->pn_gaps);
-      hipLaunchKernelGGL((anim_postnuc_gaplane_kernel<32>), lg, dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, O, A->pn_tasks + task_cap, cur + PNC_GAP_LANE + 1, A->pn_gaps);
-      hipLaunchKernelGGL((anim_postnuc_gaplane_kernel<PN_SMALL>), lg, dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, O, A->pn_tasks + 2 * task_cap, cur + PNC_GAP_LANE + 2, A->pn_gaps);
-    }
-    if (lane_small)
-      hipLaunchKernelGGL(anim_postnuc_gapbig_kernel, dim3(pn_waves_pre), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, O, cur + PNC_GAP_BIG,
-                         A->pn_gaps, A->pn_tasks + 3 * task_cap, cur + PNC_GAP_WAVE);
-    else
-      hipLaunchKernelGGL(anim_postnuc_gap_kernel, dim3(pn_waves_pre), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, O, A->wl_d, (uint32_t)n_wl,
-                         cur + PNC_GAP_BIG, A->pn_gaps, A->pn_gscratch);
+    launch_gaps(ctx, A->refs_d, A->units_d, O, A->wl_d, (uint32_t)n_wl, A->pn_tasks, task_cap, cur, A->pn_gaps, A->pn_gscratch);
     pg_prof_end(ctx);
     pg_prof_begin(ctx, PG_K_ANIM_FWD);
     hipLaunchKernelGGL(anim_postnuc_fwd_kernel, dim3(pn_waves_pre), dim3(64), 0, cur_stream(ctx), A->refs_d, A->units_d, O, A->wl_d, (uint32_t)n_wl,
@@ -1210,6 +1220,133 @@ int pg_anim_forced_rects_run(pg_ctx* ctx, int32_t ref_id, int32_t qry_id, int st
     status[i] = failed ? 2 : 0;
     errors[i] = failed ? 0 : dst[i].errors;
     w_used[i] = failed ? 0 : reqs[slot_of[i]].w;
+  }
+  return PG_OK;
+}
+
+// Development (pg_anim_searches): caller-chosen trimmed searches (A0, B0, tA, tB, m_o) of one (reference, query strand) on the engine
+// asked for.  Ids, strand, engine and pointers were checked by the caller; the searches are checked here, next to the engines' limits.
+// PREPASS / WALK / RUNG_*: anim_postnuc_searches_kernel, one wave per search (PREPASS: one launch per pre-pass kernel, with that
+// kernel's cursor chunk — match-to-match gaps 8, forward extensions 4, backward searches 8).  LANES: every search a chain of two
+// one-base matches (start, target) in a ClusterOut of one unit, through launch_gaps — the batch's own launches; a gap no kernel
+// answered comes back as held = 0.  out[5 n]: endA, endB, errors, reached, held.
+int pg_anim_searches_run(pg_ctx* ctx, int32_t ref_id, int32_t qry_id, int strand, int engine, uint32_t n, const int32_t* searches, int32_t* out) {
+  const PgGenome& G = ctx->genomes[ref_id];
+  const PgGenome& H = ctx->genomes[qry_id];
+  std::vector<PnSearchReq> reqs(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const int64_t A0 = searches[5 * i], B0 = searches[5 * i + 1], tA = searches[5 * i + 2], tB = searches[5 * i + 3];
+    const unsigned m_o = (unsigned)searches[5 * i + 4];
+    if (m_o & pgn::FORCED_BIT) return pg_fail(ctx, PG_E_ARG, "pg_anim_searches: a forced run (FORCED_BIT) is not a search: pg_anim_forced_rects has those");
+    if (m_o != pgn::FORWARD_ALIGN && m_o != (pgn::FORWARD_ALIGN | pgn::OPTIMAL_BIT) && m_o != pgn::BACKWARD_SEARCH && m_o != (pgn::BACKWARD_SEARCH | pgn::OPTIMAL_BIT))
+      return pg_fail(ctx, PG_E_ARG, "pg_anim_searches: m_o must be FORWARD_ALIGN or BACKWARD_SEARCH, with or without OPTIMAL_BIT");
+    if (engine == PN_SEARCH_LANES && m_o != pgn::FORWARD_ALIGN) return pg_fail(ctx, PG_E_ARG, "pg_anim_searches: LANES takes FORWARD_ALIGN searches only (match-to-match gaps)");
+    if (A0 < 0 || A0 >= (int64_t)G.stream_len || tA < 0 || tA >= (int64_t)G.stream_len || B0 < 0 || B0 >= (int64_t)H.stream_len || tB < 0 || tB >= (int64_t)H.stream_len)
+      return pg_fail(ctx, PG_E_ARG, "pg_anim_searches: a position outside its stream");
+    const bool fwd = m_o & pgn::DIRECTION_BIT;
+    const int64_t N = fwd ? tA - A0 + 1 : A0 - tA + 1, M = fwd ? tB - B0 + 1 : B0 - tB + 1;
+    if (N < 1 || M < 1) return pg_fail(ctx, PG_E_ARG, "pg_anim_searches: a target on the wrong side of the start for the direction");
+    if (N > pgn::MAX_ALIGNMENT_LENGTH || M > pgn::MAX_ALIGNMENT_LENGTH)
+      return pg_fail(ctx, PG_E_ARG, "pg_anim_searches: a side longer than one engine call aligns (MAX_ALIGNMENT_LENGTH)");
+    reqs[i] = PnSearchReq{(int32_t)A0, (int32_t)B0, (int32_t)tA, (int32_t)tB, m_o};
+  }
+  if (engine == PN_SEARCH_LANES && !ctx->anim_gap_lanes) return pg_fail(ctx, PG_E_ARG, "pg_anim_searches: LANES with the lane kernels switched off (PYANI_ANIM_GAP_LANES=0)");
+  AnimScratch* A = anim_scratch(ctx);
+  (void)hipGetLastError();
+  const RefDesc ref{ctx->d_codes + G.arena_start / 16, ctx->d_mask + G.arena_start / 32, (int32_t)G.stream_len, nullptr, 0};
+  const UnitDesc unit{ctx->d_codes + H.arena_start / 16, ctx->d_mask + H.arena_start / 32, (int32_t)H.stream_len, nullptr, 0, strand, 0, 0};
+  PgDevBuf<RefDesc> refs_d;
+  PgDevBuf<UnitDesc> units_d;
+  PgDevBuf<uint32_t> cur_d;
+  PG_HIP(ctx, refs_d.reserve(1));
+  PG_HIP(ctx, units_d.reserve(1));
+  PG_HIP(ctx, cur_d.reserve(PNC_WORDS));
+  hipStream_t st = cur_stream(ctx);
+  PG_HIP(ctx, hipMemcpyAsync(refs_d, &ref, sizeof(ref), hipMemcpyHostToDevice, st));
+  PG_HIP(ctx, hipMemcpyAsync(units_d, &unit, sizeof(unit), hipMemcpyHostToDevice, st));
+  PG_HIP(ctx, hipMemsetAsync(cur_d, 0, PNC_WORDS * 4, st));
+  if (engine == PN_SEARCH_LANES) {
+    // the chains: matches 2 i (the start base) and 2 i + 1 (the target base) of chain i, the gap's answer at match slot 2 i
+    std::vector<Match> cm(2 * (size_t)n);
+    std::vector<Chain> chains(2 * (size_t)n, Chain{0, 0, strand, 0, 0});
+    std::vector<uint2> wl(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      cm[2 * i] = Match{reqs[i].A0, reqs[i].B0, 1, strand};
+      cm[2 * i + 1] = Match{reqs[i].tA, reqs[i].tB, 1, strand};
+      chains[i] = Chain{(int32_t)(2 * i), 2, strand, 0, 0};
+      wl[i] = make_uint2(0u, i);
+    }
+    const uint32_t moff[2] = {0u, 2 * n};
+    PgDevBuf<uint32_t> moff_d;
+    PgDevBuf<Match> cm_d;
+    PgDevBuf<Chain> chains_d;
+    PgDevBuf<uint2> wl_d;
+    PgDevBuf<PnGapTask> tasks_d;
+    PgDevBuf<pgn::PnGap> gaps_d;
+    const size_t task_cap = n;
+    PG_HIP(ctx, moff_d.reserve(2));
+    PG_HIP(ctx, reserve_all(2 * (size_t)n, 2 * (size_t)n, cm_d, chains_d, gaps_d));
+    PG_HIP(ctx, wl_d.reserve(n));
+    PG_HIP(ctx, tasks_d.reserve(4 * task_cap));
+    PG_HIP(ctx, hipMemcpyAsync(moff_d, moff, sizeof(moff), hipMemcpyHostToDevice, st));
+    PG_HIP(ctx, hipMemcpyAsync(cm_d, cm.data(), cm.size() * sizeof(Match), hipMemcpyHostToDevice, st));
+    PG_HIP(ctx, hipMemcpyAsync(chains_d, chains.data(), chains.size() * sizeof(Chain), hipMemcpyHostToDevice, st));
+    PG_HIP(ctx, hipMemcpyAsync(wl_d, wl.data(), wl.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
+    PG_HIP(ctx, hipMemsetAsync(gaps_d, 0xFF, 2 * (size_t)n * sizeof(pgn::PnGap), st));      // reached = -1: not answered
+    const ClusterOut O{moff_d, cm_d, chains_d, nullptr, nullptr, nullptr};
+    launch_gaps(ctx, refs_d, units_d, O, wl_d, n, tasks_d, task_cap, cur_d, gaps_d, nullptr);
+    PG_HIP(ctx, hipGetLastError());
+    std::vector<pgn::PnGap> gaps(2 * (size_t)n);
+    PG_HIP(ctx, hipMemcpyAsync(gaps.data(), gaps_d, gaps.size() * sizeof(pgn::PnGap), hipMemcpyDeviceToHost, st));
+    PG_HIP(ctx, hipStreamSynchronize(st));
+    for (uint32_t i = 0; i < n; ++i) {
+      const pgn::PnGap& g = gaps[2 * i];
+      const bool held = g.reached >= 0;
+      int32_t* o = out + 5 * (size_t)i;
+      o[0] = held ? g.eA : 0; o[1] = held ? g.eB : 0; o[2] = held ? g.errors : 0; o[3] = held ? g.reached : 0; o[4] = held ? 1 : 0;
+    }
+    return PG_OK;
+  }
+  // the lists: one for every engine but PREPASS, which takes its searches as the three pre-pass kernels would (cursor chunks 8 / 4 / 8)
+  std::vector<uint32_t> list;
+  uint32_t first[4] = {0u, 0u, 0u, 0u};
+  const uint32_t chunk_of[3] = {8u, 4u, 8u};
+  const int n_lists = engine == PN_SEARCH_PREPASS ? 3 : 1;
+  for (int l = 0; l < n_lists; ++l) {
+    for (uint32_t i = 0; i < n; ++i) {
+      const unsigned m_o = reqs[i].m_o;
+      const int cls = !(m_o & pgn::DIRECTION_BIT) ? 2 : (m_o & pgn::OPTIMAL_BIT) ? 1 : 0;
+      if (n_lists == 1 || cls == l) list.push_back(i);
+    }
+    first[l + 1] = (uint32_t)list.size();
+  }
+  const bool scratch = engine == PN_SEARCH_WALK || engine == PN_SEARCH_RUNG_GLOBAL;
+  const uint32_t max_waves = scratch ? (uint32_t)ctx->num_cu * 8u : diag_only_waves(ctx);
+  PgDevBuf<PnSearchReq> reqs_d;
+  PgDevBuf<PnSearchOut> out_d;
+  PgDevBuf<uint32_t> list_d;
+  PG_HIP(ctx, reqs_d.reserve(n));
+  PG_HIP(ctx, out_d.reserve(n));
+  PG_HIP(ctx, list_d.reserve(n));
+  if (scratch) PG_HIP(ctx, A->pn_gscratch.reserve((size_t)(n < max_waves ? n : max_waves) * PN_GLOBAL_WORDS));
+  PG_HIP(ctx, hipMemcpyAsync(reqs_d, reqs.data(), (size_t)n * sizeof(PnSearchReq), hipMemcpyHostToDevice, st));
+  PG_HIP(ctx, hipMemcpyAsync(list_d, list.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+  PG_HIP(ctx, hipMemsetAsync(out_d, 0, (size_t)n * sizeof(PnSearchOut), st));
+  for (int l = 0; l < n_lists; ++l) {
+    const uint32_t nl = first[l + 1] - first[l];
+    if (!nl) continue;
+    const uint32_t chunk = engine == PN_SEARCH_PREPASS ? chunk_of[l] : 1u;
+    const uint32_t turns = (nl + chunk - 1) / chunk;
+    hipLaunchKernelGGL(anim_postnuc_searches_kernel, dim3(turns < max_waves ? turns : max_waves), dim3(64), 0, st, refs_d, units_d, reqs_d, list_d + first[l],
+                       nl, chunk, engine, cur_d + l, out_d, scratch ? A->pn_gscratch.p : nullptr);
+  }
+  PG_HIP(ctx, hipGetLastError());
+  std::vector<PnSearchOut> res(n);
+  PG_HIP(ctx, hipMemcpyAsync(res.data(), out_d, (size_t)n * sizeof(PnSearchOut), hipMemcpyDeviceToHost, st));
+  PG_HIP(ctx, hipStreamSynchronize(st));
+  for (uint32_t i = 0; i < n; ++i) {
+    int32_t* o = out + 5 * (size_t)i;
+    o[0] = res[i].eA; o[1] = res[i].eB; o[2] = res[i].errors; o[3] = res[i].reached; o[4] = res[i].held;
   }
   return PG_OK;
 }

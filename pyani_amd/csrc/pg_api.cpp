@@ -797,6 +797,28 @@ int pg_anim_forced_rects(pg_ctx* ctx, int32_t ref_id, int32_t qry_id, int strand
   catch (const std::bad_alloc&) { return pg_fail(ctx, PG_E_NOMEM, "out of host memory in pg_anim_forced_rects"); }
 }
 
+// development: see the header (the searches themselves are checked by pg_anim_searches_run, next to the engines' limits)
+int pg_anim_searches(pg_ctx* ctx, int32_t ref_id, int32_t qry_id, int strand, int engine, uint32_t n, const int32_t* searches, int32_t* out) {
+  if (!ctx) return PG_E_ARG;
+  const char* on = pg_dev_env("PYANI_DEV_KNOBS");
+  if (!on) return pg_fail(ctx, PG_E_ARG, "pg_anim_searches is a development entry (PYANI_DEV_KNOBS=1)");
+  if (n && (!searches || !out)) return pg_fail(ctx, PG_E_ARG, "bad argument");
+  if (strand != 0 && strand != 1) return pg_fail(ctx, PG_E_ARG, "strand must be 0 or 1");
+  if (engine < PG_SEARCH_PREPASS || engine > PG_SEARCH_LANES) return pg_fail(ctx, PG_E_ARG, "engine must be one of PG_SEARCH_*");
+  if (ref_id < 0 || (size_t)ref_id >= ctx->genomes.size() || qry_id < 0 || (size_t)qry_id >= ctx->genomes.size())
+    return pg_fail(ctx, PG_E_ARG, "genome id out of range");
+  if (!n) return PG_OK;
+  PG_HIP(ctx, hipSetDevice(ctx->device));
+  {
+    std::lock_guard<std::mutex> lk(ctx->anim_async_mu);
+    if (ctx->anim_async[0].busy || ctx->anim_async[1].busy) return pg_fail(ctx, PG_E_ARG, "pg_anim_searches while enqueued calls are in flight: fetch them first");
+  }
+  int rc;
+  if ((rc = pg_upload(ctx))) return rc;
+  try { return pg_anim_searches_run(ctx, ref_id, qry_id, strand, engine, n, searches, out); }
+  catch (const std::bad_alloc&) { return pg_fail(ctx, PG_E_NOMEM, "out of host memory in pg_anim_searches"); }
+}
+
 // slot_base / lane_workers: which of the context's worker slots the call drives (pg_anim_pairs: all of them from 0; the lanes of
 // pg_anim_pairs_enqueue: two each); budget_div: the share of the match budget one of its workers may take
 static int anim_pairs_body(pg_ctx* ctx, const int32_t* ref_ids, const int32_t* qry_ids, uint64_t n_pairs, int maxmatch,

@@ -268,6 +268,8 @@ int pg_anim_counters_read(pg_ctx* ctx, uint64_t* out /*[64]*/, int reset);
 // development (pg_anim_forced_rects): n checked rectangles (A0, A1, B0, B1) of one (reference, query strand) through the forced launches
 int pg_anim_forced_rects_run(pg_ctx* ctx, int32_t ref_id, int32_t qry_id, int strand, uint32_t n, const int32_t* rects, int32_t* errors,
                              int32_t* w_used, int32_t* status);
+// development (pg_anim_searches): n checked trimmed searches (A0, B0, tA, tB, m_o) of one (reference, query strand) on the engine asked for
+int pg_anim_searches_run(pg_ctx* ctx, int32_t ref_id, int32_t qry_id, int strand, int engine, uint32_t n, const int32_t* searches, int32_t* out);
 void pg_anim_set_sink(PgAlnSink* sink);           // thread-local; nullptr = none
 void pg_anim_drop_lists(pg_ctx* ctx);   // per-genome seed lists: must go when the genome store is cleared
 void pg_sketch_drop(pg_ctx* ctx);       // ... and the sketches of the sketch mode (pg_sketch.hip)

@@ -322,6 +322,7 @@ struct DiagWaveEmu {
   const RefT& R;
   const QryT& Q;
   long cells = 0, calls = 0, moves = 0, fails = 0;
+  long moves_down = 0, moves_up = 0;      // (development: moves towards lower / higher diagonals — tools/anim_debug/searches.cpp)
   uint32_t last_cells = 0, last_wmax = 0;
   DiagRegs<DPL> T[64];
   template <int PAR, bool NORM>
@@ -384,6 +385,7 @@ struct DiagWaveEmu {
         for (int l = 0; l < 64; ++l) T[l] = U[l];
         C.template window_move<DPL>(n);
         ++moves;
+        if (n > 0) ++moves_up; else ++moves_down;
       }
       if (C.Dct == C.next_refill) { if (C.Dct & 1) refill<1, !FORCED>(C, Astart, Bstart); else refill<0, !FORCED>(C, Astart, Bstart); C.next_refill = C.Dct + 32; }
       C.template note_cells<true>();
@@ -426,7 +428,7 @@ struct DiagWaveEngine {
   DiagWaveEmu<24, RefT, QryT> e24;
   DiagWaveEmu<32, RefT, QryT> e32;
   long fallbacks = 0;
-  void (*fallback_log)(int32_t N, int32_t M, unsigned m_o, int32_t band_w) = nullptr;      // development: what did not fit
+  void (*fallback_log)(int32_t Astart, int32_t Bstart, int32_t Aend, int32_t Bend, int strand, unsigned m_o, int32_t band_w) = nullptr;      // development: what did not fit (the call as it was made: start, target, the query's strand)
   DiagWaveEngine(const RefT& R, const QryT& Q, Cell* d0, Cell* d1, Cell* d2, int32_t cap)
       : slow{R, Q, d0, d1, d2, cap}, e2{R, Q}, e4{R, Q}, e6{R, Q}, e8{R, Q}, e12{R, Q}, e16{R, Q}, e24{R, Q}, e32{R, Q} {}
   bool gap_ready(int32_t, PnGap&) const { return false; }
@@ -474,7 +476,7 @@ struct DiagWaveEngine {
     }
     if (done) { Aend = a; Bend = b; return reached; }
     ++fallbacks;
-    if (fallback_log) fallback_log(N, M, m_o, band_w);
+    if (fallback_log) fallback_log(Astart, Bstart, Aend, Bend, (int)slow.Q.rc, m_o, band_w);
     return slow.run(Astart, Aend, Bstart, Bend, m_o, band_w, errors, &score);
   }
   bool align(int32_t Astart, int32_t& Aend, int32_t Bstart, int32_t& Bend, unsigned m_o, int32_t& errors) {

@@ -1348,3 +1348,59 @@ __global__ __launch_bounds__(128) void anim_postnuc_kernel(const RefDesc* __rest
   __shared__ int32_t s_sync[4];
   pn_walk_body(refs, units, n_pairs, O, cursor, pn, fused, pn_n, gscratch, reqs, n_reqs, req_cap, gaps, fwd, pair_order, pieces, n_pieces, choff, bwd, tlog, born, s_p, s_sync);
 }
+
+// ---- development: directed searches (pg_anim_searches) ------------------------------------------------------------------------
+// Caller-chosen trimmed searches of ONE (reference, query strand), one wave per search, on the product's own engines: nothing here
+// but the cursor loop of the pre-pass kernels and the calls the product makes.  engine (wave-uniform):
+//   PREPASS      PnWaveEngineDiag::align as the gap-big / forward / backward kernels call it (the host launches one list per kernel,
+//                with that kernel's chunk size); its overflow comes back as held = 0
+//   WALK         PnWaveEngine::align with the wave's slice of global scratch: the ladder 256 -> 512 -> global memory as the walk runs it
+//   RUNG_*       pn_align_diag<4> / pn_align_diag<8> / pn_align_wave<true> called directly, held = their own return value
+// A search that was not held leaves zeros.  (LANES does not come here: the host builds chains and runs launch_gaps.)
+enum PnSearchEngine : int { PN_SEARCH_PREPASS = 0, PN_SEARCH_WALK = 1, PN_SEARCH_RUNG_256 = 2, PN_SEARCH_RUNG_512 = 3, PN_SEARCH_RUNG_GLOBAL = 4, PN_SEARCH_LANES = 5 };
+struct PnSearchReq { int32_t A0, B0, tA, tB; uint32_t m_o; };
+struct PnSearchOut { int32_t eA, eB, errors, reached, held; };
+__global__ __launch_bounds__(64) void anim_postnuc_searches_kernel(const RefDesc* __restrict__ refs, const UnitDesc* __restrict__ units,
+                                                                   const PnSearchReq* __restrict__ reqs, const uint32_t* __restrict__ list, uint32_t n,
+                                                                   uint32_t chunk, int engine_, uint32_t* __restrict__ cursor,
+                                                                   PnSearchOut* __restrict__ out, uint32_t* __restrict__ gscratch) {
+  __shared__ uint32_t s_i;
+  const int lane = threadIdx.x & 63;
+  const int engine = pn_uni((int32_t)engine_);
+  pn_stats_begin();
+  const UnitDesc U = units[0];
+  const RefDesc Rd = refs[U.ref];
+  const SeqView R{Rd.codes, Rd.mask, Rd.len};
+  const StrandView Q{SeqView{U.codes, U.mask, U.len}, U.strand};
+  uint32_t* const glob = gscratch ? gscratch + (size_t)blockIdx.x * PN_GLOBAL_WORDS : nullptr;
+  for (;;) {
+    __syncthreads();
+    if (lane == 0) s_i = atomicAdd(cursor, chunk);
+    __syncthreads();
+    const uint32_t i0 = pn_uni(s_i);
+    if (i0 >= n) break;
+    const uint32_t i1 = i0 + chunk < n ? i0 + chunk : n;
+    for (uint32_t i = i0; i < i1; ++i) {
+      const uint32_t k = pn_uni(list[i]);
+      const PnSearchReq S = reqs[k];
+      const int32_t A0 = pn_uni(S.A0), B0 = pn_uni(S.B0);
+      const unsigned m_o = pn_uni(S.m_o);
+      __builtin_assume(m_o < 16u);      // (checked by the host: direction, search and best-cell bits, as every caller of the engines passes — the engines' own code stays the batch's, instruction for instruction)
+      int32_t a = pn_uni(S.tA), b = pn_uni(S.tB), err = 0, score = 0;
+      bool reached = false, held = false;
+      if (engine == PN_SEARCH_PREPASS) {
+        PnWaveEngineDiag eng{R, Q, nullptr, nullptr, 0, nullptr, nullptr, 0u, 0u, nullptr, nullptr};
+        reached = eng.align(A0, a, B0, b, m_o, err);
+        held = !eng.overflow;
+      } else if (engine == PN_SEARCH_WALK) {
+        PnWaveEngine eng{R, Q, nullptr, glob, 0, nullptr, nullptr, 0u, 0u, nullptr, nullptr};
+        reached = eng.align(A0, a, B0, b, m_o, err);
+        held = !eng.overflow;
+      } else if (engine == PN_SEARCH_RUNG_256) held = pn_align_diag<4>(R, Q, A0, a, B0, b, m_o, -1, err, score, reached);
+      else if (engine == PN_SEARCH_RUNG_512) held = pn_align_diag<8>(R, Q, A0, a, B0, b, m_o, -1, err, score, reached);
+      else if (engine == PN_SEARCH_RUNG_GLOBAL) held = pn_align_wave<true>(R, Q, glob, A0, a, B0, b, m_o, -1, err, score, reached);
+      if (lane == 0) out[k] = held ? PnSearchOut{a, b, err, reached ? 1 : 0, 1} : PnSearchOut{0, 0, 0, 0, 0};
+    }
+  }
+  pn_stats_flush();
+}

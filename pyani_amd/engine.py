@@ -211,6 +211,19 @@ class Engine:
                                                   w_used.ctypes.data, status.ctypes.data))
         return errors, w_used, status
 
+    SEARCH_ENGINES = {"PREPASS": 0, "WALK": 1, "RUNG_256": 2, "RUNG_512": 3, "RUNG_GLOBAL": 4, "LANES": 5}
+    SEARCH_FORWARD_ALIGN, SEARCH_BACKWARD_SEARCH, SEARCH_OPTIMAL_BIT = 1, 2, 8
+
+    def anim_searches(self, ref_id: int, qry_id: int, strand: int, engine, searches) -> np.ndarray:
+        """Development (pg_anim_searches, honoured under PYANI_DEV_KNOBS=1): trimmed searches (A0, B0, tA, tB, m_o) — stream positions,
+        B in strand coordinates — on one of the extender's search engines (a name of SEARCH_ENGINES or its number).  Returns int32[n, 5]:
+        endA, endB, errors, reached, held per search (held 0: the engine did not hold the band, the rest is 0)."""
+        s = np.ascontiguousarray(searches, dtype=np.int32).reshape(-1, 5)
+        out = np.zeros((len(s), 5), dtype=np.int32)
+        e = self.SEARCH_ENGINES[engine] if isinstance(engine, str) else int(engine)
+        self._check(self.lib.pg_anim_searches(self._h, int(ref_id), int(qry_id), int(strand), e, len(s), s.ctypes.data, out.ctypes.data))
+        return out
+
     def anim_set_batch_budget(self, max_pairs: int, max_matches: int) -> None:
         self._check(self.lib.pg_anim_set_batch_budget(self._h, int(max_pairs), int(max_matches)))
 
