@@ -510,6 +510,47 @@ int pg_screen_components_read(pg_ctx* ctx, int32_t* root_out, uint64_t* entries_
 int pg_screen_components_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
 int pg_screen_components_release(pg_ctx* ctx);
 
+/* ---- screen, the representatives: one genome per cluster by the greedy rule.  The list of entries (a[e], b[e],
+ * weight[e]) over n nodes is that of the components: unsorted, a pair in one direction or both, once or several times, direction ignored,
+ * an entry with a[e] == b[e] ignored altogether; weight == NULL weighs every entry 1.  score[v] (uint64, greater is better, ties to the
+ * smaller index) gives the priority: order = the nodes by (score descending, index ascending), rank its inverse.
+ *   1. Walk `order`: a node none of whose neighbours is a representative yet becomes one.
+ *   2. AFTER all representatives are known, every other node v goes to the representative neighbour r of the greatest pair weight (the
+ *      maximum of weight[e] over the entries joining v and r), ties to the r of smaller rank — a representative of lower priority than v
+ *      may take v.
+ *   rep[v] int32   the representative v belongs to; rep[v] == v for a representative
+ *   via[v] uint32  the pair weight v was assigned by; 0 for a representative
+ * All integers that depend on neither the order, direction or duplication of the list nor any schedule
+ * (pyani_amd.screen.representatives_of_pairs is the statement).  One stable radix sort of (~score, index) gives the ranks.  The walk is
+ * the lexicographically first maximal independent set under `rank`, reproduced by rounds of three launches over the entries — both ends
+ * undecided: the end of larger rank is stamped; an undecided node not stamped becomes a representative; an undecided end opposite a
+ * representative is covered — so that a node becomes a representative exactly when all its neighbours of higher priority are covered.
+ * Every round decides at least the undecided node of smallest rank: at most n rounds (1-4 on clique-like graphs, n / 2 on a chain whose
+ * scores fall along it), issued in batches with one read of the control words per batch.  The assignment is a 64-bit atomic maximum of
+ * weight << 32 | 0xFFFFFFFF - rank[r] per covered node.  No thread waits for another.
+ * pg_screen_representatives takes the list from the host and uploads it WHOLE (12 bytes an entry, 8 without weights: the rounds read it
+ * repeatedly), 1 <= n <= 2^20.  PG_E_ARG, checked before anything is copied or replaced: n outside that range, an index outside [0, n),
+ * m > 0 with a NULL a or b, a NULL score.  *n_representatives_out = the nodes with rep[v] == v.
+ * pg_screen_index_representatives takes it from the resident index instead: ALL bands are counted and selected exactly as
+ * pg_screen_index_select does (same need, rule and band setting), and every band's kept triples with a < b — the rule is symmetric, so
+ * half is the whole graph — are appended to a list on the device, 12 bytes per undirected kept pair; no pair is copied to the host.
+ * *n_pairs_out = the kept cells (both directions), what pg_screen_index_select reports; the result is that of pg_screen_representatives
+ * over the list pg_screen_index_select + _read return.  The index, its latest selection and pg_screen_index_last are left as they were.
+ * PG_E_ARG as pg_screen_index_select (no resident index, a `need` length that is not the index's n), and for a NULL score.
+ * The result stays RESIDENT in a state of its own, independent of the resident matrix, the two indexes and the components, until the next
+ * ACCEPTED representatives call (a refused one leaves it readable; an allocation that fails replaces nothing),
+ * pg_screen_representatives_release (PG_OK when there is none), pg_clear_genomes or pg_destroy.  pg_screen_representatives_read copies it
+ * out: n entries each; PG_E_ARG when there is none.
+ * pg_screen_representatives_last: counts_out[6] = n, entries worked (the list entry: those with a != b; the index entry: the undirected
+ * kept pairs), entries ignored (a == b), representatives, rounds, launches of the round kernels; ms_out[4] = band count + select (the
+ * index path only), rank sort, rounds, assign milliseconds (HIP events on the context's stream); all 0 when nothing is resident. */
+int pg_screen_representatives(pg_ctx* ctx, const int32_t* a, const int32_t* b, const uint32_t* weight, uint64_t m, uint32_t n, const uint64_t* score,
+                              uint32_t* n_representatives_out);
+int pg_screen_index_representatives(pg_ctx* ctx, const uint32_t* need, uint32_t n, const uint64_t* score, uint32_t* n_representatives_out, uint64_t* n_pairs_out);
+int pg_screen_representatives_read(pg_ctx* ctx, int32_t* rep_out, uint32_t* via_out);
+int pg_screen_representatives_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
+int pg_screen_representatives_release(pg_ctx* ctx);
+
 /* ---- screen, the search: new genomes against a resident collection.  S(g), size, kmer and scale as for
  * pg_screen_matrix.  A collection ("db") of n <= 2^20 genomes is indexed once; then, per call, q query genomes are placed against it:
  *   hits[i][b] = |S(query i) & S(db b)|, a q x n rectangle of uint32, row-major

@@ -111,6 +111,11 @@ SIGNATURES = {
     "pg_screen_components_read": (_int, [_vp, _vp, _vp, _vp]),
     "pg_screen_components_last": (_int, [_vp, _vp, _vp]),
     "pg_screen_components_release": (_int, [_vp]),
+    "pg_screen_representatives": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _vp, _P(_u32)]),
+    "pg_screen_index_representatives": (_int, [_vp, _vp, _u32, _vp, _P(_u32), _P(_u64)]),
+    "pg_screen_representatives_read": (_int, [_vp, _vp, _vp]),
+    "pg_screen_representatives_last": (_int, [_vp, _vp, _vp]),
+    "pg_screen_representatives_release": (_int, [_vp]),
     "pg_screen_search_index": (_int, [_vp, _vp, _u32, _i32, _i32, _vp]),
     "pg_screen_search_index_release": (_int, [_vp]),
     "pg_screen_search_count": (_int, [_vp, _vp, _u32, _vp]),

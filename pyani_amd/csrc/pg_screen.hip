@@ -86,6 +86,11 @@
 // pgscr_components.inc — the COMPONENTS: which genomes belong together.  pg_screen_components (a list from the host) and
 // pg_screen_index_components (the bands' kept triples, where B5 left them on the device) hook a union-find forest that only atomics write
 // and sum two 64-bit counts per node; K1 ... K3 stand there with their state.
+//
+// pgscr_representatives.inc — the REPRESENTATIVES: one genome per cluster by the greedy rule.  pg_screen_representatives
+// (a list from the host, uploaded whole) and pg_screen_index_representatives (the bands' kept triples with a < b, appended to a device list)
+// rank the nodes by score with one radix sort, decide them in rounds of three launches and assign the covered ones by a 64-bit atomic
+// maximum; P1 ... P8 stand there with their state.
 #include <algorithm>
 #include <hipcub/hipcub.hpp>
 #include <memory>
@@ -98,9 +103,9 @@
 
 namespace {
 
-// the stages whose milliseconds pg_screen_last, pg_screen_index_last, pg_screen_components_last, pg_screen_search_last, pg_screen_search_add_last,
-// pg_screen_search_remove_last and pg_screen_gather_last report
-enum ScreenStage { ST_SCAN, ST_GROUP, ST_COUNT, ST_SELECT, ST_HOOK, ST_FLATTEN, ST_LOOKUP, ST_EXPAND, ST_ARGMAX, ST_CLAIM, ST_MERGE, ST_CHECK, ST_MARK, ST_COMPACT, ST_WEIGHT, ST_ATTRIBUTE, ST_SORT, ST_STATS };
+// the stages whose milliseconds pg_screen_last, pg_screen_index_last, pg_screen_components_last, pg_screen_representatives_last, pg_screen_search_last,
+// pg_screen_search_add_last, pg_screen_search_remove_last and pg_screen_gather_last report
+enum ScreenStage { ST_SCAN, ST_GROUP, ST_COUNT, ST_SELECT, ST_HOOK, ST_FLATTEN, ST_LOOKUP, ST_EXPAND, ST_ARGMAX, ST_CLAIM, ST_MERGE, ST_CHECK, ST_MARK, ST_COMPACT, ST_WEIGHT, ST_ATTRIBUTE, ST_SORT, ST_STATS, ST_ROUNDS, ST_ASSIGN };
 
 struct ScreenEvents {      // event pairs on the context's stream, summed per stage after the call's last synchronisation
   std::vector<hipEvent_t> ev;
@@ -152,6 +157,7 @@ hipError_t tmp_room(size_t& tmp_bytes, Query query) {
 #include "pgscr_select.inc"
 #include "pgscr_index.inc"
 #include "pgscr_components.inc"
+#include "pgscr_representatives.inc"
 #include "pgscr_search.inc"
 #include "pgscr_add.inc"
 #include "pgscr_store.inc"

@@ -575,6 +575,84 @@ class Engine:
         finally:
             self.screen_components_release()
 
+    # the representatives: one genome per cluster by the greedy rule, rep and via resident on the context
+    def _screen_representatives_read(self, n: int) -> Tuple[np.ndarray, np.ndarray]:
+        rep, via = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint32)
+        self._check(self.lib.pg_screen_representatives_read(self._h, rep.ctypes.data, via.ctypes.data))
+        return rep, via
+
+    def screen_representatives(self, a, b, weight=None, n: int = 0, score=None) -> Tuple[np.ndarray, np.ndarray]:
+        """pg_screen_representatives + pg_screen_representatives_read: (rep int32[n], via uint32[n]) of the list of entries
+        (a[e], b[e], weight[e]) over n nodes under the scores score uint64[n], as pyani_amd.screen.representatives_of_pairs states them;
+        weight=None weighs every entry 1.  The number of representatives is screen_representatives_last()["representatives"]."""
+        x = np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+        y = np.ascontiguousarray(b, dtype=np.int32).reshape(-1)
+        w = None if weight is None else np.ascontiguousarray(weight, dtype=np.uint32).reshape(-1)
+        if len(x) != len(y) or (w is not None and len(w) != len(x)):
+            raise ValueError("a, b and weight must have the same length")
+        s = None if score is None else np.ascontiguousarray(score, dtype=np.uint64).reshape(-1)
+        if s is not None and len(s) != int(n):
+            raise ValueError(f"{int(n)} nodes need {int(n)} scores, not {len(s)}")
+        m = len(x)
+        c = ctypes.c_uint32(0)
+        self._check(self.lib.pg_screen_representatives(self._h, x.ctypes.data if m else None, y.ctypes.data if m else None,
+                                                       w.ctypes.data if w is not None and m else None, m, int(n),
+                                                       s.ctypes.data if s is not None and len(s) else None, ctypes.byref(c)))
+        return self._screen_representatives_read(int(n))
+
+    def screen_index_representatives(self, need, score) -> Tuple[np.ndarray, np.ndarray, int]:
+        """pg_screen_index_representatives + pg_screen_representatives_read: (rep, via, n_pairs) of the kept cells of ALL bands of the
+        resident index — screen_representatives of the list screen_index_select would return, weight = shared, n_pairs its length —
+        without a pair leaving the device."""
+        t = np.ascontiguousarray(need, dtype=np.uint32).reshape(-1)
+        s = None if score is None else np.ascontiguousarray(score, dtype=np.uint64).reshape(-1)
+        if s is not None and len(s) != len(t):
+            raise ValueError(f"{len(t)} thresholds need {len(t)} scores, not {len(s)}")
+        c, m = ctypes.c_uint32(0), ctypes.c_uint64(0)
+        self._check(self.lib.pg_screen_index_representatives(self._h, t.ctypes.data if len(t) else None, len(t),
+                                                             s.ctypes.data if s is not None and len(s) else None, ctypes.byref(c), ctypes.byref(m)))
+        return (*self._screen_representatives_read(len(t)), int(m.value))
+
+    def screen_representatives_last(self) -> dict:
+        """pg_screen_representatives_last: counts and stage milliseconds of the resident representatives (all 0 when there are none)."""
+        c = (ctypes.c_uint64 * 6)()
+        ms = (ctypes.c_double * 4)()
+        self._check(self.lib.pg_screen_representatives_last(self._h, ctypes.addressof(c), ctypes.addressof(ms)))
+        return {"n": int(c[0]), "entries": int(c[1]), "ignored": int(c[2]), "representatives": int(c[3]), "rounds": int(c[4]), "launches": int(c[5]),
+                "select_ms": float(ms[0]), "sort_ms": float(ms[1]), "rounds_ms": float(ms[2]), "assign_ms": float(ms[3])}
+
+    def screen_representatives_release(self) -> None:
+        self._check(self.lib.pg_screen_representatives_release(self._h))
+
+    def screen_dereplicate(self, ids, options, scores=None, labels=None, path: str = "auto"):
+        """The greedy clusters of the pairs the screen keeps among the resident genomes `ids`, weight = shared
+        (pyani_amd.screen.ScreenClusters).  scores: one per genome as screen.score_keys takes them, None = the sketch
+        sizes.  path "dense": screen_candidates, then the list entry (the kept pairs are read back once); "index": screen_index ->
+        identity_thresholds -> screen_index_representatives -> release, on errors too — no pair is read back; "auto" as
+        screen_candidates.  Nothing stays resident afterwards."""
+        from . import screen
+        options = screen.check_options(options)
+        ids = [int(i) for i in ids]
+        if scores is not None and len(screen.score_keys(scores)) != len(ids):      # (refused before any work)
+            raise ValueError(f"{len(ids)} genomes need {len(ids)} scores")
+        if screen.resolve_path(path, len(ids)) == "index":
+            labels = screen._labels_for(ids, labels, screen.INDEX_MAX_GENOMES)
+            if not ids:
+                return screen.clusters_from_nodes(labels, np.zeros(0, np.int32), np.zeros(0, np.uint32), np.zeros(0, np.uint64))
+            try:
+                sizes = self.screen_index(ids, options.kmer, options.scale)
+                need = screen.identity_thresholds(sizes, options.kmer, options.min_identity, options.min_shared)
+                score = screen.score_keys(scores, sizes)
+                rep, via, _ = self.screen_index_representatives(need, score)
+            finally:
+                self.screen_index_release()
+                self.screen_representatives_release()
+            return screen.clusters_from_nodes(labels, rep, via, score)
+        try:
+            return self.screen_candidates(ids, options, labels, path="dense").representatives(scores, engine=self)
+        finally:
+            self.screen_representatives_release()
+
     # the search (DESIGN.md §16.4): a collection resident as a k-mer index with its keys, new genomes placed against it
     def screen_search_index(self, ids, kmer: int = 16, scale: int = 256, labels=None) -> np.ndarray:
         """pg_screen_search_index: builds the resident SEARCH index of the genomes in the order given (up to 2^20; every distinct k-mer

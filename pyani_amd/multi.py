@@ -390,6 +390,29 @@ class MultiEngine:
         for e in self.engines:
             e.screen_components_release()
 
+    def screen_representatives(self, a, b, weight=None, n: int = 0, score=None):
+        """Engine.screen_representatives on the first engine (a list call has nothing to divide)."""
+        return self.engines[0].screen_representatives(a, b, weight, n=n, score=score)
+
+    def screen_representatives_release(self):
+        for e in self.engines:
+            e.screen_representatives_release()
+
+    def screen_dereplicate(self, ids, options, scores=None, labels=None, path: str = "auto"):
+        """Engine.screen_dereplicate over all devices.  The greedy rule needs every entry in one place — a round reads
+        the whole list, and a node's fate may hang on an entry of any band — so only the CANDIDATES are dealt as today
+        (screen_candidates: the dense path's summed matrix, the index path's dealt bands, merged), and ONE list call runs on the first
+        engine.  On the index path the kept pairs are therefore read back once, unlike one engine's.  Equal to one engine's."""
+        from . import screen
+        options = screen.check_options(options)
+        ids = [int(i) for i in ids]
+        if scores is not None and len(screen.score_keys(scores)) != len(ids):      # (refused before any work)
+            raise ValueError(f"{len(ids)} genomes need {len(ids)} scores")
+        try:
+            return self.screen_candidates(ids, options, labels, path=path).representatives(scores, engine=self.engines[0])
+        finally:
+            self.engines[0].screen_representatives_release()
+
     def screen_set_budget(self, max_keys: int = 0):
         for e in self.engines:
             e.screen_set_budget(max_keys)

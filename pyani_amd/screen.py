@@ -16,7 +16,10 @@ to ONE INTEGER COMPARISON per cell (identity_thresholds), whic
 
 Which genomes BELONG TOGETHER is the last step: the connected components of the kept pairs (components_of_pairs is
 the statement, Engine.screen_components / screen_index_components the kernels, ScreenComponents the table: one representative per
-component is the dereplicated set), had through the index without a single pair leaving the device (Engine.screen_components_of).
+component is the SINGLE-LINKAGE dereplicated set), had through the index without a single pair leaving the device
+(Engine.screen_components_of).  One genome per SPECIES is the greedy rule of dRep, galah, skani and CD-HIT:
+representatives_of_pairs is the statement, Engine.screen_representatives / screen_index_representatives the kernels, ScreenClusters the
+table, Engine.screen_dereplicate the whole step.
 
 New genomes against a resident collection: Engine.screen_search lists what each is RELATED TO (SearchHits), and
 Engine.screen_gather what each is MADE OF — the greedy minimum set of collection genomes that explains its k-mers (GatherOptions,
@@ -198,6 +201,22 @@ class ScreenedPairs(NamedTuple):
         nodes = components_of_pairs(self.a, self.b, self.shared, n) if engine is None else engine.screen_components(self.a, self.b, self.shared, n=n)
         return components_from_nodes(self.labels, *nodes)
 
+    def representatives(self, scores=None, engine=None) -> "ScreenClusters":
+        """The greedy clusters of the kept pairs, weight = shared: on `engine` (Engine.screen_representatives), or by
+        the numpy statement representatives_of_pairs when none is given.  scores: one per genome, in the order of `labels`, as
+        score_keys takes them; None = the sketch sizes.  Both give the same ScreenClusters."""
+        n = len(self.labels)
+        score = score_keys(scores, self.sizes)
+        if len(score) != n:
+            raise ValueError(f"{n} genomes need {n} scores, not {len(score)}")
+        if n == 0:
+            return clusters_from_nodes(self.labels, np.zeros(0, np.int32), np.zeros(0, np.uint32), score)
+        if engine is None:
+            rep, via = representatives_of_pairs(self.a, self.b, self.shared, n, score)
+        else:
+            rep, via = engine.screen_representatives(self.a, self.b, self.shared, n=n, score=score)
+        return clusters_from_nodes(self.labels, rep, via, score)
+
 
 # ---- the connected components of the kept pairs (DESIGN.md §16.3) ---------------------------------------------------------------------------
 def _check_entries(a, b, shared, n):
@@ -290,7 +309,7 @@ class ScreenComponents(NamedTuple):
                              "representative": self._names(self.representative[self.component])})
 
     def representatives(self) -> list:
-        """The dereplicated set: one label per component, in component order."""
+        """The single-linkage dereplicated set: one label per component, in component order (the greedy one: ScreenClusters)."""
         return self._names(self.representative)
 
 
@@ -372,6 +391,149 @@ def index_components_on(engines, run_all, ids, options, labels=None) -> ScreenCo
             e.screen_index_release()
             e.screen_components_release()
     return components_from_nodes(labels, *nodes)
+
+
+# ---- the greedy representatives of the kept pairs ---------------------------------------------------------------------------
+def score_keys(scores, sizes=None) -> np.ndarray:
+    """uint64 keys of the genomes' scores, greater is better.  scores=None: the sketch sizes (ScreenedPairs.sizes), so that the larger
+    assembly wins.  Otherwise the scores must be float64-convertible, finite and >= 0 (ValueError), and the key is the bit pattern of
+    x + 0.0 (the addition turns -0.0 into 0.0), which is monotone for non-negative doubles."""
+    if scores is None:
+        if sizes is None:
+            raise ValueError("no scores and no sizes to take their place")
+        return np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1).copy()
+    try:
+        x = np.ascontiguousarray(scores, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError) as err:
+        raise ValueError(f"scores must be numbers: {err}") from None
+    if not np.isfinite(x).all() or (x < 0).any():
+        raise ValueError("scores must be finite and >= 0")
+    return (x + 0.0).view(np.uint64).copy()
+
+
+def rank_order(score) -> Tuple[np.ndarray, np.ndarray]:
+    """(order, rank) of uint64 scores: order = the nodes by (score descending, index ascending), rank its inverse."""
+    score = np.ascontiguousarray(score, dtype=np.uint64).reshape(-1)
+    order = np.lexsort((np.arange(len(score)), ~score))
+    rank = np.empty(len(score), dtype=np.int64)
+    rank[order] = np.arange(len(score))
+    return order, rank
+
+
+def representatives_of_pairs(a, b, weight, n, score) -> Tuple[np.ndarray, np.ndarray]:
+    """THE STATEMENT of the representatives (the host's; Engine.screen_representatives is held to it): for the list of entries
+    (a[e], b[e], weight[e]) over n nodes — unsorted, a pair in one direction or both, once or several times, an entry with a[e] == b[e]
+    ignored, weight=None counting 1 everywhere — and the scores score uint64[n] (greater is better, ties to the smaller index; order,
+    rank = rank_order(score)):
+
+      1. Walk `order`.  A node none of whose neighbours is already a representative becomes one.  Direction is ignored.
+      2. Every other node v is assigned to the representative neighbour r of the greatest pair weight — the maximum of weight[e] over
+         all entries joining v and r, in either direction — ties to the representative of smaller rank.
+
+    The assignment is made AFTER all representatives are known (galah's rule), not as CD-HIT does during the walk ("the first
+    representative met"): a representative of lower priority than v may take v.  The two differ already on chains, so the two-phase
+    form is deliberate.  Returns rep int32[n] (rep[v] == v for a representative) and via uint32[n] (the pair weight v was assigned by, 0
+    for a representative).  Integers, independent of the list's order, direction and duplication.
+
+    The walk is the lexicographically first maximal independent set under `rank`; it is computed here in rounds over the entries whose
+    ends are both undecided: the end of larger rank of each is barred, every undecided node not barred becomes a representative (all
+    its neighbours of higher priority have been covered), and the undecided neighbours of the new representatives are covered.  The
+    undecided node of smallest rank is never barred, so every round decides a node."""
+    a, b, w, n = _check_entries(a, b, weight, n)
+    score = np.ascontiguousarray(score, dtype=np.uint64).reshape(-1)
+    if len(score) != n:
+        raise ValueError(f"{n} nodes need {n} scores, not {len(score)}")
+    order, rank = rank_order(score)
+    live = a != b
+    a, b = a[live], b[live]
+    w = np.ones(len(a), dtype=np.uint64) if w is None else w[live].astype(np.uint64)
+    is_rep, covered = np.zeros(n, dtype=bool), np.zeros(n, dtype=bool)
+    ea, eb = a, b
+    while True:
+        undecided = ~(is_rep | covered)
+        if not undecided.any():
+            break
+        both = undecided[ea] & undecided[eb]      # (an entry with a decided end is never looked at again: nothing becomes undecided)
+        ea, eb = ea[both], eb[both]
+        barred = np.zeros(n, dtype=bool)
+        barred[np.where(rank[ea] > rank[eb], ea, eb)] = True
+        new = undecided & ~barred
+        is_rep |= new
+        covered[eb[new[ea]]] = True
+        covered[ea[new[eb]]] = True
+    # the assignment: per covered node the greatest (weight, -rank of the representative) over the entries that join it to a representative
+    fwd, bwd = is_rep[a] & covered[b], is_rep[b] & covered[a]
+    v = np.concatenate([b[fwd], a[bwd]])
+    r = np.concatenate([a[fwd], b[bwd]])
+    key = (np.concatenate([w[fwd], w[bwd]]) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - rank[r].astype(np.uint64))
+    by = np.lexsort((key, v))
+    v, key = v[by], key[by]
+    last = np.flatnonzero(np.append(v[1:] != v[:-1], True)) if len(v) else np.zeros(0, np.int64)      # the greatest key of every covered node
+    rep = np.arange(n, dtype=np.int64)
+    via = np.zeros(n, dtype=np.uint32)
+    rep[v[last]] = order[(np.uint64(0xFFFFFFFF) - (key[last] & np.uint64(0xFFFFFFFF))).astype(np.int64)]
+    via[v[last]] = (key[last] >> np.uint64(32)).astype(np.uint32)
+    return rep.astype(np.int32), via
+
+
+class ScreenClusters(NamedTuple):
+    """The greedy clusters of a list of kept pairs over the genomes `labels` (None: the nodes go by their index).  rep, via and score are
+    the node arrays of representatives_of_pairs and its scores; everything else is derived from them by clusters_from_nodes: clusters
+    numbered by ascending representative, members ascending inside a cluster."""
+    labels: Optional[List[str]]
+    rep: np.ndarray              # int32[n]
+    via: np.ndarray              # uint32[n]
+    score: np.ndarray            # uint64[n]
+    representative: np.ndarray   # int32[R]: ascending node index
+    cluster: np.ndarray          # int32[n]: the cluster of every node
+    start: np.ndarray            # int64[R + 1]: cluster c owns member[start[c]:start[c + 1]]
+    member: np.ndarray           # int32[n]
+    size: np.ndarray             # int64[R]
+
+    def _names(self, nodes) -> list:
+        nodes = np.asarray(nodes)
+        return nodes.tolist() if self.labels is None else [self.labels[i] for i in nodes.tolist()]
+
+    def members(self, c: int) -> np.ndarray:
+        """The nodes of cluster c, ascending."""
+        if not 0 <= int(c) < len(self.size):
+            raise IndexError(f"cluster {c} does not exist ({len(self.size)} clusters)")
+        return self.member[int(self.start[c]):int(self.start[c + 1])]
+
+    def frame(self) -> pd.DataFrame:
+        """One row per representative: cluster, representative (label), size, score (the uint64 key)."""
+        return pd.DataFrame({"cluster": np.arange(len(self.size), dtype=np.int64), "representative": self._names(self.representative), "size": self.size,
+                             "score": self.score[self.representative]})
+
+    def membership_frame(self) -> pd.DataFrame:
+        """One row per genome, in the order of `labels`: genome, representative, via."""
+        return pd.DataFrame({"genome": self._names(np.arange(len(self.rep))), "representative": self._names(self.rep), "via": self.via.astype(np.int64)})
+
+    def representatives(self) -> list:
+        """The dereplicated set: one label per cluster, in cluster order."""
+        return self._names(self.representative)
+
+
+def clusters_from_nodes(labels, rep, via, score) -> ScreenClusters:
+    """The ScreenClusters of the node arrays (numpy on the host: n <= 2^20)."""
+    rep = np.ascontiguousarray(rep, dtype=np.int32).reshape(-1)
+    via = np.ascontiguousarray(via, dtype=np.uint32).reshape(-1)
+    score = np.ascontiguousarray(score, dtype=np.uint64).reshape(-1)
+    n = len(rep)
+    if labels is not None:
+        labels = [str(x) for x in labels]
+        if len(labels) != n:
+            raise ValueError("labels and nodes must have the same length")
+    if len(via) != n or len(score) != n:
+        raise ValueError("rep, via and score must have the same length")
+    if n and ((rep < 0).any() or (rep >= n).any() or (rep[rep] != rep).any()):
+        raise ValueError("rep names no representatives (0 <= rep[v] < n and rep[rep[v]] == rep[v])")
+    representative, cluster = np.unique(rep, return_inverse=True)      # (ascending representatives: the numbering)
+    cluster = cluster.reshape(-1)
+    size = np.bincount(cluster, minlength=len(representative)).astype(np.int64)
+    start = np.concatenate([[0], np.cumsum(size)]).astype(np.int64)
+    member = np.argsort(cluster, kind="stable")
+    return ScreenClusters(labels, rep, via, score, representative.astype(np.int32), cluster.astype(np.int32), start, member.astype(np.int32), size)
 
 
 def _labels_for(ids, labels, limit: int = MAX_GENOMES) -> List[str]:

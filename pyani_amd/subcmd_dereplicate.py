@@ -1,0 +1,169 @@
+"""Dereplicate: one genome per species, by the greedy rule of dRep, galah, skani and CD-HIT.  pyani has no such step.
+
+The genomes are loaded once and screened; then the genomes are walked from the best score to the worst, a genome within the threshold
+of an already chosen representative joins one, any other becomes a representative (pyani_amd.screen.representatives_of_pairs is the
+statement, Engine.screen_representatives the kernels).  Unlike the connected components of run_anim_components — single linkage, where
+a chain a-b-c-d is one component although a and d may be far apart — no two representatives are within the threshold of each other,
+and every other genome is within it of its representative.
+
+exact=None: the rule runs on the screen's kept pairs, weight = the shared sampled k-mers.  exact="anim": ONE anim_pairs call aligns the
+kept pairs; an undirected pair is an edge iff both ordered comparisons have a result and, in both, identity >= min_ani and the
+alignment coverage of the query >= min_coverage (the quantities of run_anim's matrices: identity, aln_length / query length); its
+weight is floor(min(identity_ab, identity_ba) * 1e6); the rule runs on that list through the same list entry.
+
+With write_output: `screen_output/screen_pairs.tab` (the screen's kept pairs), `screen_representatives.tab` (one line per
+representative: cluster, representative, size, score) and `screen_clusters.tab` (one line per genome: genome, representative, via).
+
+OUT OF SCOPE here: ANIb as the exact step, recovery, collective runs, and secondary clustering by linkage (pyani_amd.heatmap has the
+linkage for callers who want it).  Single-process: one engine, or several GPUs of this node (devices / workers).
+"""
+from pathlib import Path
+from typing import Dict, List, Mapping, NamedTuple, Optional, Tuple
+
+import numpy as np
+
+from . import _lib, files, screen as screen_mod
+from .engine import Engine, default_engine
+
+EXACT = (None, "anim")
+
+
+class DereplicateRun(NamedTuple):
+    genome_ids: Dict[str, int]                 # stem -> 1-based id in sorted-path order
+    lengths: Dict[str, int]
+    screened: screen_mod.ScreenedPairs
+    records: Optional[np.ndarray]              # exact="anim": the anim_pairs records of the kept pairs, in their order; None otherwise
+    edges: Tuple[np.ndarray, np.ndarray, np.ndarray]      # (a, b, weight) the greedy rule ran on: positions in the order of the stems
+    clusters: screen_mod.ScreenClusters
+    written: List[Path]
+
+    def representatives(self) -> List[str]:
+        return self.clusters.representatives()
+
+
+def read_scores(scores) -> Optional[Dict[str, float]]:
+    """{stem: score} of `scores`: None, a mapping, or the path of a two-column TSV (stem, score; lines starting with # are skipped)."""
+    if scores is None:
+        return None
+    if isinstance(scores, Mapping):
+        return {str(k): v for k, v in scores.items()}
+    out: Dict[str, float] = {}
+    for no, line in enumerate(Path(scores).read_text().splitlines(), 1):
+        if not line.strip() or line.startswith("#"):
+            continue
+        cols = line.rstrip("\n").split("\t")
+        if len(cols) != 2:
+            raise ValueError(f"{scores}, line {no}: two tab-separated columns are needed (stem, score)")
+        try:
+            out[cols[0]] = float(cols[1])
+        except ValueError:
+            raise ValueError(f"{scores}, line {no}: {cols[1]!r} is no number") from None
+    return out
+
+
+def scores_for(stems: List[str], scores: Optional[Mapping]) -> Optional[np.ndarray]:
+    """The scores in the order of the stems (None stays None).  ValueError for a score of an unknown stem, a stem without a score, and
+    what screen.score_keys refuses."""
+    if scores is None:
+        return None
+    unknown = sorted(set(scores) - set(stems))
+    if unknown:
+        raise ValueError(f"a score is given for {unknown[0]!r}, which is no genome of this run")
+    missing = [s for s in stems if s not in scores]
+    if missing:
+        raise ValueError(f"{missing[0]!r} has no score")
+    out = np.array([scores[s] for s in stems], dtype=object)
+    screen_mod.score_keys(list(out))
+    return np.array([float(x) for x in out], dtype=np.float64)
+
+
+def exact_edges(a, b, recs, length, min_ani: float, min_coverage: float) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(a, b, weight) with a < b of the undirected edges among the ordered pairs (a[e], b[e]) with the anim_pairs records recs[e]
+    (a[e] the query, nucmer's reference) and length[v] the genomes' lengths: an edge iff both directions have a result and, in both,
+    identity >= min_ani and ref_aln_len / length[query] >= min_coverage; weight = floor(min of the two identities * 1e6)."""
+    a, b = np.asarray(a, dtype=np.int64), np.asarray(b, dtype=np.int64)
+    status = np.asarray(recs["status"])
+    bad = (status != 0) & (status != _lib.PG_ANIM_NO_ALIGNMENT)
+    if bad.any():
+        raise RuntimeError(f"GPU ANIm comparison failed with status {int(status[bad][0])}")
+    ident = np.asarray(recs["identity"], dtype=np.float64)
+    cov = np.asarray(recs["ref_aln_len"], dtype=np.float64) / np.asarray(length, dtype=np.float64)[a]
+    ok = (status == 0) & (ident >= min_ani) & (cov >= min_coverage)
+    good = {(x, y): i for x, y, i, k in zip(a.tolist(), b.tolist(), ident.tolist(), ok.tolist()) if k}
+    ea, eb, w = [], [], []
+    for (x, y), i in good.items():
+        if x < y and (y, x) in good:
+            ea.append(x)
+            eb.append(y)
+            w.append(int(np.floor(min(i, good[(y, x)]) * 1e6)))
+    return np.array(ea, dtype=np.int32), np.array(eb, dtype=np.int32), np.array(w, dtype=np.uint32)
+
+
+def run_dereplicate(indir, outdir=None, screen=None, scores=None, exact: Optional[str] = None, min_ani: float = 0.95, min_coverage: float = 0.1,
+                    write_output: bool = False, engine: Optional[Engine] = None, devices: Optional[List[int]] = None,
+                    workers: Optional[int] = None) -> DereplicateRun:
+    """The greedy representatives of every FASTA file of `indir`.  screen: a ScreenOptions or a bare identity threshold (required: there
+    is no default threshold).  scores: None (the sketch sizes: the larger assembly wins), a {stem: score} mapping or the path of a
+    two-column TSV; finite and >= 0, greater is better, ties to the genome earlier in sorted-path order.  exact: None or "anim" (see the
+    module's text; min_ani and min_coverage matter for "anim" only).  outdir is needed for write_output only; devices / workers: several
+    GPUs of this node, ignored when `engine` is given.  Every ValueError is raised before any work is done."""
+    if screen is None:
+        raise ValueError("run_dereplicate needs screen= (a ScreenOptions or an identity threshold)")
+    if write_output and outdir is None:
+        raise ValueError("write_output needs an output directory")
+    if exact not in EXACT:
+        raise ValueError(f"exact must be one of {EXACT}, not {exact!r}")
+    screen = screen_mod.check_options(screen)
+    paths = files.get_fasta_paths(Path(indir))
+    stems = [p.stem for p in paths]
+    if len(set(stems)) != len(stems):
+        raise ValueError("two input files share a stem (pyani keys every result by Path.stem)")
+    given = scores_for(stems, read_scores(scores))
+    own = None
+    if engine is None and (devices is not None or workers):
+        from . import multi
+        engine = multi.engine_for(devices, workers)
+        own = engine if isinstance(engine, multi.MultiEngine) else None
+    try:
+        return _run(paths, stems, outdir, screen, given, exact, float(min_ani), float(min_coverage), write_output, engine or default_engine())
+    finally:
+        if own is not None:
+            own.close()
+
+
+def _run(paths, stems, outdir, screen, given, exact, min_ani, min_coverage, write_output, eng) -> DereplicateRun:
+    genome_ids = {s: k + 1 for k, s in enumerate(stems)}
+    scratch_store = eng.genome_count() == 0
+    lengths: Dict[str, int] = {}
+    recs = None
+    try:
+        ids = np.zeros(len(paths), dtype=np.int64)
+        for k, (p, (gid, total, _)) in enumerate(zip(paths, eng.add_fasta_batch(paths))):
+            ids[k], lengths[p.stem] = gid, total
+        screened = eng.screen_candidates(ids.tolist(), screen, labels=stems)
+        n = len(stems)
+        score = screen_mod.score_keys(given, screened.sizes)
+        edges = (screened.a, screened.b, screened.shared)
+        if exact == "anim":
+            recs = np.zeros(0, dtype=Engine.ANIM_DTYPE)
+            if len(screened.a):      # the query is nucmer's reference, as in run_anim
+                recs = eng.anim_pairs(ids[screened.a], ids[screened.b])
+            edges = exact_edges(screened.a, screened.b, recs, [lengths[s] for s in stems], min_ani, min_coverage)
+        try:
+            if n:
+                rep, via = eng.screen_representatives(*edges, n=n, score=score)
+            else:
+                rep, via = np.zeros(0, np.int32), np.zeros(0, np.uint32)
+        finally:
+            eng.screen_representatives_release()
+    finally:
+        if scratch_store:
+            eng.clear_genomes()
+    clusters = screen_mod.clusters_from_nodes(stems, rep, via, score)
+    written: List[Path] = []
+    if write_output:
+        from .subcmd_screen import tab_path, write_pairs_tab
+        written = [write_pairs_tab(outdir, screened), tab_path(outdir, "representatives"), tab_path(outdir, "clusters")]
+        clusters.frame().to_csv(written[1], index=False, sep="\t")
+        clusters.membership_frame().to_csv(written[2], index=False, sep="\t")
+    return DereplicateRun(genome_ids, lengths, screened, recs, edges, clusters, written)
