@@ -134,7 +134,19 @@ void word_tier_seeds(QA&& q_at, int32_t qlen, SA&& s_at, const WordIndex& W, std
   }
 }
 
-void run_pair(const Genome& Q, const Genome& S, int32_t fragsize, std::vector<Row>& rows) {
+// ---- the trace (anib_cpu_pair_trace): what the statement did on the way to its rows.  Recording changes no row. ---------------------
+struct TraceFS {      // per (fragment, strand), of the fragment's LAST pass (the one after the word tier where it ran)
+  int32_t frag, strand, own_seeds, word_found, word_taken, cands, lone_weak, prelims, finals, rows_pre, rows_post, listed;
+};
+struct TraceExt {     // per extension; kind 0 / 1: preliminary right / left of a candidate's initial HSP, 2 + k: frag_hsp's k-th call
+  int32_t frag, strand, kind, recentres, net, lo, hi, left_low, left_high, di, dj, score;
+};
+struct Trace {
+  std::vector<TraceFS> fs;                       // index 2 * fragment + strand
+  std::vector<std::vector<TraceExt>> ext;        // per fragment
+};
+
+void run_pair(const Genome& Q, const Genome& S, int32_t fragsize, std::vector<Row>& rows, Trace* T = nullptr) {
   const SeqView SV = S.view(), QVw = Q.view();
   std::vector<std::pair<uint32_t, int32_t>> tab;
   {
@@ -184,8 +196,23 @@ void run_pair(const Genome& Q, const Genome& S, int32_t fragsize, std::vector<Ro
   int64_t db_len = 0;
   const int32_t db_seqs = (int32_t)S.rec_start.size() - 1;
   for (int32_t r = 0; r < db_seqs; ++r) db_len += S.rec_start[r + 1] - 1 - S.rec_start[r];
+  if (T) {
+    T->fs.assign(2 * frags.size(), TraceFS{});
+    T->ext.assign(frags.size(), {});
+    for (size_t i = 0; i < T->fs.size(); ++i) { T->fs[i].frag = (int32_t)(i / 2); T->fs[i].strand = (int32_t)(i & 1); }
+  }
   auto fragment_rows = [&](size_t f, std::vector<Row>& cand) {
     const int32_t fp = frags[f].first, qlen = frags[f].second;
+    if (T) {
+      T->ext[f].clear();
+      for (int st = 0; st < 2; ++st) {
+        TraceFS& t = T->fs[2 * f + st];
+        t = TraceFS{(int32_t)f, st, t.own_seeds, t.word_found, 0, 0, 0, 0, 0, 0, 0, 0};      // (own seeds: the first pass counts them, it also cuts the list)
+      }
+    }
+    auto note_ext = [&](int strand, int kind, const FragExtTrace& x) {
+      if (T && x.ran) T->ext[f].push_back(TraceExt{(int32_t)f, strand, kind, x.recentres, x.net, x.lo, x.hi, x.left_low, x.left_high, x.di, x.dj, x.score});
+    };
     FragInit init[2][FRAG_MAX_SEEDS], init2[2][FRAG_MAX_SEEDS];
     int64_t dg[2][FRAG_MAX_SEEDS];
     int pick[2][FRAG_MAX_CAND], members[2][FRAG_MAX_CAND] = {}, nc[2] = {0, 0};
@@ -195,17 +222,20 @@ void run_pair(const Genome& Q, const Genome& S, int32_t fragsize, std::vector<Ro
       if (e.empty() && (wseeds[strand].empty() || wseeds[strand][f].empty())) continue;      // (word seeds alone are a list too)
       const auto by_len = [](const FragSeed& x, const FragSeed& y) { return x.len != y.len ? x.len > y.len : (x.q != y.q ? x.q < y.q : x.s < y.s); };
       std::sort(e.begin(), e.end(), by_len);
+      if (T) T->fs[2 * f + strand].own_seeds = std::max(T->fs[2 * f + strand].own_seeds, (int32_t)e.size());
       if (!wseeds[strand].empty() && !wseeds[strand][f].empty()) {
         // the word tier's seeds come FIRST: each passed the flank test (chance: ~1e-7 per hit), while a fragment with a low-complexity
         // stretch can hold more than FRAG_MAX_SEEDS chance 16-mers, all longer than a real alignment's 11 ... 15-base words
         std::vector<FragSeed> w = wseeds[strand][f];
         std::sort(w.begin(), w.end(), by_len);
         if (w.size() > (size_t)FRAG_WORD_FIRST) w.resize(FRAG_WORD_FIRST);      // (at most half of the list: the own seeds keep the other half)
+        if (T) T->fs[2 * f + strand].word_taken = (int32_t)w.size();
         w.insert(w.end(), e.begin(), e.end());
         e.swap(w);
         wseeds[strand][f].clear();
       }
       if (e.size() > (size_t)FRAG_MAX_SEEDS) e.resize(FRAG_MAX_SEEDS);
+      if (T) T->fs[2 * f + strand].listed = (int32_t)e.size();
       auto q_at = [&](int64_t p) -> int {
         if (p < 0 || p >= qlen) return 4;
         const int64_t g = strand ? fp + (qlen - 1 - p) : fp + p;
@@ -226,6 +256,7 @@ void run_pair(const Genome& Q, const Genome& S, int32_t fragsize, std::vector<Ro
         init[strand][t] = frag_diag_best_init(match, qlen, diag, e[t].q, &init2[strand][t]);
       }
       nc[strand] = frag_pick_inits(init[strand], dg[strand], n, pick[strand], members[strand], FRAG_MAX_CAND);
+      if (T) T->fs[2 * f + strand].cands = nc[strand];
       if (getenv("ANIB_DEBUG_FRAG") && atoi(getenv("ANIB_DEBUG_FRAG")) == (int)f) {
         for (int t = 0; t < n; ++t) fprintf(stderr, "DBG frag %zu strand %d seed %d: s %d q %d len %d diag %lld -> init score %d q_start %d len %d word %d | second %d\n", f, strand, t, e[t].s, e[t].q, e[t].len, (long long)dg[strand][t], init[strand][t].score, init[strand][t].q_start, init[strand][t].len, init[strand][t].q_off, init2[strand][t].score);
         for (int c = 0; c < nc[strand]; ++c) fprintf(stderr, "DBG   cand %d: seed %d members %d\n", c, pick[strand][c], members[strand][c]);
@@ -300,8 +331,11 @@ void run_pair(const Genome& Q, const Genome& S, int32_t fragsize, std::vector<Ro
           auto ql = [&](int32_t x2) { return q_at(g0 - 1 - x2); };
           auto sl = [&](int32_t x2) { return s_at(as - 1 - x2); };
           const int32_t cap = FRAG_SIZE + FRAG_SLACK;
-          const FragExt Rp = frag_extend(qr, qlen - (g0 + 1), sr, (int32_t)std::min<int64_t>(s_hi - (as + 1), cap), FRAG_NEG, FRAG_XDROP_PRELIM);
-          const FragExt Lp = frag_extend(ql, g0, sl, (int32_t)std::min<int64_t>(as - s_lo, cap), FRAG_NEG, FRAG_XDROP_PRELIM);
+          FragExtTrace xr{}, xl{};
+          const FragExt Rp = frag_extend(qr, qlen - (g0 + 1), sr, (int32_t)std::min<int64_t>(s_hi - (as + 1), cap), FRAG_NEG, FRAG_XDROP_PRELIM, T ? &xr : nullptr);
+          const FragExt Lp = frag_extend(ql, g0, sl, (int32_t)std::min<int64_t>(as - s_lo, cap), FRAG_NEG, FRAG_XDROP_PRELIM, T ? &xl : nullptr);
+          note_ext(strand, 0, xr); note_ext(strand, 1, xl);
+          if (T) ++T->fs[2 * f + strand].prelims;
           const FragPrelim P{Rp.score + Lp.score + FRAG_MATCH, g0 - Lp.di, g0 + 1 + Rp.di, g0, as - Lp.dj, as + 1 + Rp.dj, dj};
           if (tried++ == 0) first = P;
           if (frag_evalue_ok_db(P.score, qlen, db_len, db_seqs)) pre[np++] = P;
@@ -327,6 +361,7 @@ void run_pair(const Genome& Q, const Genome& S, int32_t fragsize, std::vector<Ro
         if (!frag_keep_init(I.score, best_score)) continue;
         const bool lone_weak = frag_init_is_lone_weak(I.score, members[strand][c]);
         if (!lone_weak && !have[c]) continue;
+        if (T) { ++T->fs[2 * f + strand].finals; T->fs[2 * f + strand].lone_weak += lone_weak; }
         const int64_t diag = dg[strand][pick[strand][c]];
         const int srec = record_of(S.rec_start.data(), (int)S.rec_start.size() - 1, (int32_t)(I.q_off + diag));
         const int64_t s_lo = S.rec_start[srec], s_hi = S.rec_start[srec + 1] - 1;
@@ -344,9 +379,13 @@ void run_pair(const Genome& Q, const Genome& S, int32_t fragsize, std::vector<Ro
           const int32_t rec_lo = (int32_t)std::max<int64_t>(0, s_lo - gdiag);
           g = frag_start_point_boxed(match_b, best.g, best.g + gdiag, best.q0, best.q1, best.s0, best.s1, rec_lo);
         }
-        const FragHit h = frag_hsp(q_at, qlen, s_at, s_lo, s_hi, g, g + gdiag, 1, [&](int32_t sc) { return frag_evalue_ok_db(sc, qlen, db_len, db_seqs); }, lone_weak);
+        FragExtTrace xh[6] = {};
+        const FragHit h = frag_hsp(q_at, qlen, s_at, s_lo, s_hi, g, g + gdiag, 1, [&](int32_t sc) { return frag_evalue_ok_db(sc, qlen, db_len, db_seqs); }, lone_weak,
+                                   T ? xh : nullptr);
+        for (int k = 0; k < 6; ++k) note_ext(strand, 2 + k, xh[k]);
         if (getenv("ANIB_DUMP_STARTS")) fprintf(stderr, "PSTART %zu %d %d %lld %d init score %d q_start %d len %d word %d -> score %d\n", f, strand, g, (long long)(g + gdiag - s_lo), srec, I.score, I.q_start, I.len, I.q_off, h.score);
         if (!frag_evalue_ok_db(h.score, qlen, db_len, db_seqs)) continue;
+        if (T) ++T->fs[2 * f + strand].rows_pre;
         Row r;
         r.frag = (int32_t)f; r.length = h.length; r.mismatch = h.mismatch; r.gaps = h.gaps; r.nident = h.nident; r.qlen = qlen;
         r.srec = srec; r.score = h.score;
@@ -371,6 +410,7 @@ void run_pair(const Genome& Q, const Genome& S, int32_t fragsize, std::vector<Ro
       const int32_t keep = cand[0].srec;
       cand.erase(std::remove_if(cand.begin(), cand.end(), [keep](const Row& x) { return x.srec != keep; }), cand.end());
     }
+    if (T) for (const Row& r : cand) ++T->fs[2 * f + (r.sstart > r.send ? 1 : 0)].rows_post;
   };
   auto reportable = [](const std::vector<Row>& cand) {   // parse_blast_tab's test (anib.py:641-649) on any row of the fragment
     for (const Row& r : cand) {
@@ -405,6 +445,7 @@ void run_pair(const Genome& Q, const Genome& S, int32_t fragsize, std::vector<Ro
           for (const FragSeed& y : seeds[strand][f]) if (y.s - y.q == x.s - x.q && x.q >= y.q && x.q + x.len <= y.q + y.len) dup = true;
           if (!dup) fresh.push_back(x);
         }
+        if (T) T->fs[2 * f + strand].word_found = (int32_t)extra.size();
         if (getenv("ANIB_DUMP_STARTS")) fprintf(stderr, "WORDTIER frag %zu strand %d: %zu word seeds, %zu fresh\n", f, strand, extra.size(), fresh.size());
         if (fresh.empty() || fresh.size() > (size_t)(WORD_MAX_SEEDS - FRAG_MAX_SEEDS)) continue;   // (a repeat family: left as it is)
         if (wseeds[strand].empty()) wseeds[strand].assign(frags.size(), {});
@@ -428,6 +469,23 @@ int64_t anib_cpu_pair(const uint8_t* qseq, const uint64_t* qrec_off, uint32_t q_
   std::vector<Row> rows;
   run_pair(Q, S, fragsize, rows);
   for (size_t i = 0; i < rows.size() && i < cap; ++i) out[i] = rows[i];
+  return (int64_t)rows.size();
+}
+
+// The same rows plus the trace: fs_out receives one TraceFS per (fragment, strand), ext_out one TraceExt per extension made, in
+// fragment order; counts[0 .. 1] their numbers (written up to the caps).
+int64_t anib_cpu_pair_trace(const uint8_t* qseq, const uint64_t* qrec_off, uint32_t q_nrec, const uint8_t* sseq, const uint64_t* srec_off,
+                            uint32_t s_nrec, int32_t fragsize, Row* out, uint64_t cap, TraceFS* fs_out, uint64_t fs_cap, TraceExt* ext_out,
+                            uint64_t ext_cap, uint64_t* counts) {
+  const Genome Q = pack(qseq, qrec_off, q_nrec), S = pack(sseq, srec_off, s_nrec);
+  std::vector<Row> rows;
+  Trace T;
+  run_pair(Q, S, fragsize, rows, &T);
+  for (size_t i = 0; i < rows.size() && i < cap; ++i) out[i] = rows[i];
+  uint64_t nf = 0, ne = 0;
+  for (const TraceFS& t : T.fs) { if (nf < fs_cap) fs_out[nf] = t; ++nf; }
+  for (const auto& v : T.ext) for (const TraceExt& x : v) { if (ne < ext_cap) ext_out[ne] = x; ++ne; }
+  counts[0] = nf; counts[1] = ne;
   return (int64_t)rows.size();
 }
 }

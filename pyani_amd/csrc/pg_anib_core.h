@@ -30,7 +30,10 @@ constexpr int FRAG_MATCH = 2, FRAG_MISMATCH = -3, FRAG_GAP_OPEN = -7, FRAG_GAP_E
 #define PGA_FRAG_BAND 256
 #endif
 constexpr int FRAG_BAND = PGA_FRAG_BAND;                   // diagonals of the DP band (4 per lane on the device): a 5 + 2k gap of ~80 bases still fits the X-drop
-constexpr int FRAG_SLACK = 200;                // subject bases an extension may use beyond the fragment's own length
+#ifndef PGA_FRAG_SLACK
+#define PGA_FRAG_SLACK 200
+#endif
+constexpr int FRAG_SLACK = PGA_FRAG_SLACK;     // subject bases an extension may use beyond the fragment's own length
 
 struct FragExt {             // one directional extension off an anchor
   int32_t score;             // best score (>= 0; 0 = no extension)
@@ -58,7 +61,16 @@ struct FragHit {             // one HSP: the row of the BLAST table
 #ifndef PGA_FRAG_XDROP
 #define PGA_FRAG_XDROP 166
 #endif
-constexpr int FRAG_TRACK = 16, FRAG_SHIFT_MAX = 8, FRAG_XDROP = PGA_FRAG_XDROP, FRAG_XSYNC = 4;
+#ifndef PGA_FRAG_TRACK
+#define PGA_FRAG_TRACK 16
+#endif
+#ifndef PGA_FRAG_SHIFT_MAX
+#define PGA_FRAG_SHIFT_MAX 8
+#endif
+#ifndef PGA_FRAG_XSYNC
+#define PGA_FRAG_XSYNC 4
+#endif
+constexpr int FRAG_TRACK = PGA_FRAG_TRACK, FRAG_SHIFT_MAX = PGA_FRAG_SHIFT_MAX, FRAG_XDROP = PGA_FRAG_XDROP, FRAG_XSYNC = PGA_FRAG_XSYNC;
 constexpr int FRAG_XDROP_PRELIM = 33;          // blastn's preliminary gapped extension: 30 bits in raw 2 / -3 scores (frag_hsp: chance hits only)
 constexpr int32_t FRAG_NEG = -(1 << 28);
 
@@ -97,8 +109,20 @@ PG_HD FragCellIn frag_cell(bool has_u, const FragCellIn& u, bool has_l, const Fr
   return c;
 }
 
+// What one extension did with its band, for the trace of the CPU checker build: `tr` is an optional pointer that the device
+// build never sets (the device has its own frag_extend_wave and never calls this function); recording changes no result.
+struct FragExtTrace {
+  int32_t ran;                    // 1: this extension was made
+  int32_t recentres;              // re-centrings that moved the band, up to the best cell
+  int32_t net, lo, hi;            // band offset relative to its start when the best cell was found: then, lowest and highest until then
+  int32_t left_low, left_high;    // a live H was computed on the band's first / last diagonal or shifted out there: its path leaves the band
+  int32_t di, dj, score;          // the result
+};
 template <typename QB, typename SB>
-PG_HD FragExt frag_extend(QB&& qbase, int32_t qmax, SB&& sbase, int32_t smax, int32_t abs_floor = FRAG_NEG, int32_t xdrop = FRAG_XDROP) {
+PG_HD FragExt frag_extend(QB&& qbase, int32_t qmax, SB&& sbase, int32_t smax, int32_t abs_floor = FRAG_NEG, int32_t xdrop = FRAG_XDROP,
+                          FragExtTrace* tr = nullptr) {
+  if (tr) *tr = FragExtTrace{1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int32_t tr_n = 0, tr_lo = 0, tr_hi = 0;      // (the trace's running values: what follows the best cell is the search dying out)
   if (qmax <= 0 || smax <= 0) return FragExt{0, 0, 0, 0, 0};   // nothing to extend into (the anchor reaches the fragment's end)
   FragCellIn S[FRAG_BAND];                  // latest cell of every diagonal (index k <-> diagonal K = k + koff)
   const FragCellIn dead{FRAG_NEG, FRAG_NEG, FRAG_NEG, 0, 0, 0};
@@ -117,6 +141,13 @@ PG_HD FragExt frag_extend(QB&& qbase, int32_t qmax, SB&& sbase, int32_t smax, in
         if (s > FRAG_SHIFT_MAX) s = FRAG_SHIFT_MAX;
         if (s < -FRAG_SHIFT_MAX) s = -FRAG_SHIFT_MAX;
         s &= ~1;
+        if (tr && s != 0) {
+          ++tr_n;
+          for (int k = 0; k < s; ++k) tr->left_low |= S[k].h > FRAG_NEG / 2;
+          for (int k = FRAG_BAND + s; k < FRAG_BAND; ++k) tr->left_high |= S[k].h > FRAG_NEG / 2;
+          const int32_t rel = koff + s + FRAG_BAND / 2;
+          tr_lo = rel < tr_lo ? rel : tr_lo; tr_hi = rel > tr_hi ? rel : tr_hi;
+        }
         if (s > 0) { for (int k = 0; k < FRAG_BAND; ++k) S[k] = k + s < FRAG_BAND ? S[k + s] : dead; }
         if (s < 0) { for (int k = FRAG_BAND - 1; k >= 0; --k) S[k] = k + s >= 0 ? S[k + s] : dead; }
         koff += s;
@@ -136,12 +167,17 @@ PG_HD FragExt frag_extend(QB&& qbase, int32_t qmax, SB&& sbase, int32_t smax, in
       const FragCellIn c = frag_cell(i >= 1 && k + 1 < FRAG_BAND, S[k + 1 < FRAG_BAND ? k + 1 : k], j >= 1 && k >= 1, S[k >= 1 ? k - 1 : k],
                                      i >= 1 && j >= 1, S[k], ok, xbest, abs_floor, xdrop);
       S[k] = c;
+      if (tr && c.h > FRAG_NEG / 2) { tr->left_low |= k == 0; tr->left_high |= k == FRAG_BAND - 1; }
       if (c.h > FRAG_NEG / 2 || c.x > FRAG_NEG / 2 || c.y > FRAG_NEG / 2) alive = true;
-      if (c.h > best.score) { best.score = c.h; best.di = i; best.dj = j; best.mm = c.hs >> 16; best.gaps = c.hs & 0xFFFF; }
+      if (c.h > best.score) {
+        best.score = c.h; best.di = i; best.dj = j; best.mm = c.hs >> 16; best.gaps = c.hs & 0xFFFF;
+        if (tr) { tr->recentres = tr_n; tr->net = koff + FRAG_BAND / 2; tr->lo = tr_lo; tr->hi = tr_hi; }
+      }
     }
     dead_run = alive ? 0 : dead_run + 1;
     if (dead_run >= 2) break;
   }
+  if (tr) { tr->di = best.di; tr->dj = best.dj; tr->score = best.score; }
   return best;
 }
 
@@ -165,7 +201,10 @@ PG_HD FragHit frag_join(const FragExt& L, const FragExt& R, int32_t aq, int64_t 
 // out-vote the long true match, but they cannot out-grow it.  The second candidate is found the same way among the matches at
 // least FRAG_VOTE_FAR diagonals away from the first anchor.  Returns the number of candidates (0..2), their indices in cand[].
 struct FragSeed { int32_t s, q, len; };
-constexpr int FRAG_VOTE_WIN = 16, FRAG_VOTE_FAR = 48, FRAG_MAX_SEEDS = 64, FRAG_MIN_CLIP = 11;
+#ifndef PGA_FRAG_MIN_CLIP
+#define PGA_FRAG_MIN_CLIP 11
+#endif
+constexpr int FRAG_VOTE_WIN = 16, FRAG_VOTE_FAR = 48, FRAG_MAX_SEEDS = 64, FRAG_MIN_CLIP = PGA_FRAG_MIN_CLIP;
 PG_HD bool frag_seed_before(const FragSeed& a, const FragSeed& o) {      // a is preferred to o at equal votes / as the longer anchor
   return a.len > o.len || (a.len == o.len && (a.q < o.q || (a.q == o.q && a.s < o.s)));
 }
@@ -516,7 +555,10 @@ constexpr int WORD_K = 11, WORD_FLANK = 32, WORD_FLANK_MIN = 18, WORD_MAX_SEEDS 
 // each passed the flank test (chance: ~1e-7 per hit), while a fragment with a low-complexity stretch can hold more than FRAG_MAX_SEEDS
 // chance 16-mers, all longer than the 11 ... 15-base words of a real 72 % alignment (NC_002696 vs NC_010338, fragments 1573, 2911, 2930:
 // found by the tier and cut from the list again by the length ranking of rounds 3-5).
-constexpr int FRAG_WORD_FIRST = 32;
+#ifndef PGA_FRAG_WORD_FIRST
+#define PGA_FRAG_WORD_FIRST 32
+#endif
+constexpr int FRAG_WORD_FIRST = PGA_FRAG_WORD_FIRST;
 
 // BLAST's e-value for raw score S (blastn 2 / -3, gap costs 5 / 2: lambda = 0.625, K = 0.41), search space m * n without length
 // adjustment; pyani runs blastn with -evalue 1e-15 (anib.py:466).
@@ -549,7 +591,7 @@ PG_HD bool frag_prelim_goes_on(int32_t prelim_score, OK&& reportable) { return p
 // X-drop, ~5 x the cells, which was most of what the fragment kernel did on a C5 grid.
 template <typename QA, typename SA, typename OK>
 PG_HD FragHit frag_hsp(QA&& q_at, int32_t qlen, SA&& s_at, int64_t s_lo, int64_t s_hi, int32_t aq, int64_t as, int32_t alen, OK&& reportable,
-                       bool weak = false) {
+                       bool weak = false, FragExtTrace* tr = nullptr) {      // tr: six entries (the order of the calls below), or none
   const int64_t room_r = s_hi - (as + alen), room_l = as - s_lo;
   const int32_t cap = FRAG_SIZE + FRAG_SLACK;
   auto qr = [&](int32_t t) { return q_at(aq + alen + t); };
@@ -558,19 +600,19 @@ PG_HD FragHit frag_hsp(QA&& q_at, int32_t qlen, SA&& s_at, int64_t s_lo, int64_t
   auto sl = [&](int32_t t) { return s_at(as - 1 - t); };
   const int32_t nr = (int32_t)(room_r < cap ? room_r : cap), nl = (int32_t)(room_l < cap ? room_l : cap);
   if (weak) {
-    const FragExt Rp = frag_extend(qr, qlen - (aq + alen), sr, nr, FRAG_NEG, FRAG_XDROP_PRELIM);
-    const FragExt Lp = frag_extend(ql, aq, sl, nl, FRAG_NEG, FRAG_XDROP_PRELIM);
+    const FragExt Rp = frag_extend(qr, qlen - (aq + alen), sr, nr, FRAG_NEG, FRAG_XDROP_PRELIM, tr ? tr + 0 : nullptr);
+    const FragExt Lp = frag_extend(ql, aq, sl, nl, FRAG_NEG, FRAG_XDROP_PRELIM, tr ? tr + 1 : nullptr);
     if (!frag_prelim_goes_on(Rp.score + Lp.score + FRAG_MATCH * alen, reportable)) return frag_join(Lp, Rp, aq, as, alen);      // (fails the cut-off: the caller drops it)
   }
-  FragExt R = frag_extend(qr, qlen - (aq + alen), sr, nr);
-  FragExt L = frag_extend(ql, aq, sl, nl);
+  FragExt R = frag_extend(qr, qlen - (aq + alen), sr, nr, FRAG_NEG, FRAG_XDROP, tr ? tr + 2 : nullptr);
+  FragExt L = frag_extend(ql, aq, sl, nl, FRAG_NEG, FRAG_XDROP, tr ? tr + 3 : nullptr);
   // The second look (frag_second_look): where one side scores less than the X-drop, the other side may have crossed a dip deeper than
   // that side is worth — blastn then reports the far part as an HSP of its own and cuts this one at it.  That side is grown again
   // with the running score not allowed below minus the other side's total; without such a dip the result is the same extension.
   const int32_t r_total = R.score + FRAG_MATCH * alen, l_total = L.score;
   if (reportable(r_total + l_total)) {      // (a second look can only lower the score: a row that fails the e-value already is not looked at again)
-    if (frag_second_look(r_total, L.score)) L = frag_extend(ql, aq, sl, nl, -r_total);
-    if (frag_second_look(l_total, R.score)) R = frag_extend(qr, qlen - (aq + alen), sr, nr, -l_total);
+    if (frag_second_look(r_total, L.score)) L = frag_extend(ql, aq, sl, nl, -r_total, FRAG_XDROP, tr ? tr + 4 : nullptr);
+    if (frag_second_look(l_total, R.score)) R = frag_extend(qr, qlen - (aq + alen), sr, nr, -l_total, FRAG_XDROP, tr ? tr + 5 : nullptr);
   }
   return frag_join(L, R, aq, as, alen);
 }
