@@ -551,6 +551,49 @@ int pg_screen_representatives_read(pg_ctx* ctx, int32_t* rep_out, uint32_t* via_
 int pg_screen_representatives_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
 int pg_screen_representatives_release(pg_ctx* ctx);
 
+/* ---- screen, the sweep: the components over a ladder of thresholds in ONE pass.  The list of entries (a[e], b[e],
+ * shared[e]) over n nodes is that of the components (unsorted, a pair in one direction or both, once or several times, an entry with
+ * a[e] == b[e] ignored altogether; shared == NULL weighs every entry 1), and every entry carries level[e] (uint16) in 0 ... steps: the
+ * number of leading steps of the ladder that keep it.  The entry is present at step s iff level[e] > s, so the graphs of the steps are
+ * nested.  For every step s of 0 ... steps - 1, over the entries with a != b present at s:
+ *   entries[s]    uint64  their number
+ *   components[s] uint32  the connected components over all n nodes, singletons included
+ *   singletons[s] uint32  the components of one node
+ *   largest[s]    uint32  the size of the largest component
+ *   pair_slots[s] uint64  the sum over the components of size * (size - 1)
+ * and, for every step named in snapshot_steps (at most 32, each < steps; a step may be named twice), the three node arrays root, entries,
+ * weight that pg_screen_components gives on the entries present at that step.  All integers that depend on neither the order of the list
+ * nor any schedule (pyani_amd.screen.sweep_of_pairs is the statement).  The entries are bucketed by level with one stable radix sort and
+ * hooked bucket after bucket, from level `steps` down, into ONE forest of the kind pg_screen_components builds; after every non-empty
+ * bucket a census of the forest gives the step's row, and a step whose bucket is empty has the row of the step above it.
+ * pg_screen_sweep takes the list from the host and keeps it WHOLE on the device for the sort (14 bytes an entry, 10 without weights, twice
+ * during the call), 1 <= n <= 2^20, 1 <= steps <= 4096.  PG_E_ARG, checked before anything is copied or replaced: n or steps outside
+ * their range, more than 32 snapshots or a snapshot step >= steps, m > 0 with a NULL a, b or level, an index outside [0, n), a level
+ * greater than steps.
+ * pg_screen_index_sweep takes the list from the resident index instead: need is a table uint32[steps][n], row s the thresholds of step s
+ * (pyani_amd.screen.sweep_thresholds), every column non-decreasing in s.  The bands band_first, band_first + band_step, ... are counted
+ * and selected by ROW 0 exactly as pg_screen_index_select does; every kept triple gets its level on the device — the first step s with
+ * shared < min(need[s][a], need[s][b]), or steps — and is appended to a list there; no pair is copied to the host.  *n_pairs_out = the
+ * kept cells, what pg_screen_index_select reports for row 0; the result is that of pg_screen_sweep over that list.  The index, its latest
+ * selection and pg_screen_index_last are left as they were.  PG_E_ARG as above and as pg_screen_index_select (no resident index, n that is
+ * not the index's), for steps * n > 2^28 (the table's 1 GB) and for a table with a column that falls.
+ * The result stays RESIDENT in a state of its own, independent of the resident matrix, the indexes, the components and the
+ * representatives, until the next ACCEPTED sweep call (a refused one leaves it readable; an allocation that fails replaces nothing),
+ * pg_screen_sweep_release (PG_OK when there is none), pg_clear_genomes or pg_destroy.  pg_screen_sweep_read copies the five per-step
+ * arrays out, `steps` entries each; pg_screen_sweep_read_snapshot the node arrays of snapshot k (its position in snapshot_steps), n
+ * entries each; PG_E_ARG when there is no sweep or no such snapshot.
+ * pg_screen_sweep_last: counts_out[6] = n, steps, entries worked (those with a != b), entries ignored (a == b), worked entries of level 0
+ * (present at no step), non-empty buckets (= censuses); ms_out[4] = band count + select + levels (the index path only), histogram + sort,
+ * hook + accumulate, census milliseconds (HIP events on the context's stream); all 0 when nothing is resident. */
+int pg_screen_sweep(pg_ctx* ctx, const int32_t* a, const int32_t* b, const uint32_t* shared, const uint16_t* level, uint64_t m, uint32_t n, uint32_t steps,
+                    const uint32_t* snapshot_steps, uint32_t n_snapshots);
+int pg_screen_index_sweep(pg_ctx* ctx, const uint32_t* need, uint32_t n, uint32_t steps, uint32_t band_first, uint32_t band_step, const uint32_t* snapshot_steps,
+                          uint32_t n_snapshots, uint64_t* n_pairs_out);
+int pg_screen_sweep_read(pg_ctx* ctx, uint64_t* entries_out, uint32_t* components_out, uint32_t* singletons_out, uint32_t* largest_out, uint64_t* pair_slots_out);
+int pg_screen_sweep_read_snapshot(pg_ctx* ctx, uint32_t k, int32_t* root_out, uint64_t* entries_out, uint64_t* weight_out);
+int pg_screen_sweep_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
+int pg_screen_sweep_release(pg_ctx* ctx);
+
 /* ---- screen, the search: new genomes against a resident collection.  S(g), size, kmer and scale as for
  * pg_screen_matrix.  A collection ("db") of n <= 2^20 genomes is indexed once; then, per call, q query genomes are placed against it:
  *   hits[i][b] = |S(query i) & S(db b)|, a q x n rectangle of uint32, row-major

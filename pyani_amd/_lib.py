@@ -116,6 +116,12 @@ SIGNATURES = {
     "pg_screen_representatives_read": (_int, [_vp, _vp, _vp]),
     "pg_screen_representatives_last": (_int, [_vp, _vp, _vp]),
     "pg_screen_representatives_release": (_int, [_vp]),
+    "pg_screen_sweep": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _u32, _vp, _u32]),
+    "pg_screen_index_sweep": (_int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _u32, _P(_u64)]),
+    "pg_screen_sweep_read": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "pg_screen_sweep_read_snapshot": (_int, [_vp, _u32, _vp, _vp, _vp]),
+    "pg_screen_sweep_last": (_int, [_vp, _vp, _vp]),
+    "pg_screen_sweep_release": (_int, [_vp]),
     "pg_screen_search_index": (_int, [_vp, _vp, _u32, _i32, _i32, _vp]),
     "pg_screen_search_index_release": (_int, [_vp]),
     "pg_screen_search_count": (_int, [_vp, _vp, _u32, _vp]),

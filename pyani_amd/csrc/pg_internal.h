@@ -62,6 +62,11 @@ struct PgScreenRepresentativesStats {      // pg_screen_representatives_last: th
   double select_ms = 0.0, sort_ms = 0.0, rounds_ms = 0.0, assign_ms = 0.0;                          // band count + select (index path), rank sort, rounds, assign
 };
 
+struct PgScreenSweepStats {      // pg_screen_sweep_last: the resident sweep's call
+  uint64_t nodes = 0, steps = 0, worked = 0, ignored = 0, level0 = 0, buckets = 0;      // worked: entries with a != b; level0: those of them present at no step; buckets: non-empty
+  double select_ms = 0.0, sort_ms = 0.0, hook_ms = 0.0, census_ms = 0.0;                // band count + select + levels (index path), histogram + sort, hook + accumulate, census
+};
+
 struct PgScreenSearchStats {
   uint64_t keys = 0, kmers = 0, entries = 0, slices = 0, index_bytes = 0;                // the search index: sampled keys, distinct k-mers, (k-mer, genome) entries, device bytes its buffers hold
   uint64_t query_keys = 0, lookups = 0, matched = 0, increments = 0, query_slices = 0;   // the latest count: lookups = the distinct k-mers of the queries
@@ -161,6 +166,8 @@ struct pg_ctx {
   PgScreenComponentsStats screen_components_stats;      // pg_screen_components_last: the resident components' call
   void* screen_representatives_state = nullptr;      // resident representatives of the latest pg_screen_representatives / pg_screen_index_representatives (pg_screen.hip); independent of the three above
   PgScreenRepresentativesStats screen_representatives_stats;      // pg_screen_representatives_last: the resident representatives' call
+  void* screen_sweep_state = nullptr;      // resident sweep of the latest pg_screen_sweep / pg_screen_index_sweep (pg_screen.hip); independent of the four above
+  PgScreenSweepStats screen_sweep_stats;      // pg_screen_sweep_last: the resident sweep's call
   void* screen_search_state = nullptr;          // resident search index of pg_screen_search_index and the latest rectangle counted against it (pg_screen.hip); independent of the three above and of the genome store
   PgScreenGatherStats screen_gather_stats;      // pg_screen_gather_last
   PgScreenGatherAbundStats screen_gather_abund_stats;      // pg_screen_gather_abund_last
@@ -285,6 +292,7 @@ void pg_dist_drop(pg_ctx* ctx);         // ... the distribution calls' resident 
 void pg_screen_drop(pg_ctx* ctx);       // ... the screen's resident matrix and selection (pg_screen.hip): the same, and with the genome store
 void pg_screen_components_drop(pg_ctx* ctx); // ... the screen's resident components (pg_screen.hip): with the context, the genome store or on request
 void pg_screen_representatives_drop(pg_ctx* ctx); // ... the screen's resident representatives (pg_screen.hip): the same
+void pg_screen_sweep_drop(pg_ctx* ctx); // ... the screen's resident sweep (pg_screen.hip): the same
 void pg_screen_index_drop(pg_ctx* ctx); // ... the screen's resident k-mer index and its selection (pg_screen.hip): with the context, the genome store or on request
 void pg_screen_search_drop(pg_ctx* ctx); // ... the screen's resident search index and rectangle (pg_screen.hip): with the context or on request — NOT with the genome store: it names genomes by call index only
 int pg_anib_reduce_run(pg_ctx* ctx, uint32_t n_pairs, const uint64_t* offsets, const uint32_t* n_frags, const int32_t* frag,

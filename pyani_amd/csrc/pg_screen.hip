@@ -91,6 +91,11 @@
 // (a list from the host, uploaded whole) and pg_screen_index_representatives (the bands' kept triples with a < b, appended to a device list)
 // rank the nodes by score with one radix sort, decide them in rounds of three launches and assign the covered ones by a 64-bit atomic
 // maximum; P1 ... P8 stand there with their state.
+//
+// pgscr_sweep.inc — the SWEEP: the components over a ladder of thresholds in one descending pass.  pg_screen_sweep (a
+// list with a level per entry, from the host) and pg_screen_index_sweep (the bands' kept triples, their levels found on the device from the
+// resident need table) bucket the entries by level with one stable radix sort, hook bucket after bucket into ONE forest through the body of
+// K2 and take a census of it after every bucket; W1 ... W8 stand there with their state.
 #include <algorithm>
 #include <hipcub/hipcub.hpp>
 #include <memory>
@@ -103,9 +108,9 @@
 
 namespace {
 
-// the stages whose milliseconds pg_screen_last, pg_screen_index_last, pg_screen_components_last, pg_screen_representatives_last, pg_screen_search_last,
+// the stages whose milliseconds pg_screen_last, pg_screen_index_last, pg_screen_components_last, pg_screen_representatives_last, pg_screen_sweep_last, pg_screen_search_last,
 // pg_screen_search_add_last, pg_screen_search_remove_last and pg_screen_gather_last report
-enum ScreenStage { ST_SCAN, ST_GROUP, ST_COUNT, ST_SELECT, ST_HOOK, ST_FLATTEN, ST_LOOKUP, ST_EXPAND, ST_ARGMAX, ST_CLAIM, ST_MERGE, ST_CHECK, ST_MARK, ST_COMPACT, ST_WEIGHT, ST_ATTRIBUTE, ST_SORT, ST_STATS, ST_ROUNDS, ST_ASSIGN };
+enum ScreenStage { ST_SCAN, ST_GROUP, ST_COUNT, ST_SELECT, ST_HOOK, ST_FLATTEN, ST_LOOKUP, ST_EXPAND, ST_ARGMAX, ST_CLAIM, ST_MERGE, ST_CHECK, ST_MARK, ST_COMPACT, ST_WEIGHT, ST_ATTRIBUTE, ST_SORT, ST_STATS, ST_ROUNDS, ST_ASSIGN, ST_CENSUS };
 
 struct ScreenEvents {      // event pairs on the context's stream, summed per stage after the call's last synchronisation
   std::vector<hipEvent_t> ev;
@@ -158,6 +163,7 @@ hipError_t tmp_room(size_t& tmp_bytes, Query query) {
 #include "pgscr_index.inc"
 #include "pgscr_components.inc"
 #include "pgscr_representatives.inc"
+#include "pgscr_sweep.inc"
 #include "pgscr_search.inc"
 #include "pgscr_add.inc"
 #include "pgscr_store.inc"

@@ -7,7 +7,8 @@
 //   K1 components_init_kernel     parent[v] = v, entries = weight = 0
 //   K2 components_hook_kernel     one pass over a list (a chunk of the host's, or a band's kept triples): accumulate — a run of equal a
 //                                 inside a wave is summed by a segmented shuffle reduction and adds ONCE to entries[a] and weight[a], 64-bit
-//                                 atomics without return value — and hook: both roots found, the larger hooked under the smaller
+//                                 atomics without return value — and hook: both roots found, the larger hooked under the smaller; its
+//                                 body, components_hook_entry, is the sweep's bucket pass as well (pgscr_sweep.inc)
 //   K3 components_flatten_kernel  root[v] = the root of v's tree (halving as it goes); the roots counted, one atomic per wave
 namespace {
 
@@ -43,6 +44,39 @@ __device__ __forceinline__ uint32_t components_find(uint32_t* parent, uint32_t u
   }
 }
 
+// The accumulate and the hook of ONE entry per lane — the body of K2, and of the sweep's bucket pass (pgscr_sweep.inc).  Every lane of the
+// wave calls it (the shuffles); in = the lane holds an entry e, (ua, ub) its nodes (0xFFFFFFFF both where it holds none).  Returns whether
+// THIS lane's compare-and-swap hooked a root: each success takes one tree away, so the successes of a list are n - its components.
+__device__ __forceinline__ bool components_hook_entry(uint32_t lane, bool in, uint32_t ua, uint32_t ub, const uint32_t* __restrict__ s, uint64_t e, uint32_t n,
+                                                      uint32_t* parent, unsigned long long* __restrict__ entries, unsigned long long* __restrict__ weight) {
+  const bool work = in && ua != ub && ua < n && ub < n;      // (the host has refused an index outside [0, n): the bound is kept for the memory's sake)
+  unsigned long long cnt = work ? 1ull : 0ull, w = work ? (s ? (unsigned long long)s[e] : 1ull) : 0ull;
+  // accumulate: runs of equal a in consecutive lanes; run = the number of run heads up to this lane, so equal run numbers are one run
+  const uint32_t prev = __shfl_up(ua, 1, 64);
+  const bool head = lane == 0u || ua != prev;
+  const unsigned long long heads = __ballot(head);
+  const uint32_t run = (uint32_t)__popcll(heads & ((2ull << lane) - 1ull));      // (lane 63: 2 << 63 wraps to 0, minus one = every bit)
+  for (uint32_t d = 1; d < 64u; d <<= 1) {
+    const uint32_t r2 = __shfl_down(run, d, 64);
+    const unsigned long long c2 = __shfl_down(cnt, d, 64), w2 = __shfl_down(w, d, 64);
+    if (lane + d < 64u && r2 == run) { cnt += c2; w += w2; }
+  }
+  if (head && cnt) { atomicAdd(entries + ua, cnt); atomicAdd(weight + ua, w); }
+  // hook
+  bool hooked = false;
+  if (work) {
+    uint32_t u = components_find(parent, ua), v = components_find(parent, ub);
+    while (u != v) {      // u in a's tree, v in b's; max(u, v) drops with every failed round
+      if (u < v) { const uint32_t t = u; u = v; v = t; }
+      const uint32_t old = atomicCAS(parent + u, u, v);
+      if (old == u) { hooked = true; break; }      // u was a root and now hangs under v < u
+      if (old > u) break;       // (never: a cell only decreases; kept so that a broken array cannot spin)
+      u = components_find(parent, old);      // old < u: u's parent when the swap looked; on from its tree's top
+    }
+  }
+  return hooked;
+}
+
 __global__ __launch_bounds__(256) void components_hook_kernel(const int32_t* __restrict__ a, const int32_t* __restrict__ b, const uint32_t* __restrict__ s,
                                                                uint64_t m, uint32_t n, uint32_t* parent, unsigned long long* __restrict__ entries,
                                                                unsigned long long* __restrict__ weight) {
@@ -52,30 +86,7 @@ __global__ __launch_bounds__(256) void components_hook_kernel(const int32_t* __r
     const uint64_t e = base + lane;
     const bool in = e < m;
     const uint32_t ua = in ? (uint32_t)a[e] : 0xFFFFFFFFu, ub = in ? (uint32_t)b[e] : 0xFFFFFFFFu;
-    const bool work = in && ua != ub && ua < n && ub < n;      // (the host has refused an index outside [0, n): the bound is kept for the memory's sake)
-    unsigned long long cnt = work ? 1ull : 0ull, w = work ? (s ? (unsigned long long)s[e] : 1ull) : 0ull;
-    // accumulate: runs of equal a in consecutive lanes; run = the number of run heads up to this lane, so equal run numbers are one run
-    const uint32_t prev = __shfl_up(ua, 1, 64);
-    const bool head = lane == 0u || ua != prev;
-    const unsigned long long heads = __ballot(head);
-    const uint32_t run = (uint32_t)__popcll(heads & ((2ull << lane) - 1ull));      // (lane 63: 2 << 63 wraps to 0, minus one = every bit)
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-      const uint32_t r2 = __shfl_down(run, d, 64);
-      const unsigned long long c2 = __shfl_down(cnt, d, 64), w2 = __shfl_down(w, d, 64);
-      if (lane + d < 64u && r2 == run) { cnt += c2; w += w2; }
-    }
-    if (head && cnt) { atomicAdd(entries + ua, cnt); atomicAdd(weight + ua, w); }
-    // hook
-    if (work) {
-      uint32_t u = components_find(parent, ua), v = components_find(parent, ub);
-      while (u != v) {      // u in a's tree, v in b's; max(u, v) drops with every failed round
-        if (u < v) { const uint32_t t = u; u = v; v = t; }
-        const uint32_t old = atomicCAS(parent + u, u, v);
-        if (old == u) break;      // u was a root and now hangs under v < u
-        if (old > u) break;       // (never: a cell only decreases; kept so that a broken array cannot spin)
-        u = components_find(parent, old);      // old < u: u's parent when the swap looked; on from its tree's top
-      }
-    }
+    (void)components_hook_entry(lane, in, ua, ub, s, e, n, parent, entries, weight);
   }
 }
 

@@ -653,6 +653,93 @@ class Engine:
         finally:
             self.screen_representatives_release()
 
+    # the sweep: the components over a ladder of thresholds in one pass, per-step arrays and snapshots resident on the context
+    def _screen_sweep_read(self, n: int, steps: int, n_snapshots: int):
+        entries, pair_slots = np.zeros(steps, dtype=np.uint64), np.zeros(steps, dtype=np.uint64)
+        components, singletons, largest = (np.zeros(steps, dtype=np.uint32) for _ in range(3))
+        self._check(self.lib.pg_screen_sweep_read(self._h, entries.ctypes.data, components.ctypes.data, singletons.ctypes.data, largest.ctypes.data,
+                                                  pair_slots.ctypes.data))
+        snaps = []
+        for k in range(n_snapshots):
+            root, e, w = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+            self._check(self.lib.pg_screen_sweep_read_snapshot(self._h, k, root.ctypes.data, e.ctypes.data, w.ctypes.data))
+            snaps.append((root, e, w))
+        return entries, components, singletons, largest, pair_slots, snaps
+
+    def screen_sweep(self, a, b, shared=None, level=None, n: int = 0, steps: int = 0, snapshots=()):
+        """pg_screen_sweep + pg_screen_sweep_read (+ _read_snapshot): (entries uint64[steps], components, singletons, largest
+        uint32[steps], pair_slots uint64[steps], [(root, entries, weight) per snapshot]) of the list of entries (a[e], b[e], shared[e])
+        with levels level[e] over n nodes, as pyani_amd.screen.sweep_of_pairs states them; shared=None counts 1 everywhere."""
+        x = np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+        y = np.ascontiguousarray(b, dtype=np.int32).reshape(-1)
+        s = None if shared is None else np.ascontiguousarray(shared, dtype=np.uint32).reshape(-1)
+        lv = np.ascontiguousarray(np.zeros(0, np.uint16) if level is None else level, dtype=np.uint16).reshape(-1)
+        if len(x) != len(y) or len(lv) != len(x) or (s is not None and len(s) != len(x)):
+            raise ValueError("a, b, shared and level must have the same length")
+        snaps = np.ascontiguousarray(list(snapshots), dtype=np.uint32).reshape(-1)
+        m = len(x)
+        self._check(self.lib.pg_screen_sweep(self._h, x.ctypes.data if m else None, y.ctypes.data if m else None, s.ctypes.data if s is not None and m else None,
+                                             lv.ctypes.data if m else None, m, int(n), int(steps), snaps.ctypes.data if len(snaps) else None, len(snaps)))
+        return self._screen_sweep_read(int(n), int(steps), len(snaps))
+
+    def screen_index_sweep(self, need, band_first: int = 0, band_step: int = 1, snapshots=()):
+        """pg_screen_index_sweep + the reads: screen_sweep's tuple, and n_pairs as its last member, of the kept cells of the bands of the
+        resident index under the table need uint32[steps][n] (pyani_amd.screen.sweep_thresholds): selected by row 0, levels found on the
+        device — screen_sweep of the list screen_index_select(need[0]) would return with screen.sweep_levels — without a pair leaving
+        the device."""
+        t = np.ascontiguousarray(need, dtype=np.uint32)
+        if t.ndim != 2:
+            raise ValueError("a need table is uint32[steps][n]")
+        steps, n = t.shape
+        snaps = np.ascontiguousarray(list(snapshots), dtype=np.uint32).reshape(-1)
+        m = ctypes.c_uint64(0)
+        self._check(self.lib.pg_screen_index_sweep(self._h, t.ctypes.data if t.size else None, n, steps, int(band_first), int(band_step),
+                                                   snaps.ctypes.data if len(snaps) else None, len(snaps), ctypes.byref(m)))
+        return (*self._screen_sweep_read(n, steps, len(snaps)), int(m.value))
+
+    def screen_sweep_last(self) -> dict:
+        """pg_screen_sweep_last: counts and stage milliseconds of the resident sweep (all 0 when there is none)."""
+        c = (ctypes.c_uint64 * 6)()
+        ms = (ctypes.c_double * 4)()
+        self._check(self.lib.pg_screen_sweep_last(self._h, ctypes.addressof(c), ctypes.addressof(ms)))
+        return {"n": int(c[0]), "steps": int(c[1]), "entries": int(c[2]), "ignored": int(c[3]), "level0": int(c[4]), "buckets": int(c[5]),
+                "select_ms": float(ms[0]), "sort_ms": float(ms[1]), "hook_ms": float(ms[2]), "census_ms": float(ms[3])}
+
+    def screen_sweep_release(self) -> None:
+        self._check(self.lib.pg_screen_sweep_release(self._h))
+
+    def screen_sweep_of(self, ids, options, identities, labels=None, path: str = "auto", snapshots=()):
+        """The components of the pairs the screen keeps among the resident genomes `ids` at EVERY identity of the ladder `identities`
+        (strictly ascending, at most 4096; pyani_amd.screen.ScreenSweep).  options.min_identity is IGNORED in favour
+        of the ladder: the pairs are those kept at identities[0]; kmer, scale and min_shared are the options'.  path "dense":
+        screen_candidates at identities[0], levels on the host, then the list entry (the kept pairs are read back once); "index":
+        screen_index -> sweep_thresholds -> screen_index_sweep -> release, on errors too — no pair is read back; "auto" as
+        screen_candidates.  Nothing stays resident afterwards.  A single engine: MultiEngine has no sweep."""
+        from . import screen
+        options = screen.check_options(options)
+        t = screen.check_ladder(identities)
+        options = options._replace(min_identity=float(t[0]))
+        snaps = screen.check_snapshots(snapshots, len(t))
+        ids = [int(i) for i in ids]
+        if not ids:
+            raise ValueError("a sweep needs one genome or more")
+        if screen.resolve_path(path, len(ids)) == "index":
+            labels = screen._labels_for(ids, labels, screen.INDEX_MAX_GENOMES)
+            if len(t) * len(ids) > screen.SWEEP_MAX_TABLE:
+                raise ValueError(f"{len(t)} steps x {len(ids)} genomes are more than the 2^28 words of a need table")
+            try:
+                sizes = self.screen_index(ids, options.kmer, options.scale)
+                need = screen.sweep_thresholds(sizes, options.kmer, t, options.min_shared)
+                arrays = self.screen_index_sweep(need, snapshots=snaps)[:6]
+            finally:
+                self.screen_index_release()
+                self.screen_sweep_release()
+            return screen.sweep_from_arrays(labels, t, arrays, snaps)
+        try:
+            return self.screen_candidates(ids, options, labels, path="dense").sweep(t, snaps, engine=self)
+        finally:
+            self.screen_sweep_release()
+
     # the search (DESIGN.md §16.4): a collection resident as a k-mer index with its keys, new genomes placed against it
     def screen_search_index(self, ids, kmer: int = 16, scale: int = 256, labels=None) -> np.ndarray:
         """pg_screen_search_index: builds the resident SEARCH index of the genomes in the order given (up to 2^20; every distinct k-mer

@@ -217,6 +217,24 @@ class ScreenedPairs(NamedTuple):
             rep, via = engine.screen_representatives(self.a, self.b, self.shared, n=n, score=score)
         return clusters_from_nodes(self.labels, rep, via, score)
 
+    def sweep(self, identities, snapshots=(), engine=None) -> "ScreenSweep":
+        """The components of the kept pairs at every identity of a ladder: levels by sweep_thresholds + sweep_levels,
+        then ONE pass on `engine` (Engine.screen_sweep), or the numpy statement sweep_of_pairs when none is given.  Both give the same
+        ScreenSweep.  The ladder must start at or above options.min_identity (ValueError): these are the pairs kept THERE, and a lower
+        step would miss pairs this list never held.  snapshots: at most 32 steps whose node arrays are kept (ScreenSweep.components_at)."""
+        t = check_ladder(identities)
+        if t[0] < self.options.min_identity:
+            raise ValueError(f"the ladder starts at {t[0]!r}, below the {self.options.min_identity!r} these pairs were kept at")
+        snaps = check_snapshots(snapshots, len(t))
+        n = len(self.labels)
+        need = sweep_thresholds(self.sizes, self.options.kmer, t, self.options.min_shared)
+        level = sweep_levels(self.a, self.b, self.shared, need)
+        if engine is None:
+            arrays = sweep_of_pairs(self.a, self.b, level, n, len(t), self.shared, snaps)
+        else:
+            arrays = engine.screen_sweep(self.a, self.b, self.shared, level, n=n, steps=len(t), snapshots=snaps)
+        return sweep_from_arrays(self.labels, t, arrays, snaps)
+
 
 # ---- the connected components of the kept pairs (DESIGN.md §16.3) ---------------------------------------------------------------------------
 def _check_entries(a, b, shared, n):
@@ -391,6 +409,164 @@ def index_components_on(engines, run_all, ids, options, labels=None) -> ScreenCo
             e.screen_index_release()
             e.screen_components_release()
     return components_from_nodes(labels, *nodes)
+
+
+# ---- the sweep: the components over a ladder of thresholds ------------------------------------------------------------------
+SWEEP_MAX_STEPS = 4096
+SWEEP_MAX_SNAPSHOTS = 32
+SWEEP_MAX_TABLE = 1 << 28          # words of the need table the index form takes (Engine.screen_index_sweep)
+
+
+def check_ladder(identities) -> np.ndarray:
+    """A ladder: 1 ... SWEEP_MAX_STEPS identities as float64, none NaN, STRICTLY ascending (ValueError otherwise)."""
+    t = np.ascontiguousarray(identities, dtype=np.float64).reshape(-1)
+    if not 1 <= len(t) <= SWEEP_MAX_STEPS:
+        raise ValueError(f"a ladder has 1 ... {SWEEP_MAX_STEPS} steps, not {len(t)}")
+    if np.isnan(t).any() or (np.diff(t) <= 0).any():
+        raise ValueError("a ladder's identities must be numbers in strictly ascending order")
+    return t
+
+
+def check_snapshots(snapshots, steps: int) -> List[int]:
+    snaps = [int(s) for s in snapshots]
+    if len(snaps) > SWEEP_MAX_SNAPSHOTS:
+        raise ValueError(f"a sweep keeps at most {SWEEP_MAX_SNAPSHOTS} snapshots, not {len(snaps)}")
+    if any(not 0 <= s < steps for s in snaps):
+        raise ValueError(f"a snapshot step lies outside [0, {steps})")
+    return snaps
+
+
+def sweep_thresholds(sizes, kmer: int, identities, min_shared: int = DEFAULT_MIN_SHARED) -> np.ndarray:
+    """need uint32[S][n]: row s = identity_thresholds(sizes, kmer, T_s, min_shared) for the ladder T_0 < ... < T_{S-1} (check_ladder).
+    Every column is non-decreasing in s — a higher identity never asks for fewer shared k-mers; this is checked, ValueError otherwise —
+    so the graphs of the steps are nested."""
+    t = check_ladder(identities)
+    need = np.stack([identity_thresholds(sizes, kmer, float(x), min_shared) for x in t])
+    check_need_table(need)
+    return need
+
+
+def check_need_table(need) -> np.ndarray:
+    need = np.asarray(need)
+    if need.ndim != 2 or not 1 <= need.shape[0] <= SWEEP_MAX_STEPS:
+        raise ValueError(f"a need table is uint32[steps][n] with 1 ... {SWEEP_MAX_STEPS} steps")
+    if need.shape[0] > 1 and (need[1:] < need[:-1]).any():
+        raise ValueError("a need table's columns must not fall from one step to the next")
+    return need
+
+
+def sweep_levels(a, b, shared, need) -> np.ndarray:
+    """level uint16[m] of the entries (a, b, shared) under the table `need` of sweep_thresholds: the number of leading steps that keep
+    the entry — the smallest s with shared < min(need[s][a], need[s][b]), or S when there is none.  The entry is present at step s iff
+    level > s, which is the very rule screen_candidates applies at T_s."""
+    need = check_need_table(need)
+    a = np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+    b = np.ascontiguousarray(b, dtype=np.int64).reshape(-1)
+    s = np.ascontiguousarray(shared, dtype=np.uint32).reshape(-1)
+    if len(a) != len(b) or len(s) != len(a):
+        raise ValueError("a, b and shared must have the same length")
+    level = np.zeros(len(a), dtype=np.uint16)
+    alive = np.arange(len(a))      # the entries every step so far has kept
+    for row in need:
+        if not len(alive):
+            break
+        alive = alive[s[alive] >= np.minimum(row[a[alive]], row[b[alive]])]
+        level[alive] += np.uint16(1)
+    return level
+
+
+def levels_of_values(values, thresholds) -> np.ndarray:
+    """level uint16[m] of any float weight under a ladder of thresholds (check_ladder): the number of thresholds <= value, NaN giving 0 —
+    present at step s iff value >= thresholds[s].  With it a list of exact identities can be swept as well."""
+    t = check_ladder(thresholds)
+    v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+    level = np.searchsorted(t, v, side="right")
+    level[np.isnan(v)] = 0
+    return level.astype(np.uint16)
+
+
+def sweep_of_pairs(a, b, level, n, steps, shared=None, snapshots=()):
+    """THE STATEMENT of the sweep (the host's; Engine.screen_sweep is held to it): the list of entries (a[e], b[e], shared[e]) is that
+    of components_of_pairs, and entry e is present at step s iff level[e] > s (0 <= level[e] <= steps).  For every step s of
+    0 ... steps - 1, over the entries with a != b present at s:
+
+        entries[s]    uint64  their number
+        components[s] uint32  the connected components over all n nodes, singletons included
+        singletons[s] uint32  the components of one node
+        largest[s]    uint32  the size of the largest component
+        pair_slots[s] uint64  the sum over the components of size * (size - 1)
+
+    and for every step of `snapshots` the (root, entries, weight) of components_of_pairs on the entries present there.  Returns
+    (entries, components, singletons, largest, pair_slots, [node arrays per snapshot]).  One components_of_pairs call per step: slow,
+    obvious, and independent of the device's single pass."""
+    a, b, s, n = _check_entries(a, b, shared, n)
+    steps = int(steps)
+    if not 1 <= steps <= SWEEP_MAX_STEPS:
+        raise ValueError(f"a sweep has 1 ... {SWEEP_MAX_STEPS} steps, not {steps}")
+    level = np.ascontiguousarray(level, dtype=np.int64).reshape(-1)
+    if len(level) != len(a):
+        raise ValueError("a, b and level must have the same length")
+    if len(level) and (level.min() < 0 or level.max() > steps):
+        raise ValueError(f"a level lies outside [0, {steps}]")
+    snaps = check_snapshots(snapshots, steps)
+    entries, pair_slots = np.zeros(steps, dtype=np.uint64), np.zeros(steps, dtype=np.uint64)
+    components, singletons, largest = (np.zeros(steps, dtype=np.uint32) for _ in range(3))
+    nodes_at = {}
+    for step in range(steps):
+        here = level > step
+        nodes = components_of_pairs(a[here], b[here], None if s is None else s[here], n)
+        size = np.bincount(nodes[0], minlength=n).astype(np.uint64)
+        size = size[size > 0]
+        entries[step] = int((a[here] != b[here]).sum())
+        components[step], singletons[step], largest[step] = len(size), int((size == 1).sum()), int(size.max())
+        pair_slots[step] = int((size * (size - np.uint64(1))).sum())
+        if step in snaps:
+            nodes_at[step] = nodes
+    return entries, components, singletons, largest, pair_slots, [nodes_at[k] for k in snaps]
+
+
+class ScreenSweep(NamedTuple):
+    """The components of a list of entries over a ladder of identities: one value per step of every array of
+    sweep_of_pairs, complete = (pair_slots == entries) — for a duplicate-free list that holds both directions, such as a selection,
+    "every component is a clique", the sense of ScreenComponents.complete — and the node arrays of the snapshot steps."""
+    labels: Optional[List[str]]
+    identities: np.ndarray       # float64[S], ascending
+    entries: np.ndarray          # uint64[S]
+    components: np.ndarray       # uint32[S]
+    singletons: np.ndarray       # uint32[S]
+    largest: np.ndarray          # uint32[S]
+    pair_slots: np.ndarray       # uint64[S]
+    complete: np.ndarray         # bool[S]
+    snapshot_steps: List[int]
+    snapshots: list              # [(root, entries, weight)] in the order of snapshot_steps
+
+    def frame(self) -> pd.DataFrame:
+        """One row per step: step, identity, entries, components, singletons, largest, pair_slots, complete."""
+        return pd.DataFrame({"step": np.arange(len(self.identities), dtype=np.int64), "identity": self.identities, "entries": self.entries,
+                             "components": self.components, "singletons": self.singletons, "largest": self.largest, "pair_slots": self.pair_slots,
+                             "complete": self.complete})
+
+    def special(self) -> pd.DataFrame:
+        """The steps at which every component is a clique (classify.special_intervals' sense): the rows of frame() with `complete`."""
+        return self.frame()[self.complete].reset_index(drop=True)
+
+    def components_at(self, step: int) -> ScreenComponents:
+        """The ScreenComponents of a SNAPSHOT step (IndexError for any other step: its node arrays were not kept)."""
+        if int(step) not in self.snapshot_steps:
+            raise IndexError(f"step {step} is no snapshot of this sweep (snapshots: {self.snapshot_steps})")
+        return components_from_nodes(self.labels, *self.snapshots[self.snapshot_steps.index(int(step))])
+
+
+def sweep_from_arrays(labels, identities, arrays, snapshot_steps) -> ScreenSweep:
+    """The ScreenSweep of what sweep_of_pairs or Engine.screen_sweep returned."""
+    entries, components, singletons, largest, pair_slots, snapshots = arrays
+    t = check_ladder(identities)
+    if any(len(x) != len(t) for x in (entries, components, singletons, largest, pair_slots)):
+        raise ValueError("the ladder and the per-step arrays must have the same length")
+    entries, pair_slots = np.ascontiguousarray(entries, dtype=np.uint64), np.ascontiguousarray(pair_slots, dtype=np.uint64)
+    return ScreenSweep(None if labels is None else [str(x) for x in labels], t, entries, np.ascontiguousarray(components, dtype=np.uint32),
+                       np.ascontiguousarray(singletons, dtype=np.uint32), np.ascontiguousarray(largest, dtype=np.uint32), pair_slots,
+                       pair_slots == entries, [int(s) for s in snapshot_steps], list(snapshots))
 
 
 # ---- the greedy representatives of the kept pairs (DESIGN.md §16.9) ---------------------------------------------------------------------------
