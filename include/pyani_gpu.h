@@ -594,6 +594,45 @@ int pg_screen_sweep_read_snapshot(pg_ctx* ctx, uint32_t k, int32_t* root_out, ui
 int pg_screen_sweep_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
 int pg_screen_sweep_release(pg_ctx* ctx);
 
+/* ---- screen, the linkage: species clusters by average or complete linkage inside every connected component.  The
+ * list of entries (a[e], b[e], dist[e]) over n nodes is that of the components (unsorted, a pair in one direction or both, once or several
+ * times, an entry with a[e] == b[e] ignored altogether); dist[e] is a finite double >= 0.
+ *   1. root[v] = the smallest node of v's connected component (pg_screen_components' root); the local index of a node is its position
+ *      among its component's members in ascending order.
+ *   2. Per component of s >= 2 nodes an s x s matrix: D[i][j] = the MAXIMUM of dist[e] over the entries joining the two nodes, in either
+ *      direction; `fill` where no entry joins them; 0 on the diagonal.
+ *   3. scipy's nearest-neighbour chain on it (method: PG_CLUSTER_AVERAGE or PG_CLUSTER_COMPLETE, the arithmetic and tie rules of
+ *      pg_cluster_linkage): s - 1 merge records (lower slot, higher slot, height, size) in merge order, slots as local indices.
+ *   4. Two nodes share a cluster iff merges of height <= cutoff join them (scipy's fcluster(Z, cutoff, "distance"));
+ *      cluster[v] = the smallest node of v's cluster.
+ *   5. rep[v] = the member of v's cluster of the greatest score (uint64, greater is better), ties to the smaller index.
+ * Integers, and doubles whose bits the statement fixes (pyani_amd.screen.linkage_of_pairs); nothing depends on the list's order,
+ * direction or duplication.  *n_clusters_out = the nodes with cluster[v] == v.
+ * PG_E_ARG, checked before anything is copied or replaced: n outside 1 ... 2^20, an index outside [0, n), m > 0 with a NULL a, b or dist,
+ * a NULL score, a distance that is not finite or below 0, a method other than the two, cutoff or fill not finite or below 0, cutoff not
+ * STRICTLY below fill.  PG_E_CAPACITY for a component of more than 8192 nodes (the linkage kernel's own limit; the message names the size;
+ * a tighter screen threshold splits such a component), found before any matrix is allocated.
+ * The result stays RESIDENT in a state of its own, independent of every other resident screen state, until the next ACCEPTED linkage call
+ * (a refused one leaves it readable; an allocation that fails replaces nothing), pg_screen_linkage_release (PG_OK when there is none),
+ * pg_clear_genomes or pg_destroy.  pg_screen_linkage_read copies root, cluster and rep out, n entries each; pg_screen_linkage_read_merges
+ * the n - components merge records, 4 doubles each: the components' blocks in ascending root order (merges_out may be NULL when there is
+ * none).  PG_E_ARG when nothing is resident.
+ * pg_screen_linkage_set: components of 2 ... small_limit nodes run one per WAVE, larger ones one per workgroup; small_limit is 0 (the
+ * workgroup kernel only) ... 64, or PG_SCREEN_LINKAGE_DEFAULT; work_bytes is the budget for the working matrices (8 s^2 bytes a component)
+ * of one batch, at most 2^40, 0 = the default (1 GiB); a component beyond the budget has a batch to itself.  Values out of range are
+ * PG_E_ARG and change nothing.  The result does not depend on either setting.
+ * pg_screen_linkage_last: counts_out[8] = n, entries worked (a != b), entries ignored (a == b), components, components of >= 2 nodes, the
+ * largest component, clusters, batches; ms_out[5] = group, fill, wave linkage, workgroup linkage, cut + representatives milliseconds (HIP
+ * events on the context's stream); all 0 when nothing is resident. */
+#define PG_SCREEN_LINKAGE_DEFAULT 0xFFFFFFFFu
+int pg_screen_linkage(pg_ctx* ctx, const int32_t* a, const int32_t* b, const double* dist, uint64_t m, uint32_t n, const uint64_t* score, int method, double cutoff,
+                      double fill, uint32_t* n_clusters_out);
+int pg_screen_linkage_read(pg_ctx* ctx, int32_t* root_out, int32_t* cluster_out, int32_t* rep_out);
+int pg_screen_linkage_read_merges(pg_ctx* ctx, double* merges_out);
+int pg_screen_linkage_set(pg_ctx* ctx, uint32_t small_limit, uint64_t work_bytes);
+int pg_screen_linkage_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
+int pg_screen_linkage_release(pg_ctx* ctx);
+
 /* ---- screen, the search: new genomes against a resident collection.  S(g), size, kmer and scale as for
  * pg_screen_matrix.  A collection ("db") of n <= 2^20 genomes is indexed once; then, per call, q query genomes are placed against it:
  *   hits[i][b] = |S(query i) & S(db b)|, a q x n rectangle of uint32, row-major

@@ -24,6 +24,7 @@ PG_OK, PG_E_ARG, PG_E_NODEVICE, PG_E_HIP, PG_E_IO, PG_E_NOMEM, PG_E_KEYSET, PG_E
 PG_E_CAPACITY, PG_ANIM_NO_ALIGNMENT = -9, 1
 PG_E_NONFINITE = -11
 PG_CLUSTER_COMPLETE, PG_CLUSTER_AVERAGE = 0, 1
+PG_SCREEN_LINKAGE_DEFAULT = 0xFFFFFFFF
 K_TETRA_COUNT, K_TETRA_FINALIZE, K_TETRA_STATS, K_TETRA_PAIRS = 0, 1, 2, 3
 (K_ANIM_SEED, K_ANIM_HIT, K_ANIM_CLUSTER, K_ANIM_GAPS, K_ANIM_EXTLANE, K_ANIM_EXTEND, K_ANIM_FINISH) = 4, 5, 6, 7, 8, 9, 10
 K_ANIB_BUCKET, K_ANIB_FRAG = 11, 12
@@ -116,6 +117,12 @@ SIGNATURES = {
     "pg_screen_representatives_read": (_int, [_vp, _vp, _vp]),
     "pg_screen_representatives_last": (_int, [_vp, _vp, _vp]),
     "pg_screen_representatives_release": (_int, [_vp]),
+    "pg_screen_linkage": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _vp, _int, ctypes.c_double, ctypes.c_double, _P(_u32)]),
+    "pg_screen_linkage_read": (_int, [_vp, _vp, _vp, _vp]),
+    "pg_screen_linkage_read_merges": (_int, [_vp, _vp]),
+    "pg_screen_linkage_set": (_int, [_vp, _u32, _u64]),
+    "pg_screen_linkage_last": (_int, [_vp, _vp, _vp]),
+    "pg_screen_linkage_release": (_int, [_vp]),
     "pg_screen_sweep": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _u32, _vp, _u32]),
     "pg_screen_index_sweep": (_int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _u32, _P(_u64)]),
     "pg_screen_sweep_read": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),

@@ -96,6 +96,12 @@
 // list with a level per entry, from the host) and pg_screen_index_sweep (the bands' kept triples, their levels found on the device from the
 // resident need table) bucket the entries by level with one stable radix sort, hook bucket after bucket into ONE forest through the body of
 // K2 and take a census of it after every bucket; W1 ... W8 stand there with their state.
+//
+// pgscr_linkage.inc — the LINKAGE: species clusters by average or complete linkage inside every component of a list of
+// pairs with distances.  pg_screen_linkage groups the nodes by component (the hook of K2, one stable radix sort), fills the components'
+// distance matrices by 64-bit atomic maxima, runs scipy's nearest-neighbour chain — one wave per small component (L8), the heatmap's
+// workgroup kernel (pg_cluster_linkage.h) for the others — cuts the trees through a second forest and names one representative per cluster;
+// L1 ... L12 stand there with their state.
 #include <algorithm>
 #include <hipcub/hipcub.hpp>
 #include <memory>
@@ -108,9 +114,9 @@
 
 namespace {
 
-// the stages whose milliseconds pg_screen_last, pg_screen_index_last, pg_screen_components_last, pg_screen_representatives_last, pg_screen_sweep_last, pg_screen_search_last,
+// the stages whose milliseconds pg_screen_last, pg_screen_index_last, pg_screen_components_last, pg_screen_representatives_last, pg_screen_sweep_last, pg_screen_linkage_last, pg_screen_search_last,
 // pg_screen_search_add_last, pg_screen_search_remove_last and pg_screen_gather_last report
-enum ScreenStage { ST_SCAN, ST_GROUP, ST_COUNT, ST_SELECT, ST_HOOK, ST_FLATTEN, ST_LOOKUP, ST_EXPAND, ST_ARGMAX, ST_CLAIM, ST_MERGE, ST_CHECK, ST_MARK, ST_COMPACT, ST_WEIGHT, ST_ATTRIBUTE, ST_SORT, ST_STATS, ST_ROUNDS, ST_ASSIGN, ST_CENSUS };
+enum ScreenStage { ST_SCAN, ST_GROUP, ST_COUNT, ST_SELECT, ST_HOOK, ST_FLATTEN, ST_LOOKUP, ST_EXPAND, ST_ARGMAX, ST_CLAIM, ST_MERGE, ST_CHECK, ST_MARK, ST_COMPACT, ST_WEIGHT, ST_ATTRIBUTE, ST_SORT, ST_STATS, ST_ROUNDS, ST_ASSIGN, ST_CENSUS, ST_FILL, ST_SMALL, ST_LARGE, ST_CUT };
 
 struct ScreenEvents {      // event pairs on the context's stream, summed per stage after the call's last synchronisation
   std::vector<hipEvent_t> ev;
@@ -164,6 +170,7 @@ hipError_t tmp_room(size_t& tmp_bytes, Query query) {
 #include "pgscr_components.inc"
 #include "pgscr_representatives.inc"
 #include "pgscr_sweep.inc"
+#include "pgscr_linkage.inc"
 #include "pgscr_search.inc"
 #include "pgscr_add.inc"
 #include "pgscr_store.inc"

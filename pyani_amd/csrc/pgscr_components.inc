@@ -44,6 +44,20 @@ __device__ __forceinline__ uint32_t components_find(uint32_t* parent, uint32_t u
   }
 }
 
+// The hook alone: the trees of ua and ub (both < n, ua != ub) joined, the larger root under the smaller.  Returns whether THIS call's
+// compare-and-swap hooked a root.  The linkage's two forests (pgscr_linkage.inc) hook through it as well.
+__device__ __forceinline__ bool components_hook_nodes(uint32_t* parent, uint32_t ua, uint32_t ub) {
+  uint32_t u = components_find(parent, ua), v = components_find(parent, ub);
+  while (u != v) {      // u in a's tree, v in b's; max(u, v) drops with every failed round
+    if (u < v) { const uint32_t t = u; u = v; v = t; }
+    const uint32_t old = atomicCAS(parent + u, u, v);
+    if (old == u) return true;      // u was a root and now hangs under v < u
+    if (old > u) break;       // (never: a cell only decreases; kept so that a broken array cannot spin)
+    u = components_find(parent, old);      // old < u: u's parent when the swap looked; on from its tree's top
+  }
+  return false;
+}
+
 // The accumulate and the hook of ONE entry per lane — the body of K2, and of the sweep's bucket pass (pgscr_sweep.inc).  Every lane of the
 // wave calls it (the shuffles); in = the lane holds an entry e, (ua, ub) its nodes (0xFFFFFFFF both where it holds none).  Returns whether
 // THIS lane's compare-and-swap hooked a root: each success takes one tree away, so the successes of a list are n - its components.
@@ -62,19 +76,7 @@ __device__ __forceinline__ bool components_hook_entry(uint32_t lane, bool in, ui
     if (lane + d < 64u && r2 == run) { cnt += c2; w += w2; }
   }
   if (head && cnt) { atomicAdd(entries + ua, cnt); atomicAdd(weight + ua, w); }
-  // hook
-  bool hooked = false;
-  if (work) {
-    uint32_t u = components_find(parent, ua), v = components_find(parent, ub);
-    while (u != v) {      // u in a's tree, v in b's; max(u, v) drops with every failed round
-      if (u < v) { const uint32_t t = u; u = v; v = t; }
-      const uint32_t old = atomicCAS(parent + u, u, v);
-      if (old == u) { hooked = true; break; }      // u was a root and now hangs under v < u
-      if (old > u) break;       // (never: a cell only decreases; kept so that a broken array cannot spin)
-      u = components_find(parent, old);      // old < u: u's parent when the swap looked; on from its tree's top
-    }
-  }
-  return hooked;
+  return work && components_hook_nodes(parent, ua, ub);
 }
 
 __global__ __launch_bounds__(256) void components_hook_kernel(const int32_t* __restrict__ a, const int32_t* __restrict__ b, const uint32_t* __restrict__ s,

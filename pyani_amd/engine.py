@@ -653,6 +653,54 @@ class Engine:
         finally:
             self.screen_representatives_release()
 
+    # the linkage: species clusters by average / complete linkage inside every component, resident on the context
+    def screen_linkage(self, a, b, dist, n: int = 0, score=None, method: str = "average", cutoff: float = 0.05, fill: float = 1.0):
+        """pg_screen_linkage + pg_screen_linkage_read + pg_screen_linkage_read_merges: (root, cluster, rep int32[n], merges
+        float64[n - components, 4]) of the list of entries (a[e], b[e], dist[e]) over n nodes under the scores score uint64[n], as
+        pyani_amd.screen.linkage_of_pairs states them.  ValueError as the statement's, before the library is called.  The number of
+        clusters is screen_linkage_last()["clusters"]."""
+        from . import screen
+        x = np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+        y = np.ascontiguousarray(b, dtype=np.int32).reshape(-1)
+        if len(x) != len(y):
+            raise ValueError("a, b and dist must have the same length")
+        d = screen.check_distances(dist, len(x))
+        method, cutoff, fill = screen.check_linkage(method, cutoff, fill)
+        s = None if score is None else np.ascontiguousarray(score, dtype=np.uint64).reshape(-1)
+        if s is not None and len(s) != int(n):
+            raise ValueError(f"{int(n)} nodes need {int(n)} scores, not {len(s)}")
+        m = len(x)
+        c = ctypes.c_uint32(0)
+        self._check(self.lib.pg_screen_linkage(self._h, x.ctypes.data if m else None, y.ctypes.data if m else None, d.ctypes.data if m else None, m, int(n),
+                                               s.ctypes.data if s is not None and len(s) else None,
+                                               _lib.PG_CLUSTER_AVERAGE if method == "average" else _lib.PG_CLUSTER_COMPLETE, cutoff, fill, ctypes.byref(c)))
+        return self._screen_linkage_read(int(n))
+
+    def _screen_linkage_read(self, n: int):
+        root, cluster, rep = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        self._check(self.lib.pg_screen_linkage_read(self._h, root.ctypes.data, cluster.ctypes.data, rep.ctypes.data))
+        rows = n - int(self.screen_linkage_last()["components"])
+        merges = np.zeros((rows, 4), dtype=np.float64)
+        self._check(self.lib.pg_screen_linkage_read_merges(self._h, merges.ctypes.data if rows else None))
+        return root, cluster, rep, merges
+
+    def screen_linkage_set(self, small_limit: Optional[int] = None, work_bytes: int = 0) -> None:
+        """pg_screen_linkage_set: components of 2 ... small_limit nodes (0 ... 64; 0: none) run one per wave, the others one per
+        workgroup; work_bytes: the working matrices of one batch.  None / 0 restore the defaults.  The results do not depend on either."""
+        self._check(self.lib.pg_screen_linkage_set(self._h, _lib.PG_SCREEN_LINKAGE_DEFAULT if small_limit is None else int(small_limit), int(work_bytes)))
+
+    def screen_linkage_last(self) -> dict:
+        """pg_screen_linkage_last: counts and stage milliseconds of the resident linkage (all 0 when there is none)."""
+        c = (ctypes.c_uint64 * 8)()
+        ms = (ctypes.c_double * 5)()
+        self._check(self.lib.pg_screen_linkage_last(self._h, ctypes.addressof(c), ctypes.addressof(ms)))
+        return {"n": int(c[0]), "entries": int(c[1]), "ignored": int(c[2]), "components": int(c[3]), "worked_components": int(c[4]), "largest": int(c[5]),
+                "clusters": int(c[6]), "batches": int(c[7]), "group_ms": float(ms[0]), "fill_ms": float(ms[1]), "small_ms": float(ms[2]),
+                "large_ms": float(ms[3]), "cut_ms": float(ms[4])}
+
+    def screen_linkage_release(self) -> None:
+        self._check(self.lib.pg_screen_linkage_release(self._h))
+
     # the sweep (DESIGN.md §16.10): the components over a ladder of thresholds in one pass, per-step arrays and snapshots resident on the context
     def _screen_sweep_read(self, n: int, steps: int, n_snapshots: int):
         entries, pair_slots = np.zeros(steps, dtype=np.uint64), np.zeros(steps, dtype=np.uint64)

@@ -398,6 +398,21 @@ class MultiEngine:
         for e in self.engines:
             e.screen_representatives_release()
 
+    def screen_linkage(self, a, b, dist, n: int = 0, score=None, method: str = "average", cutoff: float = 0.05, fill: float = 1.0):
+        """Engine.screen_linkage on the first engine (a list call has nothing to divide; dealing components is out of scope)."""
+        return self.engines[0].screen_linkage(a, b, dist, n=n, score=score, method=method, cutoff=cutoff, fill=fill)
+
+    def screen_linkage_set(self, small_limit=None, work_bytes: int = 0):
+        for e in self.engines:
+            e.screen_linkage_set(small_limit, work_bytes)
+
+    def screen_linkage_last(self) -> dict:
+        return self.engines[0].screen_linkage_last()
+
+    def screen_linkage_release(self):
+        for e in self.engines:
+            e.screen_linkage_release()
+
     def screen_dereplicate(self, ids, options, scores=None, labels=None, path: str = "auto"):
         """Engine.screen_dereplicate over all devices.  The greedy rule needs every entry in one place — a round reads
         the whole list, and a node's fate may hang on an entry of any band — so only the CANDIDATES are dealt as today

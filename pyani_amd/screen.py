@@ -19,7 +19,8 @@ the statement, Engine.screen_components / screen_index_components the kernels, S
 component is the SINGLE-LINKAGE dereplicated set), had through the index without a single pair leaving the device
 (Engine.screen_components_of).  One genome per SPECIES is the greedy rule of dRep, galah, skani and CD-HIT:
 representatives_of_pairs is the statement, Engine.screen_representatives / screen_index_representatives the kernels, ScreenClusters the
-table, Engine.screen_dereplicate the whole step.
+table, Engine.screen_dereplicate the whole step.  dRep's SECONDARY clustering — average or complete linkage inside every component, cut at
+1 - ANI — is linkage_of_pairs (the statement), Engine.screen_linkage (the kernels) and ScreenLinkage.
 
 New genomes against a resident collection: Engine.screen_search lists what each is RELATED TO (SearchHits), and
 Engine.screen_gather what each is MADE OF — the greedy minimum set of collection genomes that explains its k-mers (GatherOptions,
@@ -710,6 +711,230 @@ def clusters_from_nodes(labels, rep, via, score) -> ScreenClusters:
     start = np.concatenate([[0], np.cumsum(size)]).astype(np.int64)
     member = np.argsort(cluster, kind="stable")
     return ScreenClusters(labels, rep, via, score, representative.astype(np.int32), cluster.astype(np.int32), start, member.astype(np.int32), size)
+
+
+# ---- species clusters by linkage inside every component ---------------------------------------------------------------------
+LINKAGE_METHODS = ("average", "complete")
+LINKAGE_MAX_COMPONENT = 8192       # Engine.screen_linkage: nodes of one component (the linkage kernel's own limit); the statement has none
+
+
+def check_linkage(method, cutoff, fill) -> Tuple[str, float, float]:
+    """(method, cutoff, fill) of a linkage call: the method one of LINKAGE_METHODS, cutoff and fill finite and >= 0, cutoff STRICTLY below
+    fill (ValueError otherwise): an absent pair sits at `fill` and must never be joined by the cut."""
+    if method not in LINKAGE_METHODS:
+        raise ValueError(f"method must be one of {LINKAGE_METHODS}, not {method!r}")
+    try:
+        cutoff, fill = float(cutoff), float(fill)
+    except (TypeError, ValueError) as err:
+        raise ValueError(f"cutoff and fill must be numbers: {err}") from None
+    if not (math.isfinite(cutoff) and math.isfinite(fill)) or cutoff < 0 or fill < 0:
+        raise ValueError("cutoff and fill must be finite and >= 0")
+    if not cutoff < fill:
+        raise ValueError(f"cutoff ({cutoff!r}) must be strictly below fill ({fill!r})")
+    return method, cutoff, fill
+
+
+def check_distances(dist, m: int) -> np.ndarray:
+    """The float64 distances of m entries: the array must BE float64 (no silent conversion: the bits are the statement's), finite, >= 0."""
+    dist = np.asarray(dist)
+    if dist.dtype != np.float64:
+        raise ValueError(f"dist must be float64, not {dist.dtype}")
+    dist = np.ascontiguousarray(dist).reshape(-1)
+    if len(dist) != m:
+        raise ValueError("a, b and dist must have the same length")
+    if not np.isfinite(dist).all() or (dist < 0).any():
+        raise ValueError("distances must be finite and >= 0")
+    return dist + 0.0      # (-0.0 becomes 0.0: the bit pattern of a distance is then monotone)
+
+
+def _chain_linkage(D: np.ndarray, average: bool) -> np.ndarray:
+    """scipy's nearest-neighbour chain on the symmetric matrix D (changed in place): the s - 1 records (lower slot, higher slot, height,
+    size) in merge order.  Ascending scan, strict <, lowest index wins; average as (n_lo a + n_hi b) / (n_lo + n_hi), every operation
+    rounded on its own — what cluster_linkage_kernel does, in numpy's float64."""
+    s = len(D)
+    size = np.ones(s, dtype=np.int64)
+    out = np.zeros((s - 1, 4), dtype=np.float64)
+    chain: List[int] = []
+    for k in range(s - 1):
+        if not chain:
+            chain.append(int(np.flatnonzero(size)[0]))
+        while True:
+            x = chain[-1]
+            row = np.where(size > 0, D[x], np.inf)
+            row[x] = np.inf
+            y = int(np.argmin(row))      # (the first index attaining the minimum)
+            cur = row[y]
+            if len(chain) > 1:
+                prev = chain[-2]
+                if not cur < D[x, prev]:      # the incumbent stays unless strictly beaten
+                    y, cur = prev, D[x, prev]
+                if y == prev:
+                    break
+            chain.append(y)
+        y, x = chain.pop(), chain.pop()
+        lo, hi = (x, y) if x < y else (y, x)
+        nlo, nhi = int(size[lo]), int(size[hi])
+        out[k] = (lo, hi, cur, nlo + nhi)
+        if average:
+            new = (np.float64(nlo) * D[lo] + np.float64(nhi) * D[hi]) / np.float64(nlo + nhi)
+        else:
+            new = np.maximum(D[lo], D[hi])
+        keep = size > 0
+        keep[lo] = keep[hi] = False
+        D[hi, keep] = new[keep]
+        D[keep, hi] = new[keep]
+        size[lo], size[hi] = 0, nlo + nhi
+    return out
+
+
+def linkage_of_pairs(a, b, dist, n, score, method: str = "average", cutoff: float = 0.05, fill: float = 1.0):
+    """THE STATEMENT of the linkage (the host's; Engine.screen_linkage is held to it): for the list of entries (a[e], b[e], dist[e]) over n
+    nodes — unsorted, a pair in one direction or both, once or several times, an entry with a[e] == b[e] ignored — and the scores score
+    uint64[n] (score_keys):
+
+      1. root[v] = the smallest node of v's connected component, as components_of_pairs gives it.  The local index of a node is its
+         position among its component's members in ascending node order.
+      2. Per component of s >= 2 nodes the matrix D: D[i][j] = the MAXIMUM of dist[e] over all entries joining the two nodes, in either
+         direction (the order-independent counterpart of exact_edges' minimum identity); `fill` where no entry joins them (dRep treats an
+         uncompared pair as ANI 0); 0 on the diagonal.
+      3. scipy's nearest-neighbour chain on D for "average" or "complete" (_chain_linkage): the s - 1 merge records in merge order, which
+         graphics.merges_to_linkage turns into scipy's Z.
+      4. Two nodes share a cluster iff merges of height <= cutoff join them — fcluster(Z, cutoff, "distance"): both methods are monotone,
+         so a union over those records is the whole rule.  cluster[v] = the smallest member of v's cluster.
+      5. rep[v] = the member of v's cluster of the greatest score, ties to the smaller index.
+
+    Returns root, cluster, rep (int32[n]) and merges float64[n - components, 4]: the components' blocks in ascending root order, slots as
+    local indices.  Integers, and doubles whose bits the steps fix; nothing depends on the list's order, direction or duplication.
+    ValueError before any work: check_distances, check_linkage.
+
+    A property, tested and not assumed: absent pairs sit exactly at `fill` and cutoff < fill, and then the partition equals fcluster of ONE
+    linkage over the whole n x n matrix with the absent cells at `fill`; the components only save the n^2 work."""
+    a, b, _, n = _check_entries(a, b, None, n)
+    dist = check_distances(dist, len(a))
+    method, cutoff, fill = check_linkage(method, cutoff, fill)
+    score = np.ascontiguousarray(score, dtype=np.uint64).reshape(-1)
+    if len(score) != n:
+        raise ValueError(f"{n} nodes need {n} scores, not {len(score)}")
+    live = a != b
+    a, b, dist = a[live], b[live], dist[live]
+    root = components_of_pairs(a, b, None, n)[0].astype(np.int64)
+    order = np.lexsort((np.arange(n), root))      # by (root, node)
+    heads = np.flatnonzero(root[order] == order)
+    start = np.append(heads, n)
+    pos = np.empty(n, dtype=np.int64)
+    pos[order] = np.arange(n)
+    comp = np.searchsorted(heads, pos, side="right") - 1      # of every node
+    local = pos - start[comp]
+    # the entries by component, each cell once: the maximum over both directions and every duplicate
+    ec = comp[a]
+    by = np.argsort(ec, kind="stable")
+    ec, ei, ej, ed = ec[by], local[a][by], local[b][by], dist[by]
+    cuts = np.searchsorted(ec, np.arange(len(heads) + 1))
+    cluster = np.arange(n, dtype=np.int64)
+    blocks = []
+    for c in range(len(heads)):
+        s = int(start[c + 1] - start[c])
+        if s < 2:
+            continue
+        sl = slice(cuts[c], cuts[c + 1])
+        D = np.full((s, s), -1.0)
+        np.maximum.at(D, (ei[sl], ej[sl]), ed[sl])
+        D = np.maximum(D, D.T)
+        D[D < 0] = fill
+        np.fill_diagonal(D, 0.0)
+        rec = _chain_linkage(D, method == "average")
+        blocks.append(rec)
+        nodes = order[start[c]:start[c + 1]]
+        label = np.arange(s)      # the cut: a union over the records of height <= cutoff, the smaller label taking the other's members
+        for lo, hi, h, _ in rec:
+            if h <= cutoff:
+                x, y = label[int(lo)], label[int(hi)]
+                if x != y:
+                    label[label == max(x, y)] = min(x, y)
+        cluster[nodes] = nodes[label]      # (a label is the smallest local index of its cluster; the members ascend with it)
+    merges = np.concatenate(blocks) if blocks else np.zeros((0, 4), dtype=np.float64)
+    best = np.lexsort((np.arange(n), ~score, cluster))      # by cluster, then score descending, then index ascending
+    first = np.flatnonzero(np.append(True, cluster[best][1:] != cluster[best][:-1]))
+    rep_of = np.empty(n, dtype=np.int64)
+    rep_of[cluster[best][first]] = best[first]
+    return root.astype(np.int32), cluster.astype(np.int32), rep_of[cluster].astype(np.int32), merges
+
+
+class ScreenLinkage(NamedTuple):
+    """The species clusters by linkage of a list of pairs with distances over the genomes `labels` (None: the nodes go by their index):
+    the node arrays and merge records of linkage_of_pairs, its scores and its three parameters."""
+    labels: Optional[List[str]]
+    root: np.ndarray             # int32[n]
+    cluster: np.ndarray          # int32[n]
+    rep: np.ndarray              # int32[n]
+    score: np.ndarray            # uint64[n]
+    merges: np.ndarray           # float64[n - components, 4]
+    method: str
+    cutoff: float
+    fill: float
+
+    def clusters(self) -> "ScreenClusters":
+        """The clusters as the greedy rule's table (clusters_from_nodes): representative, members, sizes; `via` is 0 everywhere."""
+        return clusters_from_nodes(self.labels, self.rep, np.zeros(len(self.rep), dtype=np.uint32), self.score)
+
+    def _blocks(self):
+        """(roots ascending, start of every component among the nodes in (root, node) order, first merge record of every component)"""
+        roots, size = np.unique(self.root, return_counts=True)
+        return roots, np.concatenate([[0], np.cumsum(size)]), np.concatenate([[0], np.cumsum(size - 1)])
+
+    def linkage_of(self, root: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(Z, members) of the component whose smallest node is `root`: scipy's linkage matrix (graphics.merges_to_linkage; 0 rows for a
+        component of one node) and the member nodes in ascending order — leaf i of Z is members[i]."""
+        from .graphics import merges_to_linkage
+        roots, _, first = self._blocks()
+        c = int(np.searchsorted(roots, int(root)))
+        if c >= len(roots) or roots[c] != int(root):
+            raise IndexError(f"node {root} is no component's root")
+        members = np.flatnonzero(self.root == int(root)).astype(np.int32)
+        block = self.merges[int(first[c]):int(first[c + 1])]
+        return (merges_to_linkage(block) if len(block) else np.zeros((0, 4), dtype=np.float64)), members
+
+    def frame(self) -> pd.DataFrame:
+        """One row per cluster: cluster, representative (label), size, score (the uint64 key), component (the root's label)."""
+        t = self.clusters()
+        out = t.frame()
+        out["component"] = t._names(self.root[t.representative])
+        return out
+
+    def merges_frame(self) -> pd.DataFrame:
+        """One row per merge: component (the root's label), left, right, height, size — left and right in scipy's numbering (a leaf is its
+        local index, the cluster made by row r of a component of s nodes is s + r)."""
+        roots, _, first = self._blocks()
+        comp, left, right, height, size = [], [], [], [], []
+        for c, r in enumerate(roots.tolist()):
+            if first[c + 1] == first[c]:
+                continue
+            Z, _ = self.linkage_of(r)
+            comp += [r] * len(Z)
+            left += Z[:, 0].astype(np.int64).tolist()
+            right += Z[:, 1].astype(np.int64).tolist()
+            height += Z[:, 2].tolist()
+            size += Z[:, 3].astype(np.int64).tolist()
+        names = comp if self.labels is None else [self.labels[i] for i in comp]
+        return pd.DataFrame({"component": names, "left": left, "right": right, "height": height, "size": size})
+
+
+def linkage_from_nodes(labels, root, cluster, rep, score, merges, method, cutoff, fill) -> ScreenLinkage:
+    """The ScreenLinkage of what linkage_of_pairs or Engine.screen_linkage returned."""
+    root, cluster, rep = (np.ascontiguousarray(x, dtype=np.int32).reshape(-1) for x in (root, cluster, rep))
+    score = np.ascontiguousarray(score, dtype=np.uint64).reshape(-1)
+    merges = np.ascontiguousarray(merges, dtype=np.float64).reshape(-1, 4)
+    n = len(root)
+    if labels is not None:
+        labels = [str(x) for x in labels]
+        if len(labels) != n:
+            raise ValueError("labels and nodes must have the same length")
+    if len(cluster) != n or len(rep) != n or len(score) != n:
+        raise ValueError("root, cluster, rep and score must have the same length")
+    if len(merges) != n - len(np.unique(root)):
+        raise ValueError("the merge records do not match the components")
+    method, cutoff, fill = check_linkage(method, cutoff, fill)
+    return ScreenLinkage(labels, root, cluster, rep, score, merges, method, cutoff, fill)
 
 
 def _labels_for(ids, labels, limit: int = MAX_GENOMES) -> List[str]:

@@ -14,8 +14,17 @@ weight is floor(min(identity_ab, identity_ba) * 1e6); the rule runs on that list
 With write_output: `screen_output/screen_pairs.tab` (the screen's kept pairs), `screen_representatives.tab` (one line per
 representative: cluster, representative, size, score) and `screen_clusters.tab` (one line per genome: genome, representative, via).
 
-OUT OF SCOPE here: ANIb as the exact step, recovery, collective runs, and secondary clustering by linkage (pyani_amd.heatmap has the
-linkage for callers who want it).  Single-process: one engine, or several GPUs of this node (devices / workers).
+secondary="average" / "complete"  replaces the greedy rule by dRep's SECONDARY CLUSTERING: average- or complete-linkage
+hierarchical clustering of the distances inside every connected component, the tree cut at `cutoff`, the member of the greatest score
+representing each cluster (pyani_amd.screen.linkage_of_pairs is the statement, Engine.screen_linkage the kernels).  exact=None: the
+distance of a pair is 1 minus the smaller of the two directions' screen identities (the numbers of screen_identity.tab), the default
+cutoff 1 - screen.min_identity.  exact="anim": an undirected pair carries a distance iff both ordered comparisons have a result and, in
+both, coverage >= min_coverage — min_ani does NOT filter, the tree needs the far pairs too —, dist = 1 - min(identity_ab, identity_ba),
+the default cutoff 1 - min_ani.  Both defaults are the float64 results of those subtractions, unrounded (1 - 0.95 is
+0.050000000000000044).  A pair without a distance sits at 1.0, dRep's ANI 0.  `screen_linkage.tab` is added: one line per merge.
+
+OUT OF SCOPE here: ANIb as the exact step, recovery, collective runs, linkage methods other than the two, and distances formed from the
+index's shared counts on the device.  Single-process: one engine, or several GPUs of this node (devices / workers).
 """
 from pathlib import Path
 from typing import Dict, List, Mapping, NamedTuple, Optional, Tuple
@@ -26,6 +35,7 @@ from . import _lib, files, screen as screen_mod
 from .engine import Engine, default_engine
 
 EXACT = (None, "anim")
+LINKAGE_FILL = 1.0      # secondary=: the distance of a pair that carries none (ANI 0)
 
 
 class DereplicateRun(NamedTuple):
@@ -36,6 +46,7 @@ class DereplicateRun(NamedTuple):
     edges: Tuple[np.ndarray, np.ndarray, np.ndarray]      # (a, b, weight) the greedy rule ran on: positions in the order of the stems
     clusters: screen_mod.ScreenClusters
     written: List[Path]
+    linkage: Optional[screen_mod.ScreenLinkage] = None      # secondary=: the linkage the clusters come from (edges is then (a, b, dist))
 
     def representatives(self) -> List[str]:
         return self.clusters.representatives()
@@ -99,14 +110,46 @@ def exact_edges(a, b, recs, length, min_ani: float, min_coverage: float) -> Tupl
     return np.array(ea, dtype=np.int32), np.array(eb, dtype=np.int32), np.array(w, dtype=np.uint32)
 
 
+def linkage_edges(a, b, recs, length, min_coverage: float) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(a, b, dist) with a < b of the undirected pairs that carry a distance, among the ordered pairs (a[e], b[e]) with the anim_pairs
+    records recs[e] (as exact_edges takes them): a pair carries one iff both directions have a result and, in both,
+    ref_aln_len / length[query] >= min_coverage; dist = 1 - min of the two identities (float64; an identity above 1 gives 0).  No
+    identity threshold: the tree needs the far pairs too."""
+    a, b = np.asarray(a, dtype=np.int64), np.asarray(b, dtype=np.int64)
+    status = np.asarray(recs["status"])
+    bad = (status != 0) & (status != _lib.PG_ANIM_NO_ALIGNMENT)
+    if bad.any():
+        raise RuntimeError(f"GPU ANIm comparison failed with status {int(status[bad][0])}")
+    ident = np.asarray(recs["identity"], dtype=np.float64)
+    cov = np.asarray(recs["ref_aln_len"], dtype=np.float64) / np.asarray(length, dtype=np.float64)[a]
+    ok = (status == 0) & (cov >= min_coverage)
+    good = {(x, y): i for x, y, i, k in zip(a.tolist(), b.tolist(), ident.tolist(), ok.tolist()) if k}
+    ea, eb, d = [], [], []
+    for (x, y), i in good.items():
+        if x < y and (y, x) in good:
+            ea.append(x)
+            eb.append(y)
+            d.append(max(0.0, 1.0 - min(i, good[(y, x)])))
+    return np.array(ea, dtype=np.int32), np.array(eb, dtype=np.int32), np.array(d, dtype=np.float64)
+
+
+def screen_linkage_edges(screened) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(a, b, dist) of a screen's kept pairs as they stand (both directions): dist = 1 - the direction's screen identity
+    (ScreenedPairs.identity, the numbers of screen_identity.tab).  The linkage takes the maximum over a pair's entries, which is 1 minus
+    the smaller of the two directions' identities."""
+    return screened.a, screened.b, np.maximum(0.0, 1.0 - np.asarray(screened.identity(), dtype=np.float64))
+
+
 def run_dereplicate(indir, outdir=None, screen=None, scores=None, exact: Optional[str] = None, min_ani: float = 0.95, min_coverage: float = 0.1,
                     write_output: bool = False, engine: Optional[Engine] = None, devices: Optional[List[int]] = None,
-                    workers: Optional[int] = None) -> DereplicateRun:
+                    workers: Optional[int] = None, secondary: Optional[str] = None, cutoff: Optional[float] = None) -> DereplicateRun:
     """The greedy representatives of every FASTA file of `indir`.  screen: a ScreenOptions or a bare identity threshold (required: there
     is no default threshold).  scores: None (the sketch sizes: the larger assembly wins), a {stem: score} mapping or the path of a
     two-column TSV; finite and >= 0, greater is better, ties to the genome earlier in sorted-path order.  exact: None or "anim" (see the
     module's text; min_ani and min_coverage matter for "anim" only).  outdir is needed for write_output only; devices / workers: several
-    GPUs of this node, ignored when `engine` is given.  Every ValueError is raised before any work is done."""
+    GPUs of this node, ignored when `engine` is given.  secondary: None (the greedy rule), "average" or "complete" (linkage inside every
+    component, see the module's text); cutoff: where its trees are cut, None = 1 - min_ani with exact="anim" and 1 - screen.min_identity
+    otherwise; it must lie in [0, 1).  Every ValueError is raised before any work is done."""
     if screen is None:
         raise ValueError("run_dereplicate needs screen= (a ScreenOptions or an identity threshold)")
     if write_output and outdir is None:
@@ -114,6 +157,13 @@ def run_dereplicate(indir, outdir=None, screen=None, scores=None, exact: Optiona
     if exact not in EXACT:
         raise ValueError(f"exact must be one of {EXACT}, not {exact!r}")
     screen = screen_mod.check_options(screen)
+    if secondary is None:
+        if cutoff is not None:
+            raise ValueError("cutoff belongs to secondary= (the greedy rule has none)")
+    else:
+        if cutoff is None:
+            cutoff = 1.0 - (float(min_ani) if exact == "anim" else float(screen.min_identity))
+        secondary, cutoff, _ = screen_mod.check_linkage(secondary, cutoff, LINKAGE_FILL)
     paths = files.get_fasta_paths(Path(indir))
     stems = [p.stem for p in paths]
     if len(set(stems)) != len(stems):
@@ -125,13 +175,13 @@ def run_dereplicate(indir, outdir=None, screen=None, scores=None, exact: Optiona
         engine = multi.engine_for(devices, workers)
         own = engine if isinstance(engine, multi.MultiEngine) else None
     try:
-        return _run(paths, stems, outdir, screen, given, exact, float(min_ani), float(min_coverage), write_output, engine or default_engine())
+        return _run(paths, stems, outdir, screen, given, exact, float(min_ani), float(min_coverage), write_output, engine or default_engine(), secondary, cutoff)
     finally:
         if own is not None:
             own.close()
 
 
-def _run(paths, stems, outdir, screen, given, exact, min_ani, min_coverage, write_output, eng) -> DereplicateRun:
+def _run(paths, stems, outdir, screen, given, exact, min_ani, min_coverage, write_output, eng, secondary=None, cutoff=None) -> DereplicateRun:
     genome_ids = {s: k + 1 for k, s in enumerate(stems)}
     scratch_store = eng.genome_count() == 0
     lengths: Dict[str, int] = {}
@@ -148,22 +198,61 @@ def _run(paths, stems, outdir, screen, given, exact, min_ani, min_coverage, writ
             recs = np.zeros(0, dtype=Engine.ANIM_DTYPE)
             if len(screened.a):      # the query is nucmer's reference, as in run_anim
                 recs = eng.anim_pairs(ids[screened.a], ids[screened.b])
-            edges = exact_edges(screened.a, screened.b, recs, [lengths[s] for s in stems], min_ani, min_coverage)
+            if secondary is None:
+                edges = exact_edges(screened.a, screened.b, recs, [lengths[s] for s in stems], min_ani, min_coverage)
+            else:
+                edges = linkage_edges(screened.a, screened.b, recs, [lengths[s] for s in stems], min_coverage)
+        elif secondary is not None:
+            edges = screen_linkage_edges(screened)
+        nodes = None
         try:
-            if n:
+            if n and secondary is None:
                 rep, via = eng.screen_representatives(*edges, n=n, score=score)
+            elif n:
+                nodes = eng.screen_linkage(*edges, n=n, score=score, method=secondary, cutoff=cutoff, fill=LINKAGE_FILL)
             else:
                 rep, via = np.zeros(0, np.int32), np.zeros(0, np.uint32)
+                nodes = (rep, rep, rep, np.zeros((0, 4))) if secondary is not None else None
         finally:
-            eng.screen_representatives_release()
+            if secondary is None:
+                eng.screen_representatives_release()
+            else:
+                eng.screen_linkage_release()
     finally:
         if scratch_store:
             eng.clear_genomes()
-    clusters = screen_mod.clusters_from_nodes(stems, rep, via, score)
+    linkage = None
+    if secondary is None:
+        clusters = screen_mod.clusters_from_nodes(stems, rep, via, score)
+    else:
+        linkage = screen_mod.linkage_from_nodes(stems, *nodes[:3], score, nodes[3], secondary, cutoff, LINKAGE_FILL)
+        clusters = linkage.clusters()
     written: List[Path] = []
     if write_output:
         from .subcmd_screen import tab_path, write_pairs_tab
         written = [write_pairs_tab(outdir, screened), tab_path(outdir, "representatives"), tab_path(outdir, "clusters")]
         clusters.frame().to_csv(written[1], index=False, sep="\t")
         clusters.membership_frame().to_csv(written[2], index=False, sep="\t")
-    return DereplicateRun(genome_ids, lengths, screened, recs, edges, clusters, written)
+        if linkage is not None:
+            written.append(tab_path(outdir, "linkage"))
+            write_linkage_tab(written[3], linkage)
+    return DereplicateRun(genome_ids, lengths, screened, recs, edges, clusters, written, linkage)
+
+
+def write_linkage_tab(path, linkage) -> None:
+    """`screen_linkage.tab`: one line per merge — component, left, right, height, size in scipy's numbering (ScreenLinkage.merges_frame),
+    the heights with repr's precision, so that float(text) gives the bits back."""
+    t = linkage.merges_frame()
+    with open(path, "w") as out:
+        out.write("component\tleft\tright\theight\tsize\n")
+        for c, x, y, h, s in zip(t["component"], t["left"], t["right"], t["height"], t["size"]):
+            out.write(f"{c}\t{x}\t{y}\t{float(h)!r}\t{s}\n")
+
+
+def read_linkage_tab(path) -> List[Tuple[str, int, int, float, int]]:
+    """The lines of a `screen_linkage.tab` as (component, left, right, height, size)."""
+    rows = []
+    for line in Path(path).read_text().splitlines()[1:]:
+        c, x, y, h, s = line.split("\t")
+        rows.append((c, int(x), int(y), float(h), int(s)))
+    return rows
