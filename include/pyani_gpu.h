@@ -633,6 +633,58 @@ int pg_screen_linkage_set(pg_ctx* ctx, uint32_t small_limit, uint64_t work_bytes
 int pg_screen_linkage_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
 int pg_screen_linkage_release(pg_ctx* ctx);
 
+/* ---- screen, the evaluation: how good a partition of the kept pairs is.  The list of entries (a[e], b[e], weight[e])
+ * over n nodes is that of the representatives (unsorted, a pair in one direction or both, once or several times, an entry with
+ * a[e] == b[e] ignored altogether; weight == NULL weighs every entry 1).  label (int32[n]) is a partition given by naming nodes:
+ * 0 <= label[v] < n and label[label[v]] == label[v] — rep of the representatives, cluster and rep of the linkage, root of the components.
+ * score[v] (uint64, greater is better, ties to the smaller index) gives `rank` as for the representatives.
+ * A PAIR is a distinct unordered {u, v}, u != v, joined by at least one entry; its weight is the MAXIMUM of weight[e] over those entries in
+ * either direction.  It is INSIDE iff label[u] == label[v], otherwise OUTSIDE.  Per node v:
+ *   in_pairs[v]   uint32  the inside pairs at v
+ *   in_weight[v]  uint64  the sum of their weights
+ *   in_min[v]     uint32  the smallest of them; 0xFFFFFFFF when in_pairs[v] == 0
+ *   out_pairs[v]  uint32  the outside pairs at v
+ *   out_weight[v] uint32, out_node[v] int32  the greatest outside pair weight at v and the node at its other end, ties to the smaller
+ *                         node; 0, -1 when there is none (a pair of weight 0 gives 0 and its node)
+ *   to_medoid[v]  uint32  the weight of the pair joining v and its cluster's medoid; 0 when there is none or v is the medoid
+ * Per cluster, indexed by the naming node c = label[v] and meaningful where label[c] == c (0 or -1 elsewhere):
+ *   size[c]   uint32  the members
+ *   pairs[c], weight[c] uint64  the inside pairs and the sum of their weights
+ *   min[c]    uint32  the weakest inside pair; 0xFFFFFFFF without one
+ *   medoid[c] int32   the member of the greatest in_weight, ties to the smaller rank; the member itself in a singleton
+ *   near_weight[c] uint32, near_cluster[c] int32  the greatest weight of a pair joining a member and a non-member and the label of the
+ *                     non-member, ties to the smaller label; 0, -1 without one
+ * All integers that depend on neither the order, direction or duplication of the list nor any schedule
+ * (pyani_amd.screen.evaluate_of_pairs is the statement).  The distinct pairs come from one radix sort of the 40-bit keys
+ * min(a, b) << 20 | max(a, b) (a self entry sorts last) and one reduce-by-key with maximum; the pair pass reduces runs of equal
+ * destination inside a wave before its atomics; the outside maxima are 64-bit atomic maxima of weight << 32 | ~other, whose low word is
+ * never 0, so that 0 means "no pair"; the medoid takes two node passes (the maximum of in_weight, then the minimum of rank among the
+ * members that reach it).  No thread waits for another.
+ * pg_screen_evaluate takes the list from the host and keeps it on the device for the sort (12 bytes an entry in, 24 while sorting),
+ * 1 <= n <= 2^20.  PG_E_ARG, checked before anything is copied or replaced: n outside that range, a NULL label or score, a label outside
+ * [0, n) or one that does not name itself (the message names the first such node), m > 2^32 - 1 (so that no 64-bit sum can overflow),
+ * m > 0 with a NULL a or b, an index outside [0, n).
+ * pg_screen_index_evaluate takes the list from the resident index instead, exactly as pg_screen_index_representatives does: ALL bands are
+ * counted and selected as pg_screen_index_select does, every band's kept triples with a < b appended to a list on the device, which is
+ * distinct already; no pair is copied to the host.  *n_pairs_out = the kept cells (both directions).  The index, its latest selection and
+ * pg_screen_index_last are left as they were.  PG_E_ARG as pg_screen_index_select and as above.
+ * The result stays RESIDENT in a state of its own, independent of every other resident screen state, until the next ACCEPTED evaluate
+ * call (a refused one leaves it readable; an allocation that fails replaces nothing), pg_screen_evaluate_release (PG_OK when there is
+ * none), pg_clear_genomes or pg_destroy.  pg_screen_evaluate_read copies the seven node arrays out and pg_screen_evaluate_read_clusters
+ * the seven cluster arrays, n entries each; any pointer may be NULL (that array is skipped); PG_E_ARG when nothing is resident.
+ * pg_screen_evaluate_last: counts_out[6] = n, entries worked (the list entry: those with a != b; the index entry: the undirected kept
+ * pairs), entries ignored (a == b), distinct pairs, inside pairs, clusters; ms_out[4] = band count + select (the index path only),
+ * canonicalise + sort + reduce (with the rank sort), pair passes, node passes milliseconds (HIP events on the context's stream); all 0
+ * when nothing is resident. */
+int pg_screen_evaluate(pg_ctx* ctx, const int32_t* a, const int32_t* b, const uint32_t* weight, uint64_t m, uint32_t n, const int32_t* label, const uint64_t* score);
+int pg_screen_index_evaluate(pg_ctx* ctx, const uint32_t* need, uint32_t n, const int32_t* label, const uint64_t* score, uint64_t* n_pairs_out);
+int pg_screen_evaluate_read(pg_ctx* ctx, uint32_t* in_pairs_out, uint64_t* in_weight_out, uint32_t* in_min_out, uint32_t* out_pairs_out, uint32_t* out_weight_out,
+                            int32_t* out_node_out, uint32_t* to_medoid_out);
+int pg_screen_evaluate_read_clusters(pg_ctx* ctx, uint32_t* size_out, uint64_t* pairs_out, uint64_t* weight_out, uint32_t* min_out, int32_t* medoid_out,
+                                     uint32_t* near_weight_out, int32_t* near_cluster_out);
+int pg_screen_evaluate_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
+int pg_screen_evaluate_release(pg_ctx* ctx);
+
 /* ---- screen, the search: new genomes against a resident collection.  S(g), size, kmer and scale as for
  * pg_screen_matrix.  A collection ("db") of n <= 2^20 genomes is indexed once; then, per call, q query genomes are placed against it:
  *   hits[i][b] = |S(query i) & S(db b)|, a q x n rectangle of uint32, row-major

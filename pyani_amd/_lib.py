@@ -117,6 +117,12 @@ SIGNATURES = {
     "pg_screen_representatives_read": (_int, [_vp, _vp, _vp]),
     "pg_screen_representatives_last": (_int, [_vp, _vp, _vp]),
     "pg_screen_representatives_release": (_int, [_vp]),
+    "pg_screen_evaluate": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp]),
+    "pg_screen_index_evaluate": (_int, [_vp, _vp, _u32, _vp, _vp, _P(_u64)]),
+    "pg_screen_evaluate_read": (_int, [_vp] * 8),
+    "pg_screen_evaluate_read_clusters": (_int, [_vp] * 8),
+    "pg_screen_evaluate_last": (_int, [_vp, _vp, _vp]),
+    "pg_screen_evaluate_release": (_int, [_vp]),
     "pg_screen_linkage": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _vp, _int, ctypes.c_double, ctypes.c_double, _P(_u32)]),
     "pg_screen_linkage_read": (_int, [_vp, _vp, _vp, _vp]),
     "pg_screen_linkage_read_merges": (_int, [_vp, _vp]),

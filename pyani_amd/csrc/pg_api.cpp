@@ -359,6 +359,7 @@ void pg_destroy(pg_ctx* ctx) {
   pg_screen_representatives_drop(ctx);
   pg_screen_sweep_drop(ctx);
   pg_screen_linkage_drop(ctx);
+  pg_screen_evaluate_drop(ctx);
   pg_screen_search_drop(ctx);
   prof_drain(ctx);
   delete ctx;                // the buffers and the streams go here, on the context's device
@@ -471,6 +472,7 @@ int pg_clear_genomes(pg_ctx* ctx) {
   pg_screen_representatives_drop(ctx);
   pg_screen_sweep_drop(ctx);
   pg_screen_linkage_drop(ctx);
+  pg_screen_evaluate_drop(ctx);
   ctx->genomes.clear();
   ctx->arena_used = 0;
   ctx->n_resident = 0;

@@ -72,6 +72,11 @@ struct PgScreenLinkageStats {      // pg_screen_linkage_last: the resident linka
   double group_ms = 0.0, fill_ms = 0.0, small_ms = 0.0, large_ms = 0.0, cut_ms = 0.0;      // group, fill, wave linkage, workgroup linkage, cut + representatives
 };
 
+struct PgScreenEvaluateStats {      // pg_screen_evaluate_last: the resident evaluation's call
+  uint64_t nodes = 0, worked = 0, ignored = 0, pairs = 0, inside = 0, clusters = 0;      // pairs: distinct; inside: those with both ends in one cluster
+  double select_ms = 0.0, sort_ms = 0.0, pair_ms = 0.0, node_ms = 0.0;                    // band count + select (index path), canonicalise + sort + reduce, pair passes, node passes
+};
+
 struct PgScreenSearchStats {
   uint64_t keys = 0, kmers = 0, entries = 0, slices = 0, index_bytes = 0;                // the search index: sampled keys, distinct k-mers, (k-mer, genome) entries, device bytes its buffers hold
   uint64_t query_keys = 0, lookups = 0, matched = 0, increments = 0, query_slices = 0;   // the latest count: lookups = the distinct k-mers of the queries
@@ -177,6 +182,8 @@ struct pg_ctx {
   PgScreenLinkageStats screen_linkage_stats;      // pg_screen_linkage_last: the resident linkage's call
   uint32_t screen_linkage_small = 0xFFFFFFFFu;      // pg_screen_linkage_set: components up to here go one per wave (PG_SCREEN_LINKAGE_DEFAULT: the default, pgscr_linkage.inc)
   uint64_t screen_linkage_work = 0;                 // ... and the bytes of working matrices of one batch (0: the default)
+  void* screen_evaluate_state = nullptr;      // resident evaluation of the latest pg_screen_evaluate / pg_screen_index_evaluate (pg_screen.hip); independent of the six above
+  PgScreenEvaluateStats screen_evaluate_stats;      // pg_screen_evaluate_last: the resident evaluation's call
   void* screen_search_state = nullptr;          // resident search index of pg_screen_search_index and the latest rectangle counted against it (pg_screen.hip); independent of the three above and of the genome store
   PgScreenGatherStats screen_gather_stats;      // pg_screen_gather_last
   PgScreenGatherAbundStats screen_gather_abund_stats;      // pg_screen_gather_abund_last
@@ -303,6 +310,7 @@ void pg_screen_components_drop(pg_ctx* ctx); // ... the screen's resident compon
 void pg_screen_representatives_drop(pg_ctx* ctx); // ... the screen's resident representatives (pg_screen.hip): the same
 void pg_screen_sweep_drop(pg_ctx* ctx); // ... the screen's resident sweep (pg_screen.hip): the same
 void pg_screen_linkage_drop(pg_ctx* ctx); // ... the screen's resident linkage (pg_screen.hip): the same
+void pg_screen_evaluate_drop(pg_ctx* ctx); // ... the screen's resident evaluation (pg_screen.hip): the same
 void pg_screen_index_drop(pg_ctx* ctx); // ... the screen's resident k-mer index and its selection (pg_screen.hip): with the context, the genome store or on request
 void pg_screen_search_drop(pg_ctx* ctx); // ... the screen's resident search index and rectangle (pg_screen.hip): with the context or on request — NOT with the genome store: it names genomes by call index only
 int pg_anib_reduce_run(pg_ctx* ctx, uint32_t n_pairs, const uint64_t* offsets, const uint32_t* n_frags, const int32_t* frag,

@@ -102,6 +102,11 @@
 // distance matrices by 64-bit atomic maxima, runs scipy's nearest-neighbour chain — one wave per small component (L8), the heatmap's
 // workgroup kernel (pg_cluster_linkage.h) for the others — cuts the trees through a second forest and names one representative per cluster;
 // L1 ... L12 stand there with their state.
+//
+// pgscr_evaluate.inc — the EVALUATION: how good a partition of the kept pairs is.  pg_screen_evaluate (a list from the
+// host: one radix sort and one reduce-by-key give the distinct pairs) and pg_screen_index_evaluate (the list the representatives' index
+// entry appends) reduce the pairs per node and per cluster — inside sums and minima, the nearest outside node and cluster by 64-bit atomic
+// maxima, the medoid in two node passes; E1 ... E7 stand there with their state.
 #include <algorithm>
 #include <hipcub/hipcub.hpp>
 #include <memory>
@@ -114,7 +119,7 @@
 
 namespace {
 
-// the stages whose milliseconds pg_screen_last, pg_screen_index_last, pg_screen_components_last, pg_screen_representatives_last, pg_screen_sweep_last, pg_screen_linkage_last, pg_screen_search_last,
+// the stages whose milliseconds pg_screen_last, pg_screen_index_last, pg_screen_components_last, pg_screen_representatives_last, pg_screen_sweep_last, pg_screen_linkage_last, pg_screen_evaluate_last, pg_screen_search_last,
 // pg_screen_search_add_last, pg_screen_search_remove_last and pg_screen_gather_last report
 enum ScreenStage { ST_SCAN, ST_GROUP, ST_COUNT, ST_SELECT, ST_HOOK, ST_FLATTEN, ST_LOOKUP, ST_EXPAND, ST_ARGMAX, ST_CLAIM, ST_MERGE, ST_CHECK, ST_MARK, ST_COMPACT, ST_WEIGHT, ST_ATTRIBUTE, ST_SORT, ST_STATS, ST_ROUNDS, ST_ASSIGN, ST_CENSUS, ST_FILL, ST_SMALL, ST_LARGE, ST_CUT };
 
@@ -171,6 +176,7 @@ hipError_t tmp_room(size_t& tmp_bytes, Query query) {
 #include "pgscr_representatives.inc"
 #include "pgscr_sweep.inc"
 #include "pgscr_linkage.inc"
+#include "pgscr_evaluate.inc"
 #include "pgscr_search.inc"
 #include "pgscr_add.inc"
 #include "pgscr_store.inc"

@@ -179,6 +179,58 @@ __global__ __launch_bounds__(256) void representatives_append_kernel(const int32
   }
 }
 
+// The undirected kept pairs of ALL bands of the resident index, a < b, appended band by band to a list on the device: 12 bytes each.  The
+// room grows ahead of every band by what the band kept (its triples with a < b cannot be more), at least doubling, the list copied over
+// on the device.  Shared by pg_screen_index_representatives and pg_screen_index_evaluate; the bands are timed under ST_SELECT.
+struct KeptList {
+  PgDevBuf<int32_t> a, b;
+  PgDevBuf<uint32_t> w;
+  uint64_t held = 0;
+};
+
+int representatives_collect(pg_ctx* ctx, const IndexState* I, const uint32_t* need, ScreenEvents& T, KeptList& L, BandTotals& tot) {
+  hipStream_t st = ctx->stream;
+  PgDevBuf<unsigned long long> cursor;
+  int rc;
+  if ((rc = pg_dev_alloc(ctx, "screen", cursor, 1, "the kept pairs' cursor"))) return rc;
+  PG_HIP(ctx, hipMemsetAsync(cursor, 0, 8, st));
+  uint64_t cap = 0;
+  uint64_t& held = L.held;
+  const BandStages stages{ST_SELECT, ST_SELECT, ST_SELECT, false};
+  rc = band_loop(ctx, I, need, 0, 1, T, stages, tot, [&](uint32_t, uint32_t, unsigned long long total, BandWork& W) -> int {
+    if (!total) return PG_OK;
+    if (held + total > cap) {
+      const uint64_t room = std::max<uint64_t>(held + total, 2 * cap);
+      PgDevBuf<int32_t> g_a, g_b;
+      PgDevBuf<uint32_t> g_w;
+      int r;
+      if ((r = pg_dev_alloc(ctx, "screen", g_a, (size_t)room, "the kept pairs")) || (r = pg_dev_alloc(ctx, "screen", g_b, (size_t)room, "the kept pairs")) ||
+          (r = pg_dev_alloc(ctx, "screen", g_w, (size_t)room, "the kept pairs")))
+        return r;
+      if (held) {
+        PG_HIP(ctx, hipMemcpyAsync(g_a, L.a, (size_t)held * 4, hipMemcpyDeviceToDevice, st));
+        PG_HIP(ctx, hipMemcpyAsync(g_b, L.b, (size_t)held * 4, hipMemcpyDeviceToDevice, st));
+        PG_HIP(ctx, hipMemcpyAsync(g_w, L.w, (size_t)held * 4, hipMemcpyDeviceToDevice, st));
+        PG_HIP(ctx, hipStreamSynchronize(st));      // (the old blocks go with the moves below)
+      }
+      L.a = std::move(g_a); L.b = std::move(g_b); L.w = std::move(g_w);
+      cap = room;
+    }
+    hipLaunchKernelGGL(representatives_append_kernel, dim3(grid_for(total, 256 * 4, (uint32_t)ctx->num_cu * 8u)), dim3(256), 0, st, (const int32_t*)W.a.p, (const int32_t*)W.b.p,
+                       (const uint32_t*)W.s.p, (uint64_t)total, L.a.p, L.b.p, L.w.p, cap, cursor.p);
+    PG_HIP(ctx, hipGetLastError());
+    unsigned long long at = 0;
+    PG_HIP(ctx, hipMemcpyAsync(&at, cursor, 8, hipMemcpyDeviceToHost, st));
+    PG_HIP(ctx, hipStreamSynchronize(st));
+    if (at < held || at > held + total || at > cap) return pg_fail(ctx, PG_E_INTERNAL, "screen: a band appended more pairs than it kept");
+    held = at;
+    return PG_OK;
+  });
+  if (rc) return rc;
+  if (held * 2 != tot.kept) return pg_fail(ctx, PG_E_INTERNAL, "screen: " + std::to_string(tot.kept) + " kept cells but " + std::to_string(held) + " undirected pairs");
+  return PG_OK;
+}
+
 // Everything after the entries stand on the device (w may be null: every entry weighs 1): ranks, rounds, assign, and the finished state
 // made the context's (the earlier one goes here, not before).  score is the host's.
 int representatives_run(pg_ctx* ctx, uint32_t n, const int32_t* d_a, const int32_t* d_b, const uint32_t* d_w, uint64_t m, const uint64_t* score, ScreenEvents& T,
@@ -354,49 +406,11 @@ extern "C" int pg_screen_index_representatives(pg_ctx* ctx, const uint32_t* need
   if (n < 1) return pg_fail(ctx, PG_E_ARG, "screen: representatives are of 1 ... 1048576 (2^20) nodes, not 0");
   PG_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  // the undirected kept pairs, a < b, appended band by band: 12 bytes each.  The room grows ahead of every band by what the band kept
-  // (its triples with a < b cannot be more), at least doubling, the list copied over on the device.
-  PgDevBuf<int32_t> l_a, l_b;
-  PgDevBuf<uint32_t> l_w;
-  PgDevBuf<unsigned long long> cursor;
-  if ((rc = pg_dev_alloc(ctx, "screen", cursor, 1, "the kept pairs' cursor"))) return rc;
-  PG_HIP(ctx, hipMemsetAsync(cursor, 0, 8, st));
-  uint64_t held = 0, cap = 0;
+  KeptList L;
   ScreenEvents T;
   BandTotals tot;
-  const BandStages stages{ST_SELECT, ST_SELECT, ST_SELECT, false};
-  rc = band_loop(ctx, I, need, 0, 1, T, stages, tot, [&](uint32_t, uint32_t, unsigned long long total, BandWork& W) -> int {
-    if (!total) return PG_OK;
-    if (held + total > cap) {
-      const uint64_t room = std::max<uint64_t>(held + total, 2 * cap);
-      PgDevBuf<int32_t> g_a, g_b;
-      PgDevBuf<uint32_t> g_w;
-      int r;
-      if ((r = pg_dev_alloc(ctx, "screen", g_a, (size_t)room, "the kept pairs")) || (r = pg_dev_alloc(ctx, "screen", g_b, (size_t)room, "the kept pairs")) ||
-          (r = pg_dev_alloc(ctx, "screen", g_w, (size_t)room, "the kept pairs")))
-        return r;
-      if (held) {
-        PG_HIP(ctx, hipMemcpyAsync(g_a, l_a, (size_t)held * 4, hipMemcpyDeviceToDevice, st));
-        PG_HIP(ctx, hipMemcpyAsync(g_b, l_b, (size_t)held * 4, hipMemcpyDeviceToDevice, st));
-        PG_HIP(ctx, hipMemcpyAsync(g_w, l_w, (size_t)held * 4, hipMemcpyDeviceToDevice, st));
-        PG_HIP(ctx, hipStreamSynchronize(st));      // (the old blocks go with the moves below)
-      }
-      l_a = std::move(g_a); l_b = std::move(g_b); l_w = std::move(g_w);
-      cap = room;
-    }
-    hipLaunchKernelGGL(representatives_append_kernel, dim3(grid_for(total, 256 * 4, (uint32_t)ctx->num_cu * 8u)), dim3(256), 0, st, (const int32_t*)W.a.p, (const int32_t*)W.b.p,
-                       (const uint32_t*)W.s.p, (uint64_t)total, l_a.p, l_b.p, l_w.p, cap, cursor.p);
-    PG_HIP(ctx, hipGetLastError());
-    unsigned long long at = 0;
-    PG_HIP(ctx, hipMemcpyAsync(&at, cursor, 8, hipMemcpyDeviceToHost, st));
-    PG_HIP(ctx, hipStreamSynchronize(st));
-    if (at < held || at > held + total || at > cap) return pg_fail(ctx, PG_E_INTERNAL, "screen: a band appended more pairs than it kept");
-    held = at;
-    return PG_OK;
-  });
-  if (rc) return rc;
-  if (held * 2 != tot.kept) return pg_fail(ctx, PG_E_INTERNAL, "screen: " + std::to_string(tot.kept) + " kept cells but " + std::to_string(held) + " undirected pairs");
-  if ((rc = representatives_run(ctx, n, l_a.p, l_b.p, l_w.p, held, score, T, held, 0, n_representatives_out))) { (void)hipStreamSynchronize(st); return rc; }
+  if ((rc = representatives_collect(ctx, I, need, T, L, tot))) return rc;
+  if ((rc = representatives_run(ctx, n, L.a.p, L.b.p, L.w.p, L.held, score, T, L.held, 0, n_representatives_out))) { (void)hipStreamSynchronize(st); return rc; }
   *n_pairs_out = tot.kept;
   return PG_OK;
 }

@@ -653,6 +653,101 @@ class Engine:
         finally:
             self.screen_representatives_release()
 
+    # the evaluation: how good a partition of the kept pairs is, seven node and seven cluster arrays resident on the context
+    def _screen_evaluate_read(self, n: int):
+        from . import screen
+        nodes = [np.zeros(n, dtype=t) for t in screen._EVALUATE_NODE_TYPES]
+        clusters = [np.zeros(n, dtype=t) for t in screen._EVALUATE_CLUSTER_TYPES]
+        self._check(self.lib.pg_screen_evaluate_read(self._h, *(x.ctypes.data for x in nodes)))
+        self._check(self.lib.pg_screen_evaluate_read_clusters(self._h, *(x.ctypes.data for x in clusters)))
+        return tuple(nodes), tuple(clusters)
+
+    @staticmethod
+    def _evaluate_inputs(n: int, label, score):
+        """label int32[n] and score uint64[n] as the statement checks them (ValueError before the library is called)."""
+        from . import screen
+        if not 1 <= int(n) <= screen.INDEX_MAX_GENOMES:
+            raise ValueError(f"an evaluation is of 1 ... {screen.INDEX_MAX_GENOMES} nodes, not {int(n)}")
+        if label is None or score is None:
+            raise ValueError("an evaluation needs label= and score=")
+        lab = np.ascontiguousarray(screen.check_partition(label, int(n)), dtype=np.int32)
+        s = np.ascontiguousarray(score, dtype=np.uint64).reshape(-1)
+        if len(s) != int(n):
+            raise ValueError(f"{int(n)} nodes need {int(n)} scores, not {len(s)}")
+        return lab, s
+
+    def screen_evaluate(self, a, b, weight=None, n: int = 0, label=None, score=None):
+        """pg_screen_evaluate + pg_screen_evaluate_read + _read_clusters: (the seven node arrays, the seven cluster arrays) of the list of
+        entries (a[e], b[e], weight[e]) over n nodes under the partition label int32[n] and the scores score uint64[n], as
+        pyani_amd.screen.evaluate_of_pairs states them; weight=None weighs every entry 1.  ValueError as the statement's, before the
+        library is called.  The counts are screen_evaluate_last()."""
+        from . import screen
+        lab, s = self._evaluate_inputs(n, label, score)
+        x, y = np.asarray(a).reshape(-1), np.asarray(b).reshape(-1)
+        w = None if weight is None else np.ascontiguousarray(weight, dtype=np.uint32).reshape(-1)
+        m = len(x)
+        if len(y) != m or (w is not None and len(w) != m):
+            raise ValueError("a, b and weight must have the same length")
+        if m > screen.EVALUATE_MAX_ENTRIES:
+            raise ValueError(f"an evaluation is of at most {screen.EVALUATE_MAX_ENTRIES} entries, not {m}")
+        if m and (min(x.min(), y.min()) < 0 or max(x.max(), y.max()) >= int(n)):      # (on the caller's own type: a cast to int32 could hide it)
+            raise ValueError(f"an entry names a node outside [0, {int(n)})")
+        x, y = np.ascontiguousarray(x, dtype=np.int32), np.ascontiguousarray(y, dtype=np.int32)
+        self._check(self.lib.pg_screen_evaluate(self._h, x.ctypes.data if m else None, y.ctypes.data if m else None,
+                                                w.ctypes.data if w is not None and m else None, m, int(n), lab.ctypes.data, s.ctypes.data))
+        return self._screen_evaluate_read(int(n))
+
+    def screen_index_evaluate(self, need, label, score):
+        """pg_screen_index_evaluate + the two reads: (node arrays, cluster arrays, n_pairs) of the kept cells of ALL bands of the
+        resident index — screen_evaluate of the list screen_index_select would return, weight = shared, n_pairs its length — without a
+        pair leaving the device."""
+        t = np.ascontiguousarray(need, dtype=np.uint32).reshape(-1)
+        lab, s = self._evaluate_inputs(len(t), label, score)
+        m = ctypes.c_uint64(0)
+        self._check(self.lib.pg_screen_index_evaluate(self._h, t.ctypes.data, len(t), lab.ctypes.data, s.ctypes.data, ctypes.byref(m)))
+        return (*self._screen_evaluate_read(len(t)), int(m.value))
+
+    def screen_evaluate_last(self) -> dict:
+        """pg_screen_evaluate_last: counts and stage milliseconds of the resident evaluation (all 0 when there is none)."""
+        c = (ctypes.c_uint64 * 6)()
+        ms = (ctypes.c_double * 4)()
+        self._check(self.lib.pg_screen_evaluate_last(self._h, ctypes.addressof(c), ctypes.addressof(ms)))
+        return {"n": int(c[0]), "entries": int(c[1]), "ignored": int(c[2]), "pairs": int(c[3]), "inside": int(c[4]), "clusters": int(c[5]),
+                "select_ms": float(ms[0]), "sort_ms": float(ms[1]), "pair_ms": float(ms[2]), "node_ms": float(ms[3])}
+
+    def screen_evaluate_release(self) -> None:
+        self._check(self.lib.pg_screen_evaluate_release(self._h))
+
+    def screen_evaluate_of(self, ids, options, label, scores=None, labels=None, path: str = "auto"):
+        """How good the partition `label` of the pairs the screen keeps among the resident genomes `ids` is, weight = shared
+        (pyani_amd.screen.ScreenEvaluation).  label: one naming position per genome (screen.check_partition), e.g. the
+        rep of screen_dereplicate; scores as screen_dereplicate takes them.  path "dense": screen_candidates, then the list entry (the
+        kept pairs are read back once); "index": screen_index -> identity_thresholds -> screen_index_evaluate -> release, on errors too
+        — no pair is read back; "auto" as screen_candidates.  Nothing stays resident afterwards."""
+        from . import screen
+        options = screen.check_options(options)
+        ids = [int(i) for i in ids]
+        if scores is not None and len(screen.score_keys(scores)) != len(ids):      # (refused before any work)
+            raise ValueError(f"{len(ids)} genomes need {len(ids)} scores")
+        label = screen.check_partition(label, len(ids))
+        if screen.resolve_path(path, len(ids)) == "index":
+            labels = screen._labels_for(ids, labels, screen.INDEX_MAX_GENOMES)
+            if not ids:
+                return screen.evaluation_from_nodes(labels, label, np.zeros(0, np.uint64), [np.zeros(0)] * 7, [np.zeros(0)] * 7)
+            try:
+                sizes = self.screen_index(ids, options.kmer, options.scale)
+                need = screen.identity_thresholds(sizes, options.kmer, options.min_identity, options.min_shared)
+                score = screen.score_keys(scores, sizes)
+                nodes, clusters, _ = self.screen_index_evaluate(need, label, score)
+            finally:
+                self.screen_index_release()
+                self.screen_evaluate_release()
+            return screen.evaluation_from_nodes(labels, label, score, nodes, clusters)
+        try:
+            return self.screen_candidates(ids, options, labels, path="dense").evaluate(label, scores, engine=self)
+        finally:
+            self.screen_evaluate_release()
+
     # the linkage (DESIGN.md §16.11): species clusters by average / complete linkage inside every component, resident on the context
     def screen_linkage(self, a, b, dist, n: int = 0, score=None, method: str = "average", cutoff: float = 0.05, fill: float = 1.0):
         """pg_screen_linkage + pg_screen_linkage_read + pg_screen_linkage_read_merges: (root, cluster, rep int32[n], merges

@@ -413,6 +413,27 @@ class MultiEngine:
         for e in self.engines:
             e.screen_linkage_release()
 
+    # the evaluation runs on the FIRST engine, as the linkage does: one list call has nothing to divide, and a dealt or
+    # collective variant is out of scope.  The genome store is replicated, so the first engine's screen_evaluate_of sees every genome.
+    def screen_evaluate(self, a, b, weight=None, n: int = 0, label=None, score=None):
+        """Engine.screen_evaluate on the first engine (a list call has nothing to divide)."""
+        return self.engines[0].screen_evaluate(a, b, weight, n=n, label=label, score=score)
+
+    def screen_index_evaluate(self, need, label, score):
+        """Engine.screen_index_evaluate on the first engine, over ITS resident index (all bands)."""
+        return self.engines[0].screen_index_evaluate(need, label, score)
+
+    def screen_evaluate_of(self, ids, options, label, scores=None, labels=None, path: str = "auto"):
+        """Engine.screen_evaluate_of on the first engine alone (its own screen, not a dealt one).  Equal to one engine's."""
+        return self.engines[0].screen_evaluate_of(ids, options, label, scores=scores, labels=labels, path=path)
+
+    def screen_evaluate_last(self) -> dict:
+        return self.engines[0].screen_evaluate_last()
+
+    def screen_evaluate_release(self):
+        for e in self.engines:
+            e.screen_evaluate_release()
+
     def screen_dereplicate(self, ids, options, scores=None, labels=None, path: str = "auto"):
         """Engine.screen_dereplicate over all devices.  The greedy rule needs every entry in one place — a round reads
         the whole list, and a node's fate may hang on an entry of any band — so only the CANDIDATES are dealt as today

@@ -218,6 +218,23 @@ class ScreenedPairs(NamedTuple):
             rep, via = engine.screen_representatives(self.a, self.b, self.shared, n=n, score=score)
         return clusters_from_nodes(self.labels, rep, via, score)
 
+    def evaluate(self, label, scores=None, engine=None) -> "ScreenEvaluation":
+        """How good the partition `label` (check_partition: rep of .representatives(), root of .components(), ...) of the kept pairs
+        is, weight = shared: on `engine` (Engine.screen_evaluate), or by the numpy statement evaluate_of_pairs when
+        none is given.  scores as .representatives takes them.  Both give the same ScreenEvaluation."""
+        n = len(self.labels)
+        score = score_keys(scores, self.sizes)
+        if len(score) != n:
+            raise ValueError(f"{n} genomes need {n} scores, not {len(score)}")
+        label = check_partition(label, n)
+        if n == 0:
+            return evaluation_from_nodes(self.labels, label, score, [np.zeros(0)] * 7, [np.zeros(0)] * 7)
+        if engine is None:
+            nodes, clusters = evaluate_of_pairs(self.a, self.b, self.shared, n, label, score)
+        else:
+            nodes, clusters = engine.screen_evaluate(self.a, self.b, self.shared, n=n, label=label, score=score)
+        return evaluation_from_nodes(self.labels, label, score, nodes, clusters)
+
     def sweep(self, identities, snapshots=(), engine=None) -> "ScreenSweep":
         """The components of the kept pairs at every identity of a ladder: levels by sweep_thresholds + sweep_levels,
         then ONE pass on `engine` (Engine.screen_sweep), or the numpy statement sweep_of_pairs when none is given.  Both give the same
@@ -935,6 +952,247 @@ def linkage_from_nodes(labels, root, cluster, rep, score, merges, method, cutoff
         raise ValueError("the merge records do not match the components")
     method, cutoff, fill = check_linkage(method, cutoff, fill)
     return ScreenLinkage(labels, root, cluster, rep, score, merges, method, cutoff, fill)
+
+
+# ---- the evaluation of a partition of the kept pairs -----------------------------------------------------------------------
+EVALUATE_MAX_ENTRIES = 0xFFFFFFFF      # with at most 2^32 - 1 entries of uint32 weights no 64-bit sum can overflow
+EVALUATE_NONE = 0xFFFFFFFF             # in_min / min of a node / cluster without an inside pair
+EVALUATE_NODE_ARRAYS = ("in_pairs", "in_weight", "in_min", "out_pairs", "out_weight", "out_node", "to_medoid")
+EVALUATE_CLUSTER_ARRAYS = ("size", "pairs", "weight", "min", "medoid", "near_weight", "near_cluster")
+_EVALUATE_NODE_TYPES = (np.uint32, np.uint64, np.uint32, np.uint32, np.uint32, np.int32, np.uint32)
+_EVALUATE_CLUSTER_TYPES = (np.uint32, np.uint64, np.uint64, np.uint32, np.int32, np.uint32, np.int32)
+
+
+def check_partition(label, n: int) -> np.ndarray:
+    """int64[n] of a partition given by naming nodes: 0 <= label[v] < n and label[label[v]] == label[v] (ValueError names the first node
+    that breaks it).  rep of the representatives, cluster and rep of the linkage and root of the components all satisfy it."""
+    try:
+        label = np.ascontiguousarray(label, dtype=np.int64).reshape(-1)
+    except (TypeError, ValueError) as err:
+        raise ValueError(f"labels must be node indices: {err}") from None
+    if len(label) != int(n):
+        raise ValueError(f"{int(n)} nodes need {int(n)} labels, not {len(label)}")
+    bad = (label < 0) | (label >= n)
+    if bad.any():
+        v = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"node {v} has the label {int(label[v])} outside [0, {int(n)})")
+    bad = label[label] != label
+    if bad.any():
+        v = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"node {v} has the label {int(label[v])}, which does not name itself (label[label[v]] == label[v])")
+    return label
+
+
+def _sum_by(group, w, n) -> np.ndarray:
+    """uint64[n]: the sum of the uint64 values w < 2^32 per group (float64 sums of 16-bit halves: exact below 2^37 entries)."""
+    lo = np.bincount(group, weights=(w & np.uint64(0xFFFF)).astype(np.float64), minlength=n).astype(np.uint64)
+    hi = np.bincount(group, weights=(w >> np.uint64(16)).astype(np.float64), minlength=n).astype(np.uint64)
+    return lo + (hi << np.uint64(16))
+
+
+def _pick_by(group, key, largest: bool) -> Tuple[np.ndarray, np.ndarray]:
+    """(groups, keys): per group that occurs, its largest or its smallest key (one lexsort; the run's last or first entry)."""
+    if not len(group):
+        return group, key
+    by = np.lexsort((key, group))
+    g, k = group[by], key[by]
+    edge = g[1:] != g[:-1]
+    at = np.flatnonzero(np.append(edge, True)) if largest else np.flatnonzero(np.append(True, edge))
+    return g[at], k[at]
+
+
+def evaluate_of_pairs(a, b, weight, n, label, score):
+    """THE STATEMENT of the evaluation (the host's; Engine.screen_evaluate is held to it): for the list of entries (a[e], b[e], weight[e])
+    over n nodes — unsorted, a pair in one direction or both, once or several times, an entry with a[e] == b[e] ignored, weight=None
+    weighing every entry 1 —, a partition label (check_partition) and the scores score uint64[n] (rank = rank_order(score)[1]):
+
+    A PAIR is a distinct unordered {u, v}, u != v, joined by at least one entry; its weight is the MAXIMUM of weight[e] over those
+    entries, in either direction.  It is INSIDE iff label[u] == label[v], otherwise OUTSIDE.  Per node v (EVALUATE_NODE_ARRAYS):
+
+        in_pairs[v]   uint32  the inside pairs at v
+        in_weight[v]  uint64  the sum of their weights
+        in_min[v]     uint32  the smallest of them, 0xFFFFFFFF when there is none
+        out_pairs[v]  uint32  the outside pairs at v
+        out_weight[v] uint32, out_node[v] int32  the greatest outside pair weight at v and the node at its other end, ties to the
+                              smaller node; 0, -1 when there is none
+        to_medoid[v]  uint32  the weight of the pair joining v and its cluster's medoid; 0 when there is none or v is the medoid
+
+    Per cluster (EVALUATE_CLUSTER_ARRAYS), arrays of length n indexed by the naming node c = label[v] and read only where label[c] == c;
+    0 or -1 elsewhere:
+
+        size[c]   uint32  the members
+        pairs[c], weight[c] uint64  the inside pairs and the sum of their weights
+        min[c]    uint32  the weakest inside pair, 0xFFFFFFFF without one
+        medoid[c] int32   the member of the greatest in_weight, ties to the smaller rank (greater score, then smaller index)
+        near_weight[c] uint32, near_cluster[c] int32  the greatest weight of a pair joining a member and a non-member and the label of
+                          the non-member, ties to the smaller label; 0, -1 without one
+
+    Returns (the seven node arrays, the seven cluster arrays).  Integers, independent of the list's order, direction and duplication.
+    More than 2^32 - 1 entries are refused: below that no 64-bit sum can overflow."""
+    a, b, w, n = _check_entries(a, b, weight, n)
+    if len(a) > EVALUATE_MAX_ENTRIES:
+        raise ValueError(f"an evaluation is of at most {EVALUATE_MAX_ENTRIES} entries, not {len(a)}")
+    label = check_partition(label, n)
+    score = np.ascontiguousarray(score, dtype=np.uint64).reshape(-1)
+    if len(score) != n:
+        raise ValueError(f"{n} nodes need {n} scores, not {len(score)}")
+    _, rank = rank_order(score)
+    # the distinct pairs (lo < hi) with the greatest weight of their entries: sorted by (lo, hi, weight), a run's last entry
+    live = a != b
+    lo, hi = np.minimum(a, b)[live], np.maximum(a, b)[live]
+    w = np.ones(len(lo), dtype=np.uint64) if w is None else w[live].astype(np.uint64)
+    if len(lo):
+        by = np.lexsort((w, hi, lo))
+        lo, hi, w = lo[by], hi[by], w[by]
+        last = np.flatnonzero(np.append((lo[1:] != lo[:-1]) | (hi[1:] != hi[:-1]), True))
+        lo, hi, w = lo[last], hi[last], w[last]
+    # every pair seen from both of its ends: v the node, o the other end
+    v, o, wv = np.concatenate([lo, hi]), np.concatenate([hi, lo]), np.concatenate([w, w])
+    inside = label[v] == label[o]
+    vi, oi, wi = v[inside], o[inside], wv[inside]
+    vo, oo, wo = v[~inside], o[~inside], wv[~inside]
+    low = np.uint64(0xFFFFFFFF)
+    in_pairs = np.bincount(vi, minlength=n).astype(np.uint32)
+    in_weight = _sum_by(vi, wi, n)
+    in_min = np.full(n, EVALUATE_NONE, dtype=np.uint32)
+    g, k = _pick_by(vi, wi, largest=False)
+    in_min[g] = k.astype(np.uint32)
+    out_pairs = np.bincount(vo, minlength=n).astype(np.uint32)
+    out_weight, out_node = np.zeros(n, dtype=np.uint32), np.full(n, -1, dtype=np.int32)
+    g, k = _pick_by(vo, (wo << np.uint64(32)) | (low - oo.astype(np.uint64)), largest=True)      # the greatest weight, then the smaller node
+    out_weight[g], out_node[g] = (k >> np.uint64(32)).astype(np.uint32), (low - (k & low)).astype(np.int32)
+    # per cluster: the naming nodes are those with label[c] == c
+    names = label == np.arange(n)
+    size = np.bincount(label, minlength=n).astype(np.uint32)
+    once = lo[label[lo] == label[hi]]      # every inside pair once, by its lower end
+    pairs = np.bincount(label[once], minlength=n).astype(np.uint64)
+    weight_c = _sum_by(label[once], w[label[lo] == label[hi]], n)
+    min_c = np.where(names, EVALUATE_NONE, 0).astype(np.uint32)
+    g, k = _pick_by(label[vi], wi, largest=False)
+    min_c[g] = k.astype(np.uint32)
+    medoid = np.full(n, -1, dtype=np.int32)
+    by = np.lexsort((rank, ~in_weight, label))      # by cluster, then in_weight descending (~ reverses uint64), then rank ascending
+    first = np.flatnonzero(np.append(True, label[by][1:] != label[by][:-1]))
+    medoid[label[by][first]] = by[first]
+    near_weight, near_cluster = np.zeros(n, dtype=np.uint32), np.full(n, -1, dtype=np.int32)
+    g, k = _pick_by(label[vo], (wo << np.uint64(32)) | (low - label[oo].astype(np.uint64)), largest=True)
+    near_weight[g], near_cluster[g] = (k >> np.uint64(32)).astype(np.uint32), (low - (k & low)).astype(np.int32)
+    to_medoid = np.zeros(n, dtype=np.uint32)
+    hit = oi == medoid[label[vi]]
+    to_medoid[vi[hit]] = wi[hit].astype(np.uint32)
+    return ((in_pairs, in_weight, in_min, out_pairs, out_weight, out_node, to_medoid),
+            (size, pairs, weight_c, min_c, medoid, near_weight, near_cluster))
+
+
+class ScreenEvaluation(NamedTuple):
+    """How good a partition of a list of kept pairs is, over the genomes `labels` (None: the nodes go by their index): label and score as
+    they were given, then the seven node arrays and the seven cluster arrays of evaluate_of_pairs (the cluster arrays have length n and
+    are indexed by the naming node).  Built by evaluation_from_nodes; clusters are numbered by ascending naming node."""
+    labels: Optional[List[str]]
+    label: np.ndarray            # int32[n]
+    score: np.ndarray            # uint64[n]
+    in_pairs: np.ndarray         # uint32[n]
+    in_weight: np.ndarray        # uint64[n]
+    in_min: np.ndarray           # uint32[n]
+    out_pairs: np.ndarray        # uint32[n]
+    out_weight: np.ndarray       # uint32[n]
+    out_node: np.ndarray         # int32[n]
+    to_medoid: np.ndarray        # uint32[n]
+    size: np.ndarray             # uint32[n], by naming node, as the six below
+    pairs: np.ndarray            # uint64[n]
+    weight: np.ndarray           # uint64[n]
+    min: np.ndarray              # uint32[n]
+    medoid: np.ndarray           # int32[n]
+    near_weight: np.ndarray      # uint32[n]
+    near_cluster: np.ndarray     # int32[n]
+
+    def node_arrays(self) -> tuple:
+        return tuple(getattr(self, k) for k in EVALUATE_NODE_ARRAYS)
+
+    def cluster_arrays(self) -> tuple:
+        return tuple(getattr(self, k) for k in EVALUATE_CLUSTER_ARRAYS)
+
+    def _names(self, nodes) -> list:
+        """Labels of the nodes; "" for -1."""
+        nodes = np.asarray(nodes).tolist()
+        return [("" if i < 0 else (i if self.labels is None else self.labels[i])) for i in nodes]
+
+    def naming(self) -> np.ndarray:
+        """The naming nodes, ascending: cluster c of the frames is naming()[c]."""
+        return np.flatnonzero(self.label == np.arange(len(self.label))).astype(np.int32)
+
+    def cluster_of(self) -> np.ndarray:
+        """int32[n]: the number of every node's cluster (the position of its label in naming())."""
+        return np.searchsorted(self.naming(), self.label).astype(np.int32)
+
+    def centrality(self) -> np.ndarray:
+        """float64[n]: in_weight / (size - 1) of the node's cluster — the mean weight of a genome's pairs with the OTHER members of its
+        cluster, an absent pair counting 0 (dRep's ANI 0); 0.0 in a singleton."""
+        others = self.size[self.label].astype(np.float64) - 1.0
+        return np.where(others > 0, self.in_weight.astype(np.float64) / np.where(others > 0, others, 1.0), 0.0)
+
+    def complete(self) -> np.ndarray:
+        """bool per cluster, in cluster order: every pair of members is a pair of the list (pairs == size (size - 1) / 2)."""
+        s = self.size[self.naming()].astype(np.uint64)
+        return self.pairs[self.naming()] == s * (s - np.uint64(1)) // np.uint64(2)
+
+    def genome_frame(self) -> pd.DataFrame:
+        """One row per genome, in the order of `labels`: genome, cluster, medoid (of its cluster), is_medoid, centrality, in_pairs,
+        in_weight, in_min, to_medoid, out_pairs, out_weight, out_node ("" when there is none)."""
+        n = len(self.label)
+        med = self.medoid[self.label]
+        return pd.DataFrame({"genome": self._names(np.arange(n)), "cluster": self.cluster_of().astype(np.int64), "medoid": self._names(med),
+                             "is_medoid": med == np.arange(n), "centrality": self.centrality(), "in_pairs": self.in_pairs.astype(np.int64),
+                             "in_weight": self.in_weight, "in_min": self.in_min.astype(np.int64), "to_medoid": self.to_medoid.astype(np.int64),
+                             "out_pairs": self.out_pairs.astype(np.int64), "out_weight": self.out_weight.astype(np.int64), "out_node": self._names(self.out_node)})
+
+    def cluster_frame(self) -> pd.DataFrame:
+        """One row per cluster, by ascending naming node: cluster, name (the naming node), size, pairs, complete, weight, mean_weight
+        (weight / pairs, 0.0 without a pair), min, medoid, near_weight, near_cluster (a cluster number, -1 when there is none)."""
+        c = self.naming()
+        pairs = self.pairs[c]
+        mean = np.where(pairs > 0, self.weight[c].astype(np.float64) / np.where(pairs > 0, pairs, 1).astype(np.float64), 0.0)
+        near = self.near_cluster[c]
+        near_no = np.where(near >= 0, np.searchsorted(c, np.maximum(near, 0)), -1).astype(np.int64)
+        return pd.DataFrame({"cluster": np.arange(len(c), dtype=np.int64), "name": self._names(c), "size": self.size[c].astype(np.int64), "pairs": pairs,
+                             "complete": self.complete(), "weight": self.weight[c], "mean_weight": mean, "min": self.min[c].astype(np.int64),
+                             "medoid": self._names(self.medoid[c]), "near_weight": self.near_weight[c].astype(np.int64), "near_cluster": near_no})
+
+    def proximity(self, min_weight: int = 0) -> pd.DataFrame:
+        """The "these two nearly merge" table: one row per cluster that has an outside pair of weight near_weight >= min_weight —
+        cluster, name, near_cluster, near_name, near_weight, in cluster order.  A cluster without an outside pair has no row."""
+        t = self.cluster_frame()
+        keep = ((t["near_cluster"] >= 0) & (t["near_weight"] >= int(min_weight))).to_numpy()
+        t = t[keep].reset_index(drop=True)
+        names = self._names(self.naming())
+        return pd.DataFrame({"cluster": t["cluster"], "name": t["name"], "near_cluster": t["near_cluster"],
+                             "near_name": [names[i] for i in t["near_cluster"].tolist()], "near_weight": t["near_weight"]})
+
+    def recentred(self) -> "ScreenClusters":
+        """The same clusters with every cluster's MEDOID as its representative: rep[v] = medoid[label[v]], via = to_medoid."""
+        return clusters_from_nodes(self.labels, self.medoid[self.label], self.to_medoid, self.score)
+
+
+def evaluation_from_nodes(labels, label, score, node_arrays, cluster_arrays) -> ScreenEvaluation:
+    """The ScreenEvaluation of what evaluate_of_pairs or Engine.screen_evaluate returned."""
+    score = np.ascontiguousarray(score, dtype=np.uint64).reshape(-1)
+    n = len(score)
+    label = check_partition(label, n).astype(np.int32)
+    if labels is not None:
+        labels = [str(x) for x in labels]
+        if len(labels) != n:
+            raise ValueError("labels and nodes must have the same length")
+    if len(node_arrays) != len(EVALUATE_NODE_ARRAYS) or len(cluster_arrays) != len(EVALUATE_CLUSTER_ARRAYS):
+        raise ValueError(f"an evaluation has {len(EVALUATE_NODE_ARRAYS)} node arrays and {len(EVALUATE_CLUSTER_ARRAYS)} cluster arrays")
+    nodes = [np.ascontiguousarray(x, dtype=t).reshape(-1) for x, t in zip(node_arrays, _EVALUATE_NODE_TYPES)]
+    clusters = [np.ascontiguousarray(x, dtype=t).reshape(-1) for x, t in zip(cluster_arrays, _EVALUATE_CLUSTER_TYPES)]
+    if any(len(x) != n for x in nodes + clusters):
+        raise ValueError("every array of an evaluation has one entry per node")
+    medoid = clusters[4]
+    names = label == np.arange(n)
+    if n and ((medoid[names] < 0).any() or (medoid[names] >= n).any() or (label[medoid[names]] != np.flatnonzero(names)).any()):
+        raise ValueError("a cluster's medoid is no member of it")
+    return ScreenEvaluation(labels, label, score, *nodes, *clusters)
 
 
 def _labels_for(ids, labels, limit: int = MAX_GENOMES) -> List[str]:

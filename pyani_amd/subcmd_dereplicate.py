@@ -23,6 +23,16 @@ both, coverage >= min_coverage — min_ani does NOT filter, the tree needs the f
 the default cutoff 1 - min_ani.  Both defaults are the float64 results of those subtractions, unrounded (1 - 0.95 is
 0.050000000000000044).  A pair without a distance sits at 1.0, dRep's ANI 0.  `screen_linkage.tab` is added: one line per merge.
 
+evaluate=True adds dRep's EVALUATE step to either rule: for the clusters the run returns, every genome's centrality
+(its mean pair weight to the other members of its cluster, an absent pair counting 0), every cluster's medoid, weakest inside pair and
+whether it is a clique, and the cluster each cluster comes closest to (pyani_amd.screen.evaluate_of_pairs is the statement,
+Engine.screen_evaluate the kernels).  The list evaluated is the one the clusters come from: the greedy rule's own edges; with secondary=
+and exact=None the screen's kept pairs, weight = the shared sampled k-mers; with secondary= and exact="anim" the pairs that carry a
+distance, weight = floor(min(identity_ab, identity_ba) * 1e6) (exact_edges with min_ani = 0).  `screen_evaluation_genomes.tab` and
+`screen_evaluation_clusters.tab` are added.  winner="medoid" (implies evaluate) makes every cluster's medoid its representative — the
+member most central by the pair weights, ties to the greater score — where winner="score", the default, keeps the best-scored member;
+the clusters themselves do not change.  dRep's completeness and contamination terms are not computed: pass them through scores=.
+
 OUT OF SCOPE here: ANIb as the exact step, recovery, collective runs, linkage methods other than the two, and distances formed from the
 index's shared counts on the device.  Single-process: one engine, or several GPUs of this node (devices / workers).
 """
@@ -35,6 +45,7 @@ from . import _lib, files, screen as screen_mod
 from .engine import Engine, default_engine
 
 EXACT = (None, "anim")
+WINNERS = ("score", "medoid")
 LINKAGE_FILL = 1.0      # secondary=: the distance of a pair that carries none (ANI 0)
 
 
@@ -50,6 +61,23 @@ class DereplicateRun(NamedTuple):
 
     def representatives(self) -> List[str]:
         return self.clusters.representatives()
+
+    @property
+    def evaluation(self) -> Optional[screen_mod.ScreenEvaluation]:
+        """The evaluation of the clusters: None unless the run was asked for one (EvaluatedDereplicateRun)."""
+        return None
+
+
+class EvaluatedDereplicateRun(DereplicateRun):
+    """The DereplicateRun of evaluate=True / winner="medoid": the same eight fields, in the same order, and the ScreenEvaluation of the
+    clusters as the attribute `evaluation`.  The tuple itself is unchanged, so that whatever unpacks or compares a DereplicateRun
+    keeps working."""
+    evaluation = None
+
+    def __new__(cls, *fields, evaluation=None):
+        self = super().__new__(cls, *fields)
+        self.evaluation = evaluation
+        return self
 
 
 def read_scores(scores) -> Optional[Dict[str, float]]:
@@ -142,20 +170,26 @@ def screen_linkage_edges(screened) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
 
 def run_dereplicate(indir, outdir=None, screen=None, scores=None, exact: Optional[str] = None, min_ani: float = 0.95, min_coverage: float = 0.1,
                     write_output: bool = False, engine: Optional[Engine] = None, devices: Optional[List[int]] = None,
-                    workers: Optional[int] = None, secondary: Optional[str] = None, cutoff: Optional[float] = None) -> DereplicateRun:
+                    workers: Optional[int] = None, evaluate: bool = False, winner: str = "score", secondary: Optional[str] = None,
+                    cutoff: Optional[float] = None) -> DereplicateRun:
     """The greedy representatives of every FASTA file of `indir`.  screen: a ScreenOptions or a bare identity threshold (required: there
     is no default threshold).  scores: None (the sketch sizes: the larger assembly wins), a {stem: score} mapping or the path of a
     two-column TSV; finite and >= 0, greater is better, ties to the genome earlier in sorted-path order.  exact: None or "anim" (see the
     module's text; min_ani and min_coverage matter for "anim" only).  outdir is needed for write_output only; devices / workers: several
     GPUs of this node, ignored when `engine` is given.  secondary: None (the greedy rule), "average" or "complete" (linkage inside every
     component, see the module's text); cutoff: where its trees are cut, None = 1 - min_ani with exact="anim" and 1 - screen.min_identity
-    otherwise; it must lie in [0, 1).  Every ValueError is raised before any work is done."""
+    otherwise; it must lie in [0, 1).  evaluate: the clusters are evaluated too (DereplicateRun.evaluation, two more tables; see the
+    module's text); winner: "score" (every cluster's best-scored member represents it) or "medoid" (its medoid does; implies evaluate).
+    With both at their defaults nothing changes.  Every ValueError is raised before any work is done."""
     if screen is None:
         raise ValueError("run_dereplicate needs screen= (a ScreenOptions or an identity threshold)")
     if write_output and outdir is None:
         raise ValueError("write_output needs an output directory")
     if exact not in EXACT:
         raise ValueError(f"exact must be one of {EXACT}, not {exact!r}")
+    if winner not in WINNERS:
+        raise ValueError(f"winner must be one of {WINNERS}, not {winner!r}")
+    evaluate = bool(evaluate) or winner == "medoid"
     screen = screen_mod.check_options(screen)
     if secondary is None:
         if cutoff is not None:
@@ -175,13 +209,26 @@ def run_dereplicate(indir, outdir=None, screen=None, scores=None, exact: Optiona
         engine = multi.engine_for(devices, workers)
         own = engine if isinstance(engine, multi.MultiEngine) else None
     try:
-        return _run(paths, stems, outdir, screen, given, exact, float(min_ani), float(min_coverage), write_output, engine or default_engine(), secondary, cutoff)
+        return _run(paths, stems, outdir, screen, given, exact, float(min_ani), float(min_coverage), write_output, engine or default_engine(), secondary, cutoff,
+                    evaluate, winner)
     finally:
         if own is not None:
             own.close()
 
 
-def _run(paths, stems, outdir, screen, given, exact, min_ani, min_coverage, write_output, eng, secondary=None, cutoff=None) -> DereplicateRun:
+def evaluated_edges(screened, edges, recs, length, exact, min_coverage, secondary) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(a, b, weight) of the list an evaluation reads: the greedy rule's own edges; under secondary= the screen's kept pairs with weight =
+    shared (exact=None), or the pairs that carry a distance with weight = floor(min of the two identities * 1e6) (exact="anim":
+    exact_edges without an identity threshold)."""
+    if secondary is None:
+        return edges
+    if exact == "anim":
+        return exact_edges(screened.a, screened.b, recs, length, 0.0, min_coverage)
+    return screened.a, screened.b, screened.shared
+
+
+def _run(paths, stems, outdir, screen, given, exact, min_ani, min_coverage, write_output, eng, secondary=None, cutoff=None, evaluate=False,
+         winner="score") -> DereplicateRun:
     genome_ids = {s: k + 1 for k, s in enumerate(stems)}
     scratch_store = eng.genome_count() == 0
     lengths: Dict[str, int] = {}
@@ -204,7 +251,7 @@ def _run(paths, stems, outdir, screen, given, exact, min_ani, min_coverage, writ
                 edges = linkage_edges(screened.a, screened.b, recs, [lengths[s] for s in stems], min_coverage)
         elif secondary is not None:
             edges = screen_linkage_edges(screened)
-        nodes = None
+        nodes = measured = None
         try:
             if n and secondary is None:
                 rep, via = eng.screen_representatives(*edges, n=n, score=score)
@@ -213,11 +260,16 @@ def _run(paths, stems, outdir, screen, given, exact, min_ani, min_coverage, writ
             else:
                 rep, via = np.zeros(0, np.int32), np.zeros(0, np.uint32)
                 nodes = (rep, rep, rep, np.zeros((0, 4))) if secondary is not None else None
+            if evaluate and n:
+                measured = eng.screen_evaluate(*evaluated_edges(screened, edges, recs, [lengths[s] for s in stems], exact, min_coverage, secondary), n=n,
+                                               label=rep if secondary is None else nodes[2], score=score)
         finally:
             if secondary is None:
                 eng.screen_representatives_release()
             else:
                 eng.screen_linkage_release()
+            if evaluate:
+                eng.screen_evaluate_release()
     finally:
         if scratch_store:
             eng.clear_genomes()
@@ -227,6 +279,13 @@ def _run(paths, stems, outdir, screen, given, exact, min_ani, min_coverage, writ
     else:
         linkage = screen_mod.linkage_from_nodes(stems, *nodes[:3], score, nodes[3], secondary, cutoff, LINKAGE_FILL)
         clusters = linkage.clusters()
+    evaluation = None
+    if evaluate:
+        if measured is None:
+            measured = ([np.zeros(0)] * 7, [np.zeros(0)] * 7)
+        evaluation = screen_mod.evaluation_from_nodes(stems, clusters.rep, score, *measured)
+        if winner == "medoid":
+            clusters = evaluation.recentred()
     written: List[Path] = []
     if write_output:
         from .subcmd_screen import tab_path, write_pairs_tab
@@ -236,7 +295,28 @@ def _run(paths, stems, outdir, screen, given, exact, min_ani, min_coverage, writ
         if linkage is not None:
             written.append(tab_path(outdir, "linkage"))
             write_linkage_tab(written[3], linkage)
-    return DereplicateRun(genome_ids, lengths, screened, recs, edges, clusters, written, linkage)
+        if evaluation is not None:
+            written += [tab_path(outdir, "evaluation_genomes"), tab_path(outdir, "evaluation_clusters")]
+            write_evaluation_tabs(written[-2], written[-1], evaluation)
+    run = DereplicateRun(genome_ids, lengths, screened, recs, edges, clusters, written, linkage)
+    return run if evaluation is None else EvaluatedDereplicateRun(*run, evaluation=evaluation)
+
+
+def write_evaluation_tabs(genomes_path, clusters_path, evaluation) -> None:
+    """`screen_evaluation_genomes.tab` (ScreenEvaluation.genome_frame) and `screen_evaluation_clusters.tab` (.cluster_frame); the floats
+    with repr's precision, so that float(text) gives the bits back."""
+    for path, t in ((genomes_path, evaluation.genome_frame()), (clusters_path, evaluation.cluster_frame())):
+        floats = [c for c in t.columns if t[c].dtype == np.float64]
+        t = t.astype({c: object for c in floats})
+        for c in floats:
+            t[c] = [repr(float(x)) for x in t[c]]
+        t.to_csv(path, index=False, sep="\t")
+
+
+def read_evaluation_tab(path):
+    """A table of write_evaluation_tabs as a DataFrame (names as text, an absent name as ""; the floats parsed to the bits written)."""
+    import pandas as pd
+    return pd.read_csv(path, sep="\t", keep_default_na=False, float_precision="round_trip")
 
 
 def write_linkage_tab(path, linkage) -> None:
