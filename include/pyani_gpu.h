@@ -846,6 +846,49 @@ int pg_screen_gather_abund_read(pg_ctx* ctx, uint64_t* sum_out, uint64_t* sumsq_
 int pg_screen_gather_abund_matched(pg_ctx* ctx, uint64_t* matched_weight_out);
 int pg_screen_gather_abund_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
 
+/* ---- screen, the profile: core, private and marker k-mers of every cluster.  Over the resident search index — n genomes,
+ * D k-mers, E entries, H(d) the holders of k-mer d and h(d) = |H(d)| >= 1 — and a partition label int32[n] in the convention of
+ * pg_screen_evaluate (label[label[v]] == label[v]; a cluster is named by the node c = label[v]; size[c] its members), with two thresholds
+ * per cluster, read at naming nodes only: 1 <= shell_need[c] <= core_need[c] <= size[c].
+ * A CELL is a pair (d, c) with occ(d, c) = |H(d) & c| > 0.  It is core iff occ == size[c]; soft iff occ >= core_need[c]; shell iff
+ * shell_need[c] <= occ < core_need[c]; private iff occ == h(d) (no holder outside c); a marker iff private and soft.
+ * Per cluster, n entries indexed by the naming node, 0 where label[c] != c: size uint32; kmers, core, soft, shell, private, marker
+ * uint64, the cluster's cells of each kind (kmers: all of them).
+ * Spectrum, uint64[n]: with the clusters in ascending order of their naming nodes and off the exclusive prefix sum of their sizes,
+ * spectrum[off[c] + occ - 1] = the cells of c with that occ: a cluster's words add up to kmers[c], the last of them is core[c].
+ * Per genome v of cluster c, uint32[n]: held = |S(v)|; core_held = its k-mers whose cell in c is soft; private_held = those whose cell in
+ * c is private; alone = those with occ(d, c) == 1; foreign = those of alone with h(d) > 1 (shared with other clusters only).
+ * Marker list: the marker cells of the clusters with size >= marker_min_size, as (cluster int32, the k-mer's value uint32, occ uint32),
+ * by ascending cluster, then by the k-mer's position in the index.  marker[c] counts every cluster whatever marker_min_size is.
+ * Integers only, equal to a statement (pyani_amd.screen.profile_of_index); nothing depends on a schedule, a tier, a batch or the index's
+ * cut into slices.  The k-mers go three ways by h(d): up to lane_limit holders one thread each, up to wave_limit one wave each, the others
+ * through a radix sort of (k-mer, cluster, member) keys in batches of at most batch_keys entries cut at k-mer boundaries (a larger k-mer
+ * is a batch of its own); pg_screen_search_profile_set: lane_limit 0 ... 8, wave_limit 0 ... 64 (a wave limit below the lane limit counts
+ * as the lane limit), either PG_SCREEN_PROFILE_DEFAULT; batch_keys 0: the budget of pg_screen_set_budget.  PG_E_ARG beyond those.
+ * pg_screen_search_profile: *n_markers_out = the entries of the list (may be NULL).  PG_E_ARG, before anything is replaced: no resident
+ * search index; n outside 1 ... 2^20 or not the index's; a NULL array; a label outside [0, n) or one that does not name itself (the message names the first such
+ * node); a naming node whose thresholds break the inequality (sizes come from label; the message names the node); marker_min_size == 0.
+ * The result is a resident state of its own until the next ACCEPTED profile (an allocation that fails replaces nothing),
+ * pg_screen_search_profile_release (PG_OK when there is none) or pg_destroy; it reads nothing of the genome store and survives
+ * pg_clear_genomes, as the index does.  The call reads the index and changes nothing else: the index, the counted rectangle, the selection
+ * and the gather's state stay exactly as they were.
+ * pg_screen_search_profile_read copies the five genome arrays out, _read_clusters the seven cluster arrays, _read_spectrum the spectrum
+ * (n entries each), _read_markers the list's three columns; any pointer may be NULL (that array is skipped); PG_E_ARG without a profile.
+ * pg_screen_search_profile_last: counts_out[10] = n, clusters, D, E, cells, k-mers of the lane tier, of the wave tier, of the sorted tier,
+ * batches of the sorted tier, markers listed; ms_out[5] = relabel, lane tier, wave tier (with its selection), sorted tier (selection, keys,
+ * sort, runs, entries), markers milliseconds (HIP events; no pair spans a host synchronisation); all 0 when nothing is resident. */
+#define PG_SCREEN_PROFILE_DEFAULT 0xFFFFFFFFu
+int pg_screen_search_profile(pg_ctx* ctx, const int32_t* label, const uint32_t* core_need, const uint32_t* shell_need, uint32_t n, uint32_t marker_min_size,
+                             uint64_t* n_markers_out);
+int pg_screen_search_profile_read(pg_ctx* ctx, uint32_t* held_out, uint32_t* core_held_out, uint32_t* private_held_out, uint32_t* alone_out, uint32_t* foreign_out);
+int pg_screen_search_profile_read_clusters(pg_ctx* ctx, uint32_t* size_out, uint64_t* kmers_out, uint64_t* core_out, uint64_t* soft_out, uint64_t* shell_out,
+                                           uint64_t* private_out, uint64_t* marker_out);
+int pg_screen_search_profile_read_spectrum(pg_ctx* ctx, uint64_t* spectrum_out);
+int pg_screen_search_profile_read_markers(pg_ctx* ctx, int32_t* cluster_out, uint32_t* kmer_out, uint32_t* occ_out);
+int pg_screen_search_profile_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
+int pg_screen_search_profile_release(pg_ctx* ctx);
+int pg_screen_search_profile_set(pg_ctx* ctx, uint32_t lane_limit, uint32_t wave_limit, uint64_t batch_keys);
+
 /* ---- classify: clique sweep over identity thresholds ------------------------------------------------------------------
  * The compute of `pyani classify`.  These calls read caller matrices only: they touch no genome, seed list or ANIm worker slot, so
  * they need no interlock with the pg_anim_pairs_enqueue / _fetch lanes and may run while enqueued ANIm calls are in flight (own

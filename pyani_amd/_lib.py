@@ -25,6 +25,7 @@ PG_E_CAPACITY, PG_ANIM_NO_ALIGNMENT = -9, 1
 PG_E_NONFINITE = -11
 PG_CLUSTER_COMPLETE, PG_CLUSTER_AVERAGE = 0, 1
 PG_SCREEN_LINKAGE_DEFAULT = 0xFFFFFFFF
+PG_SCREEN_PROFILE_DEFAULT = 0xFFFFFFFF
 K_TETRA_COUNT, K_TETRA_FINALIZE, K_TETRA_STATS, K_TETRA_PAIRS = 0, 1, 2, 3
 (K_ANIM_SEED, K_ANIM_HIT, K_ANIM_CLUSTER, K_ANIM_GAPS, K_ANIM_EXTLANE, K_ANIM_EXTEND, K_ANIM_FINISH) = 4, 5, 6, 7, 8, 9, 10
 K_ANIB_BUCKET, K_ANIB_FRAG = 11, 12
@@ -160,6 +161,14 @@ SIGNATURES = {
     "pg_screen_gather_abund_read": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "pg_screen_gather_abund_matched": (_int, [_vp, _vp]),
     "pg_screen_gather_abund_last": (_int, [_vp, _vp, _vp]),
+    "pg_screen_search_profile": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _P(_u64)]),
+    "pg_screen_search_profile_read": (_int, [_vp] * 6),
+    "pg_screen_search_profile_read_clusters": (_int, [_vp] * 8),
+    "pg_screen_search_profile_read_spectrum": (_int, [_vp, _vp]),
+    "pg_screen_search_profile_read_markers": (_int, [_vp] * 4),
+    "pg_screen_search_profile_last": (_int, [_vp, _vp, _vp]),
+    "pg_screen_search_profile_release": (_int, [_vp]),
+    "pg_screen_search_profile_set": (_int, [_vp, _u32, _u32, _u64]),
     "pg_classify_edges": (_int, [_vp, _vp, _vp, _u32, ctypes.c_double, ctypes.c_double, _P(_u64), _P(_u32)]),
     "pg_classify_edge_identities": (_int, [_vp, _vp, _u64]),
     "pg_classify_sweep": (_int, [_vp, _vp, _u64, _vp, _vp, _vp]),

@@ -360,6 +360,7 @@ void pg_destroy(pg_ctx* ctx) {
   pg_screen_sweep_drop(ctx);
   pg_screen_linkage_drop(ctx);
   pg_screen_evaluate_drop(ctx);
+  pg_screen_profile_drop(ctx);
   pg_screen_search_drop(ctx);
   prof_drain(ctx);
   delete ctx;                // the buffers and the streams go here, on the context's device

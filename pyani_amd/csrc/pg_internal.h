@@ -77,6 +77,12 @@ struct PgScreenEvaluateStats {      // pg_screen_evaluate_last: the resident eva
   double select_ms = 0.0, sort_ms = 0.0, pair_ms = 0.0, node_ms = 0.0;                    // band count + select (index path), canonicalise + sort + reduce, pair passes, node passes
 };
 
+struct PgScreenProfileStats {      // pg_screen_search_profile_last: the resident profile's call
+  uint64_t nodes = 0, clusters = 0, kmers = 0, entries = 0, cells = 0;                     // n, clusters, D, E of the index, cells counted
+  uint64_t lane_kmers = 0, wave_kmers = 0, sorted_kmers = 0, batches = 0, markers = 0;     // k-mers per tier, batches of the sorted tier, markers listed
+  double relabel_ms = 0.0, lane_ms = 0.0, wave_ms = 0.0, sorted_ms = 0.0, marker_ms = 0.0;
+};
+
 struct PgScreenSearchStats {
   uint64_t keys = 0, kmers = 0, entries = 0, slices = 0, index_bytes = 0;                // the search index: sampled keys, distinct k-mers, (k-mer, genome) entries, device bytes its buffers hold
   uint64_t query_keys = 0, lookups = 0, matched = 0, increments = 0, query_slices = 0;   // the latest count: lookups = the distinct k-mers of the queries
@@ -184,6 +190,10 @@ struct pg_ctx {
   uint64_t screen_linkage_work = 0;                 // ... and the bytes of working matrices of one batch (0: the default)
   void* screen_evaluate_state = nullptr;      // resident evaluation of the latest pg_screen_evaluate / pg_screen_index_evaluate (pg_screen.hip); independent of the six above
   PgScreenEvaluateStats screen_evaluate_stats;      // pg_screen_evaluate_last: the resident evaluation's call
+  void* screen_profile_state = nullptr;      // resident profile of the latest pg_screen_search_profile (pg_screen.hip); independent of the seven above and of the genome store
+  PgScreenProfileStats screen_profile_stats;      // pg_screen_search_profile_last: the resident profile's call
+  uint32_t screen_profile_lane = 0xFFFFFFFFu, screen_profile_wave = 0xFFFFFFFFu;      // pg_screen_search_profile_set: the tiers' limits (PG_SCREEN_PROFILE_DEFAULT: the defaults, pgscr_profile.inc)
+  uint64_t screen_profile_batch = 0;                                                  // ... and the entries of one sorted batch (0: the budget of pg_screen_set_budget)
   void* screen_search_state = nullptr;          // resident search index of pg_screen_search_index and the latest rectangle counted against it (pg_screen.hip); independent of the three above and of the genome store
   PgScreenGatherStats screen_gather_stats;      // pg_screen_gather_last
   PgScreenGatherAbundStats screen_gather_abund_stats;      // pg_screen_gather_abund_last
@@ -311,6 +321,7 @@ void pg_screen_representatives_drop(pg_ctx* ctx); // ... the screen's resident r
 void pg_screen_sweep_drop(pg_ctx* ctx); // ... the screen's resident sweep (pg_screen.hip): the same
 void pg_screen_linkage_drop(pg_ctx* ctx); // ... the screen's resident linkage (pg_screen.hip): the same
 void pg_screen_evaluate_drop(pg_ctx* ctx); // ... the screen's resident evaluation (pg_screen.hip): the same
+void pg_screen_profile_drop(pg_ctx* ctx); // ... the screen's resident profile (pg_screen.hip): with the context or on request — NOT with the genome store, as the search index
 void pg_screen_index_drop(pg_ctx* ctx); // ... the screen's resident k-mer index and its selection (pg_screen.hip): with the context, the genome store or on request
 void pg_screen_search_drop(pg_ctx* ctx); // ... the screen's resident search index and rectangle (pg_screen.hip): with the context or on request — NOT with the genome store: it names genomes by call index only
 int pg_anib_reduce_run(pg_ctx* ctx, uint32_t n_pairs, const uint64_t* offsets, const uint32_t* n_frags, const int32_t* frag,

@@ -107,6 +107,11 @@
 // host: one radix sort and one reduce-by-key give the distinct pairs) and pg_screen_index_evaluate (the list the representatives' index
 // entry appends) reduce the pairs per node and per cluster — inside sums and minima, the nearest outside node and cluster by 64-bit atomic
 // maxima, the medoid in two node passes; E1 ... E7 stand there with their state.
+//
+// pgscr_profile.inc — the PROFILE: what the genomes of a cluster share.  pg_screen_search_profile reads the resident search
+// index under a partition: every (k-mer, cluster) cell with its occupancy is core, soft, shell, private or a marker; the cells are counted per
+// cluster with their spectrum, the entries per genome, and the marker cells listed.  The k-mers go three ways by their holders — a thread, a
+// wave, or one radix sort of (k-mer, cluster, member) keys in batches — into one accounting body; F1 ... F8 stand there with their state.
 #include <algorithm>
 #include <hipcub/hipcub.hpp>
 #include <memory>
@@ -119,9 +124,9 @@
 
 namespace {
 
-// the stages whose milliseconds pg_screen_last, pg_screen_index_last, pg_screen_components_last, pg_screen_representatives_last, pg_screen_sweep_last, pg_screen_linkage_last, pg_screen_evaluate_last, pg_screen_search_last,
+// the stages whose milliseconds pg_screen_last, pg_screen_index_last, pg_screen_components_last, pg_screen_representatives_last, pg_screen_sweep_last, pg_screen_linkage_last, pg_screen_evaluate_last, pg_screen_search_profile_last, pg_screen_search_last,
 // pg_screen_search_add_last, pg_screen_search_remove_last and pg_screen_gather_last report
-enum ScreenStage { ST_SCAN, ST_GROUP, ST_COUNT, ST_SELECT, ST_HOOK, ST_FLATTEN, ST_LOOKUP, ST_EXPAND, ST_ARGMAX, ST_CLAIM, ST_MERGE, ST_CHECK, ST_MARK, ST_COMPACT, ST_WEIGHT, ST_ATTRIBUTE, ST_SORT, ST_STATS, ST_ROUNDS, ST_ASSIGN, ST_CENSUS, ST_FILL, ST_SMALL, ST_LARGE, ST_CUT };
+enum ScreenStage { ST_SCAN, ST_GROUP, ST_COUNT, ST_SELECT, ST_HOOK, ST_FLATTEN, ST_LOOKUP, ST_EXPAND, ST_ARGMAX, ST_CLAIM, ST_MERGE, ST_CHECK, ST_MARK, ST_COMPACT, ST_WEIGHT, ST_ATTRIBUTE, ST_SORT, ST_STATS, ST_ROUNDS, ST_ASSIGN, ST_CENSUS, ST_FILL, ST_SMALL, ST_LARGE, ST_CUT, ST_RELABEL, ST_LANE, ST_WAVE, ST_SORTED, ST_MARKERS };
 
 struct ScreenEvents {      // event pairs on the context's stream, summed per stage after the call's last synchronisation
   std::vector<hipEvent_t> ev;
@@ -182,3 +187,4 @@ hipError_t tmp_room(size_t& tmp_bytes, Query query) {
 #include "pgscr_store.inc"
 #include "pgscr_gather.inc"
 #include "pgscr_abund.inc"
+#include "pgscr_profile.inc"

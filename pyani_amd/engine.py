@@ -1081,6 +1081,65 @@ class Engine:
         self._check(self.lib.pg_screen_search_index_release(self._h))
         self._search, self._search_q = None, 0
 
+    # the profile: core, private and marker k-mers of every cluster of a partition, read off the resident search index
+    def screen_search_profile(self, label, core: float = 0.95, shell: float = 0.15, marker_min_size: int = 2, thresholds=None):
+        """pg_screen_search_profile + the four reads: the pyani_amd.screen.ScreenProfile of the resident search index under the partition
+        label int32[n] (screen.check_partition: e.g. the rep of screen_dereplicate over the indexed genomes), as
+        pyani_amd.screen.profile_of_index states it.  The thresholds are screen.profile_thresholds(size, core, shell), or thresholds =
+        (core_need, shell_need), two integer arrays read at naming nodes.  ValueError as the statement's, before the library is called.
+        The index, the counted rectangle, the selection and the gather's state stay as they were; the result stays resident until the
+        next profile, screen_search_profile_release or close, and survives clear_genomes.  The counts are screen_search_profile_last()."""
+        from . import screen
+        info = getattr(self, "_search", None)
+        if not info:
+            raise ValueError("no search index on this engine (call screen_search_index first)")
+        n = info["n"]
+        lab = screen.check_partition(label, n)
+        if thresholds is None:
+            core_need, shell_need = screen.profile_thresholds(np.bincount(lab, minlength=n), core, shell)
+        else:
+            core_need, shell_need = thresholds
+        _, core_need, shell_need = screen.check_profile_thresholds(lab, core_need, shell_need)
+        if isinstance(marker_min_size, (bool, float)) or not 1 <= int(marker_min_size) < (1 << 32):
+            raise ValueError(f"marker_min_size is an integer >= 1, not {marker_min_size!r}")
+        lab32 = np.ascontiguousarray(lab, dtype=np.int32)
+        m = ctypes.c_uint64(0)
+        self._check(self.lib.pg_screen_search_profile(self._h, lab32.ctypes.data, core_need.ctypes.data, shell_need.ctypes.data, n, int(marker_min_size), ctypes.byref(m)))
+        genomes, clusters, spectrum, markers = self._screen_search_profile_read(n, int(m.value))
+        return screen.profile_from_arrays(info["labels"], lab32, core_need, shell_need, int(marker_min_size), genomes, clusters, spectrum, markers, kmer=info["kmer"])
+
+    def _screen_search_profile_read(self, n: int, m: int):
+        from . import screen
+        genomes = [np.zeros(n, dtype=t) for t in screen._PROFILE_GENOME_TYPES]
+        clusters = [np.zeros(n, dtype=t) for t in screen._PROFILE_CLUSTER_TYPES]
+        spectrum = np.zeros(n, dtype=np.uint64)
+        markers = [np.zeros(m, dtype=t) for t in screen._PROFILE_MARKER_TYPES]
+        self._check(self.lib.pg_screen_search_profile_read(self._h, *(x.ctypes.data for x in genomes)))
+        self._check(self.lib.pg_screen_search_profile_read_clusters(self._h, *(x.ctypes.data for x in clusters)))
+        self._check(self.lib.pg_screen_search_profile_read_spectrum(self._h, spectrum.ctypes.data))
+        self._check(self.lib.pg_screen_search_profile_read_markers(self._h, *(x.ctypes.data if m else None for x in markers)))
+        return tuple(genomes), tuple(clusters), spectrum, tuple(markers)
+
+    def screen_search_profile_last(self) -> dict:
+        """pg_screen_search_profile_last: counts and stage milliseconds of the resident profile (all 0 when there is none)."""
+        c = (ctypes.c_uint64 * 10)()
+        ms = (ctypes.c_double * 5)()
+        self._check(self.lib.pg_screen_search_profile_last(self._h, ctypes.addressof(c), ctypes.addressof(ms)))
+        return {"n": int(c[0]), "clusters": int(c[1]), "kmers": int(c[2]), "entries": int(c[3]), "cells": int(c[4]), "lane_kmers": int(c[5]),
+                "wave_kmers": int(c[6]), "sorted_kmers": int(c[7]), "sorted_batches": int(c[8]), "markers": int(c[9]),
+                "relabel_ms": float(ms[0]), "lane_ms": float(ms[1]), "wave_ms": float(ms[2]), "sorted_ms": float(ms[3]), "marker_ms": float(ms[4])}
+
+    def screen_search_profile_release(self) -> None:
+        self._check(self.lib.pg_screen_search_profile_release(self._h))
+
+    def screen_search_profile_set(self, lane_limit: Optional[int] = None, wave_limit: Optional[int] = None, batch_keys: int = 0) -> None:
+        """pg_screen_search_profile_set: k-mers of up to lane_limit holders (0 ... 8) go one per thread, up to wave_limit (0 ... 64) one per
+        wave, the others through the sorted tier in batches of at most batch_keys entries (0: the budget of screen_set_budget).  None:
+        the default.  The result of a profile does not depend on any of them."""
+        default = _lib.PG_SCREEN_PROFILE_DEFAULT
+        self._check(self.lib.pg_screen_search_profile_set(self._h, default if lane_limit is None else int(lane_limit), default if wave_limit is None else int(wave_limit),
+                                                          int(batch_keys)))
+
     def screen_search(self, query_ids, options, query_labels=None):
         """The db genomes each of the resident genomes `query_ids` is related to (pyani_amd.screen.SearchHits; options: a ScreenOptions
         with the index's kmer and scale, or a bare identity threshold for an index of the defaults): chunks of band_rows queries are

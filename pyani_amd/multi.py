@@ -382,6 +382,20 @@ class MultiEngine:
     def screen_search_index_remove(self, which):
         raise ValueError("a search index dealt over several devices cannot be shrunk: remove on a single Engine")
 
+    # the profile is a single Engine's for the same reason: every engine holds a range of the columns, and the occupancy of a
+    # (k-mer, cluster) cell is a count over ALL of a cluster's columns
+    def screen_search_profile(self, label, core: float = 0.95, shell: float = 0.15, marker_min_size: int = 2, thresholds=None):
+        raise ValueError("a search index dealt over several devices cannot be profiled: build it on a single Engine")
+
+    def screen_search_profile_last(self):
+        raise ValueError("a search index dealt over several devices cannot be profiled: there is no profile to report on; use a single Engine")
+
+    def screen_search_profile_release(self):
+        raise ValueError("a search index dealt over several devices cannot be profiled: there is no profile to release; use a single Engine")
+
+    def screen_search_profile_set(self, lane_limit=None, wave_limit=None, batch_keys: int = 0):
+        raise ValueError("a search index dealt over several devices cannot be profiled: set the tiers on a single Engine")
+
     def screen_components(self, a, b, shared=None, n: int = 0):
         """Engine.screen_components on the first engine (a list call has nothing to divide)."""
         return self.engines[0].screen_components(a, b, shared, n=n)

@@ -1195,6 +1195,261 @@ def evaluation_from_nodes(labels, label, score, node_arrays, cluster_arrays) -> 
     return ScreenEvaluation(labels, label, score, *nodes, *clusters)
 
 
+# ---- the profile of a partition over the search index ----------------------------------------------------------------------
+PROFILE_GENOME_ARRAYS = ("held", "core_held", "private_held", "alone", "foreign")
+PROFILE_CLUSTER_ARRAYS = ("size", "kmers", "core", "soft", "shell", "private", "marker")
+PROFILE_MARKER_ARRAYS = ("marker_cluster", "marker_kmer", "marker_occ")
+_PROFILE_GENOME_TYPES = (np.uint32,) * 5
+_PROFILE_CLUSTER_TYPES = (np.uint32,) + (np.uint64,) * 6
+_PROFILE_MARKER_TYPES = (np.int32, np.uint32, np.uint32)
+PROFILE_LANE_MAX, PROFILE_WAVE_MAX = 8, 64      # Engine.screen_search_profile_set: the largest settable tier limits
+
+
+def profile_thresholds(size, core: float = 0.95, shell: float = 0.15) -> Tuple[np.ndarray, np.ndarray]:
+    """(core_need, shell_need) uint32 per entry of `size`: max(1, ceil(fraction * size)), computed exactly from the rational value of the
+    float (fractions.Fraction), never in floating point; 0 where size is 0 (a node that names no cluster).  ValueError unless
+    0 < shell <= core <= 1."""
+    from fractions import Fraction
+    try:
+        ok = 0 < shell <= core <= 1
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError(f"the profile's fractions must satisfy 0 < shell <= core <= 1, not shell={shell!r}, core={core!r}")
+    size = np.ascontiguousarray(size, dtype=np.int64).reshape(-1)
+    if (size < 0).any():
+        raise ValueError("a cluster's size is not negative")
+    distinct, where = np.unique(size, return_inverse=True)
+    out = []
+    for fraction in (Fraction(core), Fraction(shell)):
+        p, q = fraction.numerator, fraction.denominator
+        need = [max(1, -((-p * s) // q)) if s else 0 for s in distinct.tolist()]      # (Python integers: exact at any size)
+        out.append(np.array(need, dtype=np.uint32)[where.reshape(-1)])
+    return out[0], out[1]
+
+
+def check_profile_thresholds(label, core_need, shell_need) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(size, core_need, shell_need) uint32[n] of a partition (check_partition) with its thresholds: size[c] the members of the cluster that
+    node c names, 0 elsewhere; ValueError names the first naming node with other than 1 <= shell_need <= core_need <= size."""
+    n = len(label)
+    size = np.bincount(label, minlength=n).astype(np.uint32)
+    try:
+        need = [np.ascontiguousarray(x).reshape(-1) for x in (core_need, shell_need)]
+    except (TypeError, ValueError) as err:
+        raise ValueError(f"thresholds must be integers: {err}") from None
+    if any(len(x) != n for x in need) or any(x.dtype.kind not in "iu" for x in need):
+        raise ValueError(f"{n} nodes need {n} integer core_need and shell_need each")
+    c64, s64 = (x.astype(np.int64) for x in need)
+    bad = (size > 0) & ((s64 < 1) | (s64 > c64) | (c64 > size))
+    if bad.any():
+        c = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"node {c} names a cluster of {int(size[c])} with the thresholds {int(s64[c])} and {int(c64[c])} (1 <= shell_need <= core_need <= size)")
+    names = size > 0
+    return size, np.where(names, c64, 0).astype(np.uint32), np.where(names, s64, 0).astype(np.uint32)
+
+
+def profile_of_index(kmer, start, member, n, label, core_need, shell_need, marker_min_size: int = 2):
+    """THE STATEMENT of the profile (the host's; Engine.screen_search_profile is held to it), over the arrays of an exported search index
+    (kmer uint32[D], start uint64[D + 1], member uint32[E]: k-mer d is held by H(d) = member[start[d]:start[d + 1]], h(d) = |H(d)| >= 1), a
+    partition label (check_partition) and two thresholds per naming node, 1 <= shell_need[c] <= core_need[c] <= size[c].
+
+    A CELL is a pair (d, c) with occ = |H(d) & c| > 0.  It is core iff occ == size[c], soft iff occ >= core_need[c], shell iff
+    shell_need[c] <= occ < core_need[c], private iff occ == h(d), a marker iff private and soft.  Returns (genome arrays, cluster arrays,
+    spectrum, off, marker arrays):
+
+        per genome v of cluster c, uint32[n] (PROFILE_GENOME_ARRAYS): held = its k-mers; core_held = those whose cell in c is soft;
+            private_held = those whose cell in c is private; alone = those with occ == 1; foreign = those of alone with h(d) > 1
+        per cluster, length n by naming node, 0 elsewhere (PROFILE_CLUSTER_ARRAYS): size uint32; kmers, core, soft, shell, private, marker
+            uint64, its cells of each kind (kmers: all)
+        spectrum uint64[n], off int64[n]: off[c] = the members of the clusters with a smaller naming node (0 where c names none);
+            spectrum[off[c] + occ - 1] = the cells of c with that occ
+        markers (PROFILE_MARKER_ARRAYS): the marker cells of the clusters with size >= marker_min_size as (cluster int32, the k-mer's
+            value uint32, occ uint32), by ascending cluster, then by the k-mer's position in the index
+
+    One lexsort of the entries by (k-mer position, cluster), then runs.  Integers only."""
+    n = int(n)
+    label = check_partition(label, n)
+    size, core_need, shell_need = check_profile_thresholds(label, core_need, shell_need)
+    if isinstance(marker_min_size, (bool, float)) or int(marker_min_size) < 1:
+        raise ValueError(f"marker_min_size is an integer >= 1, not {marker_min_size!r}")
+    kmer = np.ascontiguousarray(kmer, dtype=np.uint32).reshape(-1)
+    start = np.ascontiguousarray(start, dtype=np.uint64).reshape(-1).astype(np.int64)
+    member = np.ascontiguousarray(member, dtype=np.uint32).reshape(-1).astype(np.int64)
+    d, e = len(kmer), len(member)
+    if len(start) != d + 1 or start[0] != 0 or start[-1] != e or (np.diff(start) < 1).any() or (e and member.max() >= n):
+        raise ValueError("the arrays are not those of a search index over n genomes")
+    names = size > 0
+    off = np.where(names, np.cumsum(np.where(names, size, 0).astype(np.int64)) - size, 0).astype(np.int64)
+    h = np.diff(start)
+    pos = np.repeat(np.arange(d, dtype=np.int64), h)              # the k-mer of every entry
+    cl = label[member]
+    by = np.lexsort((cl, pos))
+    pos_s, cl_s, mem_s = pos[by], cl[by], member[by]
+    head = np.ones(e, dtype=bool)
+    head[1:] = (pos_s[1:] != pos_s[:-1]) | (cl_s[1:] != cl_s[:-1])
+    first = np.flatnonzero(head)
+    occ = np.diff(np.append(first, e))                            # per cell
+    cd, cc = pos_s[first], cl_s[first]
+    ch = h[cd]
+    core = occ == size[cc]
+    soft = occ >= core_need[cc]
+    shell = ~soft & (occ >= shell_need[cc])
+    private = occ == ch
+    marker = private & soft
+
+    def per_cluster(mask):
+        return np.bincount(cc[mask], minlength=n).astype(np.uint64)
+
+    every = np.ones(len(cc), dtype=bool)
+    clusters = (size, per_cluster(every), per_cluster(core), per_cluster(soft), per_cluster(shell), per_cluster(private), per_cluster(marker))
+    spectrum = np.bincount(off[cc] + occ - 1, minlength=n).astype(np.uint64)
+    cell = np.cumsum(head) - 1                                    # the cell of every sorted entry
+    e_occ, e_h = occ[cell], ch[cell]
+
+    def per_genome(mask):
+        return np.bincount(mem_s[mask], minlength=n).astype(np.uint32)
+
+    genomes = (per_genome(np.ones(e, dtype=bool)), per_genome(soft[cell]), per_genome(private[cell]), per_genome(e_occ == 1), per_genome((e_occ == 1) & (e_h > 1)))
+    listed = np.flatnonzero(marker & (size[cc] >= int(marker_min_size)))
+    listed = listed[np.lexsort((cd[listed], cc[listed]))]
+    markers = (cc[listed].astype(np.int32), kmer[cd[listed]], occ[listed].astype(np.uint32))
+    return genomes, clusters, spectrum, off, markers
+
+
+_KMER_BASES = np.frombuffer(b"ACGT", dtype=np.uint8)
+
+
+def kmer_string(value, k: int) -> str:
+    """The canonical k-mer `value` as ACGT text in the scan's own 2-bit code: A, C, G, T = 0, 1, 2, 3, the first base in the high bits of
+    the 2 k bit word."""
+    k, value = int(k), int(value)
+    if not 1 <= k <= 16 or not 0 <= value < 4 ** k:
+        raise ValueError(f"a {k}-mer's value is below 4^{k} (k <= 16), not {value}")
+    return "".join("ACGT"[(value >> (2 * (k - 1 - i))) & 3] for i in range(k))
+
+
+class ScreenProfile(NamedTuple):
+    """What the genomes of every cluster share, over the genomes `labels` (None: the nodes go by their index): the partition and its
+    thresholds as they were given, then the arrays of profile_of_index.  Built by profile_from_arrays; clusters are numbered by ascending
+    naming node.  Every count is of SAMPLED k-mers: at scale s it estimates 1 / s of the count over all k-mers (scale 1: all of them)."""
+    labels: Optional[List[str]]
+    kmer: int                      # the index's k, for markers_frame's text (0: unknown, values are printed as numbers)
+    label: np.ndarray              # int32[n]
+    core_need: np.ndarray          # uint32[n], by naming node, 0 elsewhere
+    shell_need: np.ndarray         # uint32[n]
+    marker_min_size: int
+    held: np.ndarray               # uint32[n]
+    core_held: np.ndarray          # uint32[n]
+    private_held: np.ndarray       # uint32[n]
+    alone: np.ndarray              # uint32[n]
+    foreign: np.ndarray            # uint32[n]
+    size: np.ndarray               # uint32[n], by naming node, as the six below
+    kmers: np.ndarray              # uint64[n]
+    core: np.ndarray               # uint64[n]
+    soft: np.ndarray               # uint64[n]
+    shell: np.ndarray              # uint64[n]
+    private: np.ndarray            # uint64[n]
+    marker: np.ndarray             # uint64[n]
+    spectrum: np.ndarray           # uint64[n]
+    off: np.ndarray                # int64[n]: the first spectrum word of the cluster a node names
+    marker_cluster: np.ndarray     # int32[m]: naming nodes
+    marker_kmer: np.ndarray        # uint32[m]
+    marker_occ: np.ndarray         # uint32[m]
+
+    def genome_arrays(self) -> tuple:
+        return tuple(getattr(self, k) for k in PROFILE_GENOME_ARRAYS)
+
+    def cluster_arrays(self) -> tuple:
+        return tuple(getattr(self, k) for k in PROFILE_CLUSTER_ARRAYS)
+
+    def marker_arrays(self) -> tuple:
+        return tuple(getattr(self, k) for k in PROFILE_MARKER_ARRAYS)
+
+    def _names(self, nodes) -> list:
+        nodes = np.asarray(nodes).tolist()
+        return [(i if self.labels is None else self.labels[i]) for i in nodes]
+
+    def naming(self) -> np.ndarray:
+        """The naming nodes, ascending: cluster c of the frames is naming()[c]."""
+        return np.flatnonzero(self.label == np.arange(len(self.label))).astype(np.int32)
+
+    def cluster_of(self) -> np.ndarray:
+        """int32[n]: the number of every node's cluster (the position of its label in naming())."""
+        return np.searchsorted(self.naming(), self.label).astype(np.int32)
+
+    def spectrum_of(self, c) -> np.ndarray:
+        """uint64[size]: entry occ - 1 = the cells of the cluster that node c names with that occupancy."""
+        c = int(c)
+        if not 0 <= c < len(self.label) or int(self.label[c]) != c:
+            raise ValueError(f"node {c} names no cluster")
+        return self.spectrum[int(self.off[c]):int(self.off[c]) + int(self.size[c])]
+
+    def genome_frame(self) -> pd.DataFrame:
+        """One row per genome, in the order of `labels`: genome, cluster, held, core_held, core_missing (soft of its cluster - core_held),
+        core_fraction (core_held / soft, NaN when soft is 0), private_held, alone, foreign, singleton (alone - foreign)."""
+        n = len(self.label)
+        soft = self.soft[self.label].astype(np.int64)
+        core_held = self.core_held.astype(np.int64)
+        fraction = np.where(soft > 0, core_held.astype(np.float64) / np.where(soft > 0, soft, 1).astype(np.float64), np.nan)
+        return pd.DataFrame({"genome": self._names(np.arange(n)), "cluster": self.cluster_of().astype(np.int64), "held": self.held.astype(np.int64),
+                             "core_held": core_held, "core_missing": soft - core_held, "core_fraction": fraction,
+                             "private_held": self.private_held.astype(np.int64), "alone": self.alone.astype(np.int64), "foreign": self.foreign.astype(np.int64),
+                             "singleton": self.alone.astype(np.int64) - self.foreign.astype(np.int64)})
+
+    def cluster_frame(self) -> pd.DataFrame:
+        """One row per cluster, by ascending naming node: cluster, name (the naming node), size, core_need, shell_need, kmers, core, soft,
+        shell, cloud (kmers - soft - shell), private, marker."""
+        c = self.naming()
+        cols = {"cluster": np.arange(len(c), dtype=np.int64), "name": self._names(c), "size": self.size[c].astype(np.int64),
+                "core_need": self.core_need[c].astype(np.int64), "shell_need": self.shell_need[c].astype(np.int64)}
+        for k in ("kmers", "core", "soft", "shell"):
+            cols[k] = getattr(self, k)[c].astype(np.int64)
+        cols["cloud"] = cols["kmers"] - cols["soft"] - cols["shell"]
+        cols["private"], cols["marker"] = self.private[c].astype(np.int64), self.marker[c].astype(np.int64)
+        return pd.DataFrame(cols)
+
+    def spectrum_frame(self) -> pd.DataFrame:
+        """cluster, occupancy, kmers: the spectrum without its zero rows, by cluster, then occupancy."""
+        c = self.naming()
+        number = np.repeat(np.arange(len(c), dtype=np.int64), self.size[c].astype(np.int64))      # (the spectrum's words stand in this order)
+        occupancy = np.arange(len(self.spectrum), dtype=np.int64) - np.repeat(self.off[c], self.size[c].astype(np.int64)) + 1
+        keep = self.spectrum > 0
+        return pd.DataFrame({"cluster": number[keep], "occupancy": occupancy[keep], "kmers": self.spectrum[keep].astype(np.int64)})
+
+    def markers_frame(self) -> pd.DataFrame:
+        """One row per listed marker, in the list's order: cluster (its number), name, kmer (ACGT text when the index's k is known),
+        occupancy."""
+        text = [kmer_string(x, self.kmer) for x in self.marker_kmer.tolist()] if self.kmer else self.marker_kmer.astype(np.int64)
+        return pd.DataFrame({"cluster": np.searchsorted(self.naming(), self.marker_cluster).astype(np.int64), "name": self._names(self.marker_cluster),
+                             "kmer": text, "occupancy": self.marker_occ.astype(np.int64)})
+
+
+def profile_from_arrays(labels, label, core_need, shell_need, marker_min_size, genome_arrays, cluster_arrays, spectrum, marker_arrays, kmer: int = 0) -> ScreenProfile:
+    """The ScreenProfile of what profile_of_index or Engine.screen_search_profile returned (off is computed from the sizes)."""
+    label = np.ascontiguousarray(label, dtype=np.int64).reshape(-1)
+    n = len(label)
+    label = check_partition(label, n)
+    if labels is not None:
+        labels = [str(x) for x in labels]
+        if len(labels) != n:
+            raise ValueError("labels and nodes must have the same length")
+    if len(genome_arrays) != len(PROFILE_GENOME_ARRAYS) or len(cluster_arrays) != len(PROFILE_CLUSTER_ARRAYS) or len(marker_arrays) != len(PROFILE_MARKER_ARRAYS):
+        raise ValueError(f"a profile has {len(PROFILE_GENOME_ARRAYS)} genome arrays, {len(PROFILE_CLUSTER_ARRAYS)} cluster arrays and {len(PROFILE_MARKER_ARRAYS)} marker arrays")
+    genomes = [np.ascontiguousarray(x, dtype=t).reshape(-1) for x, t in zip(genome_arrays, _PROFILE_GENOME_TYPES)]
+    clusters = [np.ascontiguousarray(x, dtype=t).reshape(-1) for x, t in zip(cluster_arrays, _PROFILE_CLUSTER_TYPES)]
+    markers = [np.ascontiguousarray(x, dtype=t).reshape(-1) for x, t in zip(marker_arrays, _PROFILE_MARKER_TYPES)]
+    spectrum = np.ascontiguousarray(spectrum, dtype=np.uint64).reshape(-1)
+    if any(len(x) != n for x in genomes + clusters + [spectrum]) or len({len(x) for x in markers}) != 1:
+        raise ValueError("every array of a profile has one entry per node, and the markers' columns one length")
+    size = clusters[0]
+    if not np.array_equal(size, np.bincount(label, minlength=n)):
+        raise ValueError("the sizes are not those of the partition")
+    _, core_need, shell_need = check_profile_thresholds(label, core_need, shell_need)
+    names = size > 0
+    off = np.where(names, np.cumsum(np.where(names, size, 0).astype(np.int64)) - size, 0).astype(np.int64)
+    return ScreenProfile(labels, int(kmer), label.astype(np.int32), core_need, shell_need, int(marker_min_size), *genomes, *clusters, spectrum, off, *markers)
+
+
 def _labels_for(ids, labels, limit: int = MAX_GENOMES) -> List[str]:
     labels = [str(x) for x in (ids if labels is None else labels)]
     if len(labels) != len(ids):
