@@ -982,6 +982,30 @@ int pg_dist_release(pg_ctx* ctx);
  * PG_K_* slot: the slot count is published.) */
 int pg_dist_last_ms(pg_ctx* ctx, double* out3);
 
+/* ---- neighbour-joining tree of a distance matrix ------------------------------------------------------------------------
+ * The unrooted tree of a collection from its distance matrix (an ANI, sketch or screen matrix turned into distances:
+ * pyani_amd.tree).  Like the cluster calls these read a caller matrix only: they touch no genome, index or worker slot and keep
+ * nothing resident but the counters below.  d: n x n float64, row-major, finite, symmetric bit for bit, zero diagonal; 3 <= n <= 8192.
+ * Leaves are nodes 0 ... n - 1, join t (t = 0 ... n - 4) creates node n + t, the last node is 2 n - 3.
+ * Results EQUAL pyani_amd.tree.nj_of_matrix, the numpy statement, integers exactly and doubles bit for bit: every operation is
+ * rounded on its own, the row sums are carried and updated as the statement updates them, and equal criteria go to the smallest
+ * (lower node id, higher node id).
+ *   join_out      (n - 3) x 2 int32: the two nodes of every join, lower id first
+ *   len_out       (n - 3) x 2 float64: their branch lengths to the new node (negative lengths as they come)
+ *   last_out      3 int32: the three survivors by ascending id;  last_len_out  3 float64: their lengths to node 2 n - 3
+ * Any of the four may be NULL.  PG_E_ARG, before any work: n < 3, n > 8192, a NULL matrix, an asymmetric cell, a non-zero diagonal.
+ * PG_E_NONFINITE: a NaN or infinite cell, or a row sum or criterion that overflows.  PG_E_NOMEM when the working matrix (8 n^2 bytes)
+ * does not fit.  A refused call leaves the four outputs untouched. */
+int pg_tree_nj(pg_ctx* ctx, const double* d, uint32_t n, int32_t* join_out, double* len_out, int32_t* last_out, double* last_len_out);
+/* From tail_limit live nodes down, one workgroup runs every remaining step in one launch; above it a step is two launches over the
+ * whole device.  3 ... 1024 (PG_E_ARG outside, the setting unchanged); 3 runs every step wide.  The result does not depend on it. */
+int pg_tree_nj_set(pg_ctx* ctx, uint32_t tail_limit);
+/* The latest successful pg_tree_nj: counts_out 5 uint64 (n, wide steps, tail steps, kernel launches, cells the wide steps scanned: the
+ * sum of m (m - 1) / 2 over them, dead slots are not scanned); ms_out 3 float64 (validation and row sums, wide steps, tail: HIP events
+ * on the context's stream, taken while pg_profile_enable is on; zeros when it is off.  These kernels have no PG_K_* slot: the slot
+ * count is published).  Either may be NULL. */
+int pg_tree_nj_last(pg_ctx* ctx, uint64_t* counts_out, double* ms_out);
+
 /* ---- measurement ---------------------------------------------------------------------------------------- */
 /* When enabled, every kernel launch is bracketed by HIP events on the context's stream. */
 int pg_profile_enable(pg_ctx* ctx, int on);

@@ -181,6 +181,9 @@ SIGNATURES = {
     "pg_dist_kde": (_int, [_vp, _vp, _u32, ctypes.c_double, _vp]),
     "pg_dist_release": (_int, [_vp]),
     "pg_dist_last_ms": (_int, [_vp, _vp]),
+    "pg_tree_nj": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "pg_tree_nj_set": (_int, [_vp, _u32]),
+    "pg_tree_nj_last": (_int, [_vp, _vp, _vp]),
     "pg_profile_enable": (_int, [_vp, _int]),
     "pg_profile_config": (_int, [_vp, _u32, _u32]),
     "pg_profile_reset": (_int, [_vp]),

@@ -201,6 +201,9 @@ struct pg_ctx {
   PgScreenSearchRemoveStats screen_search_remove_stats;      // pg_screen_search_remove_last
   PgScreenSearchStats screen_search_stats;      // pg_screen_search_last: the resident search index, the latest count and selection over it
   double dist_ms[3] = {0.0, 0.0, 0.0};   // kernel milliseconds of the latest pg_dist_load / _hist / _kde while profiling is on (pg_dist_last_ms)
+  uint32_t tree_tail_limit = 512;        // pg_tree_nj_set: from this many live nodes down one workgroup runs every remaining step (pg_tree.hip)
+  uint64_t tree_counts[5] = {0, 0, 0, 0, 0};   // pg_tree_nj_last: n, wide steps, tail steps, launches, cells scanned of the latest pg_tree_nj
+  double tree_ms[3] = {0.0, 0.0, 0.0};   // ... and its validate, wide-step and tail milliseconds while profiling is on
   std::mutex anim_mu, err_mu, prof_mu;
   int anib_word_tier = 1;      // fragment mode: search failed fragments again with blastn-sized (11-mer) seeds
   uint32_t anib_search = 0;    // fragment mode: PG_ANIB_SEARCH_SEEDS, or PG_ANIB_SEARCH_ALL_DIAGS (pg_anib_set_search)

@@ -5,7 +5,7 @@ only currency across the ctypes boundary; nothing here computes on the CPU.
 """
 import ctypes
 from pathlib import Path
-from typing import Iterable, List, Optional, Sequence, Tuple
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -1317,6 +1317,36 @@ class Engine:
             arr[k].columns, arr[k].method, arr[k].merges = int(bool(columns)), int(method), out.ctypes.data
         self._check(self.lib.pg_cluster_linkage_batch(self._h, ctypes.cast(arr, ctypes.c_void_p), len(problems)))
         return [None if arr[k].status == _lib.PG_E_NONFINITE else outs[k] for k in range(len(problems))]
+
+    # -- neighbour-joining tree of a distance matrix (pyani_amd.tree drives these) -------------------------------------------------
+    def tree_nj(self, d) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """pg_tree_nj: (joins (n - 3) x 2 int32, lengths (n - 3) x 2, last 3 int32, last_lengths 3) of the n x n distance matrix d,
+        EQUAL to pyani_amd.tree.nj_of_matrix bit for bit.  PyaniGpuError with code PG_E_ARG for n outside 3 ... 8192, an asymmetric
+        cell or a non-zero diagonal, PG_E_NONFINITE for a NaN or infinite cell or an overflow."""
+        d = np.ascontiguousarray(d, dtype=np.float64)
+        if d.ndim != 2 or d.shape[0] != d.shape[1]:
+            raise ValueError(f"a square matrix is needed, not shape {d.shape}")
+        n = d.shape[0]
+        joins, lengths = np.zeros((max(n - 3, 0), 2), dtype=np.int32), np.zeros((max(n - 3, 0), 2), dtype=np.float64)
+        last, last_lengths = np.zeros(3, dtype=np.int32), np.zeros(3, dtype=np.float64)
+        self._check(self.lib.pg_tree_nj(self._h, d.ctypes.data if d.size else None, n, joins.ctypes.data if n > 3 else None,
+                                        lengths.ctypes.data if n > 3 else None, last.ctypes.data, last_lengths.ctypes.data))
+        return joins, lengths, last, last_lengths
+
+    def tree_nj_set(self, tail_limit: int = 512) -> None:
+        """pg_tree_nj_set: from tail_limit live nodes down one workgroup runs every remaining step (3 ... 1024; 3 = every step wide).
+        The result does not depend on it."""
+        if not 0 <= int(tail_limit) <= 0xFFFFFFFF:
+            raise ValueError(f"tail_limit must be 3 ... 1024, not {tail_limit}")
+        self._check(self.lib.pg_tree_nj_set(self._h, int(tail_limit)))
+
+    def tree_nj_last(self) -> Tuple[Dict[str, int], Dict[str, float]]:
+        """pg_tree_nj_last: the latest tree_nj's counts (n, wide_steps, tail_steps, launches, cells_scanned) and its stage
+        milliseconds (validate_ms, wide_ms, tail_ms; zeros unless profile_enable() is on)."""
+        counts, ms = (ctypes.c_uint64 * 5)(), (ctypes.c_double * 3)()
+        self._check(self.lib.pg_tree_nj_last(self._h, ctypes.addressof(counts), ctypes.addressof(ms)))
+        return (dict(zip(("n", "wide_steps", "tail_steps", "launches", "cells_scanned"), (int(c) for c in counts))),
+                dict(zip(("validate_ms", "wide_ms", "tail_ms"), (float(v) for v in ms))))
 
     # -- distribution plots: histogram and kernel density estimate (pyani_amd.graphics drives these) ------------------------------
     def dist_load(self, x) -> Tuple[float, float, int, int]:

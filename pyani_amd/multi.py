@@ -152,6 +152,16 @@ class MultiEngine:
     def cluster_linkage_batch(self, problems):
         return self.engines[0].cluster_linkage_batch(problems)
 
+    # ... and so does the neighbour-joining tree
+    def tree_nj(self, d):
+        return self.engines[0].tree_nj(d)
+
+    def tree_nj_set(self, tail_limit: int = 512):
+        return self.engines[0].tree_nj_set(tail_limit)
+
+    def tree_nj_last(self):
+        return self.engines[0].tree_nj_last()
+
     # ... and so do the distribution calls
     def dist_load(self, x):
         return self.engines[0].dist_load(x)
